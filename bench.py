@@ -1,6 +1,14 @@
 """bench.py — images/s of the full T-step IR-SDE reverse sampler (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W          (N>1: launched by torch.distributed.run)
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]          (N>1: launched by torch.distributed.run)
+
+A plain run sets up, runs W untimed and K timed steps, writes the outputs if asked and prints the result line (`value`, `ms_per_step` =
+milliseconds of one timed step, ...).  Everything else this file measures (`roofline` with its live `traffic` passes, `secondary`,
+`cpu_baseline`) runs only with `--full`, which the `--no-*` options then trim.
+
+`--dump-outputs DIR` writes what the timed path returned in its LAST timed step (rank 0: the restored, gathered batch) as
+DIR/restored.npy in float32 (a fixed, seeded sample of it, DIR/restored_sample.npy, past 64 MB).  Weights, inputs and the noise seed are
+synthetic and seeded, so two builds run with the same arguments can be compared file for file.
 
 A "step" = one pass of the hot path over one batch: `IRSDE.reverse_sde` (T=100 network evaluations + state
 updates) on a synthetic batch of 16 x 3 x 256 x 256 per GPU (BASELINE.json configs[1]); weak scaling: every
@@ -11,14 +19,14 @@ of the restored images (RCCL over xGMI), which is inside the timed region.
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1` (one rank per GPU).
 
 `value` is timed on the production path: one captured hipGraph per step replayed T times (`sde.use_graph`), no
-per-kernel events.  After the timed region rank 0 runs ONE more, untimed, event-instrumented pass (eager launches
+per-kernel events.  With `--full`, after the timed region rank 0 runs ONE more, untimed, event-instrumented pass (eager launches
 with a hipEvent pair around every kernel on the engine's stream) to fill `roofline`:
     roofline.frac = FLOPs the MFMA pipe executed (Winograd layers counted at their reduced multiply count)
                     / (time of the MFMA kernels + the Winograd transform kernels that belong to them) / peak   (<= 1)
 `mfma_kernel_frac` is the same over the MFMA kernels alone; the direct-convolution-equivalent rate (which exceeds the
 fp32 peak because Winograd skips multiplies) is reported as `algorithmic_equiv_TFLOPs`, never as a fraction.
 `roofline.dominant_kernel` names the kernel class with the largest share of that pass and its own fraction of the roof.
-`roofline.traffic` (r05): HBM bytes per conv launch MEASURED in the default 1-GPU run — after the timed region the script spawns two bounded rocprofv3
+`roofline.traffic` (r05): HBM bytes per conv launch MEASURED in the `--full` default-workload 1-GPU run — after the timed region the script spawns two bounded rocprofv3
 counter passes of itself (`--pmc FETCH_SIZE`, `--pmc WRITE_SIZE`, T = 3; `live_traffic()`); without rocprofv3 (or with `--no-live-pmc` / `--no-secondary`)
 it falls back to the committed summary of the builder's passes; `traffic_source` says which.
 `cpu_baseline`: the torch-CPU port of the reference timed on this box's host cores on a bounded sample.
@@ -26,7 +34,7 @@ it falls back to the committed summary of the builder's passes; `traffic_source`
 `--scaling strong` splits ONE global batch of --batch images over the ranks (north_star: "image batches shard across the 8
 GPUs"); the default, weak, gives every rank its own --batch images.  `rank_ms_per_step` lists min / max over the ranks.
 
-`secondary` (default N-rank run only, after the headline is timed; `--no-secondary` skips it): the other BASELINE.json
+`secondary` (`--full` default-workload N-rank run only, after the headline is timed; `--no-secondary` skips it): the other BASELINE.json
 configs and the 512x512 UNet batch, each timed for ONE sampler call on the same production path and carrying its own
 roofline fraction from a 3-evaluation event pass.  They never change the headline keys.
 """
@@ -460,6 +468,26 @@ def timed(wl, steps, warmup, world, dev):
     return dt, per_rank, out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """`--dump-outputs`: one DIR/<name>.npy per array (float64 stays float64, everything else becomes float32).  Past the
+    DUMP_LIMIT_BYTES budget an array is replaced by a fixed, seeded sample of its flattened elements, DIR/<name>_sample.npy
+    (the same element positions for the same shape, so two builds still compare element for element)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    budget = DUMP_LIMIT_BYTES
+    for name in sorted(arrays):
+        a = np.asarray(arrays[name])
+        a = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+        if a.nbytes > budget:
+            idx = np.unique(np.random.default_rng(0).integers(0, a.size, budget // a.itemsize))
+            a, name = a.reshape(-1)[idx], name + "_sample"
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        budget -= a.nbytes
+
+
 def main():
     # RCCL / device-tensor sharing across the ranks of one node needs dmabuf IPC on this driver; the GPU box exports this already — set it for any other launcher too
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
@@ -480,14 +508,22 @@ def main():
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak: --batch images per GPU; strong: one global batch of --batch images split over the GPUs")
     ap.add_argument("--engine-flags", type=int, default=0, help="measurement only: extra IRSDE_FLAG_* bits for the score network (A/B of plan choices); never part of a reported line's default")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile", action="store_true", help="skip the untimed event-instrumented pass (no `roofline` object)")
-    ap.add_argument("--no-secondary", action="store_true", help="headline workload only")
-    ap.add_argument("--no-live-pmc", action="store_true", help="do not spawn the two rocprofv3 counter passes that measure `roofline.traffic` (default N=1 run only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (rank 0: the restored batch) to DIR/restored.npy, float32, at most 64 MB")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: `roofline` (event pass + live traffic), `secondary`, `cpu_baseline`")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip `cpu_baseline`")
+    ap.add_argument("--no-profile", action="store_true", help="with --full: skip the untimed event-instrumented pass (no `roofline` object)")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: headline workload only")
+    ap.add_argument("--no-live-pmc", action="store_true", help="with --full: do not spawn the two rocprofv3 counter passes that measure `roofline.traffic` (default N=1 run only)")
     a = ap.parse_args()
 
     if a.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
+    if a.steps < 1 or a.warmup < 0:
+        sys.exit("bench.py: --steps must be >= 1 and --warmup >= 0")
+    if not a.full:   # a plain run: the headline only
+        a.no_cpu_baseline = a.no_profile = a.no_secondary = a.no_live_pmc = True
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # not under torchrun: launch one rank per GPU ourselves (the driver may call `python bench.py --gpus 8` directly)
         sk = socket.socket()
@@ -559,6 +595,8 @@ def main():
         setup_s = [float(x) for x in parts]
     dt, per_rank, out = timed(wl, a.steps, a.warmup, world, dev)
     assert out.shape[0] == wl.nglobal and bool(torch.isfinite(out).all())
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"restored": out.detach().float().cpu().numpy()})
 
     prof = None
     if not a.no_profile and rank == 0 and a.model != "dsde" and wl.hi > wl.lo:

@@ -691,6 +691,21 @@ def gen_fullres2(sde_utils, ConditionalUNet, ref_root):
     print("fullres2.npz")
 
 
+def gen_seam(sde_utils, ConditionalUNet):
+    """The reference's own `IRSDE.reverse_ode` (`sde_utils.py:268-282`, no noise drawn) around its own `ConditionalUNet`
+    at 1x3x32x32, T=6: the pin of tests/test_gpu_fullres.py's seam test, which used to import the reference at run time."""
+    params = O.synth_params(seed=0, nf=64, depth=4)
+    net = build_ref_net(ConditionalUNet, params, 64, 4)
+    lq, xT = O.synth_inputs(2, 1, 32, 32)
+    sde = sde_utils.IRSDE(max_sigma=10, T=6, schedule="cosine", eps=0.005, device="cpu")
+    sde.set_model(net)
+    sde.set_mu(torch.from_numpy(lq))
+    with torch.no_grad():
+        y = sde.reverse_ode(torch.from_numpy(xT)).numpy()
+    np.savez_compressed(os.path.join(GOLD, "seam.npz"), **{"nf64d4_1x32x32_T6/ode": y})
+    print("seam.npz", float(np.abs(y).max()))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ref", default="/root/reference")
@@ -728,6 +743,10 @@ def main():
         if a.only == "":
             sde_utils, ConditionalUNet = load_reference_again(a.ref)
         gen_fullres2(sde_utils, ConditionalUNet, a.ref)
+    if a.only in ("", "seam"):
+        if a.only == "":
+            sde_utils, ConditionalUNet = load_reference_again(a.ref)
+        gen_seam(sde_utils, ConditionalUNet)
 
 
 if __name__ == "__main__":

@@ -5,7 +5,7 @@ shapes are committed (tests/golden/fullres.npz, oracle/gen_golden.py --only full
 
 Also: batch independence of the production plan (B=16 vs 16 x B=1), the reduced-precision modes at 256x256, the N>1
 launch path on real devices, the dataset evaluation driver, the T=0 / x0 corner semantics, and the seam with
-reference-style foreign objects.  /root/reference is read only by the one test that is guarded on its presence.
+reference-style foreign objects.  The reference itself is never read here: its outputs are committed under tests/golden/.
 """
 import ctypes
 import json
@@ -647,23 +647,17 @@ def test_product_sde_with_a_foreign_torch_model():
     assert relerr(a, b) < 1e-5
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/codes"), reason="the reference tree exists only in the build container")
-def test_product_classes_inside_the_real_reference_wrapper():
-    """Cross-seam test against the reference's OWN code (runs wherever a GPU and /root/reference are both present): the
-    reference's `IRSDE` drives the product ConditionalUNet, and the product `IRSDE` is handed to a reference-style
-    DenoisingModel.test; both must agree with the product's fused path."""
-    sys.path.insert(0, ROOT)
-    from oracle import gen_golden as G
-    sde_utils, _RefUNet = G.load_reference("/root/reference")
+def test_product_sampler_vs_reference_wrapper_golden():
+    """Cross-seam test against the reference's OWN code: the reference's `IRSDE.reverse_ode` around its own ConditionalUNet
+    (tests/golden/seam.npz, oracle/gen_golden.py --only seam) must agree with the product's fused path on the same weights
+    and inputs.  (The product classes inside reference-style wrappers: test_product_unet_inside_a_reference_style_sde and
+    test_product_sde_with_a_foreign_torch_model.)"""
+    g = np.load(os.path.join(ROOT, "tests", "golden", "seam.npz"))
+    a = g["nf64d4_1x32x32_T6/ode"]
     m = unet64()
     T = 6
     lq, xT = O.synth_inputs(2, 1, 32, 32)
     x, mu = torch.from_numpy(xT).to(DEV), torch.from_numpy(lq).to(DEV)
-    ref_sde = sde_utils.IRSDE(max_sigma=10, T=T, schedule="cosine", eps=0.005, device=DEV)
-    ref_sde.set_model(m)
-    ref_sde.set_mu(mu)
-    with torch.no_grad():
-        a = ref_sde.reverse_ode(x).cpu().numpy()
     prod = P.IRSDE(10, T, "cosine", 0.005, device=DEV)
     prod.set_model(m)
     prod.set_mu(mu)
@@ -689,8 +683,8 @@ def test_bench_self_launches_two_ranks():
     1-GPU box the two ranks share the GPU (IRSDE_BENCH_OVERSUBSCRIBE=1: gloo gather through the host, a test hook); with
     >= 2 GPUs this is the real thing over RCCL."""
     two = torch.cuda.device_count() >= 2
-    res = _run_bench(["--gpus", "2", "--steps", "1", "--warmup", "1", "--batch", "2", "--size", "64", "--T", "6", "--no-cpu-baseline"],
-                     None if two else {"IRSDE_BENCH_OVERSUBSCRIBE": "1"})
+    res = _run_bench(["--gpus", "2", "--steps", "1", "--warmup", "1", "--batch", "2", "--size", "64", "--T", "6", "--no-cpu-baseline",
+                      "--full"], None if two else {"IRSDE_BENCH_OVERSUBSCRIBE": "1"})
     assert res["n_gpus"] == 2 and res["config"]["global_batch"] == 4 and res["value"] > 0 and res["scaling"] == "weak"
     assert ("RCCL" in res["config"]["parallelism"]) == two
     r = res["roofline"]
@@ -702,7 +696,7 @@ def test_bench_strong_scaling_ragged_two_ranks():
     over 2 ranks = shards of 3 and 2 through `sample_shard` + the final gather; per-rank times are reported."""
     two = torch.cuda.device_count() >= 2
     res = _run_bench(["--gpus", "2", "--scaling", "strong", "--steps", "1", "--warmup", "1", "--batch", "5", "--size", "64", "--T", "6",
-                      "--no-cpu-baseline"], None if two else {"IRSDE_BENCH_OVERSUBSCRIBE": "1"})
+                      "--no-cpu-baseline", "--full"], None if two else {"IRSDE_BENCH_OVERSUBSCRIBE": "1"})
     assert res["n_gpus"] == 2 and res["scaling"] == "strong" and res["config"]["global_batch"] == 5 and res["value"] > 0
     assert 0 < res["rank_ms_per_step"]["min"] <= res["rank_ms_per_step"]["max"]
     assert "secondary" not in res
@@ -716,12 +710,30 @@ def test_bench_rejects_mismatched_world():
 
 
 def test_bench_single_gpu_line_small():
-    """The default code path of bench.py (N=1) at a small shape: value on graph replay, roofline from the untimed pass."""
-    res = _run_bench(["--steps", "1", "--warmup", "1", "--batch", "2", "--size", "64", "--T", "8", "--no-cpu-baseline"])
+    """The --full code path of bench.py (N=1) at a small shape: value on graph replay, roofline from the untimed pass."""
+    res = _run_bench(["--steps", "1", "--warmup", "1", "--batch", "2", "--size", "64", "--T", "8", "--no-cpu-baseline", "--full"])
     assert res["n_gpus"] == 1 and res["unit"] == "images/s" and res["vs_baseline"] is None and res["dtype"] == "f32"
     r = res["roofline"]
     assert r["bound"] == "mfma" and 0 < r["frac"] <= 1 and r["unit"] == "TFLOP/s" and r["algorithmic_equiv_TFLOPs"] > 0
     assert abs(r["achieved"] / r["peak"] - r["frac"]) < 1e-3   # (the compact line rounds both to 4 significant digits)
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain run (no --full) is the headline only: --steps timed steps, `ms_per_step`, no `roofline` / `secondary` / `cpu_baseline`.  --dump-outputs
+    writes the last timed step's restored batch, and a second run with the same arguments writes the same array."""
+    args = ["--steps", "2", "--warmup", "1", "--batch", "2", "--size", "64", "--T", "6"]
+    outs = []
+    for k in range(2):
+        d = tmp_path / ("run%d" % k)
+        res = _run_bench(args + ["--dump-outputs", str(d)])
+        assert res["steps"] == 2 and res["ms_per_step"] > 0 and res["value"] > 0 and res["higher_is_better"] is True
+        assert abs(res["value"] - 2 * 1000.0 / res["ms_per_step"]) < 1e-6 * res["value"]   # 2 images per step
+        assert not {"roofline", "secondary", "cpu_baseline"} & set(res)
+        assert sorted(os.listdir(d)) == ["restored.npy"]
+        y = np.load(d / "restored.npy")
+        assert y.dtype == np.float32 and y.shape == (2, 3, 64, 64) and np.isfinite(y).all()
+        outs.append(y)
+    assert np.array_equal(outs[0], outs[1])
 
 
 def _shard_worker(rank, world, port, q):
@@ -776,7 +788,8 @@ def test_sample_sharded_one_rank_over_rccl():
 
 def test_bench_one_rank_over_rccl():
     """bench.py's N > 1 code path (RCCL group, barrier fences, gather_batch, all_reduce'd phase agreement, max over ranks) with a group of one rank."""
-    res = _run_bench(["--steps", "1", "--warmup", "1", "--batch", "3", "--size", "64", "--T", "6", "--no-cpu-baseline"], {"IRSDE_BENCH_FORCE_RCCL": "1"})
+    res = _run_bench(["--steps", "1", "--warmup", "1", "--batch", "3", "--size", "64", "--T", "6", "--no-cpu-baseline", "--full"],
+                     {"IRSDE_BENCH_FORCE_RCCL": "1"})
     assert res["n_gpus"] == 1 and res["value"] > 0 and res["config"]["global_batch"] == 3
     assert 0 < res["rank_ms_per_step"]["min"] <= res["rank_ms_per_step"]["max"]
 

@@ -339,6 +339,29 @@ def test_bench_roofline_object_from_an_op_profile():
     assert not any((w["model"], w["dtype"], w["batch"], w["size"], w["T"], w["mode"]) == ("unet", "fp32", 16, 256, 100, "sde") for w in bench.SECONDARY)
 
 
+def test_bench_dump_outputs_budget(tmp_path):
+    """bench.py --dump-outputs (no GPU): arrays within the 64 MB budget are written whole in float32 (float64 kept); past it, a fixed
+    seeded sample of the flattened array that fits the budget and is the same from call to call."""
+    import importlib.util
+    import os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    small = np.random.RandomState(0).rand(2, 3, 8, 8)
+    bench.dump_outputs(str(tmp_path / "a"), {"restored": small.astype(np.float16), "x64": small})
+    a = np.load(tmp_path / "a" / "restored.npy")
+    assert a.dtype == np.float32 and a.shape == small.shape and np.array_equal(a, small.astype(np.float16).astype(np.float32))
+    assert np.load(tmp_path / "a" / "x64.npy").dtype == np.float64
+    big = np.arange(bench.DUMP_LIMIT_BYTES // 8 + 1000, dtype=np.float64)   # just past the budget (integers: exact in float64)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"restored": big})
+        assert os.listdir(tmp_path / d) == ["restored_sample.npy"]
+    s, s2 = np.load(tmp_path / "b" / "restored_sample.npy"), np.load(tmp_path / "c" / "restored_sample.npy")
+    assert s.nbytes <= bench.DUMP_LIMIT_BYTES and s.size > big.size // 2 and np.array_equal(s, s2)
+    assert np.all(np.diff(s) > 0)   # distinct elements in their original order
+
+
 def test_strong_scaling_shards_cover_the_global_batch():
     """`bench.py --scaling strong` / `sample_shard`: the shards of ONE global batch over 1 .. 8 ranks are contiguous, disjoint, cover
     the batch, differ by at most one image, and ranks beyond the batch get an empty shard (16 images over 8 GPUs = 2 each)."""
