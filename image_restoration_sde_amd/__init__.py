@@ -11,6 +11,8 @@ csrc/ -> libirsde_hip.so) with the reference's own Python interface on top:
     latent.UNet / latent.ConditionalNAFNet / LatentDenoisingModel
                        codes/config/latent-dehazing/models/{modules/UNet_arch.py, modules/DenoisingNAFNet_arch.py,
                        latent_denoising_model.py} (encode once, sample in the latent, decode once)
+    stereo_sr.ConditionalNAFNet
+                       codes/config/stereo-sr/models/modules/DenoisingNAFNet_arch.py (NAFBlocks + SCAM on stereo pairs)
     metrics            codes/utils/img_utils.py:136-234 + codes/data/util.py:177-198 (tensor2img / PSNR / SSIM / Y channel)
 """
 from ._lib import IrsdeError, IrsdeLibraryError, build_library  # noqa: F401
@@ -24,7 +26,8 @@ from .denoising_sde import DenoisingSDE  # noqa: F401
 from . import metrics  # noqa: F401
 from . import latent  # noqa: F401
 from . import latent_bokeh  # noqa: F401
+from . import stereo_sr  # noqa: F401
 from .latent import LatentDenoisingModel  # noqa: F401
 
-__all__ = ["IRSDE", "DenoisingSDE", "denoising_sde", "metrics", "latent", "latent_bokeh", "LatentDenoisingModel", "ConditionalUNet", "ConditionalNAFNet", "DenoisingModel", "ReverseSDEDenoisingModel", "create_model", "define_G", "build_library",
+__all__ = ["IRSDE", "DenoisingSDE", "denoising_sde", "metrics", "latent", "latent_bokeh", "stereo_sr", "LatentDenoisingModel", "ConditionalUNet", "ConditionalNAFNet", "DenoisingModel", "ReverseSDEDenoisingModel", "create_model", "define_G", "build_library",
            "IrsdeError", "IrsdeLibraryError", "shard_bounds", "gather_batch", "sample_shard", "sample_sharded"]

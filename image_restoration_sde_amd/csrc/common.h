@@ -282,6 +282,19 @@ void launch_attention_q_out_fused(const float* xn, const float* x, const float* 
                                   const float* ln_g = nullptr, const unsigned short* wq_pair = nullptr, const unsigned short* wout_pair = nullptr,
                                   float wq_inv = 1.f, float wout_inv = 1.f, int op16 = 0, bool act_bf16 = false);   // *_pair: fp16 hi / lo planes (IRSDE_FLAG_SPLIT_F16X2), see kernels_misc.hip
 
+// Stereo-sr SCAM (scam.hip): x [2B][H][W][c] NHWC, views stacked [L_0..L_{B-1}, R_0..R_{B-1}]; H' = H / 4, W' = W / 4 (floor).
+//   prologue  xs2 [2B][H'][W'][LN(xs) (norm_l / norm_r gain) | xs], xs = bicubic quarter-downsample of x
+//   core      qv [2B][H'][W'][Q | V] -> F [2B][H'][W'][c]: F_r2l in the left images, F_l2r in the right ones
+//   epilogue  out = x + (beta | gamma)[ch] * F[nearest]
+void scam_check_shape(int H, int W, int c);   // throws HipError for maps the reference cannot run (H or W < 4) or the kernels do not cover
+void launch_scam_prologue(const float* x, const float* g_l, const float* g_r, float* xs2, int B, int H, int W, int c, hipStream_t s);
+void launch_scam_core(const float* qv, float* F, int B, int H, int W, int c, hipStream_t s);
+void launch_scam_epilogue(const float* x, const float* F, const float* beta, const float* gamma, float* out, int B, int H, int W, int c, hipStream_t s);
+void scam_pack_proj(const float* w1, const float* b1, const float* w2, const float* b2, int c, std::vector<float>& w, std::vector<float>& bias);
+// stereo network glue: 6-channel pair tensors <-> the 2B-view network batch
+void launch_stereo_prep(const float* xt, const float* cond, float* x0, int B, int ic, int P, int H, int W, int Hp, int Wp, hipStream_t s);
+void launch_stereo_pack_pred(const float* in, float* out, int B, int ic, int Hp, int Wp, int in_stride, int out_stride, hipStream_t s);
+
 // Full softmax attention over N tokens (denoising-sde bottleneck): qkv [B][N][384] -> out [B][N][128].
 void launch_full_attention(const float* qkv, float* out, int B, int N, hipStream_t s);
 

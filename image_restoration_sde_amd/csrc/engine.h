@@ -111,6 +111,10 @@ struct NafBlockW {
     int film_off = 0;                            // [shift_att | scale_att | shift_ffn | scale_ffn]
     float *cam_w = nullptr, *cam_b = nullptr;    // latent-bokeh: cam_mlp.1: Linear(time_dim/2, 2c)
     int cam_off = 0;                             // [cam_scale | cam_shift] inside a row of the lens table
+    // stereo-sr (IRSDE_FLAG_NAF_STEREO): fusion = SCAM(c) after the block (stereo-sr DenoisingNAFNet_arch.py:15-60, 131)
+    float *scam_gl = nullptr, *scam_gr = nullptr;  // fusion.norm_l.g / norm_r.g
+    ConvW scam_l, scam_r;                          // [[proj1, 0], [0, proj2]] per view: [LN(xs) | xs] (2c) -> [Q | V] (2c), bias [b1 | b2]
+    float *scam_beta = nullptr, *scam_gamma = nullptr;
 };
 
 // a run of consecutive 512-channel NAFBlocks packed for naf_chain_kernel (fp16 mode): fragment streams + fp32 vectors
@@ -318,6 +322,7 @@ struct irsde_engine {
 
     // ConditionalNAFNet (arch == 1)
     int arch = 0;
+    int naf_ic = 0;   // the network's img_channel (cfg.in_nc is the sampler state's channel count: 2 naf_ic for IRSDE_FLAG_NAF_STEREO)
     std::vector<int> naf_enc_nums, naf_dec_nums;
     int naf_mid_num = 0;
     std::vector<std::vector<NafBlockW>> naf_enc, naf_dec;
@@ -450,6 +455,7 @@ struct irsde_engine {
 namespace irsde {
 
 inline bool naf_lens(const irsde_engine* e) { return (e->cfg.flags & IRSDE_FLAG_NAF_LENS) != 0; }
+inline bool naf_stereo(const irsde_engine* e) { return e->arch == 1 && (e->cfg.flags & IRSDE_FLAG_NAF_STEREO) != 0; }
 inline int rup32(int c) { return (c + 31) & ~31; }
 
 // engine_weights.hip: weight inventory (reference state_dict names), packing into kernel layouts, FiLM rows

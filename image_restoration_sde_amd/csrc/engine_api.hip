@@ -121,6 +121,7 @@ int irsde_create(const irsde_config* cfg, irsde_engine** out) {
             throw HipError("in_nc/out_nc must be in 1..4");
         if (cfg->in_nc != cfg->out_nc) throw HipError("sampler needs in_nc == out_nc");
         if ((cfg->nf << cfg->depth) > 2048) throw HipError("nf * 2^depth must be <= 2048");
+        if (cfg->flags & IRSDE_FLAG_NAF_STEREO) throw HipError("IRSDE_FLAG_NAF_STEREO: the stereo network is a ConditionalNAFNet (irsde_create_nafnet)");
         auto* e = new irsde_engine();
         e->cfg = *cfg;
         if (cfg->flags & IRSDE_FLAG_BF16_ACT) {
@@ -145,9 +146,18 @@ int irsde_create_nafnet(const irsde_nafnet_config* cfg, irsde_engine** out) {
         if (cfg->n_enc < 1 || cfg->n_enc > 6 || cfg->n_dec != cfg->n_enc) throw HipError("need 1..6 encoder stages and as many decoder stages");
         if ((cfg->width << cfg->n_enc) > 2048) throw HipError("width * 2^stages must be <= 2048");
         if (cfg->flags & IRSDE_FLAG_BF16_ACT) throw HipError("IRSDE_FLAG_BF16_ACT: conditional UNet only");
+        const bool stereo = (cfg->flags & IRSDE_FLAG_NAF_STEREO) != 0;
+        if (stereo) {
+            if (cfg->flags & (IRSDE_FLAG_NAF_LENS | IRSDE_FLAG_NAF_INTRO_SKIP))
+                throw HipError("IRSDE_FLAG_NAF_STEREO cannot be combined with IRSDE_FLAG_NAF_LENS / IRSDE_FLAG_NAF_INTRO_SKIP");
+            if (cfg->img_channel > 4) throw HipError("IRSDE_FLAG_NAF_STEREO: img_channel must be in 1..4 (pairs of 2 img_channel channels)");
+            if ((cfg->flags & (IRSDE_FLAG_SPLIT_BF16X2 | IRSDE_FLAG_SPLIT_F16X2)) || ((cfg->flags & IRSDE_FLAG_BF16) && !(cfg->flags & IRSDE_FLAG_FP16)))
+                throw HipError("IRSDE_FLAG_NAF_STEREO runs in fp32 or with IRSDE_FLAG_FP16 only (the bf16 and split-operand modes are not covered for the SCAM network)");
+        }
         auto* e = new irsde_engine();
         e->arch = 1;
-        e->cfg.in_nc = e->cfg.out_nc = cfg->img_channel;
+        e->naf_ic = cfg->img_channel;
+        e->cfg.in_nc = e->cfg.out_nc = (stereo ? 2 : 1) * cfg->img_channel;   // stereo: the sampler state holds [L | R] per pair
         e->cfg.nf = cfg->width;
         e->cfg.depth = cfg->n_enc;  // pad multiple 2^stages (padder_size, DenoisingNAFNet_arch.py:147)
         e->cfg.device = cfg->device;
@@ -283,12 +293,14 @@ int irsde_unet_forward(irsde_engine* e, const float* xt, const float* cond, cons
             IRSDE_HIP_CHECK(hipMemcpyAsync(e->film_cur, e->film_table + (size_t)t_host[0] * e->film_row,
                                            (size_t)e->film_row * 4, hipMemcpyDeviceToDevice, s));
         } else {
-            std::vector<float> tv(nt);
-            for (int i = 0; i < nt; ++i) tv[i] = (float)t_host[i];
+            // stereo with per-pair times: one row per view v B + b (time = torch.cat([time, time], 0), stereo-sr DenoisingNAFNet_arch.py:213)
+            const int rows = (naf_stereo(e) && nt > 1 ? 2 : 1) * nt;
+            std::vector<float> tv(rows);
+            for (int i = 0; i < rows; ++i) tv[i] = (float)t_host[i % nt];
             float* dtv = nullptr;
-            IRSDE_HIP_CHECK(hipMalloc(&dtv, nt * sizeof(float)));
-            IRSDE_HIP_CHECK(hipMemcpy(dtv, tv.data(), nt * sizeof(float), hipMemcpyHostToDevice));
-            compute_film_rows(e, dtv, nt, e->film_cur, s);
+            IRSDE_HIP_CHECK(hipMalloc(&dtv, rows * sizeof(float)));
+            IRSDE_HIP_CHECK(hipMemcpy(dtv, tv.data(), rows * sizeof(float), hipMemcpyHostToDevice));
+            compute_film_rows(e, dtv, rows, e->film_cur, s);
             (void)hipFree(dtv);
         }
         run_net(pl, s);
@@ -575,6 +587,59 @@ int irsde_work_model(irsde_engine* e, int B, int H, int W, double out[2]) {
         Plan* pl = get_plan(e, B, H, W, false);
         out[0] = pl->conv_flops;
         out[1] = pl->conv_bytes;
+    });
+}
+
+int irsde_debug_scam(const float* x, int B, int H, int W, int C, const float* norm_l_g, const float* norm_r_g, const float* l_proj1_w,
+                     const float* l_proj1_b, const float* r_proj1_w, const float* r_proj1_b, const float* l_proj2_w, const float* l_proj2_b,
+                     const float* r_proj2_w, const float* r_proj2_b, const float* beta, const float* gamma, float* out, void* stream) {
+    return guard([&] {
+        if (!x || !out || !norm_l_g || !norm_r_g || !l_proj1_w || !l_proj1_b || !r_proj1_w || !r_proj1_b || !l_proj2_w || !l_proj2_b || !r_proj2_w ||
+            !r_proj2_b || !beta || !gamma)
+            throw HipError("null argument");
+        if (B < 1) throw HipError("debug_scam: bad shape");
+        scam_check_shape(H, W, C);
+        hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+        conv_global_init();
+        const int Hs = H / 4, Ws = W / 4;
+        std::vector<float> wl, bl, wr, br;
+        scam_pack_proj(l_proj1_w, l_proj1_b, l_proj2_w, l_proj2_b, C, wl, bl);
+        scam_pack_proj(r_proj1_w, r_proj1_b, r_proj2_w, r_proj2_b, C, wr, br);
+        std::vector<float*> bufs;
+        auto up = [&](const float* h, size_t n) {
+            float* d = nullptr;
+            IRSDE_HIP_CHECK(hipMalloc(&d, std::max<size_t>(n, 16) * 4));
+            bufs.push_back(d);
+            if (h) IRSDE_HIP_CHECK(hipMemcpy(d, h, n * 4, hipMemcpyHostToDevice));
+            return d;
+        };
+        try {
+            float *dgl = up(norm_l_g, C), *dgr = up(norm_r_g, C), *dbe = up(beta, C), *dga = up(gamma, C);
+            float *dwl = up(wl.data(), wl.size()), *dbl = up(bl.data(), bl.size()), *dwr = up(wr.data(), wr.size()), *dbr = up(br.data(), br.size());
+            const size_t vsz = (size_t)B * Hs * Ws * 2 * C;
+            float *xs2 = up(nullptr, 2 * vsz), *qv = up(nullptr, 2 * vsz), *F = up(nullptr, vsz), *dz = up(nullptr, 256);
+            IRSDE_HIP_CHECK(hipMemset(dz, 0, 1024));
+            launch_scam_prologue(x, dgl, dgr, xs2, B, H, W, C, s);
+            for (int v = 0; v < 2; ++v) {
+                ConvParams p;
+                p.in0 = xs2 + v * vsz; p.C0 = 2 * C; p.pix0 = 2 * C;
+                p.Hin = Hs; p.Win = Ws;
+                p.w = v ? dwr : dwl; p.Cout = 2 * C; p.KH = p.KW = 1; p.stride = 1;
+                p.B = B; p.Ho = Hs; p.Wo = Ws;
+                p.out = qv + v * vsz; p.out_stride = 2 * C;
+                p.bias = v ? dbr : dbl;
+                p.zeros = dz;
+                launch_conv(p, s);
+            }
+            launch_scam_core(qv, F, B, H, W, C, s);
+            launch_scam_epilogue(x, F, dbe, dga, out, B, H, W, C, s);
+            IRSDE_HIP_CHECK(hipStreamSynchronize(s));
+        } catch (...) {
+            (void)hipStreamSynchronize(s);
+            for (float* p : bufs) (void)hipFree(p);
+            throw;
+        }
+        for (float* p : bufs) (void)hipFree(p);
     });
 }
 

@@ -433,7 +433,8 @@ struct Builder {
 
     // a run of NAFBlocks as one launch (naf_chain.hip): one work-group per image walks the whole run
     bool naf_chain_ok(const NafChainW& cw, const Tensor& x) const {
-        return cw.nblocks > 0 && !naive && !x.bf16 && naf_chain_shape_ok(x.H, x.W, x.C);
+        // (stereo: the SCAM after every block couples the two views of a pair — no per-image chain)
+        return cw.nblocks > 0 && !naive && !x.bf16 && !naf_stereo(e) && naf_chain_shape_ok(x.H, x.W, x.C);
     }
     // r06: G work-groups per image where they all fit the compute units at the same time (a spinning group holds its CU): the batch's groups next to
     // those of the call's other concurrent sub-batches
@@ -478,6 +479,55 @@ struct Builder {
             o.fn = [=](hipStream_t s) { launch_naf_chain(xp, op, c.w, c.vecs, c.nblocks, B, film, fb, c.film_off, cam, cb, c.cam_off, s); };
         }
         pl->net_ops.push_back(std::move(o));
+        return out;
+    }
+
+    // SCAM.forward — stereo-sr DenoisingNAFNet_arch.py:33-60 (csrc/scam.hip): x holds the 2 B views [L | R] of B pairs
+    Tensor scam(const NafBlockW& w, const Tensor& x) {
+        const int c = x.C, Bp = x.B / 2, Hs = x.H / 4, Ws = x.W / 4, H = x.H, W = x.W;
+        scam_check_shape(x.H, x.W, c);
+        const size_t vsz = (size_t)Bp * Hs * Ws * 2 * c;   // one view's [LN(xs) | xs] / [Q | V]
+        float* xs2 = pl->alloc(2 * vsz, reuse);
+        float* qv = pl->alloc(2 * vsz, reuse);
+        float* F = pl->alloc(vsz, reuse);
+        Tensor out = talloc(x.B, x.H, x.W, c);
+        char buf[160];
+        auto name = [&](const char* what) {
+            snprintf(buf, sizeof buf, "scam_%s B=%d c=%d hw=%dx%d W'=%d H'=%d", what, x.B, c, H, W, Ws, Hs);
+            pl->net_ops.back().desc = buf;
+        };
+        {
+            const float *xp = x.p, *gl = w.scam_gl, *gr = w.scam_gr;
+            push_other(OP_LN, [=](hipStream_t s) { launch_scam_prologue(xp, gl, gr, xs2, Bp, H, W, c, s); });
+            name("prologue(bicubic/4 + LayerNorm)");
+        }
+        for (int v = 0; v < 2; ++v) {   // [Q | V] = [[proj1, 0], [0, proj2]] [LN(xs) | xs] + [b1 | b2]: one GEMM per view (its weights)
+            const ConvW& cw = v ? w.scam_r : w.scam_l;
+            ConvParams p;
+            p.in0 = xs2 + v * vsz; p.C0 = 2 * c; p.pix0 = 2 * c;
+            p.Hin = Hs; p.Win = Ws;
+            p.w = cw.w; p.Cout = 2 * c; p.KH = p.KW = 1; p.stride = 1;
+            p.B = Bp; p.Ho = Hs; p.Wo = Ws;
+            p.out = qv + v * vsz; p.out_stride = 2 * c;
+            p.bias = cw.bias;
+            push_conv(p);
+            pl->net_ops.back().desc = std::string(v ? "scam_proj(r) " : "scam_proj(l) ") + pl->net_ops.back().desc;
+        }
+        {
+            push_other(OP_ATTN, [=](hipStream_t s) { launch_scam_core(qv, F, Bp, H, W, c, s); });
+            name("core(S strips + softmax + PV, fp32 MFMA)");
+        }
+        {
+            const float *xp = x.p, *be = w.scam_beta, *ga = w.scam_gamma;
+            float* op = out.p;
+            push_other(OP_OTHER, [=](hipStream_t s) { launch_scam_epilogue(xp, F, be, ga, op, Bp, H, W, c, s); });
+            name("epilogue(scale + nearest up + residual)");
+        }
+        if (reuse) {
+            pl->release(xs2);
+            pl->release(qv);
+            pl->release(F);
+        }
         return out;
     }
 
@@ -675,7 +725,18 @@ struct Builder {
 
 // ConditionalNAFNet.forward — DenoisingNAFNet_arch.py:149-187
 void build_naf_plan(irsde_engine* e, Plan* pl, Builder& b, int P) {
-    const int B = pl->B;
+    const bool stereo = naf_stereo(e);
+    const int B = stereo ? 2 * pl->B : pl->B;   // stereo: the network runs on the 2B views of B pairs
+    // NAFBlock (stereo: + fusion = SCAM; taps <path>.fusion.in = the SCAM input, <path> = the block output as in the reference)
+    auto block = [&](const NafBlockW& blk, const Tensor& in, const std::string& path) {
+        Tensor y = b.nafblock(blk, in);
+        if (!stereo) return y;
+        b.tap(path + ".fusion.in", y);
+        Tensor z = b.scam(blk, y);
+        b.tfree(y);
+        b.tap(path, z);
+        return z;
+    };
     Tensor x;
     {   // intro 3x3 (+bias) as 3 row taps over the zero-bordered NHWC input (border 3: first tap row/col = +2)
         ConvParams p;
@@ -687,7 +748,7 @@ void build_naf_plan(irsde_engine* e, Plan* pl, Builder& b, int P) {
         x = b.talloc(B, pl->Hp, pl->Wp, p.Cout);
         p.out = x.p; p.out_stride = p.Cout;
         b.push_conv(p);
-        const double real = 2.0 * (double)B * pl->Hp * pl->Wp * p.Cout * 9.0 * (2.0 * e->cfg.in_nc);
+        const double real = 2.0 * (double)B * pl->Hp * pl->Wp * p.Cout * 9.0 * (2.0 * e->naf_ic);
         pl->conv_flops += real - pl->net_ops.back().flops;
         pl->net_ops.back().flops = real;
     }
@@ -702,8 +763,8 @@ void build_naf_plan(irsde_engine* e, Plan* pl, Builder& b, int P) {
             if (!(intro_skip && x.p == intro.p)) b.tfree(x);
             x = y;
         } else
-        for (auto& blk : e->naf_enc[i]) {
-            Tensor y = b.nafblock(blk, x);
+        for (size_t j = 0; j < e->naf_enc[i].size(); ++j) {
+            Tensor y = block(e->naf_enc[i][j], x, "encoders." + std::to_string(i) + "." + std::to_string(j));
             if (!(intro_skip && x.p == intro.p)) b.tfree(x);
             x = y;
         }
@@ -719,8 +780,8 @@ void build_naf_plan(irsde_engine* e, Plan* pl, Builder& b, int P) {
         b.tfree(x);
         x = y;
     } else
-    for (auto& blk : e->naf_mid) {
-        Tensor y = b.nafblock(blk, x);
+    for (size_t j = 0; j < e->naf_mid.size(); ++j) {
+        Tensor y = block(e->naf_mid[j], x, "middle_blks." + std::to_string(j));
         b.tfree(x);
         x = y;
     }
@@ -739,8 +800,8 @@ void build_naf_plan(irsde_engine* e, Plan* pl, Builder& b, int P) {
             b.tfree(x);
             x = z;
         } else
-        for (auto& blk : e->naf_dec[i]) {
-            Tensor z = b.nafblock(blk, x);
+        for (size_t j = 0; j < e->naf_dec[i].size(); ++j) {
+            Tensor z = block(e->naf_dec[i][j], x, "decoders." + std::to_string(i) + "." + std::to_string(j));
             b.tfree(x);
             x = z;
         }
@@ -757,9 +818,18 @@ void build_naf_plan(irsde_engine* e, Plan* pl, Builder& b, int P) {
         x = y;
     }
     Builder::ConvOpts oe;
-    oe.pad = 1; oe.out_stride = pl->pred_stride;
+    oe.pad = 1; oe.out_stride = stereo ? (e->naf_ic + 3) & ~3 : pl->pred_stride;
     Tensor pr = b.conv_naf(e->naf_ending, x, oe);
     b.tfree(x);
+    if (stereo) {   // view v of pair b -> channels [v ic, (v + 1) ic) of the pair's eps_hat (x_l, x_r = x.chunk(2, 0); cat(dim = 1))
+        float* pred = pl->alloc((size_t)pl->B * pl->Hp * pl->Wp * pl->pred_stride, false);
+        const float* src = pr.p;
+        const int Bp = pl->B, ic = e->naf_ic, Hp = pl->Hp, Wp = pl->Wp, is = oe.out_stride, os = pl->pred_stride;
+        b.push_other(OP_OTHER, [=](hipStream_t s) { launch_stereo_pack_pred(src, pred, Bp, ic, Hp, Wp, is, os, s); });
+        pl->net_ops.back().desc = "stereo_pack_pred";
+        pl->pred = pred;
+        return;
+    }
     pl->pred = pr.p;
 }
 
@@ -775,7 +845,7 @@ int forced_chain_groups() { return g_force_chain_groups.load(std::memory_order_r
 static std::atomic<int> g_force_subbatches{0};
 void set_force_subbatches(int n) { g_force_subbatches.store(n, std::memory_order_relaxed); }
 int naf_subbatches(const irsde_engine* e, int B, int H, int W) {
-    if (e->arch == 2 || (e->cfg.flags & (IRSDE_FLAG_NAIVE_CONV | IRSDE_FLAG_KEEP_ACTIVATIONS))) return 1;
+    if (e->arch == 2 || naf_stereo(e) || (e->cfg.flags & (IRSDE_FLAG_NAIVE_CONV | IRSDE_FLAG_KEEP_ACTIVATIONS))) return 1;
     int n = g_force_subbatches.load(std::memory_order_relaxed);
     if (n <= 0) {
         static const int env = tuning_env_int("IRSDE_SUBBATCHES", 0);
@@ -837,7 +907,8 @@ Plan* get_plan(irsde_engine* e, int B, int H, int W, bool per_sample_film, int s
 }
 
 static Plan* build_plan(irsde_engine* e, int B, int H, int W, bool per_sample_film, int slot, int b0) {
-    ensure_film_cur(e, per_sample_film ? b0 + B : 1);
+    const bool stereo = naf_stereo(e);
+    ensure_film_cur(e, per_sample_film ? (stereo ? 2 : 1) * (b0 + B) : 1);   // stereo: rows of views v B + b (both rows of pair b hold its time)
     if (naf_lens(e)) {
         if (e->cam_set < b0 + B) throw HipError("latent-bokeh ConditionalNAFNet: irsde_set_lens_info must cover the batch first");
         if (e->cam_rows < b0 + B) throw HipError("internal: lens table smaller than the batch");
@@ -867,8 +938,8 @@ static Plan* build_plan(irsde_engine* e, int B, int H, int W, bool per_sample_fi
     pl->xin = pl->alloc(img, false);
     pl->cin = pl->alloc(img, false);
     const bool uncond = e->arch == 0 && (e->cfg.flags & IRSDE_FLAG_UNCOND_FULLATTN) != 0;
-    const int P = ((uncond ? 1 : 2) * in_nc + 3) & ~3;
-    const size_t x0n = (size_t)B * (pl->Hp + 6) * (pl->Wp + 6) * P + 64;
+    const int P = ((uncond ? 1 : 2) * (stereo ? e->naf_ic : in_nc) + 3) & ~3;
+    const size_t x0n = (size_t)(stereo ? 2 * B : B) * (pl->Hp + 6) * (pl->Wp + 6) * P + 64;
     pl->x0 = pl->alloc(x0n, false);
     IRSDE_HIP_CHECK(hipMemset(pl->x0, 0, x0n * sizeof(float)));
 
@@ -879,6 +950,10 @@ static Plan* build_plan(irsde_engine* e, int B, int H, int W, bool per_sample_fi
         float* x0 = pl->x0;
         const int Hp = pl->Hp, Wp = pl->Wp;
         const int reflect = e->arch == 1 ? 0 : 1;  // NAFNet zero-pads (DenoisingNAFNet_arch.py:189-194)
+        if (stereo) {   // stereo-sr forward :203-212: views prepared as cat(x_v - cond_v, cond_v) and stacked on the batch axis
+            const int ic = e->naf_ic;
+            b.push_other(OP_OTHER, [=](hipStream_t s) { launch_stereo_prep(xi, ci, x0, B, ic, P, H, W, Hp, Wp, s); });
+        } else
         b.push_other(OP_OTHER, [=](hipStream_t s) { launch_prep_input(xi, ci, x0, B, in_nc, H, W, Hp, Wp, s, reflect); });
     }
     if (e->arch == 1) {

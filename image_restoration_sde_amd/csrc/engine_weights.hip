@@ -217,9 +217,20 @@ void inv_nafblock(irsde_engine* e, const std::string& p, int c) {
     add_w(e, p + "norm2.g", {1, c, 1, 1});
     add_w(e, p + "beta", {1, c, 1, 1});
     add_w(e, p + "gamma", {1, c, 1, 1});
+    if (naf_stereo(e)) {   // SCAM(c) (stereo-sr DenoisingNAFNet_arch.py:19-31)
+        const std::string f = p + "fusion.";
+        add_w(e, f + "norm_l.g", {1, c, 1, 1});
+        add_w(e, f + "norm_r.g", {1, c, 1, 1});
+        for (const char* pr : {"l_proj1.", "r_proj1.", "l_proj2.", "r_proj2."}) {
+            add_w(e, f + pr + "weight", {c, c, 1, 1});
+            add_w(e, f + pr + "bias", {c});
+        }
+        add_w(e, f + "beta", {1, c, 1, 1});
+        add_w(e, f + "gamma", {1, c, 1, 1});
+    }
 }
 void build_inventory_naf(irsde_engine* e) {
-    const int width = e->cfg.nf, ic = e->cfg.in_nc, td = e->time_dim;
+    const int width = e->cfg.nf, ic = e->naf_ic, td = e->time_dim;
     // latent-bokeh keeps SinusoidalPosEmb outside the Sequential: indices 0 / 2 instead of 1 / 3 (:103-108)
     const std::string t1 = naf_lens(e) ? "time_mlp.0." : "time_mlp.1.", t3 = naf_lens(e) ? "time_mlp.2." : "time_mlp.3.";
     add_w(e, t1 + "weight", {td * 2, width});
@@ -309,6 +320,23 @@ NafBlockW pack_nafblock(irsde_engine* e, const std::string& p, int c) {
     if (naf_lens(e)) {
         b.cam_w = e->upload(need(e, p + "cam_mlp.1.weight").data);
         b.cam_b = e->upload(need(e, p + "cam_mlp.1.bias").data);
+    }
+    if (naf_stereo(e)) {
+        const std::string f = p + "fusion.";
+        b.scam_gl = e->upload(need(e, f + "norm_l.g").data);
+        b.scam_gr = e->upload(need(e, f + "norm_r.g").data);
+        for (int v = 0; v < 2; ++v) {
+            const std::string s1 = f + (v ? "r_proj1." : "l_proj1."), s2 = f + (v ? "r_proj2." : "l_proj2.");
+            std::vector<float> w, bias;
+            scam_pack_proj(need(e, s1 + "weight").data.data(), need(e, s1 + "bias").data.data(), need(e, s2 + "weight").data.data(),
+                           need(e, s2 + "bias").data.data(), c, w, bias);
+            ConvW& cw = v ? b.scam_r : b.scam_l;
+            cw.w = e->upload(w);
+            cw.bias = e->upload(bias);
+            cw.Cout = cw.Cin = 2 * c;
+        }
+        b.scam_beta = e->upload(need(e, f + "beta").data);
+        b.scam_gamma = e->upload(need(e, f + "gamma").data);
     }
     return b;
 }
@@ -468,7 +496,7 @@ void finalize_naf(irsde_engine* e) {
     e->naf_chain_enc.assign(e->naf_enc.size(), NafChainW());
     e->naf_chain_dec.assign(e->naf_dec.size(), NafChainW());
     e->naf_chain_mid = NafChainW();
-    if ((e->cfg.flags & IRSDE_FLAG_FP16) && !(e->cfg.flags & (IRSDE_FLAG_NO_NAF_CHAIN | IRSDE_FLAG_NAIVE_CONV))) {
+    if ((e->cfg.flags & IRSDE_FLAG_FP16) && !(e->cfg.flags & (IRSDE_FLAG_NO_NAF_CHAIN | IRSDE_FLAG_NAIVE_CONV)) && !naf_stereo(e)) {
         auto names = [](const std::string& base, size_t n) {
             std::vector<std::string> v;
             for (size_t j = 0; j < n; ++j) v.push_back(base + std::to_string(j) + ".");

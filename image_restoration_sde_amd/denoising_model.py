@@ -18,10 +18,16 @@ from . import unet as _unet
 from . import nafnet as _nafnet
 
 
-def define_G(opt):
-    """networks.define_G (deraining/models/networks.py:10-15): class looked up by name."""
+def define_G(opt, task="deraining"):
+    """networks.define_G (deraining/models/networks.py:10-15): class looked up by name (task "stereo-sr": the stereo
+    ConditionalNAFNet with SCAM, stereo-sr/models/modules/DenoisingNAFNet_arch.py)."""
     opt_net = opt["network_G"]
     name = opt_net["which_model_G"]
+    if task == "stereo-sr":
+        from . import stereo_sr
+        if name != "ConditionalNAFNet":
+            raise NotImplementedError("stereo-sr: only ConditionalNAFNet (with SCAM) is provided, not %s" % name)
+        return stereo_sr.ConditionalNAFNet(**opt_net["setting"])
     cls = getattr(_nafnet, name, None) or getattr(_unet, name)
     return cls(**opt_net["setting"])
 
@@ -34,10 +40,15 @@ def create_model(opt, task="deraining"):
         raise NotImplementedError("Model [{:s}] not recognized.".format(opt["model"]))
     if task in ("deblurring", "deshadow", "inpainting", "sisr"):
         return ReverseSDEDenoisingModel(opt)
+    if task == "stereo-sr":
+        from .stereo_sr import StereoDenoisingModel
+        return StereoDenoisingModel(opt)
     return DenoisingModel(opt)
 
 
 class DenoisingModel:
+    task = "deraining"   # network lookup of define_G
+
     def __init__(self, opt):
         self.opt = opt
         # base_model.py:12: "cuda" whenever gpu_ids is given; this implementation has no CPU path at all
@@ -45,7 +56,7 @@ class DenoisingModel:
         self.is_train = bool(opt.get("is_train", False))
         if self.is_train:
             raise NotImplementedError("training is out of scope of the MI355X sampler (SURVEY.md §2)")
-        self.model = define_G(opt).to(self.device)
+        self.model = define_G(opt, self.task).to(self.device)
         self.load()
 
     # ---- denoising_model.py:121-125 ----

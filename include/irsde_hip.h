@@ -32,6 +32,7 @@
  *   107  the per-image NAFBlock chain of the fp16 ConditionalNAFNet runs on 2 / 4 work-groups per image where they fit the compute units (results equal
  *        to the one-group kernel's: same operations in the same order); a split launch whose groups were not co-resident fails the NEXT irsde_sample
  *        call on the engine instead of hanging the GPU.  Debug header: irsde_debug_force_chain_groups; irsde_bench_naf_chain variants 22 / 24.
+ *        Additive, same version: IRSDE_FLAG_NAF_STEREO (the stereo-sr ConditionalNAFNet with SCAM); debug header: irsde_debug_scam.
  */
 #ifndef IRSDE_HIP_H
 #define IRSDE_HIP_H
@@ -122,6 +123,14 @@ enum {
                                         output before the depthwise conv, the depthwise taps, the pooled SCA mean, the SCA 1x1 conv's operands and
                                         its output (the scale vector), and the product x * sca(x) — formed in fp16 from the fp16 gated tensor on its
                                         way into conv3, i.e. that operand is rounded twice */
+    IRSDE_FLAG_NAF_STEREO = 65536,   /* irsde_create_nafnet only: the ConditionalNAFNet of stereo-sr (codes/config/stereo-sr/models/modules/
+                                        DenoisingNAFNet_arch.py): every NAFBlock is followed by fusion = SCAM(c), a cross-view attention per row of
+                                        the quarter-downsampled map (csrc/scam.hip).  xt / cond / out / sampler state are [B][2 img_channel][H][W]
+                                        stereo pairs (channels [0, img_channel) the left view); the network runs on the 2B views
+                                        [L_0..L_{B-1}, R_0..R_{B-1}].  fp32 and IRSDE_FLAG_FP16 (the SCAM projections in fp16, downsample /
+                                        LayerNorm / softmax / attention products / epilogue fp32); the other operand modes and IRSDE_FLAG_NAF_LENS /
+                                        _NAF_INTRO_SKIP are refused.  No NAFBlock chain, no concurrent sub-batches.  The padded size must leave
+                                        >= 4 rows and columns at the deepest level (the reference's interpolate fails below): IRSDE_ERR_INVALID */
     IRSDE_FLAG_NO_WINOGRAD_F43 = 8   /* Winograd F(2x2,3x3) only (>= 256 channels); default also uses F(4x4,3x3) from 128
                                         channels up where H, W are multiples of 4 */
 };

@@ -68,6 +68,14 @@ int irsde_debug_force_subbatches(int n);
  * Plans already built keep their choice: use a fresh engine (or another batch shape) per setting. */
 int irsde_debug_force_chain_groups(int g);
 
+/* Kernel-level test hook: ONE SCAM of the stereo-sr NAFBlock (csrc/scam.hip + the projection GEMM on the implicit-GEMM kernel, the engine's
+ * fp32 path).  x / out: device NHWC [2 B_pairs][H][W][C] (views stacked [L_0..L_{B-1}, R_0..R_{B-1}] as inside the reference network);
+ * every weight is a HOST pointer in reference layout: norm_*_g [C], *_proj*_w [C][C] (1x1), *_proj*_b [C], beta / gamma [C].
+ * C a multiple of 32 in [32, 1024], H and W >= 4, W / 4 <= 512.  Synchronises `stream`. */
+int irsde_debug_scam(const float* x, int B_pairs, int H, int W, int C, const float* norm_l_g, const float* norm_r_g, const float* l_proj1_w,
+                     const float* l_proj1_b, const float* r_proj1_w, const float* r_proj1_b, const float* l_proj2_w, const float* l_proj2_b,
+                     const float* r_proj2_w, const float* r_proj2_b, const float* beta, const float* gamma, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
