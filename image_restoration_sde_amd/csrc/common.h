@@ -157,13 +157,12 @@ bool wino_fused_eligible(const ConvParams& p);
 void wino_fused_pack_weights(const float* U, int Cout, int Cin, float* Uf);  // host: U[36][Cout][Cin] -> fragment order
 void launch_wino_fused(const ConvParams& p, const float* Uf, hipStream_t s, unsigned long long* dbg = nullptr, int dflags = 0);
 int wino_fused_num_blocks(const ConvParams& p);
-// r03: 16 tiles x 64 couts per block (Cout and Cin multiples of 64); its own weight fragment order
+// 16 tiles x 64 couts per work item (Cout and Cin multiples of 64), one persistent block per CU; its own weight fragment order
 bool wino_fused64_eligible(const ConvParams& p);
 void wino_fused64_pack_weights(const float* U, int Cout, int Cin, float* Uf);
 void launch_wino_fused64(const ConvParams& p, const float* Uf, hipStream_t s, int variant = 0);
-void wino_fused64_set_debug(unsigned long long* buf);   // stamp buffer of launch variant 25 (irsde_bench_conv 435)
-void wino_fused64_set_opt(int opt);                     // OPT value of the tuning twins (launch variants 26 / 27; irsde_bench_conv 436 / 437)
-// the fp16-pair twin (variant 4): V is split as V / 16, the weights as scale * U (scale a power of two), p.pair_scale undoes both
+void wino_fused64_set_debug(unsigned long long* buf);   // stamp buffer of launch variants 25 / 28 / 29 (irsde_bench_conv 435, 2001, 2002)
+// the fp16-pair kernel (variant 4): V is split as V / 16, the weights as scale * U (scale a power of two), p.pair_scale undoes both
 constexpr float kWinoFused64PairVScale = 0.0625f;
 void launch_wino_fused64_split_weights(const float* Uf, unsigned short* out, size_t nfloats, float scale, hipStream_t s);
 int wino_fused64_num_blocks(const ConvParams& p);
@@ -175,7 +174,6 @@ bool wino_fused64t_eligible(const ConvParams& p);
 long long wino_fused64t_num_items(const ConvParams& p);
 void launch_wino_fused64t(const ConvParams& p, const float* Uf, hipStream_t s, int variant = 0);
 void wino_fused64t_set_debug(unsigned long long* buf);   // stamp buffer of launch variant 5
-void wino_fused64t_set_skew(int cycles);                 // tuning: start skew per phase class
 void wino_fused_t_global_init();
 // fused NAFBlock chain (naf_chain.hip): consecutive 512-channel NAFBlocks on an 8 x 8 feature map, one work-group per image
 void naf_chain_global_init();

@@ -75,6 +75,20 @@ struct VariantScope {
     ~VariantScope() { conv_set_variant(0); }
 };
 
+// The selector codes irsde_debug_conv / irsde_bench_conv know (see their branches): any other code is refused, never run as the production dispatch.
+bool code_in(const std::initializer_list<int>& codes, int c) { return std::find(codes.begin(), codes.end(), c) != codes.end(); }
+bool debug_conv_code_known(int c) {
+    return code_in({0, 1, 2, 3, 4, 5, 12, 13, 22, 23, 33, 34, 35, 36, 37, 42, 43, 44, 45, 46, 47, 55, 56, 62, 63, 204, 260, 261, 262, 263}, c) ||
+           code_in({100, 103, 105, 106, 107, 150, 160, 161, 162, 163, 165, 166, 167, 170, 171, 172, 173}, c);   // 100 + a launch_conv tuning variant
+}
+bool bench_conv_variant_known(int v) {
+    return code_in({0, 3, 5, 6, 7, 50, 60, 61, 62, 63, 64, 65, 66, 67, 70, 71, 72, 73}, v) ||   // launch_conv and its tuning variants
+           code_in({80, 81, 82, 412, 413, 421, 422, 423, 430, 431, 432, 434, 435, 460, 461, 462, 465, 467, 468, 469, 480, 481, 482}, v) ||
+           code_in({2001, 2002, 2004, 4650, 4651, 4652, 4653}, v) ||
+           (v >= 83 && v <= 82 + 255) ||   // the 32-cout fused kernel with tuning-aid flags v - 82
+           (v >= 472 && v <= 476);         // the pair GEMM's ablation twins (launch_gemm_split_pairs refuses the ones it lacks)
+}
+
 // IRSDE_FLAG_FP16 = the 16-bit operand mode (IRSDE_FLAG_BF16's kernels, plans and weight copies) with IEEE fp16 rounding
 void apply_fp16_flag(irsde_engine* e) {
     if (!(e->cfg.flags & IRSDE_FLAG_FP16)) return;
@@ -649,6 +663,7 @@ int irsde_debug_conv(const float* in0, int C0, const float* in1, int C1, int B, 
                      int splits, void* stream) {
     return guard([&] {
         if (!in0 || !w_oihw || !out) throw HipError("null argument");
+        if (!debug_conv_code_known(naive)) throw HipError("debug_conv: unknown selector code " + std::to_string(naive));
         hipStream_t s = reinterpret_cast<hipStream_t>(stream);
         conv_global_init();
         const int Cin = C0 + C1;
@@ -727,7 +742,7 @@ int irsde_debug_conv(const float* in0, int C0, const float* in1, int C1, int B, 
             launch_wino_output(sp.out, s);
             IRSDE_HIP_CHECK(hipStreamSynchronize(s));
             (void)hipFree(dU); (void)hipFree(dUs); (void)hipFree(dVs); (void)hipFree(dM);
-        } else if (naive == 35 || naive == 37 || naive == 39 || naive == 56 || naive == 58 || naive == 61) {  // the 64-cout fused Winograd kernel on fp16 hi + lo operand pairs (IRSDE_FLAG_SPLIT_F16X2's big-feature-map path)
+        } else if (naive == 35 || naive == 37 || naive == 56) {  // the 64-cout fused Winograd kernel on fp16 hi + lo operand pairs (IRSDE_FLAG_SPLIT_F16X2's big-feature-map path)
             if (!wino_fused64_eligible(p)) throw HipError("debug_conv: shape not eligible for the fused Winograd kernel");
             std::vector<float> U((size_t)36 * Cout * Cin), Uf((size_t)36 * Cout * Cin);
             wino_transform_weights(pk.data(), Cout, Cin, U.data(), 4);
@@ -742,10 +757,10 @@ int irsde_debug_conv(const float* in0, int C0, const float* in1, int C1, int B, 
             IRSDE_HIP_CHECK(hipMemcpy(dUf, Uf.data(), Uf.size() * 4, hipMemcpyHostToDevice));
             launch_wino_fused64_split_weights(dUf, dUp, Uf.size(), usc, s);
             p.pair_scale = 1.0f / (kWinoFused64PairVScale * usc);
-            launch_wino_fused64(p, reinterpret_cast<const float*>(dUp), s, naive == 61 ? 52 : naive == 58 ? 44 : naive == 56 ? 24 : naive == 39 ? 9 : naive == 37 ? 4 + 64 : 4);   // 37: + cout block by XCD where legal; 39: r03's one-block-per-tile-group kernel
+            launch_wino_fused64(p, reinterpret_cast<const float*>(dUp), s, naive == 56 ? 24 : naive == 37 ? 4 + 64 : 4);   // 37: + cout block by XCD where legal
             IRSDE_HIP_CHECK(hipStreamSynchronize(s));
             (void)hipFree(dUf); (void)hipFree(dUp);
-        } else if (naive == 33 || naive == 34 || naive == 36 || naive == 38 || (naive >= 50 && naive <= 55) || naive == 57 || naive == 60 || naive == 62 || naive == 63) {  // fused Winograd F(4x4,3x3) kernels (wino_fused.hip): 33 = 32 couts per block, 34 = 64
+        } else if (naive == 33 || naive == 34 || naive == 36 || naive == 55 || naive == 62 || naive == 63) {  // fused Winograd F(4x4,3x3) kernels (wino_fused.hip): 33 = 32 couts per block, 34 = 64
             if (naive == 33 ? !wino_fused_eligible(p) : !wino_fused64_eligible(p)) throw HipError("debug_conv: shape not eligible for the fused Winograd kernel");
             std::vector<float> U((size_t)36 * Cout * Cin), Uf((size_t)36 * Cout * Cin);
             wino_transform_weights(pk.data(), Cout, Cin, U.data(), 4);
@@ -759,13 +774,7 @@ int irsde_debug_conv(const float* in0, int C0, const float* in1, int C1, int B, 
                 launch_wino_fused64t(p, dUf, s, naive == 63 ? 64 : 0);
             } else
             if (naive == 33) launch_wino_fused(p, dUf, s);
-            else if (naive == 60) launch_wino_fused64(p, dUf, s, 48);   // r04's single-stream kernel (61: its fp16-pair twin)
-            else if (naive == 55 || naive == 57) launch_wino_fused64(p, dUf, s, naive == 55 ? 20 : 40);   // the register-patch persistent kernel at fixed grid sizes (it IS production: launch_wino_fused64 defaults to persist = 1)
-            else if (naive >= 50) {   // r04 tuning twins of the persistent kernel: 50 .. 54 = OPT 15 / 1 / 2 / 4 / 8
-                static const int opts[5] = {15, 1, 2, 4, 8};
-                wino_fused64_set_opt(opts[naive - 50]);
-                launch_wino_fused64(p, dUf, s, 26);
-            } else launch_wino_fused64(p, dUf, s, naive == 38 ? 10 : naive == 36 ? 64 : 0);   // 36: + cout block by XCD where legal; 38: r03's one-block-per-tile-group kernel
+            else launch_wino_fused64(p, dUf, s, naive == 55 ? 20 : naive == 36 ? 64 : 0);   // 36: + cout block by XCD where legal; 55: the production variant by number
             IRSDE_HIP_CHECK(hipStreamSynchronize(s));
             (void)hipFree(dUf);
         } else if (wino_tile) {  // naive / 10: 0 = production dispatch, 1 / 2 = force the batch-loop GEMM kernel (all / 2 components per block)
@@ -802,7 +811,7 @@ int irsde_debug_conv(const float* in0, int C0, const float* in1, int C1, int B, 
             (void)hipFree(dwp);
         } else if (naive == 1) {
             launch_conv_naive(p, s);
-        } else {
+        } else {   // the direct kernels: 0 production dispatch, 4 / 5 bf16 / fp16 operands, 204 / 26x bf16 activation storage, 100 + v launch_conv tuning variant v
             unsigned short *dbf = nullptr, *a0 = nullptr, *a1 = nullptr, *ar = nullptr, *ao = nullptr;
             const bool act = naive == 204 || (naive >= 260 && naive <= 263);  // + bf16 activation storage (IRSDE_FLAG_BF16_ACT)
             if (naive == 4 || (naive >= 160 && naive <= 163) || act) {  // bf16-MFMA mode (variants 60 / 61: force the 256 / 128 tile; 64 / 65: the 512- / 256-pixel halo kernel)
@@ -908,11 +917,13 @@ int irsde_debug_force_subbatches(int n) {
 int irsde_bench_naf_chain(int variant, int nblocks, int B, int iters, double* ms_out) {
     return guard([&] {
         if (!ms_out || nblocks < 1 || nblocks > 64 || B < 1 || iters < 1) throw HipError("bench_naf_chain: bad argument");
-        const int G = variant == 22 ? 2 : (variant == 24 || variant == 25 || variant == 26) ? 4 : 1;   // (26, PROBES build: 24 with one group per image missing — must report the spin timeout)   // (25, PROBES build: 24 + its cycle stamps)   // r06: 22 / 24 = the kernel with 2 / 4 work-groups per image
+        // 0 / 1 production; 11 (PROBES build) its cycle stamps; r06: 22 / 24 = the kernel with 2 / 4 work-groups per image, 25 (PROBES build) 24 + its cycle
+        // stamps, 26 (PROBES build) 24 with one group per image missing — must report the spin timeout
+        const int G = variant == 22 ? 2 : (variant == 24 || variant == 25 || variant == 26) ? 4 : 1;
 #ifdef IRSDE_PROBES
-        if (variant != 0 && variant != 1 && variant != 2 && variant != 11 && G == 1) throw HipError("bench_naf_chain: bad variant");
+        if (variant != 0 && variant != 1 && variant != 11 && G == 1) throw HipError("bench_naf_chain: bad variant");
 #else
-        if (variant != 0 && variant != 1 && G == 1) throw HipError("bench_naf_chain: variants 2 / 11 are measurement twins (make PROBES=1)");   // (before anything is allocated)
+        if (variant != 0 && variant != 1 && G == 1) throw HipError("bench_naf_chain: variant 11 is a measurement twin (make PROBES=1)");   // (before anything is allocated)
 #endif
         conv_global_init();
         hipStream_t s;
@@ -1032,6 +1043,7 @@ int irsde_bench_conv(int variant, int B, int H, int W, int Cin, int Cout, int K,
                      double* ms_out) {
     return guard([&] {
         if (!ms_out || iters < 1) throw HipError("bad argument");
+        if (!bench_conv_variant_known(variant)) throw HipError("bench_conv: unknown variant " + std::to_string(variant));
         conv_global_init();
         hipStream_t s = nullptr;
         IRSDE_HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
@@ -1124,13 +1136,13 @@ int irsde_bench_conv(int variant, int B, int H, int W, int Cin, int Cout, int K,
         const bool split_v = variant == 412 || variant == 413 || variant == 422 || variant == 423;  // split-operand GEMMs: 41x whole three-launch layer, 42x the GEMM alone; x = planes
         unsigned short *dUs = nullptr, *dVs = nullptr;
         WinoSplitPlan sp{};
-        if (variant == 80 || variant == 81 || variant == 421 || split_v || (variant >= 83 && variant <= 82 + 255) || (variant >= 400 && variant <= 410) || (variant >= 430 && variant <= 435) || (variant >= 440 && variant <= 454) || (variant >= 460 && variant <= 469) || (variant >= 4610 && variant <= 4613) || (variant >= 4650 && variant <= 4653) || (variant >= 4700 && variant < 4800) || (variant >= 1000 && variant < 1064) || (variant >= 2000 && variant <= 2004) || (variant >= 2010 && variant <= 2012) || variant == 2020) {
+        if (variant == 80 || variant == 81 || variant == 421 || split_v || (variant >= 83 && variant <= 82 + 255) || (variant >= 430 && variant <= 469) || variant >= 2000) {
             if (K != 3 || stride != 1) throw HipError("bench_conv: Winograd variants need a 3x3 stride-1 layer");
             IRSDE_HIP_CHECK(hipMalloc(&dU, (size_t)36 * nw / 9 * 4));
             launch_fill_random(dU, (size_t)36 * nw / 9, 5, 1.0f / sqrtf((float)(9 * Cin)), s);
             if (variant != 81 && variant != 421 && !split_v && !wino_fused_eligible(p)) throw HipError("bench_conv: shape not eligible for the fused Winograd kernel");
             if (variant >= 400 && !wino_fused64_eligible(p)) throw HipError("bench_conv: shape not eligible for the 64-cout fused Winograd kernel");
-            if (variant == 404 || variant == 405 || variant == 434 || variant == 444 || variant == 452) {  // the fp16-pair twin: the random weights as hi / lo halves
+            if (variant == 434) {  // the fp16-pair kernel: the random weights as hi / lo halves
                 float* dUp = nullptr;
                 IRSDE_HIP_CHECK(hipMalloc(&dUp, (size_t)36 * nw / 9 * 4));
                 launch_wino_fused64_split_weights(dU, reinterpret_cast<unsigned short*>(dUp), (size_t)36 * nw / 9, 256.0f, s);
@@ -1236,12 +1248,9 @@ int irsde_bench_conv(int variant, int B, int H, int W, int Cin, int Cout, int K,
             (void)hipStreamDestroy(s);
             return;
         }
-        if (variant == 435 || (variant >= 2000 && variant <= 2004) || (variant >= 2010 && variant <= 2012) || variant == 2020) {  // the persistent fused Winograd kernel once with per-wave cycle stamps: prints the averaged budget
-            // 2000 + k: the stamp twins (k = 0 every r04 OPT bit, 1 no weight traffic, 2 no patch traffic, 3 patches from an L2-resident window, 4 = 435)
-            // 2010 + k: the halo kernel's stamp twins (k = 0 production, 1 no weight traffic, 2 no halo traffic)
-            const bool halo = variant >= 2010 && variant <= 2012;
-            const bool single = variant == 2020;   // the single-stream kernel: 4 waves per block, every wave both roles
-            const int stamp_variant = single ? 53 : halo ? 45 + (variant - 2010) : variant == 435 || variant == 2004 ? 25 : 27 + (variant - 2000);
+        if (variant == 435 || (variant >= 2001 && variant <= 2004)) {  // the persistent fused Winograd kernel once with per-wave cycle stamps: prints the averaged budget
+            // 2001 / 2002: the stamp twins without weight / patch traffic (2004 = 435)
+            const int stamp_variant = variant == 2001 ? 28 : variant == 2002 ? 29 : 25;
             const int nbp = 256;
             unsigned long long* dd = nullptr;
             IRSDE_HIP_CHECK(hipMalloc(&dd, (size_t)nbp * 64 * 8));
@@ -1262,42 +1271,6 @@ int irsde_bench_conv(int variant, int B, int H, int W, int Cin, int Cout, int K,
                     for (int k = 0; k < 5; ++k) acc[w >= 4][k] += (double)t[k];
                     nw[w >= 4]++;
                 }
-            if (single) {
-                const int nst = Cin / 32;
-                const double items = acc[0][4] / std::max(nw[0], 1);
-                const double chunks = items * nst;
-                printf("wino4_fused64s stamps B=%d %dx%d Cin=%d Cout=%d: %.1f items x %d chunks per block; shader cycles per wave (mean over %d waves)\n", B, p.Ho, p.Wo, Cin, Cout, items, nst, nw[0]);
-                printf("  kernel %.0f = K loop incl. transform slices %.0f (%.0f per chunk; MFMA floor 9216) + barrier wait %.0f (%.0f per chunk) + epilogue %.0f (%.0f per item)\n",
-                       acc[0][3] / nw[0], acc[0][0] / nw[0], acc[0][0] / nw[0] / chunks, acc[0][1] / nw[0], acc[0][1] / nw[0] / chunks, acc[0][2] / nw[0], acc[0][2] / nw[0] / items);
-            } else
-            if (halo) {   // per 16-channel step; producer columns: DMA issue, transform, barrier wait (both kinds of step), halo wait (off step)
-                double pa[6] = {0, 0, 0, 0, 0, 0};
-                int pn = 0;
-                for (int bi = 0; bi < nbp; ++bi)
-                    for (int w = 4; w < 8; ++w) {
-                        const unsigned long long* t = &hd[((size_t)bi * 8 + w) * 8];
-                        if (!t[3]) continue;
-                        for (int k = 0; k < 6; ++k) pa[k] += (double)t[k];
-                        pn++;
-                    }
-                const int nst = Cin / 16;
-                const double items = acc[0][4] / std::max(nw[0], 1);
-                const double steps = items * nst;
-                printf("wino4_fused64h stamps B=%d %dx%d Cin=%d Cout=%d: %.1f items x %d steps of 16 channels per block; shader cycles per wave (mean over %d + %d waves)\n", B, p.Ho,
-                       p.Wo, Cin, Cout, items, nst, nw[0], pn);
-                printf("  MFMA waves    : kernel %.0f = K-loop compute %.0f (%.0f per step; MFMA floor 4608) + barrier wait %.0f (%.0f per step) + epilogue %.0f (%.0f per item)\n",
-                       acc[0][3] / nw[0], acc[0][0] / nw[0], acc[0][0] / nw[0] / steps, acc[0][1] / nw[0], acc[0][1] / nw[0] / steps, acc[0][2] / nw[0], acc[0][2] / nw[0] / items);
-                printf("  producer waves: kernel %.0f = halo DMA issue %.0f (%.0f per DMA step) + transform %.0f (%.0f per own step) + halo wait in the off step %.0f (%.0f per off step) + barrier wait %.0f (%.0f per step)\n",
-                       pa[3] / pn, pa[0] / pn, pa[0] / pn / (steps / 2), pa[1] / pn, pa[1] / pn / (steps / 2), pa[5] / pn, pa[5] / pn / (steps / 2), pa[2] / pn, pa[2] / pn / steps);
-                fflush(stdout);
-                (void)hipFree(dd);
-                (void)hipFree(dU);
-                dU = nullptr;
-                *ms_out = 0.0;
-                (void)hipFree(din); (void)hipFree(dw); (void)hipFree(dout); (void)hipFree(dres); (void)hipFree(dfilm);
-                (void)hipStreamDestroy(s);
-                return;
-            }
             const int nchk = Cin / 32;
             const double items = acc[0][4] / std::max(nw[0], 1), chunks = acc[1][4] / std::max(nw[1], 1);
             printf("wino4_fused64p stamps B=%d %dx%d Cin=%d Cout=%d: %.1f items x %d chunks per block; shader cycles per wave (mean over %d + %d waves)\n", B, p.Ho, p.Wo,
@@ -1319,29 +1292,11 @@ int irsde_bench_conv(int variant, int B, int H, int W, int Cin, int Cout, int K,
         auto run = [&] {
             if (variant == 80) {
                 launch_wino_fused(p, dU, s);
-            } else if (variant >= 400 && variant <= 410) {  // 406 / 407 / 408: non-temporal epilogue traffic / + patch loads / no hint at all
-                 // 64-cout fused Winograd kernel: 400 production, 401 no weight traffic, 402 no patch traffic, 403 short U ring, 404 / 405 fp16 pairs (ring 12 / 18)
-                launch_wino_fused64(p, dU, s, variant - 400);
-            } else if (variant >= 4700 && variant < 4800) {  // r06 tuning: the two-tile-group kernel with a start skew of (variant - 4700) x 1000 cycles per phase class
-                wino_fused64t_set_skew((variant - 4700) * 1000);
-                launch_wino_fused64t(p, dU, s, 0);
-                wino_fused64t_set_skew(0);
-            } else if (variant == 4613) {   // the residual tile gathered into registers instead of through LDS (residual layers)
-                launch_wino_fused64t(p, dU, s, 16);
-            } else if (variant >= 4610 && variant <= 4612) {  // 8-byte twins of the two-tile-group kernel: 4610 residual loads, 4611 output stores, 4612 weight units
-                launch_wino_fused64t(p, dU, s, variant - 4601);
-            } else if (variant >= 466 && variant <= 469) {  // 466 no non-temporal hint; 467 / 468 / 469 measurement twins: no transform arithmetic / + no gathers / no gathers only
-                launch_wino_fused64t(p, dU, s, variant == 466 ? 4 : variant - 461);
-            } else if (variant >= 460 && variant <= 463) {  // r06 two-tile-group kernel: 460 production, 461 / 462 weight fragments / patch gathers read zeros, 463 three weight units in flight
+            } else if (variant >= 467 && variant <= 469) {  // measurement twins of the two-tile-group kernel: no transform arithmetic / + no gathers / no gathers only
+                launch_wino_fused64t(p, dU, s, variant - 461);
+            } else if (variant >= 460 && variant <= 462) {  // r06 two-tile-group kernel: 460 production, 461 / 462 weight fragments / patch gathers read zeros
                 launch_wino_fused64t(p, dU, s, variant - 460);
-            } else if (variant >= 448 && variant <= 454) {  // r04 single-stream kernel: 448 f32, 450 patch loads read zeros, 452 fp16 pairs; 449 / 451 / 454 measurement twins
-                launch_wino_fused64(p, dU, s, variant - 400);
-            } else if (variant >= 440 && variant <= 444) {  // r04 halo kernel: 440 production, 441 / 442 weight fragments / halo fetches read zeros, 444 fp16 pairs
-                launch_wino_fused64(p, dU, s, variant - 400);
-            } else if (variant >= 1000 && variant < 1064) {  // r04 tuning twins of the persistent kernel: OPT = variant - 1000 (see wino4_fused64p_kernel)
-                wino_fused64_set_opt(variant - 1000);
-                launch_wino_fused64(p, dU, s, 26);
-            } else if (variant >= 430 && variant <= 434) {  // r04 persistent kernel: 430 production, 431 / 432 weight fragments / patch loads read zeros, 433 no nt hint, 434 fp16 pairs
+            } else if (variant >= 430 && variant <= 434) {  // r04 persistent kernel: 430 production, 431 / 432 weight fragments / patch loads read zeros, 434 fp16 pairs
                 launch_wino_fused64(p, dU, s, variant - 410);
             } else if (variant >= 83 && variant <= 82 + 255) {  // tuning aids: dflags = variant - 82 (1 no patch traffic, 2 no weight traffic, 4 / 8 producer / MFMA waves at s_setprio 2)
                 launch_wino_fused(p, dU, s, nullptr, variant - 82);

@@ -152,7 +152,8 @@ __device__ __forceinline__ nc_h4 cvt4(const nc_f4 v) {
     return h;
 }
 
-// ---- the weight stream of one wave: ring[i] holds fragment (pos + i); slot i is refilled with fragment pos + 16 + i right after its last use ----
+// ---- the weight stream of one wave: ring[i] holds fragment (pos + i); slot i is refilled with fragment pos + NC_RING + i right after its last use ----
+constexpr int NC_RING = 8;   // weight fragments in flight per wave (x 4 registers)
 struct WStream {
     __amdgpu_buffer_rsrc_t rs;
     int lane_off;   // wave region + lane * 16 (bytes)
@@ -163,7 +164,7 @@ struct WStream {
 // 16 NT / NC_RING rounds of the fragment ring).  NPT: pixel tiles (4: the image; 1: the SCA matvec, every column carries the same vector).  SCALE: B fragments
 // are multiplied by the fp16 vector at sv (the SCA scale per input channel, DenoisingNAFNet_arch.py:68) on their way into the MFMA.
 // bsrc[c]: LDS address of this lane's B fragment of k steps ks with (ks & 3) == c (see the swizzle); + (ks >> 2) * 256, pixel tile stride 16 rows.
-template <int NT, int NPT, bool SCALE, int NC_RING>
+template <int NT, int NPT, bool SCALE>
 __device__ __forceinline__ void gemm_pass(nc_f4 (&acc)[NT][NPT], const char* const* bsrc, const char* sv, nc_f4 (&ring)[NC_RING], WStream& ws) {
     constexpr int KSU = NC_RING / NT;   // k steps per round of the ring (a multiple of 4)
     static_assert(KSU % 4 == 0 && 16 % KSU == 0, "ring rounds");
@@ -193,18 +194,15 @@ __device__ __forceinline__ void gemm_pass(nc_f4 (&acc)[NT][NPT], const char* con
     }
 }
 
-// NC_RING: weight fragments in flight per wave (x 4 registers).  XG: the fp32 residual stream lives in the output tensor (L2) instead of 64 registers —
-// every lane re-reads / updates exactly the elements it wrote itself — which frees the registers for a ring of 32 fragments (a whole GEMM pass):
-// with 64 work-groups streaming the same weights in lock-step nearly every line is a first touch for its XCD (MALL / HBM latency, not an L2 hit),
-// and a ring of 8 covers only ~0.5k cycles of it.
+// The fp32 residual stream lives in registers.  (r04 measured it in the output tensor (L2) with the freed registers spent on a ring of 16 / 32 weight
+// fragments: 1.4x / 1.55x slower, profiles/r04_naf_chain_bench_a.txt.)
 // STAMP (irsde_bench_naf_chain variant 11): per-wave cycle totals per phase into a.dbg[(block * 8 + wave) * 16 ..]: 0 norm1, 1 conv1 GEMM passes,
 // 2 depthwise conv + gate, 3 SCA pool barrier, 4 sca.1 GEMM, 5 conv3 GEMM + residual, 6 norm2, 7 conv4 GEMM + gate, 8 conv5 GEMM + residual, 9 barriers
 // behind sca / conv4, 15 whole kernel
 // G: work-groups per image (1: the r04 kernel, unchanged; 2 / 4: see the file header).  NTW = 4 / G 16-channel tiles per wave.
-template <int NC_RING, bool XG, bool STAMP = false, int G = 1>
+template <bool STAMP = false, int G = 1>
 __global__ __launch_bounds__(512, 2) void naf_chain_kernel(const NafChainArgs a) {
     static_assert(G == 1 || G == 2 || G == 4, "groups per image");
-    static_assert(G == 1 || !XG, "the split kernel keeps the residual stream in registers");
     constexpr int NTW = 4 / G;                 // 16-channel tiles per wave of a 512-wide tensor (gate pairs of a 1024-wide one)
     constexpr int NT3 = NTW >= 2 ? 2 : 1;      // weight tiles per k step of the 512 -> 512 passes (sca.1, conv3, conv5)
     constexpr int NP3 = NTW / NT3;             // ... and passes
@@ -290,21 +288,12 @@ __global__ __launch_bounds__(512, 2) void naf_chain_kernel(const NafChainArgs a)
     for (int i = 0; i < NC_RING; ++i) ring[i] = __builtin_bit_cast(nc_f4, __builtin_amdgcn_raw_buffer_load_b128(ws.rs, ws.lane_off, i * 1024, 0));
 
     // ---- residual stream: x[ct][pt] = channels cown + 16 ct + 4 q .. + 3 of pixel 16 pt + n ----
-    nc_f4 x[XG ? 1 : NTW][XG ? 1 : 4];
+    nc_f4 x[NTW][4];
     const float* xin = a.x + (size_t)b * NC_PX * NC_C;
-    float* const xg = a.out + (size_t)b * NC_PX * NC_C + cown + 4 * q + n * NC_C;   // + 16 ct + pt * 16 * NC_C
-    if constexpr (XG) {
 #pragma unroll
-        for (int ct = 0; ct < 4; ++ct)
+    for (int ct = 0; ct < NTW; ++ct)
 #pragma unroll
-            for (int pt = 0; pt < 4; ++pt)
-                *reinterpret_cast<nc_f4*>(xg + 16 * ct + pt * 16 * NC_C) = *reinterpret_cast<const nc_f4*>(xin + (16 * pt + n) * NC_C + 64 * wave + 16 * ct + 4 * q);
-    } else {
-#pragma unroll
-        for (int ct = 0; ct < NTW; ++ct)
-#pragma unroll
-            for (int pt = 0; pt < 4; ++pt) x[ct][pt] = *reinterpret_cast<const nc_f4*>(xin + (16 * pt + n) * NC_C + cown + 16 * ct + 4 * q);
-    }
+        for (int pt = 0; pt < 4; ++pt) x[ct][pt] = *reinterpret_cast<const nc_f4*>(xin + (16 * pt + n) * NC_C + cown + 16 * ct + 4 * q);
     // G > 1: the exchange tensors of the image through buffer descriptors (sc1 stores / loads)
     typedef unsigned nc_u4x __attribute__((ext_vector_type(4)));
     const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(a.out + (size_t)b * NC_PX * NC_C, 0, G > 1 ? NC_PX * NC_C * 4 : 0, 0x00020000);
@@ -358,10 +347,8 @@ __global__ __launch_bounds__(512, 2) void naf_chain_kernel(const NafChainArgs a)
             }
         }
         // (pp = index into the group's own pixel tiles; G = 1: pp = pt)
-        // XG: every pass re-reads the lane's 16 vectors from L2 instead of holding them (the ring of 32 fragments owns the registers)
         auto X = [&](const int ct, const int pp) -> nc_f4 {
             if constexpr (G > 1) return xf[ct][pp];
-            else if constexpr (XG) return *reinterpret_cast<const nc_f4*>(xg + 16 * ct + pp * 16 * NC_C);
             else return x[ct][pp];
         };
         float s[NPO];
@@ -517,7 +504,7 @@ __global__ __launch_bounds__(512, 2) void naf_chain_kernel(const NafChainArgs a)
                 tapb[hi] = *reinterpret_cast<const nc_u4*>(vec + NV_TAP + (cb + n) * 8 + 4);
             };
             dw_prefetch(0);
-            gemm_pass<2, 4, false, NC_RING>(acc, bsrcA, nullptr, ring, ws);
+            gemm_pass<2, 4, false>(acc, bsrcA, nullptr, ring, ws);
             NC_STAMP(1)
             dw_prefetch(1);
             __builtin_amdgcn_sched_barrier(0);
@@ -588,7 +575,7 @@ __global__ __launch_bounds__(512, 2) void naf_chain_kernel(const NafChainArgs a)
                 const int qg = grp * NQ + qq;   // quarter = k steps 4 qg .. 4 qg + 3
                 nc_f4 cur[4] = {nc_f4{0.f, 0.f, 0.f, 0.f}, nc_f4{0.f, 0.f, 0.f, 0.f}, nc_f4{0.f, 0.f, 0.f, 0.f}, nc_f4{0.f, 0.f, 0.f, 0.f}};
                 constexpr int KPR = NC_RING / 4;   // k steps (x 4 tiles) per round of the ring
-                static_assert(KPR == 2 || KPR == 4, "ring of 8 or 16 fragments");
+                static_assert(4 % KPR == 0, "whole rounds of the ring per quarter");
 #pragma unroll
                 for (int hf = 0; hf < 4 / KPR; ++hf) {
 #pragma unroll
@@ -647,20 +634,13 @@ __global__ __launch_bounds__(512, 2) void naf_chain_kernel(const NafChainArgs a)
                 b3v[t] = *reinterpret_cast<const nc_f4*>(vec + NV_B3 + chl + 16 * (NT3 * ps + t));
                 bev[t] = *reinterpret_cast<const nc_f4*>(vec + NV_BETA + chl + 16 * (NT3 * ps + t));
             }
-            gemm_pass<NT3, 4, true, NC_RING>(acc, bsrcB, lds + NC_OFF_S + 8 * q * 2, ring, ws);
+            gemm_pass<NT3, 4, true>(acc, bsrcB, lds + NC_OFF_S + 8 * q * 2, ring, ws);
 #pragma unroll
             for (int t = 0; t < NT3; ++t) {
                 const int ct = NT3 * ps + t;
                 const nc_f4 b3 = b3v[t], be = bev[t];
 #pragma unroll
-                for (int pt = 0; pt < 4; ++pt) {
-                    if constexpr (XG) {
-                        nc_f4* xp = reinterpret_cast<nc_f4*>(xg + 16 * ct + pt * 16 * NC_C);
-                        *xp = *xp + (acc[t][pt] + b3) * be;
-                    } else {
-                        x[ct][pt] = x[ct][pt] + (acc[t][pt] + b3) * be;
-                    }
-                }
+                for (int pt = 0; pt < 4; ++pt) x[ct][pt] = x[ct][pt] + (acc[t][pt] + b3) * be;
             }
         }
         NC_STAMP(5)
@@ -687,7 +667,7 @@ __global__ __launch_bounds__(512, 2) void naf_chain_kernel(const NafChainArgs a)
                 cs = *reinterpret_cast<const nc_f4*>(cam + ch);
                 cf = *reinterpret_cast<const nc_f4*>(cam + NC_C + ch);
             }
-            gemm_pass<2, 4, false, NC_RING>(acc, bsrcA, nullptr, ring, ws);
+            gemm_pass<2, 4, false>(acc, bsrcA, nullptr, ring, ws);
             cs = cs + 1.0f;
 #pragma unroll
             for (int pt = 0; pt < 4; ++pt) {
@@ -718,20 +698,13 @@ __global__ __launch_bounds__(512, 2) void naf_chain_kernel(const NafChainArgs a)
                 b5v[t] = *reinterpret_cast<const nc_f4*>(vec + NV_B5 + chl + 16 * (NT3 * ps + t));
                 gav[t] = *reinterpret_cast<const nc_f4*>(vec + NV_GAMMA + chl + 16 * (NT3 * ps + t));
             }
-            gemm_pass<NT3, 4, false, NC_RING>(acc, bsrcB, nullptr, ring, ws);
+            gemm_pass<NT3, 4, false>(acc, bsrcB, nullptr, ring, ws);
 #pragma unroll
             for (int t = 0; t < NT3; ++t) {
                 const int ct = NT3 * ps + t;
                 const nc_f4 b5 = b5v[t], ga = gav[t];
 #pragma unroll
-                for (int pt = 0; pt < 4; ++pt) {
-                    if constexpr (XG) {
-                        nc_f4* xp = reinterpret_cast<nc_f4*>(xg + 16 * ct + pt * 16 * NC_C);
-                        *xp = *xp + (acc[t][pt] + b5) * ga;
-                    } else {
-                        x[ct][pt] = x[ct][pt] + (acc[t][pt] + b5) * ga;
-                    }
-                }
+                for (int pt = 0; pt < 4; ++pt) x[ct][pt] = x[ct][pt] + (acc[t][pt] + b5) * ga;
             }
         }
         NC_STAMP(8)
@@ -742,7 +715,7 @@ __global__ __launch_bounds__(512, 2) void naf_chain_kernel(const NafChainArgs a)
         }
     }
     if constexpr (G > 1) nc_group_exit(ctr, G, tid);
-    if constexpr (!XG && G == 1) {
+    if constexpr (G == 1) {
         float* xout = a.out + (size_t)b * NC_PX * NC_C;
 #pragma unroll
         for (int ct = 0; ct < 4; ++ct)
@@ -771,18 +744,16 @@ static int g_nc_sabotage = 0;   // (PROBES build only reads it: irsde_bench_naf_
 void naf_chain_set_sabotage(int on) { g_nc_sabotage = on; }
 
 void naf_chain_global_init() {
-    IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(naf_chain_kernel<8, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(naf_chain_kernel<8, false, false, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(naf_chain_kernel<8, false, false, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(naf_chain_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(naf_chain_kernel<false, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(naf_chain_kernel<false, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
 #ifdef IRSDE_PROBES
-    IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(naf_chain_kernel<8, false, true, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(naf_chain_kernel<8, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(naf_chain_kernel<16, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(naf_chain_kernel<true, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(naf_chain_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
 #endif
 }
 
-// variant: 0 production (= 1); 1 residual stream in registers + ring of 8 weight fragments; 2 residual stream in L2 + ring of 16: measured 1.4x slower
-// (profiles/r04_naf_chain_bench_a.txt; the ring of 32 was 1.55x slower): kept as the measurement twin  (IRSDE_NAF_CHAIN_VARIANT under IRSDE_TUNING=1)
+// variant: 0 / 1 production; 11 (PROBES build) the cycle-stamp twin into the buffer of naf_chain_set_debug()
 void launch_naf_chain(const float* x, float* out, const unsigned short* w, const float* vecs, int nblocks, int B, const float* film, int film_bstride,
                       int film_off, const float* cam, int cam_bstride, int cam_off, hipStream_t s, int variant) {
     NafChainArgs a;
@@ -794,16 +765,12 @@ void launch_naf_chain(const float* x, float* out, const unsigned short* w, const
     const size_t wb = naf_chain_weight_halves(nblocks) * 2;
     if (wb >= 0x7fff0000ull) throw HipError("launch_naf_chain: weight stream too large for 32-bit buffer offsets");
     a.w_bytes = (unsigned)wb;
-    static const int env_variant = tuning_env_int("IRSDE_NAF_CHAIN_VARIANT", 0);
-    if (variant == 0) variant = env_variant ? env_variant : 1;
-    if (x == out && variant != 1) throw HipError("launch_naf_chain: in-place call needs the register variant");
     switch (variant) {
-        case 1: hipLaunchKernelGGL((naf_chain_kernel<8, false>), dim3((unsigned)B), dim3(512), NC_LDS_BYTES, s, a); break;
-#ifdef IRSDE_PROBES   // the cycle-stamp twin and the measured-slower residual-stream-in-L2 variant: measurement build only (make PROBES=1)
-        case 11: hipLaunchKernelGGL((naf_chain_kernel<8, false, true>), dim3((unsigned)B), dim3(512), NC_LDS_BYTES, s, a); break;
-        case 2: hipLaunchKernelGGL((naf_chain_kernel<16, true>), dim3((unsigned)B), dim3(512), NC_LDS_BYTES, s, a); break;
+        case 0: case 1: hipLaunchKernelGGL((naf_chain_kernel<false>), dim3((unsigned)B), dim3(512), NC_LDS_BYTES, s, a); break;
+#ifdef IRSDE_PROBES   // the cycle-stamp twin: measurement build only (make PROBES=1)
+        case 11: hipLaunchKernelGGL((naf_chain_kernel<true>), dim3((unsigned)B), dim3(512), NC_LDS_BYTES, s, a); break;
 #endif
-        default: throw HipError("launch_naf_chain: bad variant (11 / 2 are measurement variants: make PROBES=1)");
+        default: throw HipError("launch_naf_chain: bad variant (11 is a measurement variant: make PROBES=1)");
     }
     IRSDE_HIP_CHECK(hipGetLastError());
 }
@@ -911,13 +878,13 @@ void launch_naf_chain_split(const float* x, float* out, const unsigned short* wG
     const dim3 grid((unsigned)naf_chain_split_groups(B, G));
 #ifdef IRSDE_PROBES
     if (G == 4 && a.dbg) {
-        hipLaunchKernelGGL((naf_chain_kernel<8, false, true, 4>), grid, dim3(512), NC_LDS_BYTES, s, a);
+        hipLaunchKernelGGL((naf_chain_kernel<true, 4>), grid, dim3(512), NC_LDS_BYTES, s, a);
         IRSDE_HIP_CHECK(hipGetLastError());
         return;
     }
 #endif
-    if (G == 2) hipLaunchKernelGGL((naf_chain_kernel<8, false, false, 2>), grid, dim3(512), NC_LDS_BYTES, s, a);
-    else hipLaunchKernelGGL((naf_chain_kernel<8, false, false, 4>), grid, dim3(512), NC_LDS_BYTES, s, a);
+    if (G == 2) hipLaunchKernelGGL((naf_chain_kernel<false, 2>), grid, dim3(512), NC_LDS_BYTES, s, a);
+    else hipLaunchKernelGGL((naf_chain_kernel<false, 4>), grid, dim3(512), NC_LDS_BYTES, s, a);
     IRSDE_HIP_CHECK(hipGetLastError());
 }
 

@@ -53,18 +53,6 @@ __device__ __forceinline__ void swap32x6(float& a0, float& b0, float& a1, float&
         : "+v"(a0), "+v"(b0), "+v"(a1), "+v"(b1), "+v"(a2), "+v"(b2), "+v"(a3), "+v"(b3), "+v"(a4), "+v"(b4), "+v"(a5), "+v"(b5));
 }
 
-// 16 bytes per lane as one buffer_load_dwordx4 / buffer_store_dwordx4, or (SPLIT, measurement twins) as two 8-byte instructions
-template <bool SPLIT, int AUX>
-__device__ __forceinline__ floatx4 wt_load16(const __amdgpu_buffer_rsrc_t rs, const int voff, const int soff) {
-    if constexpr (SPLIT) {
-        const floatx2 a = __builtin_bit_cast(floatx2, __builtin_amdgcn_raw_buffer_load_b64(rs, voff, soff, AUX));
-        const floatx2 b = __builtin_bit_cast(floatx2, __builtin_amdgcn_raw_buffer_load_b64(rs, voff + 8, soff, AUX));
-        return floatx4{a.x, a.y, b.x, b.y};
-    } else {
-        return __builtin_bit_cast(floatx4, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, soff, AUX));
-    }
-}
-
 // First stage of the output transform of one work item by wave (cb, H), lane-local: u[i][sc] = sum_r A^T[i][r] M[r][3 H + sc] on the wave's three
 // component columns for both tile groups, then the partial terms of the second stage —
 //   H = 0 (columns 0 1 2): u0, s12 = u1 + u2, d12 = u1 - u2;   H = 1 (columns 3 4 5): s34 = u3 + u4, d34 = u3 - u4, u5   (index 3 i + k, i = output row)
@@ -102,11 +90,11 @@ __device__ __forceinline__ void wt_stage1(const floatx4 (&acc)[18][2], floatx4 (
 
 // Second stage + epilogue of the output rows 2 HALF, 2 HALF + 1 of tile group H by wave (cb, H): keep = this wave's partial terms, recv = the partner wave's.
 // Same expressions as wf64p_epilogue (wino_fused.hip): bit-identical outputs.
-template <int H, int HALF, bool NT, bool RES, bool SILU, bool SPLIT_ST = false>
+template <int H, int HALF, bool RES, bool SILU>
 __device__ __forceinline__ void wt_finish_rows(const ConvParams& p, const floatx4 (&keep)[12], const floatx4 (&recv)[12], const floatx4 (&rv)[2][4],
                                                const unsigned lane_off_out, const __amdgpu_buffer_rsrc_t rs_out, const floatx4 bias, const floatx4 fsc,
                                                const floatx4 fsh) {
-    constexpr int AUX = NT ? 2 : 0;
+    constexpr int AUX = 2;   // non-temporal
     const int orow = p.Wo * p.out_stride * 4, opix = p.out_stride * 4;
 #pragma unroll
     for (int ii = 0; ii < 2; ++ii) {
@@ -126,30 +114,27 @@ __device__ __forceinline__ void wt_finish_rows(const ConvParams& p, const floatx
             }
             if constexpr (RES) v = v + rv[ii][j];
             // (pixel offset in the VECTOR offset: see wf64p_epilogue — with an SGPR soffset hipcc pads no wait state behind a buffer_store_dwordx4)
-            if constexpr (SPLIT_ST) {
-                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(__attribute__((__vector_size__(2 * sizeof(unsigned)))) unsigned, floatx2{v.x, v.y}), rs_out,
-                                                      (int)(lane_off_out + (unsigned)(i * orow + j * opix)), 0, AUX);
-                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(__attribute__((__vector_size__(2 * sizeof(unsigned)))) unsigned, floatx2{v.z, v.w}), rs_out,
-                                                      (int)(lane_off_out + (unsigned)(i * orow + j * opix) + 8u), 0, AUX);
-            } else
             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((__vector_size__(4 * sizeof(unsigned)))) unsigned, v), rs_out,
                                                    (int)(lane_off_out + (unsigned)(i * orow + j * opix)), 0, AUX);
         }
     }
 }
 
-// NR: weight units in flight per wave (x 4 registers; 18 % NR == 0).  NOWT / NOPATCH: measurement twins (weight fragments / patch gathers read zeros without
-// memory traffic).  EPI: bit 0 SiLU, bit 1 residual.  STAMP: per-wave cycle totals into dbg[(block * 8 + wave) * 8 ..]: { K loops, barrier waits, epilogue +
-// (DBG, measurement twins: 1 no column pass, 2 no row pass / V writes, 4 no swaps, 8 no gathers inside the K loop — results are garbage;
-//  16 / 32 / 64: residual loads / output stores / weight units as two 8-byte instructions per lane instead of one 16-byte one; 256: the residual tile
-//  gathered into registers instead of through LDS — results unchanged)
-// first-chunk transform, whole kernel, items, first stage up to the exchange barrier, exchange (two barriers), second stage + stores }.
-template <int NR, bool NOWT, bool NOPATCH, bool NT, int EPI, bool STAMP = false, int DBG = 0>
+constexpr int WT_NR = 6;   // weight units in flight per wave (x 4 registers; 18 % WT_NR == 0)
+
+// NOWT / NOPATCH: measurement twins (weight fragments / patch gathers read zeros without memory traffic).  EPI: bit 0 SiLU, bit 1 residual.
+// STAMP: per-wave cycle totals into dbg[(block * 8 + wave) * 8 ..]: { K loops, barrier waits, epilogue + first-chunk transform, whole kernel, items,
+// first stage up to the exchange barrier, exchange (two barriers), second stage + stores }.
+// DBG, measurement twins (results are garbage): 1 no column pass, 2 no row pass / V writes, 4 no swaps, 8 no gathers inside the K loop, 128 output
+// stores / residual loads as 4 pixels x 256 contiguous bytes.
+// Residual loads and output stores carry the non-temporal hint.  (r06's rejected variants — three weight units in flight, no non-temporal hint, 8-byte
+// loads / stores, the residual tile gathered into registers, a start skew per phase class — were measured and not adopted: profiles/, git history.)
+template <bool NOWT, bool NOPATCH, int EPI, bool STAMP = false, int DBG = 0>
 __global__ __launch_bounds__(WT_NT, 2) void wino4_fused64t_kernel(const ConvParams p, const float* __restrict__ Uf, const int GX, const int GY, const int NB,
                                                                    const unsigned in0_bytes, const unsigned in1_bytes, const unsigned uf_bytes,
                                                                    const unsigned out_bytes, const unsigned res_bytes, const int xcd_nb, const int total,
-                                                                   unsigned long long* __restrict__ dbg, const int skew) {
-    static_assert(18 % NR == 0, "the ring must divide the 18 weight units of a chunk");
+                                                                   unsigned long long* __restrict__ dbg) {
+    static_assert(18 % WT_NR == 0, "the ring must divide the 18 weight units of a chunk");
     constexpr bool RES = (EPI & 2) != 0, SILU = (EPI & 1) != 0;
     unsigned long long st_a = 0, st_b = 0, st_c = 0, st_n = 0, st_t0 = 0, st_t = 0, st_e1 = 0, st_e2 = 0, st_e3 = 0;
     if constexpr (STAMP) st_t0 = st_t = __builtin_amdgcn_s_memtime();
@@ -164,10 +149,6 @@ __global__ __launch_bounds__(WT_NT, 2) void wino4_fused64t_kernel(const ConvPara
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int cb = wave & 3, h = wave >> 2;
-    if (skew) {   // start skew: the blocks of an XCD enter the kernel in 8 phase classes, `skew` cycles apart (see launch_wino_fused64t)
-        const unsigned long long until = __builtin_amdgcn_s_memtime() + (unsigned long long)skew * ((blockIdx.x >> 3) & 7);
-        while (__builtin_amdgcn_s_memtime() < until) __builtin_amdgcn_s_sleep(32);
-    }
     const int TH = p.Ho >> 2, TW = p.Wo >> 2;
     const int Ctot = p.C0 + p.C1;
     const int nch = Ctot / WT_KC;   // chunks = 16-channel k groups (one weight unit each); a multiple of 4
@@ -186,7 +167,7 @@ __global__ __launch_bounds__(WT_NT, 2) void wino4_fused64t_kernel(const ConvPara
     W6Item it = w6_item(v, total, NB, GX, GY, xcd_nb);
     int ubase = it.nblk * nch * 4096 + cb * 1024 + 3 * h * zstride;
     auto unit_rel = [&](const int zl) { return ((zl / 3) * 6 + zl % 3) * zstride; };
-    floatx4 ring[NR];
+    floatx4 ring[WT_NR];
     const int v_lane = g * 64 + (((l15 ^ (2 * g)) & 15) * 4);
     // ---- transform role: lane = (column half hh, tile 4 (wave & 3) + tl of tile group wave >> 2, channel pair cp of the chunk)
     const __amdgpu_buffer_rsrc_t rsrc0 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.in0), 0, NOPATCH ? 0u : in0_bytes, 0x00020000);
@@ -272,7 +253,7 @@ __global__ __launch_bounds__(WT_NT, 2) void wino4_fused64t_kernel(const ConvPara
         _Pragma("unroll") for (int s = 0; s < 6; ++s) *reinterpret_cast<floatx2*>(vw_ + ((RL)*6 + s) * WT_ZS) = o_[s];       \
     }
 // one chunk of the K loop: 18 weight units of { V fragments of the next unit, 8 MFMAs (k step outer, tile group inner: consecutive MFMAs hit different
-// accumulators), a slice of the transform of the next chunk (TF), refill of the unit's ring slot NR units ahead }.  The scheduling barriers pin that order.
+// accumulators), a slice of the transform of the next chunk (TF), refill of the unit's ring slot WT_NR units ahead }.  The scheduling barriers pin that order.
 #define WT_CHUNK(C, TF, GA, LAST, FIRST)                                                                                                      \
     {                                                                                                                        \
         const float* vb = smem + ((C)&1) * WT_VBUF + 3 * h * WT_PS * 2 + v_lane;                                             \
@@ -294,8 +275,8 @@ __global__ __launch_bounds__(WT_NT, 2) void wino4_fused64t_kernel(const ConvPara
                 vq[nx][1] = *reinterpret_cast<const floatx4*>(vb + zo + WT_PS);                                              \
             }                                                                                                                \
             _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                                  \
-                acc[u][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(ring[u % NR][j], vq[cu][0][j], ((FIRST) && j == 0) ? kZero4 : acc[u][0], 0, 0, 0); \
-                acc[u][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(ring[u % NR][j], vq[cu][1][j], ((FIRST) && j == 0) ? kZero4 : acc[u][1], 0, 0, 0); \
+                acc[u][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(ring[u % WT_NR][j], vq[cu][0][j], ((FIRST) && j == 0) ? kZero4 : acc[u][0], 0, 0, 0); \
+                acc[u][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(ring[u % WT_NR][j], vq[cu][1][j], ((FIRST) && j == 0) ? kZero4 : acc[u][1], 0, 0, 0); \
                 if (j < 3) __builtin_amdgcn_sched_barrier(0);                                                                \
             }                                                                                                                \
             __builtin_amdgcn_sched_barrier(0);                                                                               \
@@ -316,10 +297,10 @@ __global__ __launch_bounds__(WT_NT, 2) void wino4_fused64t_kernel(const ConvPara
                 }                                                                                                            \
                 __builtin_amdgcn_sched_barrier(0);                                                                           \
             }                                                                                                                \
-            if (!(LAST) || u + NR < 18) {   /* LAST: the ring is not live across the output transform (primed again behind its first stage) */ \
-                const int K = u + NR;                                                                                        \
+            if (!(LAST) || u + WT_NR < 18) {   /* LAST: the ring is not live across the output transform (primed again behind its first stage) */ \
+                const int K = u + WT_NR;                                                                                     \
                 const int off = K < 18 ? cur_off + unit_rel(K) : cur_off + 4096 + unit_rel(K - 18);                          \
-                ring[u % NR] = wt_load16<(DBG & 64) != 0, 0>(rsrc_u, uv_lane, off);                                        \
+                ring[u % WT_NR] = __builtin_bit_cast(floatx4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_u, uv_lane, off, 0)); \
             }                                                                                                                \
             __builtin_amdgcn_sched_barrier(0);                                                                               \
         }                                                                                                                    \
@@ -335,8 +316,8 @@ __global__ __launch_bounds__(WT_NT, 2) void wino4_fused64t_kernel(const ConvPara
     for (int i = 0; i < 6; ++i) WT_GATHER_ROW(i)
     WT_ADVANCE()
 #pragma unroll
-    for (int i = 0; i < NR; ++i)
-        ring[i] = wt_load16<(DBG & 64) != 0, 0>(rsrc_u, uv_lane, ubase + unit_rel(i));
+    for (int i = 0; i < WT_NR; ++i)
+        ring[i] = __builtin_bit_cast(floatx4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_u, uv_lane, ubase + unit_rel(i), 0));
 #pragma unroll
     for (int j = 0; j < 3; ++j) WT_COLPASS(j)
     WT_SWAPS()
@@ -368,24 +349,19 @@ __global__ __launch_bounds__(WT_NT, 2) void wino4_fused64t_kernel(const ConvPara
                 off_out = (tyy < TH && tx4 < TW) ? (pixc * (unsigned)p.out_stride + nn) * 4u : WF_OOB;
                 off_res = (tyy < TH && tx4 < TW) ? (pixc * (unsigned)p.res_stride + nn) * 4u : WF_OOB;
             }
-            constexpr int AUX = NT ? 2 : 0;
+            constexpr int AUX = 2;   // non-temporal
             const int rrow = p.Wo * p.res_stride * 4, rpix = p.res_stride * 4;
             floatx4 rv0[2][4], rv1[2][4];
             // The residual tile comes through LDS (buffer_load_dwordx4 ... lds: lane l's 16 bytes land at slot + 16 l; ~45 cycles of the CU's address unit per
             // 1 KB row where the same gather into registers takes 150 - 500, profiles/r04_vmem_issue_probe.txt, r06_notes.md): rows 0 / 1 now, rows 2 / 3 into the
-            // same slots once rows 0 / 1 have been read.  (DBG & 256: the register gathers, measurement twin.)
-            constexpr bool RDMA = RES && !(DBG & 256);
+            // same slots once rows 0 / 1 have been read.
             char* const rslot = reinterpret_cast<char*>(smem) + WT_XCH_BYTES + wave * 8192;
             if constexpr (RES) {
 #pragma unroll
                 for (int i = 0; i < 2; ++i)
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        if constexpr (RDMA)
-                            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_res, (__attribute__((address_space(3))) void*)(rslot + (i * 4 + j) * 1024), 16, (int)off_res, i * rrow + j * rpix, 0, AUX);
-                        else
-                            rv0[i][j] = wt_load16<(DBG & 16) != 0, AUX>(rs_res, (int)off_res, i * rrow + j * rpix);
-                    }
+                    for (int j = 0; j < 4; ++j)
+                        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_res, (__attribute__((address_space(3))) void*)(rslot + (i * 4 + j) * 1024), 16, (int)off_res, i * rrow + j * rpix, 0, AUX);
                 __builtin_amdgcn_sched_barrier(0);
             }
             floatx4 keep[12];
@@ -394,8 +370,8 @@ __global__ __launch_bounds__(WT_NT, 2) void wino4_fused64t_kernel(const ConvPara
             __builtin_amdgcn_sched_barrier(0);
             // the accumulators are dead: the weight ring of the next item
 #pragma unroll
-            for (int i = 0; i < NR; ++i)
-                ring[i] = wt_load16<(DBG & 64) != 0, 0>(rsrc_u, uv_lane, nubase + unit_rel(i));
+            for (int i = 0; i < WT_NR; ++i)
+                ring[i] = __builtin_bit_cast(floatx4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_u, uv_lane, nubase + unit_rel(i), 0));
             floatx4 bias = {0.f, 0.f, 0.f, 0.f}, fsc = {1.f, 1.f, 1.f, 1.f}, fsh = {0.f, 0.f, 0.f, 0.f};
             if (p.bias) bias = *reinterpret_cast<const floatx4*>(p.bias + n);
             if (p.film) {
@@ -409,16 +385,9 @@ __global__ __launch_bounds__(WT_NT, 2) void wino4_fused64t_kernel(const ConvPara
             const float* xr = smem + ((wave ^ 4) * 12 * 64 + lane) * 4;
 #pragma unroll
             for (int k = 0; k < 12; ++k) recv[k] = *reinterpret_cast<const floatx4*>(xr + k * 256);
-            if constexpr (RES && !RDMA) {
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        rv1[i][j] = wt_load16<(DBG & 16) != 0, AUX>(rs_res, (int)off_res, (2 + i) * rrow + j * rpix);
-            }
             __syncthreads();   // every wave has read its terms: V[0] may be overwritten (chunk 0 of the next item, below)
             WT_STAMP(st_e2)
-            if constexpr (RDMA) {
+            if constexpr (RES) {
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // rows 0 / 1 have landed (two barriers ago; also the ring and the bias / FiLM rows)
 #pragma unroll
                 for (int i = 0; i < 2; ++i)
@@ -439,19 +408,18 @@ __global__ __launch_bounds__(WT_NT, 2) void wino4_fused64t_kernel(const ConvPara
             for (int i = 0; i < 6; ++i) WT_GATHER_ROW(i)
             WT_ADVANCE()
             __builtin_amdgcn_sched_barrier(0);
-            if (h == 0) wt_finish_rows<0, 0, NT, RES, SILU, (DBG & 32) != 0>(p, keep, recv, rv0, off_out, rs_out, bias, fsc, fsh);
-            else wt_finish_rows<1, 0, NT, RES, SILU, (DBG & 32) != 0>(p, keep, recv, rv0, off_out, rs_out, bias, fsc, fsh);
+            if (h == 0) wt_finish_rows<0, 0, RES, SILU>(p, keep, recv, rv0, off_out, rs_out, bias, fsc, fsh);
+            else wt_finish_rows<1, 0, RES, SILU>(p, keep, recv, rv0, off_out, rs_out, bias, fsc, fsh);
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (RDMA) {
-                // behind the 8 residual rows 2 / 3: the 18 gathers and the 8 (16: 8-byte twin) stores of the first half
-                if constexpr ((DBG & 32) != 0) asm volatile("s_waitcnt vmcnt(34)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(26)" ::: "memory");
+            if constexpr (RES) {
+                asm volatile("s_waitcnt vmcnt(26)" ::: "memory");   // behind the 8 residual rows 2 / 3: the 18 gathers and the 8 stores of the first half
 #pragma unroll
                 for (int i = 0; i < 2; ++i)
 #pragma unroll
                     for (int j = 0; j < 4; ++j) rv1[i][j] = *reinterpret_cast<const floatx4*>(rslot + (i * 4 + j) * 1024 + lane * 16);
             }
-            if (h == 0) wt_finish_rows<0, 1, NT, RES, SILU, (DBG & 32) != 0>(p, keep, recv, rv1, off_out, rs_out, bias, fsc, fsh);
-            else wt_finish_rows<1, 1, NT, RES, SILU, (DBG & 32) != 0>(p, keep, recv, rv1, off_out, rs_out, bias, fsc, fsh);
+            if (h == 0) wt_finish_rows<0, 1, RES, SILU>(p, keep, recv, rv1, off_out, rs_out, bias, fsc, fsh);
+            else wt_finish_rows<1, 1, RES, SILU>(p, keep, recv, rv1, off_out, rs_out, bias, fsc, fsh);
             WT_STAMP(st_e3)
         }
         v = nv; it = nit; ubase = nubase;
@@ -483,8 +451,6 @@ __global__ __launch_bounds__(WT_NT, 2) void wino4_fused64t_kernel(const ConvPara
 #undef WT_STAMP
 }
 
-constexpr int WT_NR = 6;
-
 }  // namespace
 
 // Work items of a launch: (image, 4 x 8 tiles, 64-cout block)
@@ -503,35 +469,27 @@ bool wino_fused64t_eligible(const ConvParams& p) {
 void wino_fused_t_global_init() {
 #define WT_ATTR(...) IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(wino4_fused64t_kernel<__VA_ARGS__>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024))
 #define WT_ATTR4(...) WT_ATTR(__VA_ARGS__, 0); WT_ATTR(__VA_ARGS__, 1); WT_ATTR(__VA_ARGS__, 2); WT_ATTR(__VA_ARGS__, 3)
-    WT_ATTR4(WT_NR, false, false, true);
+    WT_ATTR4(false, false);
 #ifdef IRSDE_PROBES
-    WT_ATTR4(WT_NR, true, false, true);
-    WT_ATTR4(WT_NR, false, true, true);
-    WT_ATTR4(3, false, false, true);
-    WT_ATTR(WT_NR, false, false, true, 0, true); WT_ATTR(WT_NR, false, false, true, 1, true);
-    WT_ATTR(WT_NR, false, false, true, 2, true); WT_ATTR(WT_NR, false, false, true, 3, true);
-    WT_ATTR(WT_NR, false, true, true, 1, true); WT_ATTR(WT_NR, false, true, true, 3, true);
-    WT_ATTR(WT_NR, false, false, true, 1, false, 7); WT_ATTR(WT_NR, false, false, true, 3, false, 7);
-    WT_ATTR(WT_NR, false, false, true, 1, false, 15); WT_ATTR(WT_NR, false, false, true, 3, false, 15);
-    WT_ATTR(WT_NR, false, false, true, 1, false, 8); WT_ATTR(WT_NR, false, false, true, 3, false, 8);
-    WT_ATTR4(WT_NR, false, false, false);
-    WT_ATTR(WT_NR, false, false, true, 1, false, 16); WT_ATTR(WT_NR, false, false, true, 3, false, 16);
-    WT_ATTR(WT_NR, false, false, true, 1, false, 32); WT_ATTR(WT_NR, false, false, true, 3, false, 32);
-    WT_ATTR(WT_NR, false, false, true, 1, false, 64); WT_ATTR(WT_NR, false, false, true, 3, false, 64);
-    WT_ATTR(WT_NR, false, false, true, 1, true, 128); WT_ATTR(WT_NR, false, false, true, 3, true, 128);
-    WT_ATTR(WT_NR, false, false, true, 3, false, 256); WT_ATTR(WT_NR, false, false, true, 2, false, 256);
+    WT_ATTR4(true, false);
+    WT_ATTR4(false, true);
+    WT_ATTR(false, false, 0, true); WT_ATTR(false, false, 1, true);
+    WT_ATTR(false, false, 2, true); WT_ATTR(false, false, 3, true);
+    WT_ATTR(false, true, 1, true); WT_ATTR(false, true, 3, true);
+    WT_ATTR(false, false, 1, false, 7); WT_ATTR(false, false, 3, false, 7);
+    WT_ATTR(false, false, 1, false, 15); WT_ATTR(false, false, 3, false, 15);
+    WT_ATTR(false, false, 1, false, 8); WT_ATTR(false, false, 3, false, 8);
+    WT_ATTR(false, false, 1, true, 128); WT_ATTR(false, false, 3, true, 128);
 #endif
 #undef WT_ATTR4
 #undef WT_ATTR
 }
 
 static unsigned long long* g_wt_dbg = nullptr;
-static int g_wt_skew = 0;   // tuning: start skew in cycles per phase class (irsde_bench_conv 4700 + k: k x 1000 cycles)
-void wino_fused64t_set_skew(int cycles) { g_wt_skew = cycles; }
 void wino_fused64t_set_debug(unsigned long long* buf) { g_wt_dbg = buf; }
 
-// variant: 0 production; (PROBES build) 1 weight fragments read zeros, 2 patch gathers read zeros, 3 three instead of six weight units in flight, 5 cycle stamps
-// into the buffer of wino_fused64t_set_debug(); + 64: the cout-block-by-XCD item map wherever it is legal (test hook)
+// variant: 0 production; (PROBES build) 1 weight fragments read zeros, 2 patch gathers read zeros, 5 cycle stamps into the buffer of wino_fused64t_set_debug(),
+// 6 / 7 / 8 / 12 / 13 / 14 / 15 measurement twins (below); + 64: the cout-block-by-XCD item map wherever it is legal (test hook)
 void launch_wino_fused64t(const ConvParams& p, const float* Uf, hipStream_t s, int variant) {
     if (!wino_fused64t_eligible(p)) throw HipError("launch_wino_fused64t: layer not eligible");
     if (!Uf) throw HipError("launch_wino_fused64t: fused weights missing");
@@ -556,7 +514,7 @@ void launch_wino_fused64t(const ConvParams& p, const float* Uf, hipStream_t s, i
     // one block per CU; a multiple of 8 so that virtual item id % 8 stays the XCD of the block that runs it
     const dim3 pgrid((unsigned)std::min(total, std::max(8, ncu & ~7)));
     const int epi = (p.silu ? 1 : 0) | (p.res ? 2 : 0);
-#define WT_LAUNCH(...) hipLaunchKernelGGL((wino4_fused64t_kernel<__VA_ARGS__>), pgrid, dim3(WT_NT), WT_LDS_BYTES, s, p, Uf, GX, GY, NB, in0_bytes, in1_bytes, uf_bytes, out_bytes, res_bytes, xcd_nb, total, g_wt_dbg, g_wt_skew)
+#define WT_LAUNCH(...) hipLaunchKernelGGL((wino4_fused64t_kernel<__VA_ARGS__>), pgrid, dim3(WT_NT), WT_LDS_BYTES, s, p, Uf, GX, GY, NB, in0_bytes, in1_bytes, uf_bytes, out_bytes, res_bytes, xcd_nb, total, g_wt_dbg)
 #define WT_LAUNCH_EPI(...)                                  \
     switch (epi) {                                          \
         case 0: WT_LAUNCH(__VA_ARGS__, 0); break;           \
@@ -565,43 +523,31 @@ void launch_wino_fused64t(const ConvParams& p, const float* Uf, hipStream_t s, i
         default: WT_LAUNCH(__VA_ARGS__, 3); break;          \
     }
     switch (variant) {
-        case 0: WT_LAUNCH_EPI(WT_NR, false, false, true) break;
+        case 0: WT_LAUNCH_EPI(false, false) break;
 #ifdef IRSDE_PROBES
-        case 1: WT_LAUNCH_EPI(WT_NR, true, false, true) break;
-        case 2: WT_LAUNCH_EPI(WT_NR, false, true, true) break;
-        case 3: WT_LAUNCH_EPI(3, false, false, true) break;
+        case 1: WT_LAUNCH_EPI(true, false) break;
+        case 2: WT_LAUNCH_EPI(false, true) break;
         case 12:
             if (epi != 1 && epi != 3) throw HipError("launch_wino_fused64t: measurement twins exist for epilogues 1 / 3");
-            if (epi == 1) WT_LAUNCH(WT_NR, false, true, true, 1, true); else WT_LAUNCH(WT_NR, false, true, true, 3, true);
-            break;
-        case 16:   // the residual tile gathered into registers (r06's first form; epilogues 2 / 3)
-            if (epi == 3) WT_LAUNCH(WT_NR, false, false, true, 3, false, 256); else if (epi == 2) WT_LAUNCH(WT_NR, false, false, true, 2, false, 256);
-            else throw HipError("launch_wino_fused64t: variant 16 is a residual-layer twin");
+            if (epi == 1) WT_LAUNCH(false, true, 1, true); else WT_LAUNCH(false, true, 3, true);
             break;
         case 15:   // stamps of the coalesced-epilogue twin (garbage results)
             if (epi != 1 && epi != 3) throw HipError("launch_wino_fused64t: measurement twins exist for epilogues 1 / 3");
-            if (epi == 1) WT_LAUNCH(WT_NR, false, false, true, 1, true, 128); else WT_LAUNCH(WT_NR, false, false, true, 3, true, 128);
+            if (epi == 1) WT_LAUNCH(false, false, 1, true, 128); else WT_LAUNCH(false, false, 3, true, 128);
             break;
         case 5: case 13: case 14:
             switch (epi) {
-                case 0: WT_LAUNCH(WT_NR, false, false, true, 0, true); break;
-                case 1: WT_LAUNCH(WT_NR, false, false, true, 1, true); break;
-                case 2: WT_LAUNCH(WT_NR, false, false, true, 2, true); break;
-                default: WT_LAUNCH(WT_NR, false, false, true, 3, true); break;
+                case 0: WT_LAUNCH(false, false, 0, true); break;
+                case 1: WT_LAUNCH(false, false, 1, true); break;
+                case 2: WT_LAUNCH(false, false, 2, true); break;
+                default: WT_LAUNCH(false, false, 3, true); break;
             }
             break;
-        case 4: WT_LAUNCH_EPI(WT_NR, false, false, false) break;   // no non-temporal hint on the residual loads / output stores
         case 6: case 7: case 8:   // measurement twins (garbage results; epilogues 1 / 3): 6 no transform arithmetic / V writes, 7 + no gathers, 8 no gathers only
             if (epi != 1 && epi != 3) throw HipError("launch_wino_fused64t: measurement twins exist for epilogues 1 / 3");
-            if (variant == 6) { if (epi == 1) WT_LAUNCH(WT_NR, false, false, true, 1, false, 7); else WT_LAUNCH(WT_NR, false, false, true, 3, false, 7); }
-            if (variant == 7) { if (epi == 1) WT_LAUNCH(WT_NR, false, false, true, 1, false, 15); else WT_LAUNCH(WT_NR, false, false, true, 3, false, 15); }
-            if (variant == 8) { if (epi == 1) WT_LAUNCH(WT_NR, false, false, true, 1, false, 8); else WT_LAUNCH(WT_NR, false, false, true, 3, false, 8); }
-            break;
-        case 9: case 10: case 11:   // 8-byte twins (epilogues 1 / 3): 9 residual loads, 10 output stores, 11 weight units
-            if (epi != 1 && epi != 3) throw HipError("launch_wino_fused64t: measurement twins exist for epilogues 1 / 3");
-            if (variant == 9) { if (epi == 1) WT_LAUNCH(WT_NR, false, false, true, 1, false, 16); else WT_LAUNCH(WT_NR, false, false, true, 3, false, 16); }
-            if (variant == 10) { if (epi == 1) WT_LAUNCH(WT_NR, false, false, true, 1, false, 32); else WT_LAUNCH(WT_NR, false, false, true, 3, false, 32); }
-            if (variant == 11) { if (epi == 1) WT_LAUNCH(WT_NR, false, false, true, 1, false, 64); else WT_LAUNCH(WT_NR, false, false, true, 3, false, 64); }
+            if (variant == 6) { if (epi == 1) WT_LAUNCH(false, false, 1, false, 7); else WT_LAUNCH(false, false, 3, false, 7); }
+            if (variant == 7) { if (epi == 1) WT_LAUNCH(false, false, 1, false, 15); else WT_LAUNCH(false, false, 3, false, 15); }
+            if (variant == 8) { if (epi == 1) WT_LAUNCH(false, false, 1, false, 8); else WT_LAUNCH(false, false, 3, false, 8); }
             break;
 #endif
         default: throw HipError("launch_wino_fused64t: bad variant (the measurement twins need a make PROBES=1 build)");

@@ -60,7 +60,7 @@ def test_native_library_is_loaded():
 # kernel level: implicit-GEMM convolution (every shape class the network uses)
 # ---------------------------------------------------------------------------------------------
 def run_conv(x0, x1, w, bias, stride, pad, in_shift, film, silu, res, naive=0, splits=1, film_bstride=0, L=None):
-    """x0/x1/res: numpy NCHW.  Returns numpy NCHW.  L: the library (default: the product build; `probes_lib()` for superseded kernel generations)."""
+    """x0/x1/res: numpy NCHW.  Returns numpy NCHW.  L: the library (default: the product build; `probes_lib()` for the measurement build)."""
     L = L or _lib.lib()
     to_nhwc = lambda a: torch.from_numpy(np.ascontiguousarray(a.transpose(0, 2, 3, 1))).to(DEV)
     d0 = to_nhwc(x0)
@@ -84,8 +84,8 @@ def run_conv(x0, x1, w, bias, stride, pad, in_shift, film, silu, res, naive=0, s
 
 
 def probes_lib():
-    """libirsde_hip_probes.so (`make PROBES=1`: superseded kernel generations and measurement twins, not part of the product library); the
-    tests that compare kernel generations skip when it has not been built."""
+    """libirsde_hip_probes.so (`make PROBES=1`: the measurement twins, not part of the product library); the tests that compare the two builds
+    skip when it has not been built."""
     try:
         return _lib.probes_lib()
     except _lib.IrsdeLibraryError as ex:
@@ -200,7 +200,7 @@ def test_conv_wino_fused_edges(shape):
 @pytest.mark.parametrize("shape", [(3, 64, 0, 36, 44, 64, 0), (2, 32, 32, 8, 12, 128, 1), (1, 128, 64, 20, 28, 128, 0), (5, 96, 32, 4, 4, 192, 0),
                                    (1, 256, 0, 16, 16, 64, 1), (2, 64, 0, 64, 64, 64, 0)])
 def test_conv_wino_fused64_edges(shape):
-    """r03: the 64-cout fused Winograd kernel (wino4_fused64_kernel) on ragged 4 x 4 tile groups, concat sources whose boundary
+    """r03: the 64-cout fused Winograd kernel (wino4_fused64p_kernel) on ragged 4 x 4 tile groups, concat sources whose boundary
     falls on a 32-channel chunk, the fused upsample, per-sample FiLM rows, bias + SiLU + residual together, 2 .. 8 chunks."""
     B, C0, C1, H, W, Cout, up = shape
     rs = np.random.RandomState(B * 1000 + H + 7)
@@ -258,28 +258,21 @@ def test_conv_wino_fused64_persistent_rounds(shape):
 
 
 @pytest.mark.parametrize("shape", PERSISTENT_SHAPES)
-def test_conv_wino_fused64_kernel_generations(shape):
-    """The superseded / measurement kernels of the fused Winograd family live in the PROBES build only (libirsde_hip_probes.so, r05): r03's
-    one-block-per-tile-group kernel (38 / 39), the halo kernel (57 / 58: patches through LDS), the single-stream kernel (60 / 61), the tuning twins of
-    the persistent kernel (51 / 53: no double-fetched ring units / interleaved patch-load issue; 52: 12-operation B^T; 50: every tuning bit).  Same
-    arithmetic in the same order wherever the input transform is not re-associated: bit-identical to the PRODUCT library's production kernel."""
+def test_conv_wino_fused64_probes_build_matches_product(shape):
+    """The measurement build (libirsde_hip_probes.so, r05: the stamp / ablation twins of the fused Winograd kernels) runs the same production kernels as
+    the PRODUCT library: bit-identical f32 (34) and fp16-pair (35) results.  A selector of a retired kernel generation (38: r03's one-block-per-tile-group
+    kernel) is refused loudly by both builds instead of silently running something else."""
     PL = probes_lib()
     args, ref, fb = _persistent_rounds_case(shape)
     got = run_conv(*args, naive=34, film_bstride=fb)                      # product library, production kernel
+    assert relerr(got, ref) < 5e-5, shape
     assert np.array_equal(got, run_conv(*args, naive=34, film_bstride=fb, L=PL)), shape   # the probes build runs the same production kernel
-    old = run_conv(*args, naive=38, film_bstride=fb, L=PL)
-    assert relerr(old, ref) < 5e-5 and relerr(got, old) < 2e-5, shape
-    for nv in (57, 51, 53, 60):
-        assert np.array_equal(got, run_conv(*args, naive=nv, film_bstride=fb, L=PL)), (shape, nv)
-    for nv in (52, 50):
-        assert relerr(run_conv(*args, naive=nv, film_bstride=fb, L=PL), ref) < 5e-5, (shape, nv)
     pair = run_conv(*args, naive=35, film_bstride=fb)
-    assert relerr(pair, run_conv(*args, naive=39, film_bstride=fb, L=PL)) < 2e-5, shape
-    for nv in (58, 61):
-        assert np.array_equal(pair, run_conv(*args, naive=nv, film_bstride=fb, L=PL)), (shape, nv)
-    # the product library refuses these selectors loudly instead of silently running something else
-    with pytest.raises(P.IrsdeError, match="PROBES"):
-        run_conv(*args, naive=38, film_bstride=fb)
+    assert relerr(pair, ref) < 5e-5, shape
+    assert np.array_equal(pair, run_conv(*args, naive=35, film_bstride=fb, L=PL)), shape
+    for L in (None, PL):
+        with pytest.raises(P.IrsdeError, match="unknown selector"):
+            run_conv(*args, naive=38, film_bstride=fb, L=L)
 
 
 FUSED64T_SHAPES = [(3, 64, 0, 36, 44, 64, 0), (2, 32, 32, 8, 12, 128, 1), (1, 128, 64, 20, 28, 128, 0), (5, 96, 32, 4, 4, 192, 0), (1, 256, 0, 16, 16, 64, 1),
@@ -320,7 +313,7 @@ def test_conv_wino_fused64t(shape):
 
 @pytest.mark.parametrize("shape", [(2, 128, 0, 32, 32, 128, 0), (1, 64, 64, 16, 16, 256, 1), (4, 64, 0, 16, 32, 512, 0), (3, 64, 0, 16, 16, 128, 0)])
 def test_conv_wino_fused64_xcd_mapping(shape):
-    """wino4_fused64_kernel with cout block = XCD % NB (NB = 2 / 4 / 8; the last shape has 3 x 16 tile groups... an odd count the mapping
+    """wino4_fused64p_kernel with cout block = XCD % NB (NB = 2 / 4 / 8; the last shape has 3 x 16 tile groups... an odd count the mapping
     must refuse for NB = 2 -> falls back): f32 (36) and fp16-pair (37) instances against the oracle and bit-exact against the default mapping."""
     B, C0, C1, H, W, Cout, up = shape
     rs = np.random.RandomState(B * 77 + Cout)

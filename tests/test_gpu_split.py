@@ -224,7 +224,7 @@ def test_split_f16_out_of_range_input_fails_loudly():
 
 
 # ---------------------------------------------------------------------------------------------
-# the PAIR instance of the fused Winograd kernel (wino4_fused64_kernel<.., PAIR = true>): the big-feature-map layers of fp32_split_f16
+# the PAIR instance of the fused Winograd kernel (wino4_fused64p_kernel<.., PAIR = true, ..>): the big-feature-map layers of fp32_split_f16
 # ---------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("shape", [(3, 64, 0, 36, 44, 64, 0), (2, 32, 32, 8, 12, 128, 1), (1, 128, 64, 20, 28, 128, 0), (5, 96, 32, 4, 4, 192, 0),
                                    (1, 256, 0, 16, 16, 64, 1), (2, 64, 0, 64, 64, 64, 0), (1, 512, 0, 16, 16, 512, 0)])

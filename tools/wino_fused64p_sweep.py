@@ -1,14 +1,14 @@
 """r04 sweep of the fused Winograd F(4x4,3x3) kernels on the layer classes the B=16 256x256 plan runs them on (GPU box):
-r03's one-block-per-tile-group kernel (irsde_bench_conv 410 / 409 pair) against the persistent kernel (430; 431 / 432: weight
-fragments / patch loads read zeros; 433: no non-temporal hint; 434: fp16 pairs).  Prints ms and executed TFLOP/s (36 component
+the persistent kernel (irsde_bench_conv 430; 431 / 432: weight fragments / patch loads read zeros; 434: fp16 pairs; r03's
+one-block-per-tile-group kernel it replaced is retired).  Prints ms and executed TFLOP/s (36 component
 GEMMs = direct / 4) and the fraction of the 157.3 TFLOP/s f32 MFMA roof.
-usage: python tools/wino_fused64p_sweep.py [variants, default 410,430,431,432,433,409,434] [name filter] [B]"""
+usage: python tools/wino_fused64p_sweep.py [variants, default 430,431,432,434] [name filter] [B]"""
 import ctypes, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from image_restoration_sde_amd import _lib
 L = _lib.probes_lib()   # measurement variants live in the PROBES build (make -C image_restoration_sde_amd/csrc PROBES=1)
-variants = [int(v) for v in (sys.argv[1] if len(sys.argv) > 1 and sys.argv[1] else "410,430,431,432,433,409,434").split(",")]
+variants = [int(v) for v in (sys.argv[1] if len(sys.argv) > 1 and sys.argv[1] else "430,431,432,434").split(",")]
 flt = sys.argv[2] if len(sys.argv) > 2 else ""
 B = int(sys.argv[3]) if len(sys.argv) > 3 else 16
 # (name, H = W of the INPUT, Cin, Cout, up, epi, launches of this class per network evaluation)

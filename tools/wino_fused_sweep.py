@@ -25,28 +25,28 @@ cases = [
 cases = [c for c in cases if flt in c[0]]
 cases += [("L2 512->256 film", 64, 64, 512, 256, 0, 1), ("L2 768->512 film", 64, 64, 768, 512, 0, 1), ("L2 512->512 res", 64, 64, 512, 512, 0, 2),
           ("L3 512->512 res", 32, 32, 512, 512, 0, 2), ("L3 1024->1024", 32, 32, 1024, 1024, 0, 2)] if "deep" in sys.argv else []
-# 80: r02 fused kernel (32 tiles x 32 couts); 400: r03 (16 tiles x 64 couts); 401 / 402: 400 without weight / patch traffic; 403: short U ring
-print("B=%d  %-20s %9s %9s %9s %9s %9s %9s %9s   %s" % (B, "layer", "fused32", "fused64", "64 noW", "64 noPatch", "64 ring12", "3-launch", "direct",
+# 80: r02 fused kernel (32 tiles x 32 couts); 430: the persistent 64-cout kernel (16 tiles x 64 couts); 431 / 432: 430 without weight / patch traffic
+print("B=%d  %-20s %9s %9s %9s %9s %9s %9s   %s" % (B, "layer", "fused32", "fused64", "64 noW", "64 noPatch", "3-launch", "direct",
                                                          "TF/s executed (of 157.3): fused32 / fused64"))
-if "pair" in sys.argv:   # the fp16-pair twin of the 64-cout kernel (404; 405: 18 instead of 12 weight units in flight) next to the f32 kernel (400) and its no-traffic twins
-    print("B=%d  %-20s %9s %9s %9s %9s %9s   %s" % (B, "layer", "fused64", "f64 pair", "pair ring18", "64 noW", "64 noPatch", "f32-equivalent TF/s: fused64 / pair"))
+if "pair" in sys.argv:   # the fp16-pair kernel (434) next to the f32 kernel (430) and its no-traffic twins
+    print("B=%d  %-20s %9s %9s %9s %9s   %s" % (B, "layer", "fused64", "f64 pair", "64 noW", "64 noPatch", "f32-equivalent TF/s: fused64 / pair"))
     for name, H, W, Cin, Cout, up, epi in cases:
         if Cin % 64 or Cout % 64:
             continue
         exec_flops = 36 * 2.0 * B * ((H << up) // 4) * ((W << up) // 4) * Cin * Cout
         res = []
-        for v in (400, 404, 405, 401, 402):
+        for v in (430, 434, 431, 432):
             ms = ctypes.c_double()
             rc = L.irsde_bench_conv(v, B, H, W, Cin, Cout, 3, 1, up, epi, 10, ctypes.byref(ms))
             res.append(ms.value if rc == 0 else float("nan"))
-        print("      %-20s %9.4f %9.4f %9.4f %9.4f %9.4f   %.1f / %.1f" % ((name,) + tuple(res) + (exec_flops / res[0] / 1e9, exec_flops / res[1] / 1e9)), flush=True)
+        print("      %-20s %9.4f %9.4f %9.4f %9.4f   %.1f / %.1f" % ((name,) + tuple(res) + (exec_flops / res[0] / 1e9, exec_flops / res[1] / 1e9)), flush=True)
     sys.exit(0)
 for name, H, W, Cin, Cout, up, epi in cases:
     Ho, Wo = H << up, W << up
     exec_flops = 36 * 2.0 * B * (Ho // 4) * (Wo // 4) * Cin * Cout
     res = []
-    for v in (80, 400, 401, 402, 403, 81, 0):
+    for v in (80, 430, 431, 432, 81, 0):
         ms = ctypes.c_double()
         rc = L.irsde_bench_conv(v, B, H, W, Cin, Cout, 3, 1, up, epi, 10, ctypes.byref(ms))
         res.append(ms.value if rc == 0 else float("nan"))
-    print("      %-20s %9.4f %9.4f %9.4f %9.4f %9.4f %9.4f %9.4f   %.1f / %.1f" % ((name,) + tuple(res) + (exec_flops / res[0] / 1e9, exec_flops / res[1] / 1e9)), flush=True)
+    print("      %-20s %9.4f %9.4f %9.4f %9.4f %9.4f %9.4f   %.1f / %.1f" % ((name,) + tuple(res) + (exec_flops / res[0] / 1e9, exec_flops / res[1] / 1e9)), flush=True)
