@@ -5,8 +5,9 @@ csrc/ -> libirsde_hip.so) with the reference's own Python interface on top:
     IRSDE              codes/utils/sde_utils.py:80-361
     ConditionalUNet    codes/config/deraining/models/modules/DenoisingUNet_arch.py:18-134
     ConditionalNAFNet  codes/config/deraining/models/modules/DenoisingNAFNet_arch.py:85-187 (Refusion)
-    DenoisingSDE, denoising_sde.ConditionalUNet
-                       codes/utils/sde_utils.py:373-593, codes/config/denoising-sde/models/modules/DenoisingUNet_arch.py
+    DenoisingSDE, denoising_sde.ConditionalUNet / ConditionalNAFNet / DenoisingSDEModel / add_noise
+                       codes/utils/sde_utils.py:373-593, codes/config/denoising-sde/models/{modules/DenoisingUNet_arch.py,
+                       modules/DenoisingNAFNet_arch.py, denoising_model.py}, codes/utils/deg_utils.py:13-15
     DenoisingModel     codes/config/deraining/models/denoising_model.py (inference surface)
     latent.UNet / latent.ConditionalNAFNet / LatentDenoisingModel
                        codes/config/latent-dehazing/models/{modules/UNet_arch.py, modules/DenoisingNAFNet_arch.py,

@@ -33,6 +33,7 @@ FLAG_NO_NAF_CHAIN = 8192
 FLAG_SPLIT_BF16X2 = 16384
 FLAG_SPLIT_F16X2 = 32768
 FLAG_NAF_STEREO = 65536
+FLAG_NAF_UNCOND = 131072
 SAMPLE_GRAPH = 1
 SAMPLE_PROFILE = 2
 

@@ -456,6 +456,10 @@ namespace irsde {
 
 inline bool naf_lens(const irsde_engine* e) { return (e->cfg.flags & IRSDE_FLAG_NAF_LENS) != 0; }
 inline bool naf_stereo(const irsde_engine* e) { return e->arch == 1 && (e->cfg.flags & IRSDE_FLAG_NAF_STEREO) != 0; }
+// The networks without a condition input (denoising-sde): forward(x, time), DenoisingSDE sampler modes 3 / 4, cond / mu may be NULL
+inline bool uncond_engine(const irsde_engine* e) {
+    return (e->arch == 0 && (e->cfg.flags & IRSDE_FLAG_UNCOND_FULLATTN) != 0) || (e->arch == 1 && (e->cfg.flags & IRSDE_FLAG_NAF_UNCOND) != 0);
+}
 inline int rup32(int c) { return (c + 31) & ~31; }
 
 // engine_weights.hip: weight inventory (reference state_dict names), packing into kernel layouts, FiLM rows

@@ -136,6 +136,7 @@ int irsde_create(const irsde_config* cfg, irsde_engine** out) {
         if (cfg->in_nc != cfg->out_nc) throw HipError("sampler needs in_nc == out_nc");
         if ((cfg->nf << cfg->depth) > 2048) throw HipError("nf * 2^depth must be <= 2048");
         if (cfg->flags & IRSDE_FLAG_NAF_STEREO) throw HipError("IRSDE_FLAG_NAF_STEREO: the stereo network is a ConditionalNAFNet (irsde_create_nafnet)");
+        if (cfg->flags & IRSDE_FLAG_NAF_UNCOND) throw HipError("IRSDE_FLAG_NAF_UNCOND: irsde_create_nafnet only (the unconditional UNet is IRSDE_FLAG_UNCOND_FULLATTN)");
         auto* e = new irsde_engine();
         e->cfg = *cfg;
         if (cfg->flags & IRSDE_FLAG_BF16_ACT) {
@@ -168,6 +169,8 @@ int irsde_create_nafnet(const irsde_nafnet_config* cfg, irsde_engine** out) {
             if ((cfg->flags & (IRSDE_FLAG_SPLIT_BF16X2 | IRSDE_FLAG_SPLIT_F16X2)) || ((cfg->flags & IRSDE_FLAG_BF16) && !(cfg->flags & IRSDE_FLAG_FP16)))
                 throw HipError("IRSDE_FLAG_NAF_STEREO runs in fp32 or with IRSDE_FLAG_FP16 only (the bf16 and split-operand modes are not covered for the SCAM network)");
         }
+        if ((cfg->flags & IRSDE_FLAG_NAF_UNCOND) && (cfg->flags & (IRSDE_FLAG_NAF_STEREO | IRSDE_FLAG_NAF_LENS | IRSDE_FLAG_NAF_INTRO_SKIP)))
+            throw HipError("IRSDE_FLAG_NAF_UNCOND cannot be combined with IRSDE_FLAG_NAF_STEREO / IRSDE_FLAG_NAF_LENS / IRSDE_FLAG_NAF_INTRO_SKIP");
         auto* e = new irsde_engine();
         e->arch = 1;
         e->naf_ic = cfg->img_channel;
@@ -286,7 +289,7 @@ int irsde_set_schedule(irsde_engine* e, int T, const float* coef) {
 int irsde_unet_forward(irsde_engine* e, const float* xt, const float* cond, const int64_t* t_host, int nt, int B, int H,
                        int W, float* out, void* stream) {
     return guard([&] {
-        const bool uncond_e = e && e->arch == 0 && (e->cfg.flags & IRSDE_FLAG_UNCOND_FULLATTN);
+        const bool uncond_e = e && uncond_engine(e);
         if (!e || !xt || (!cond && !uncond_e) || !t_host || !out) throw HipError("null argument");
         if (!e->finalized) throw HipError("unet_forward: weights not finalized");
         if (nt != 1 && nt != B) throw HipError("unet_forward: need 1 or B timesteps");
@@ -331,7 +334,7 @@ int irsde_sample(irsde_engine* e, int mode, const float* xT, const float* mu, co
         if (!e || !xT || !out) throw HipError("null argument");
         if (!e->finalized || !e->film_table) throw HipError("sample: weights/schedule not set");
         if (mode < 0 || mode > 4) throw HipError("sample: bad mode");
-        const bool uncond_e = e->arch == 0 && (e->cfg.flags & IRSDE_FLAG_UNCOND_FULLATTN);
+        const bool uncond_e = uncond_engine(e);
         if ((mode >= 3) != uncond_e) throw HipError("sample: DenoisingSDE modes (3,4) go with the unconditional network and vice versa");
         if (!mu && !uncond_e) throw HipError("null argument");
         if (T < 0) T = e->T;

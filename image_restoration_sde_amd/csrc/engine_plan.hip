@@ -748,7 +748,7 @@ void build_naf_plan(irsde_engine* e, Plan* pl, Builder& b, int P) {
         x = b.talloc(B, pl->Hp, pl->Wp, p.Cout);
         p.out = x.p; p.out_stride = p.Cout;
         b.push_conv(p);
-        const double real = 2.0 * (double)B * pl->Hp * pl->Wp * p.Cout * 9.0 * (2.0 * e->naf_ic);
+        const double real = 2.0 * (double)B * pl->Hp * pl->Wp * p.Cout * 9.0 * ((uncond_engine(e) ? 1.0 : 2.0) * e->naf_ic);
         pl->conv_flops += real - pl->net_ops.back().flops;
         pl->net_ops.back().flops = real;
     }
@@ -937,7 +937,7 @@ static Plan* build_plan(irsde_engine* e, int B, int H, int W, bool per_sample_fi
     const size_t img = (size_t)B * in_nc * H * W;
     pl->xin = pl->alloc(img, false);
     pl->cin = pl->alloc(img, false);
-    const bool uncond = e->arch == 0 && (e->cfg.flags & IRSDE_FLAG_UNCOND_FULLATTN) != 0;
+    const bool uncond = uncond_engine(e);
     const int P = ((uncond ? 1 : 2) * (stereo ? e->naf_ic : in_nc) + 3) & ~3;
     const size_t x0n = (size_t)(stereo ? 2 * B : B) * (pl->Hp + 6) * (pl->Wp + 6) * P + 64;
     pl->x0 = pl->alloc(x0n, false);

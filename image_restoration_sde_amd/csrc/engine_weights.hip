@@ -243,7 +243,7 @@ void build_inventory_naf(irsde_engine* e) {
         add_w(e, "cam_mlp.2.weight", {td, td});
         add_w(e, "cam_mlp.2.bias", {td});
     }
-    add_w(e, "intro.weight", {width, 2 * ic, 3, 3});
+    add_w(e, "intro.weight", {width, (uncond_engine(e) ? 1 : 2) * ic, 3, 3});   // denoising-sde DenoisingNAFNet_arch.py:103: img_channel inputs
     add_w(e, "intro.bias", {width});
     add_w(e, "ending.weight", {ic, width, 3, 3});
     add_w(e, "ending.bias", {ic});
@@ -441,7 +441,7 @@ void finalize_naf(irsde_engine* e) {
         for (int i = 0; i < half; ++i) f[i] = expf((float)i * (float)(-emb));
         e->freqs = e->upload(f);
     }
-    {   // intro 3x3 (2*ic -> width, bias) as a 3-tap (ky) conv over rows of 3 pixels x P channels (+ zero K padding)
+    {   // intro 3x3 (2*ic -> width, or ic -> width without a condition input; bias) as a 3-tap (ky) conv over rows of 3 pixels x P channels (+ zero K padding)
         const HostTensor& t = need(e, "intro.weight");
         const int O = (int)t.shape[0], I = (int)t.shape[1];
         const int P = (I + 3) & ~3;

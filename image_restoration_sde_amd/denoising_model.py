@@ -20,7 +20,8 @@ from . import nafnet as _nafnet
 
 def define_G(opt, task="deraining"):
     """networks.define_G (deraining/models/networks.py:10-15): class looked up by name (task "stereo-sr": the stereo
-    ConditionalNAFNet with SCAM, stereo-sr/models/modules/DenoisingNAFNet_arch.py)."""
+    ConditionalNAFNet with SCAM, stereo-sr/models/modules/DenoisingNAFNet_arch.py; task "denoising-sde": the networks without a
+    condition input, denoising-sde/models/modules/)."""
     opt_net = opt["network_G"]
     name = opt_net["which_model_G"]
     if task == "stereo-sr":
@@ -28,6 +29,11 @@ def define_G(opt, task="deraining"):
         if name != "ConditionalNAFNet":
             raise NotImplementedError("stereo-sr: only ConditionalNAFNet (with SCAM) is provided, not %s" % name)
         return stereo_sr.ConditionalNAFNet(**opt_net["setting"])
+    if task == "denoising-sde":   # that task directory's own models.modules: forward(x, time), no condition input
+        from . import denoising_sde
+        if name not in ("ConditionalUNet", "ConditionalNAFNet"):
+            raise NotImplementedError("denoising-sde: ConditionalUNet and ConditionalNAFNet are provided, not %s" % name)
+        return getattr(denoising_sde, name)(**opt_net["setting"])
     cls = getattr(_nafnet, name, None) or getattr(_unet, name)
     return cls(**opt_net["setting"])
 
@@ -35,7 +41,8 @@ def define_G(opt, task="deraining"):
 def create_model(opt, task="deraining"):
     """models.create_model (deraining/models/__init__.py:6-15).  `task`: the reference keeps one copy of the wrapper per
     task directory; deblurring / deshadow / inpainting / sisr differ from deraining only in `test()` (hard-coded
-    reverse_sde, deblurring/models/denoising_model.py:150-157) -> `ReverseSDEDenoisingModel`."""
+    reverse_sde, deblurring/models/denoising_model.py:150-157) -> `ReverseSDEDenoisingModel`; denoising-sde feeds (LQ, GT) and tests with
+    `test(sde, sigma, save_states)` -> `denoising_sde.DenoisingSDEModel`."""
     if opt["model"] != "denoising":
         raise NotImplementedError("Model [{:s}] not recognized.".format(opt["model"]))
     if task in ("deblurring", "deshadow", "inpainting", "sisr"):
@@ -43,6 +50,9 @@ def create_model(opt, task="deraining"):
     if task == "stereo-sr":
         from .stereo_sr import StereoDenoisingModel
         return StereoDenoisingModel(opt)
+    if task == "denoising-sde":
+        from .denoising_sde import DenoisingSDEModel
+        return DenoisingSDEModel(opt)
     return DenoisingModel(opt)
 
 

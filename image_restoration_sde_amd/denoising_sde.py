@@ -7,17 +7,28 @@
                      bottleneck (module_util.py:182-204) — the one place the N x N QK^T / AV contractions exist; they run
                      as a flash-style fp32-MFMA kernel (csrc/kernels_misc.hip: full_attn_kernel).
 
+  `ConditionalNAFNet` codes/config/denoising-sde/models/modules/DenoisingNAFNet_arch.py:85-183 — the Refusion
+                     network of that task (options/test/refusion.yml): the deraining NAFNet with an `img_channel`-input
+                     `intro` (:103) and `forward(x, time)` without `cat(x - cond, cond)` (:147-150); IRSDE_FLAG_NAF_UNCOND,
+                     on the conditional NAFNet's kernels.
+  `DenoisingSDEModel`, `add_noise`
+                     denoising-sde/models/denoising_model.py:136-139,162-182 and codes/utils/deg_utils.py:13-15 — what
+                     denoising-sde/test.py:91-142 drives (tools/eval_folder.py --task denoising).
+
 `DenoisingModel.test(sde, sigma)` of that task (denoising-sde/models/denoising_model.py:162-170) calls
 `sde.reverse_ode(LQ, T=sde.get_optimal_timestep(sigma))`; both reverse samplers run entirely inside libirsde_hip.so when
-the model is this module's `ConditionalUNet`, and fall back to the per-step fused HIP update for foreign models.
+the model is one of this module's networks, and fall back to the per-step fused HIP update for foreign models.
 """
 import ctypes
 import math
+from collections import OrderedDict
 
 import torch
 import torch.nn as nn
 
 from . import _lib
+from .denoising_model import DenoisingModel
+from .nafnet import ConditionalNAFNet as _CondNAFNet
 from .sde import _check_fp16_range, _save_state, _unwrap
 from .unet import ConditionalUNet as _CondUNet, _Gain, _ResBlock, _Residual, _upsample
 
@@ -95,6 +106,65 @@ class ConditionalUNet(_CondUNet):
         return out
 
 
+class ConditionalNAFNet(_CondNAFNet):
+    """denoising-sde ConditionalNAFNet(img_channel, width, middle_blk_num, enc_blk_nums, dec_blk_nums, upscale); forward(x, time)."""
+
+    def __init__(self, img_channel=3, width=16, middle_blk_num=1, enc_blk_nums=[], dec_blk_nums=[], upscale=1):
+        super().__init__(img_channel, width, middle_blk_num, enc_blk_nums, dec_blk_nums, upscale)
+        self.intro = nn.Conv2d(img_channel, width, 3, padding=1)   # DenoisingNAFNet_arch.py:103
+
+    def _create_handle(self, L, device_index, flags):
+        return super()._create_handle(L, device_index, flags | _lib.FLAG_NAF_UNCOND)
+
+    forward = ConditionalUNet.forward   # noise = model(x, time): the same call with cond == NULL (DenoisingNAFNet_arch.py:147-183)
+
+
+def add_noise(tensor, sigma, seed=0, image_offset=0):
+    """codes/utils/deg_utils.py:13-15: `tensor + randn_like(tensor) * (sigma / 255 if sigma > 1 else sigma)`.  The draw is the library's keyed
+    Philox (`irsde_philox_normal`, step index 0 — the sampler draws at steps T .. 1) with the key (seed, image_offset + b) for image b of the
+    batch: the same contract as the sampler noise, so an evaluation is reproducible and does not depend on batching or on the rank count.
+    `tensor` is [B, C, H, W] (or one [C, H, W] image) on any device; the result lives where `tensor` does."""
+    sigma = sigma / 255 if sigma > 1 else sigma
+    x = tensor if tensor.dim() == 4 else tensor[None]
+    if x.dim() != 4:
+        raise _lib.IrsdeError("add_noise needs a [B, C, H, W] or [C, H, W] tensor")
+    dev = x.device if x.device.type == "cuda" else torch.device("cuda", torch.cuda.current_device())
+    B = x.shape[0]
+    z = torch.empty((B, x[0].numel()), device=dev, dtype=torch.float32)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().irsde_philox_normal(ctypes.c_void_p(z.data_ptr()), B, x[0].numel(), 0, int(seed), int(image_offset),
+                                                  _lib.stream_ptr()))
+    out = x.to(torch.float32) + (z.reshape(x.shape) * sigma).to(x.device)
+    return out if tensor.dim() == 4 else out[0]
+
+
+class DenoisingSDEModel(DenoisingModel):
+    """The wrapper of the denoising-sde task directory (models/denoising_model.py:136-139, 162-182): `feed_data(LQ, GT=None)` with LQ the
+    noisy image (the sampler's start state), `test(sde, sigma=-1, save_states=False)` = reverse_ode from `sde.T`, or from
+    `sde.get_optimal_timestep(sigma)` for a known noise level, and `get_current_visuals()` whose `Input` is that noisy image."""
+    task = "denoising-sde"
+
+    def feed_data(self, LQ, GT=None):
+        self.LQ = LQ.to(self.device)        # noisy_state
+        if GT is not None:
+            self.GT = GT.to(self.device)
+
+    def test(self, sde=None, sigma=-1, save_states=False):
+        timesteps = sde.T if sigma < 0 else sde.get_optimal_timestep(sigma)
+        self.model.eval()
+        with torch.no_grad():
+            self.output = sde.reverse_ode(self.LQ, T=timesteps, save_states=save_states)
+        self.model.train()
+
+    def get_current_visuals(self, need_GT=True):
+        out_dict = OrderedDict()
+        out_dict["Input"] = self.LQ.detach()[0].float().cpu()
+        out_dict["Output"] = self.output.detach()[0].float().cpu()
+        if need_GT and hasattr(self, "GT"):
+            out_dict["GT"] = self.GT.detach()[0].float().cpu()
+        return out_dict
+
+
 class DenoisingSDE:
     def __init__(self, max_sigma, T, schedule="cosine", device=None):
         self.T = T
@@ -166,7 +236,7 @@ class DenoisingSDE:
             stream = _lib.stream_ptr()
             # x0 replaces the model score only in reverse_sde (:489-493); reverse_ode always calls the model and uses x0
             # for nothing but the dumped [x, score, real_score] state image (:510-525)
-            if (x0 is None or ode) and isinstance(m, ConditionalUNet) and not save_states:
+            if (x0 is None or ode) and isinstance(m, (ConditionalUNet, ConditionalNAFNet)) and not save_states:
                 eng = m.engine(xt.device)
                 key = ("dsde", self.T, self.schedule, self.max_sigma)
                 if eng.schedule_key != key:

@@ -33,6 +33,7 @@
  *        to the one-group kernel's: same operations in the same order); a split launch whose groups were not co-resident fails the NEXT irsde_sample
  *        call on the engine instead of hanging the GPU.  Debug header: irsde_debug_force_chain_groups; irsde_bench_naf_chain variants 22 / 24.
  *        Additive, same version: IRSDE_FLAG_NAF_STEREO (the stereo-sr ConditionalNAFNet with SCAM); debug header: irsde_debug_scam.
+ *        Additive, same version: IRSDE_FLAG_NAF_UNCOND (the denoising-sde ConditionalNAFNet: forward(x, time), DenoisingSDE modes 3 / 4).
  */
 #ifndef IRSDE_HIP_H
 #define IRSDE_HIP_H
@@ -131,6 +132,14 @@ enum {
                                         LayerNorm / softmax / attention products / epilogue fp32); the other operand modes and IRSDE_FLAG_NAF_LENS /
                                         _NAF_INTRO_SKIP are refused.  No NAFBlock chain, no concurrent sub-batches.  The padded size must leave
                                         >= 4 rows and columns at the deepest level (the reference's interpolate fails below): IRSDE_ERR_INVALID */
+    IRSDE_FLAG_NAF_UNCOND = 131072,  /* irsde_create_nafnet only: the ConditionalNAFNet of denoising-sde (codes/config/denoising-sde/models/modules/
+                                        DenoisingNAFNet_arch.py:103, 147-150 — the four lines in which it differs from the deraining file):
+                                        intro takes img_channel inputs (intro.weight [width][img_channel][3][3]) and forward(x, time) has no
+                                        condition: no cat(x - cond, cond).  What IRSDE_FLAG_UNCOND_FULLATTN is for the UNet: irsde_unet_forward
+                                        takes cond == NULL, irsde_sample takes the DenoisingSDE modes 3 / 4 only (mu == NULL allowed) and refuses
+                                        0 - 2.  Everything behind the intro (NAFBlocks, time MLP, zero pad, every operand mode, the fp16 NAFBlock
+                                        chain, concurrent sub-batches) is the conditional network's, on the same kernels.  Refused together with
+                                        IRSDE_FLAG_NAF_STEREO / _NAF_LENS / _NAF_INTRO_SKIP */
     IRSDE_FLAG_NO_WINOGRAD_F43 = 8   /* Winograd F(2x2,3x3) only (>= 256 channels); default also uses F(4x4,3x3) from 128
                                         channels up where H, W are multiples of 4 */
 };

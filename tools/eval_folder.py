@@ -17,6 +17,18 @@ all_reduce); image I/O is PIL instead of cv2 (PNG decoding is lossless, so the t
 may differ in the last bit); LPIPS is not computed (the `lpips` package and its AlexNet weights are external
 downloads); the noise of `noise_state` is drawn per image from a generator seeded by (--seed, image index) so a run is
 reproducible and independent of batching / sharding.
+
+`--task denoising` is the loop of codes/config/denoising-sde/test.py:91-142 instead (Gaussian denoising, options/test/refusion.yml and
+ir-sde.yml): walk a clean GT folder -> `add_noise(GT, sigma)` -> `model.feed_data(LQ, GT)` / `model.test(sde, sigma=sigma)`
+(`DenoisingSDE.reverse_ode` from `get_optimal_timestep(sigma)`) -> <name>.png (restored), <name>_noisy.png, <name>_clean.png -> PSNR / SSIM per
+image (no border crop, as there) and averaged:
+
+    python tools/eval_folder.py --task denoising --gt CBSD68 --sigma 15 --max-sigma 70 --T 1000 --weights refusion.pth \
+        [--arch nafnet|unet] --out results/CBSD68_sigma15 [--gpus 8]
+
+Its stated differences: equal-sized images are batched; the restored image is written as .png where test.py writes .tif without a suffix; the
+noise is the library's keyed Philox draw (`denoising_sde.add_noise`, key = (--seed, global image index)), so the result does not depend on
+batching or on the rank count; LPIPS is not computed — its AlexNet weights are not available here.
 """
 import argparse
 import os
@@ -98,10 +110,78 @@ def build_model(a, P, torch):
     return m
 
 
+def _ints(s):
+    return [int(v) for v in s.split(",") if v != ""]
+
+
+def run_denoising(a, P, torch, np, dev, world, rank, log):
+    """denoising-sde/test.py:91-142 on `create_model(opt, task="denoising-sde")`, `DenoisingSDE` and `add_noise`."""
+    if a.arch == "nafnet":
+        net = {"which_model_G": "ConditionalNAFNet",
+               "setting": dict(width=a.naf_width, enc_blk_nums=_ints(a.naf_enc), middle_blk_num=a.naf_mid, dec_blk_nums=_ints(a.naf_dec))}
+    else:
+        net = {"which_model_G": "ConditionalUNet", "setting": dict(in_nc=3, out_nc=3, nf=a.nf, depth=a.depth)}
+    opt = {"model": "denoising", "network_G": net, "path": {"pretrain_model_G": a.weights, "strict_load": True}}
+    with torch.cuda.device(dev):
+        model = P.create_model(opt, task="denoising-sde")
+    if a.dtype != "fp32":
+        model.model.set_compute_dtype(a.dtype)
+    sde = P.DenoisingSDE(max_sigma=a.max_sigma, T=a.T, schedule=a.schedule, device=dev)
+    sde.set_model(model.model)
+    sde.seed = a.seed
+    paths = list_images(a.gt)
+    lo, hi = P.shard_bounds(len(paths), world, rank)
+    mine = list(range(lo, hi))
+    gt_np = [read_img(paths[i]) for i in mine]
+    res = {"psnr": [], "ssim": []}
+    times = []
+    for grp in batches_of_equal_size(mine, [x.shape for x in gt_np], a.batch):
+        GT = torch.from_numpy(np.stack([gt_np[j] for j in grp])).to(dev)
+        LQ = P.denoising_sde.add_noise(GT, a.sigma, seed=a.seed, image_offset=mine[grp[0]])   # util.add_noise(GT, degrad_sigma), test.py:104
+        sde.image_offset = mine[grp[0]]
+        model.feed_data(LQ, GT)
+        torch.cuda.synchronize()
+        tic = time.time()
+        model.test(sde, sigma=a.sigma, save_states=False)
+        torch.cuda.synchronize()
+        times.append((time.time() - tic) / len(grp))
+        m = P.metrics.evaluate_batch(model.output, GT, crop_border=0)   # calculate_psnr / calculate_ssim(output, GT): no crop (test.py:128-129)
+        names = [os.path.splitext(os.path.basename(paths[mine[j]]))[0] for j in grp]
+        for n, name in enumerate(names):
+            res["psnr"].append(float(m["psnr"][n]))
+            res["ssim"].append(float(m["ssim"][n]))
+            log("img%3d:%-15s - PSNR: %.6f dB; SSIM: %.6f." % (mine[grp[n]], name, m["psnr"][n], m["ssim"][n]))
+        if a.out:
+            imgs, lqi, gti = (P.metrics.tensor2img_batch(t) for t in (model.output, LQ, GT))
+            for n, name in enumerate(names):
+                save_img(imgs[n], os.path.join(a.out, name + ".png"))
+                save_img(lqi[n], os.path.join(a.out, name + "_noisy.png"))
+                save_img(gti[n], os.path.join(a.out, name + "_clean.png"))
+    summary = None
+    local = {k: np.asarray(v, dtype=np.float64) for k, v in res.items()}
+    if world > 1 or len(local["psnr"]):
+        summary = P.metrics.reduce_metrics(local)
+    if rank == 0 and summary is not None:
+        log("----Average PSNR/SSIM results for %s_sigma%g----\n\tPSNR: %.6f dB; SSIM: %.6f\n" %
+            (os.path.basename(os.path.normpath(a.gt)), a.sigma, summary["psnr"], summary["ssim"]))
+    if rank == 0 and times:
+        log("average test time per image: %.4f s (rank 0, %d images over %d rank(s))" % (float(np.mean(times)), len(paths), world))
+    return summary
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--lq", required=True)
+    ap.add_argument("--task", default=None, choices=["denoising"], help="denoising: the denoising-sde loop (clean --gt folder + --sigma, DenoisingSDE, "
+                    "reverse_ode from the optimal timestep; PSNR / SSIM, no LPIPS: its AlexNet weights are not available).  Absent: the LQ / GT loop")
+    ap.add_argument("--lq", default=None, help="degraded images (required unless --task denoising)")
     ap.add_argument("--gt", default=None)
+    ap.add_argument("--sigma", type=float, default=15, help="--task denoising: opt['degradation']['sigma'] (/ 255 when > 1)")
+    ap.add_argument("--arch", default="nafnet", choices=["nafnet", "unet"], help="--task denoising: denoising_sde.ConditionalNAFNet (refusion.yml) "
+                    "or denoising_sde.ConditionalUNet (ir-sde.yml; --nf / --depth)")
+    ap.add_argument("--naf-width", type=int, default=64)
+    ap.add_argument("--naf-enc", default="1,1,1,28")
+    ap.add_argument("--naf-mid", type=int, default=1)
+    ap.add_argument("--naf-dec", default="1,1,1,1")
     ap.add_argument("--weights", required=True, help="reference checkpoint (state_dict .pth, optional 'module.' prefixes)")
     ap.add_argument("--out", default=None, help="results folder: <name>.png, <name>_LQ.png, <name>_HQ.png as test.py:118-128")
     ap.add_argument("--model", default="unet", choices=["unet", "nafnet"])
@@ -120,6 +200,10 @@ def main(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16", "bf16_act", "fp16"])
     a = ap.parse_args(argv)
+    if a.task is None and a.lq is None:
+        ap.error("the following arguments are required: --lq")
+    if a.task == "denoising" and a.gt is None:
+        ap.error("--task denoising needs the clean images: --gt")
     crop_border = a.crop_border if a.crop_border else a.scale   # test.py:134: `opt["crop_border"] if opt["crop_border"] else scale`
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -146,6 +230,11 @@ def main(argv=None):
     if world > 1:
         dist.init_process_group("nccl", device_id=dev)
 
+    if a.task == "denoising":
+        summary = run_denoising(a, P, torch, np, dev, world, rank, (lambda *s: print(*s, flush=True)))
+        if world > 1:
+            dist.destroy_process_group()
+        return summary
     pairs = pair_paths(a.lq, a.gt)
     lo, hi = P.shard_bounds(len(pairs), world, rank)   # this rank's images; noise keyed by the global index
     model = build_model(a, P, torch).to(dev).eval()
