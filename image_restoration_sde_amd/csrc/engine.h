@@ -1,4 +1,4 @@
-// libirsde_hip.so — engine internals shared by engine_weights.hip / engine_plan.hip / engine_api.hip.
+// libirsde_hip.so — engine internals shared by engine_weights.hip / engine_plan.hip / engine_api.hip / engine_debug.hip.
 //
 // Host-side structure (all C++; PyTorch never appears here):
 //   Engine      weights in kernel layout, FiLM/time table, coefficient table, plans
@@ -212,6 +212,14 @@ inline bool wino_shape_ok(const ConvParams& d, int tile) {
            (d.C0 + d.C1) % 32 == 0 && d.Cout % 4 == 0 && d.out_stride % 4 == 0 && (!d.res || d.res_stride % 4 == 0);
 }
 
+// The power of two that brings max |host[i]| into (256, 512] (1 for all-zero input): the exact pre-scale of fp16 hi / lo operand pairs, undone by the
+// kernel that consumes them
+inline float pow2_scale_into_512(const float* host, size_t n) {
+    float mx = 0.f;
+    for (size_t i = 0; i < n; ++i) mx = std::max(mx, std::fabs(host[i]));
+    return mx > 0.f ? std::exp2(std::floor(std::log2(512.0f / mx))) : 1.f;
+}
+
 struct Tensor {
     float* p = nullptr;  // bf16 == true: really a bf16 tensor (IRSDE_FLAG_BF16_ACT)
     int B = 0, H = 0, W = 0, C = 0;
@@ -295,7 +303,7 @@ struct LatentPlan {
 
 }  // namespace irsde
 
-using namespace irsde;  // internal header: included only by the three engine_*.hip translation units
+using namespace irsde;  // internal header: included only by the four engine_*.hip translation units
 
 struct irsde_engine {
     irsde_config cfg{};
@@ -360,7 +368,8 @@ struct irsde_engine {
     float* zeros = nullptr;        // zero page: the branch-free source of out-of-image conv taps
     hipStream_t stream = nullptr;  // engine stream (graph capture needs a non-default stream)
     hipEvent_t ev_in = nullptr, ev_out = nullptr;
-    // r05: concurrent sub-batches of a NAFNet sampler step (engine_api.hip: sample_split): branch i > 0 runs on sub_stream[i - 1] between ev_fork and ev_join[i - 1]
+    // r05: concurrent sub-batches of a NAFNet sampler call (engine_api.hip: irsde_sample): part i > 0 runs all its steps on sub_stream[i - 1], forked once
+    // behind the call's inputs (ev_fork) and joined once in front of its outputs (ev_join[i - 1])
     static constexpr int kMaxSub = 4;
     hipStream_t sub_stream[kMaxSub - 1] = {nullptr, nullptr, nullptr};
     hipEvent_t ev_fork = nullptr, ev_join[kMaxSub - 1] = {nullptr, nullptr, nullptr};
@@ -400,49 +409,33 @@ struct irsde_engine {
     struct PairCopy { unsigned short* p; float inv_scale; };
     std::map<const float*, PairCopy> pair_copies;
     PairCopy pair_copy(const float* w, size_t n) {
-        auto it = pair_copies.find(w);
-        if (it != pair_copies.end()) return it->second;
-        const bool f16 = (cfg.flags & IRSDE_FLAG_SPLIT_F16X2) != 0;
-        float sc = 1.f;
-        if (f16) {
-            std::vector<float> h(n);
-            IRSDE_HIP_CHECK(hipMemcpy(h.data(), w, n * sizeof(float), hipMemcpyDeviceToHost));
-            float mx = 0.f;
-            for (float v : h) mx = std::max(mx, std::fabs(v));
-            if (mx > 0.f) sc = std::exp2(std::floor(std::log2(512.0f / mx)));
-        }
-        unsigned short* d = nullptr;
-        IRSDE_HIP_CHECK(hipMalloc(&d, 2 * n * sizeof(unsigned short)));
-        dev_allocs.push_back(reinterpret_cast<float*>(d));
-        launch_split_planes(w, d, n, n, 2, stream, f16, sc);
-        IRSDE_HIP_CHECK(hipStreamSynchronize(stream));
-        const PairCopy pc{d, 1.0f / sc};
-        pair_copies[w] = pc;
-        return pc;
+        return make_pair_copy(pair_copies, w, n, [&](unsigned short* d, bool f16, float sc) { launch_split_planes(w, d, n, n, 2, stream, f16, sc); });
     }
     // The PAIR kernels of conv_igemm.hip read their weights pair-interleaved: [rows][K / 32][hi 32 | lo 32] (split_pairs_kernel), one
     // 128-byte line per 32-k block, fetched global -> LDS by global_load_lds.  K must be a multiple of 32.
     std::map<const float*, PairCopy> pair_copies_il;
     PairCopy pair_copy_il(const float* w, size_t rows, int K) {
-        auto it = pair_copies_il.find(w);
-        if (it != pair_copies_il.end()) return it->second;
+        return make_pair_copy(pair_copies_il, w, rows * (size_t)K, [&](unsigned short* d, bool f16, float sc) { launch_split_pairs(w, d, rows, K, stream, f16, sc); });
+    }
+    // the two layouts' common part: cache lookup, scale, allocation, registration; split(d, f16, scale) launches the layout's kernel
+    template <class Split>
+    PairCopy make_pair_copy(std::map<const float*, PairCopy>& cache, const float* w, size_t n, Split split) {
+        auto it = cache.find(w);
+        if (it != cache.end()) return it->second;
         const bool f16 = (cfg.flags & IRSDE_FLAG_SPLIT_F16X2) != 0;
-        const size_t n = rows * (size_t)K;
         float sc = 1.f;
         if (f16) {
             std::vector<float> h(n);
             IRSDE_HIP_CHECK(hipMemcpy(h.data(), w, n * sizeof(float), hipMemcpyDeviceToHost));
-            float mx = 0.f;
-            for (float v : h) mx = std::max(mx, std::fabs(v));
-            if (mx > 0.f) sc = std::exp2(std::floor(std::log2(512.0f / mx)));
+            sc = pow2_scale_into_512(h.data(), n);
         }
         unsigned short* d = nullptr;
         IRSDE_HIP_CHECK(hipMalloc(&d, 2 * n * sizeof(unsigned short)));
         dev_allocs.push_back(reinterpret_cast<float*>(d));
-        launch_split_pairs(w, d, rows, K, stream, f16, sc);
+        split(d, f16, sc);
         IRSDE_HIP_CHECK(hipStreamSynchronize(stream));
         const PairCopy pc{d, 1.0f / sc};
-        pair_copies_il[w] = pc;
+        cache[w] = pc;
         return pc;
     }
     float* upload(const std::vector<float>& v) {
@@ -461,6 +454,9 @@ inline bool uncond_engine(const irsde_engine* e) {
     return (e->arch == 0 && (e->cfg.flags & IRSDE_FLAG_UNCOND_FULLATTN) != 0) || (e->arch == 1 && (e->cfg.flags & IRSDE_FLAG_NAF_UNCOND) != 0);
 }
 inline int rup32(int c) { return (c + 31) & ~31; }
+// The step counter / coefficient row and the FiLM row a plan's sampler steps run with: a sub-batch plan's own pair, else the engine's
+inline StepState* step_of(const irsde_engine* e, const Plan* pl) { return pl->own_step ? pl->own_step : e->step; }
+inline float* film_of(const irsde_engine* e, const Plan* pl) { return pl->own_film ? pl->own_film : e->film_cur; }
 
 // engine_weights.hip: weight inventory (reference state_dict names), packing into kernel layouts, FiLM rows
 void build_inventory(irsde_engine* e);
@@ -477,5 +473,8 @@ void set_force_chain_groups(int g);   // irsde_debug_force_chain_groups
 int forced_chain_groups();
 void set_force_subbatches(int n);                                 // irsde_debug_force_subbatches   // how many concurrent sub-batches the sampler splits a NAFNet batch into (1 = none)
 LatentPlan* get_latent_plan(irsde_engine* e, int B, int H, int W, bool decode);
+
+// engine_api.hip: runs the body of a C-ABI entry point; an exception becomes the IRSDE_ERR_* code and the thread's irsde_last_error() string
+int guard(const std::function<void()>& f);
 
 }  // namespace irsde

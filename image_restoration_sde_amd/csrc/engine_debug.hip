@@ -1,0 +1,681 @@
+// libirsde_hip.so — the kernel-level TEST and TUNING hooks (include/irsde_hip_debug.h): one kernel or one code path at a time on the caller's or on
+// synthetic data.  Not part of the drop-in boundary; nothing here touches an engine.  Device memory, the hook's stream and its events are scoped
+// (Scratch, OwnedStream, EventPair): every early return and every throw releases them.
+#include "engine.h"
+#include "../../include/irsde_hip_debug.h"
+
+using namespace irsde;
+
+namespace irsde {
+namespace {
+
+// Device scratch of one hook call on stream `s`: freed, after `s` has drained, however the call ends
+struct Scratch {
+    hipStream_t s;
+    std::vector<void*> bufs;
+    explicit Scratch(hipStream_t s_) : s(s_) {}
+    ~Scratch() {
+        (void)hipStreamSynchronize(s);
+        for (void* p : bufs) (void)hipFree(p);
+    }
+    Scratch(const Scratch&) = delete;
+    Scratch& operator=(const Scratch&) = delete;
+    template <class T> T* alloc(size_t n) {
+        void* p = nullptr;
+        IRSDE_HIP_CHECK(hipMalloc(&p, n * sizeof(T)));
+        bufs.push_back(p);
+        return static_cast<T*>(p);
+    }
+    float* upload(const float* host, size_t n) {
+        float* d = alloc<float>(n);
+        IRSDE_HIP_CHECK(hipMemcpy(d, host, n * sizeof(float), hipMemcpyHostToDevice));
+        return d;
+    }
+    float* upload(const std::vector<float>& v) { return upload(v.data(), v.size()); }
+};
+// The stream a bench hook runs on (declare it before the Scratch that drains it)
+struct OwnedStream {
+    hipStream_t s = nullptr;
+    explicit OwnedStream(unsigned flags) { IRSDE_HIP_CHECK(hipStreamCreateWithFlags(&s, flags)); }
+    ~OwnedStream() { (void)hipStreamDestroy(s); }
+    OwnedStream(const OwnedStream&) = delete;
+    OwnedStream& operator=(const OwnedStream&) = delete;
+};
+struct EventPair {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    EventPair() {
+        IRSDE_HIP_CHECK(hipEventCreate(&e0));
+        IRSDE_HIP_CHECK(hipEventCreate(&e1));
+    }
+    ~EventPair() {
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    }
+    EventPair(const EventPair&) = delete;
+    EventPair& operator=(const EventPair&) = delete;
+};
+// milliseconds per call of `iters` calls of run() on `s`, between two events
+template <class Run>
+double time_launches(hipStream_t s, int iters, Run&& run) {
+    EventPair ev;
+    IRSDE_HIP_CHECK(hipEventRecord(ev.e0, s));
+    for (int i = 0; i < iters; ++i) run();
+    IRSDE_HIP_CHECK(hipEventRecord(ev.e1, s));
+    IRSDE_HIP_CHECK(hipStreamSynchronize(s));
+    float ms = 0.f;
+    IRSDE_HIP_CHECK(hipEventElapsedTime(&ms, ev.e0, ev.e1));
+    return ms / iters;
+}
+
+// irsde_debug_conv / irsde_bench_conv only: selects a kernel variant for the launches of ONE call and always returns to
+// the production dispatch (also when a launch throws).
+struct VariantScope {
+    explicit VariantScope(int v) { conv_set_variant(v); }
+    ~VariantScope() { conv_set_variant(0); }
+};
+
+// The selector codes irsde_debug_conv / irsde_bench_conv know (see their branches): any other code is refused, never run as the production dispatch.
+bool code_in(const std::initializer_list<int>& codes, int c) { return std::find(codes.begin(), codes.end(), c) != codes.end(); }
+bool debug_conv_code_known(int c) {
+    return code_in({0, 1, 2, 3, 4, 5, 12, 13, 22, 23, 33, 34, 35, 36, 37, 42, 43, 44, 45, 46, 47, 55, 56, 62, 63, 204, 260, 261, 262, 263}, c) ||
+           code_in({100, 103, 105, 106, 107, 150, 160, 161, 162, 163, 165, 166, 167, 170, 171, 172, 173}, c);   // 100 + a launch_conv tuning variant
+}
+bool bench_conv_variant_known(int v) {
+    return code_in({0, 3, 5, 6, 7, 50, 60, 61, 62, 63, 64, 65, 66, 67, 70, 71, 72, 73}, v) ||   // launch_conv and its tuning variants
+           code_in({80, 81, 82, 412, 413, 421, 422, 423, 430, 431, 432, 434, 435, 460, 461, 462, 465, 467, 468, 469, 480, 481, 482}, v) ||
+           code_in({2001, 2002, 2004, 4650, 4651, 4652, 4653}, v) ||
+           (v >= 83 && v <= 82 + 255) ||   // the 32-cout fused kernel with tuning-aid flags v - 82
+           (v >= 472 && v <= 476);         // the pair GEMM's ablation twins (launch_gemm_split_pairs refuses the ones it lacks)
+}
+
+}  // namespace
+}  // namespace irsde
+
+extern "C" {
+
+int irsde_debug_scam(const float* x, int B, int H, int W, int C, const float* norm_l_g, const float* norm_r_g, const float* l_proj1_w,
+                     const float* l_proj1_b, const float* r_proj1_w, const float* r_proj1_b, const float* l_proj2_w, const float* l_proj2_b,
+                     const float* r_proj2_w, const float* r_proj2_b, const float* beta, const float* gamma, float* out, void* stream) {
+    return guard([&] {
+        if (!x || !out || !norm_l_g || !norm_r_g || !l_proj1_w || !l_proj1_b || !r_proj1_w || !r_proj1_b || !l_proj2_w || !l_proj2_b || !r_proj2_w ||
+            !r_proj2_b || !beta || !gamma)
+            throw HipError("null argument");
+        if (B < 1) throw HipError("debug_scam: bad shape");
+        scam_check_shape(H, W, C);
+        hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+        conv_global_init();
+        const int Hs = H / 4, Ws = W / 4;
+        std::vector<float> wl, bl, wr, br;
+        scam_pack_proj(l_proj1_w, l_proj1_b, l_proj2_w, l_proj2_b, C, wl, bl);
+        scam_pack_proj(r_proj1_w, r_proj1_b, r_proj2_w, r_proj2_b, C, wr, br);
+        Scratch mem(s);
+        auto up = [&](const float* h, size_t n) {
+            float* d = mem.alloc<float>(std::max<size_t>(n, 16));
+            if (h) IRSDE_HIP_CHECK(hipMemcpy(d, h, n * 4, hipMemcpyHostToDevice));
+            return d;
+        };
+        float *dgl = up(norm_l_g, C), *dgr = up(norm_r_g, C), *dbe = up(beta, C), *dga = up(gamma, C);
+        float *dwl = up(wl.data(), wl.size()), *dbl = up(bl.data(), bl.size()), *dwr = up(wr.data(), wr.size()), *dbr = up(br.data(), br.size());
+        const size_t vsz = (size_t)B * Hs * Ws * 2 * C;
+        float *xs2 = up(nullptr, 2 * vsz), *qv = up(nullptr, 2 * vsz), *F = up(nullptr, vsz), *dz = up(nullptr, 256);
+        IRSDE_HIP_CHECK(hipMemset(dz, 0, 1024));
+        launch_scam_prologue(x, dgl, dgr, xs2, B, H, W, C, s);
+        for (int v = 0; v < 2; ++v) {
+            ConvParams p;
+            p.in0 = xs2 + v * vsz; p.C0 = 2 * C; p.pix0 = 2 * C;
+            p.Hin = Hs; p.Win = Ws;
+            p.w = v ? dwr : dwl; p.Cout = 2 * C; p.KH = p.KW = 1; p.stride = 1;
+            p.B = B; p.Ho = Hs; p.Wo = Ws;
+            p.out = qv + v * vsz; p.out_stride = 2 * C;
+            p.bias = v ? dbr : dbl;
+            p.zeros = dz;
+            launch_conv(p, s);
+        }
+        launch_scam_core(qv, F, B, H, W, C, s);
+        launch_scam_epilogue(x, F, dbe, dga, out, B, H, W, C, s);
+        IRSDE_HIP_CHECK(hipStreamSynchronize(s));
+    });
+}
+
+int irsde_debug_conv(const float* in0, int C0, const float* in1, int C1, int B, int Hin, int Win, int in_shift,
+                     const float* w_oihw, int Cout, int KH, int KW, int stride, int pad, const float* bias,
+                     const float* film, int film_bstride, int silu, const float* res, float* out, int naive,
+                     int splits, void* stream) {
+    return guard([&] {
+        if (!in0 || !w_oihw || !out) throw HipError("null argument");
+        if (!debug_conv_code_known(naive)) throw HipError("debug_conv: unknown selector code " + std::to_string(naive));
+        hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+        conv_global_init();
+        const int Cin = C0 + C1;
+        std::vector<float> pk((size_t)Cout * KH * KW * Cin);
+        for (int o = 0; o < Cout; ++o)
+            for (int i = 0; i < Cin; ++i)
+                for (int ky = 0; ky < KH; ++ky)
+                    for (int kx = 0; kx < KW; ++kx)
+                        pk[(((size_t)o * KH + ky) * KW + kx) * Cin + i] = w_oihw[(((size_t)o * Cin + i) * KH + ky) * KW + kx];
+        Scratch mem(s);
+        float* dw = mem.upload(pk);
+        float* db = bias ? mem.upload(bias, Cout) : nullptr;
+        ConvParams p;
+        p.in0 = in0; p.C0 = C0; p.pix0 = C0; p.in1 = in1; p.C1 = C1; p.pix1 = C1;
+        p.Hin = Hin; p.Win = Win; p.in_shift = in_shift;
+        p.w = dw; p.Cout = Cout; p.KH = KH; p.KW = KW; p.stride = stride; p.pad_y = pad; p.pad_x = pad;
+        p.B = B;
+        p.Ho = ((Hin << in_shift) + 2 * pad - KH) / stride + 1;
+        p.Wo = ((Win << in_shift) + 2 * pad - KW) / stride + 1;
+        p.out = out; p.out_stride = Cout; p.bias = db; p.film = film; p.film_bstride = film_bstride; p.silu = silu;
+        p.res = res; p.res_stride = Cout;
+        float* dz = mem.alloc<float>(256);
+        IRSDE_HIP_CHECK(hipMemset(dz, 0, 1024));
+        p.zeros = dz;
+        const int wino_tile = (naive == 2 || naive == 12 || naive == 22) ? 2 : (naive == 3 || naive == 13 || naive == 23) ? 4 : 0;
+        if (splits > 1 && naive != 1 && !wino_tile) {
+            p.splits = splits;
+            p.partial = mem.alloc<float>((size_t)splits * B * p.Ho * p.Wo * Cout);
+        }
+        if (naive == 44 || naive == 45) {  // three-launch Winograd F(4x4,3x3) with the engine's pair GEMM: 44 fp16 pairs, 45 bf16 pairs
+            const bool f16 = naive == 44;
+            if (!wino_shape_ok(p, 4) || Cin % 32) throw HipError("debug_conv: shape not eligible for the pair GEMM");
+            std::vector<float> U((size_t)36 * Cout * Cin);
+            wino_transform_weights(pk.data(), Cout, Cin, U.data(), 4);
+            const float us = f16 ? pow2_scale_into_512(U.data(), U.size()) : 1.f;
+            const long long T = (long long)B * (p.Ho / 4) * (p.Wo / 4);
+            float* dU = mem.upload(U);
+            unsigned short* dUp = mem.alloc<unsigned short>(2 * U.size());
+            unsigned short* dVp = mem.alloc<unsigned short>((size_t)36 * T * Cin * 2);
+            float* dM = mem.alloc<float>((size_t)36 * T * Cout);
+            launch_split_pairs(dU, dUp, (size_t)36 * Cout, Cin, s, f16, us);
+            const WinoSplitPlan sp = make_wino_pairs(p, dUp, dVp, dM, f16, us);
+            launch_wino_input(sp.in, s);
+            launch_gemm_split_pairs(sp.gemm, 36, s, 0, f16);
+            launch_wino_output(sp.out, s);
+        } else if (naive == 42 || naive == 43) {  // three-launch Winograd F(4x4,3x3) with split-operand component GEMMs: 2 / 3 bf16 planes
+            const int npl = naive - 40;
+            if (!wino_shape_ok(p, 4)) throw HipError("debug_conv: shape not eligible for Winograd");
+            std::vector<float> U((size_t)36 * Cout * Cin);
+            wino_transform_weights(pk.data(), Cout, Cin, U.data(), 4);
+            const long long T = (long long)B * (p.Ho / 4) * (p.Wo / 4);
+            float* dU = mem.upload(U);
+            unsigned short* dUs = mem.alloc<unsigned short>(U.size() * npl);
+            unsigned short* dVs = mem.alloc<unsigned short>((size_t)36 * T * Cin * npl);
+            float* dM = mem.alloc<float>((size_t)36 * T * Cout);
+            launch_split_planes(dU, dUs, U.size(), U.size(), npl, s);
+            const WinoSplitPlan sp = make_wino_split(p, dUs, dVs, dM, npl);
+            launch_wino_input(sp.in, s);
+            launch_gemm_split(sp.gemm, npl, 36, s);
+            launch_wino_output(sp.out, s);
+        } else if (naive == 35 || naive == 37 || naive == 56) {  // the 64-cout fused Winograd kernel on fp16 hi + lo operand pairs (IRSDE_FLAG_SPLIT_F16X2's big-feature-map path)
+            if (!wino_fused64_eligible(p)) throw HipError("debug_conv: shape not eligible for the fused Winograd kernel");
+            std::vector<float> U((size_t)36 * Cout * Cin), Uf((size_t)36 * Cout * Cin);
+            wino_transform_weights(pk.data(), Cout, Cin, U.data(), 4);
+            wino_fused64_pack_weights(U.data(), Cout, Cin, Uf.data());
+            const float usc = pow2_scale_into_512(U.data(), U.size());
+            float* dUf = mem.upload(Uf);
+            unsigned short* dUp = mem.alloc<unsigned short>(2 * Uf.size());
+            launch_wino_fused64_split_weights(dUf, dUp, Uf.size(), usc, s);
+            p.pair_scale = 1.0f / (kWinoFused64PairVScale * usc);
+            launch_wino_fused64(p, reinterpret_cast<const float*>(dUp), s, naive == 56 ? 24 : naive == 37 ? 4 + 64 : 4);   // 37: + cout block by XCD where legal
+        } else if (naive == 33 || naive == 34 || naive == 36 || naive == 55 || naive == 62 || naive == 63) {  // fused Winograd F(4x4,3x3) kernels (wino_fused.hip): 33 = 32 couts per block, 34 = 64
+            if (naive == 33 ? !wino_fused_eligible(p) : !wino_fused64_eligible(p)) throw HipError("debug_conv: shape not eligible for the fused Winograd kernel");
+            std::vector<float> U((size_t)36 * Cout * Cin), Uf((size_t)36 * Cout * Cin);
+            wino_transform_weights(pk.data(), Cout, Cin, U.data(), 4);
+            if (naive == 33) wino_fused_pack_weights(U.data(), Cout, Cin, Uf.data());
+            else wino_fused64_pack_weights(U.data(), Cout, Cin, Uf.data());
+            float* dUf = mem.upload(Uf);
+            if (naive == 62 || naive == 63) {   // r06: the two-tile-group kernel (wino_fused_t.hip; 63: + cout block by XCD where legal)
+                if (!wino_fused64t_eligible(p)) throw HipError("debug_conv: shape not eligible for the two-tile-group fused Winograd kernel");
+                launch_wino_fused64t(p, dUf, s, naive == 63 ? 64 : 0);
+            } else
+            if (naive == 33) launch_wino_fused(p, dUf, s);
+            else launch_wino_fused64(p, dUf, s, naive == 55 ? 20 : naive == 36 ? 64 : 0);   // 36: + cout block by XCD where legal; 55: the production variant by number
+        } else if (wino_tile) {  // naive / 10: 0 = production dispatch, 1 / 2 = force the batch-loop GEMM kernel (all / 2 components per block)
+            const int tile = wino_tile, ncomp = (tile + 2) * (tile + 2);
+            if (!wino_shape_ok(p, tile)) throw HipError("debug_conv: shape not eligible for Winograd");
+            std::vector<float> U((size_t)ncomp * Cout * Cin);
+            wino_transform_weights(pk.data(), Cout, Cin, U.data(), tile);
+            const long long T = (long long)B * (p.Ho / tile) * (p.Wo / tile);
+            float* dU = mem.upload(U);
+            float* dV = mem.alloc<float>((size_t)ncomp * T * Cin);
+            float* dM = mem.alloc<float>((size_t)ncomp * T * Cout);
+            const WinoPlan wp = make_wino(p, dU, dV, dM, tile);
+            launch_wino_input(wp.in, s);
+            {
+                VariantScope vs(naive >= 20 ? 72 : naive >= 10 ? 71 : 0);
+                launch_conv(wp.gemm, s);
+            }
+            launch_wino_output(wp.out, s);
+        } else if (naive == 46 || naive == 47) {   // direct implicit GEMM on the PAIR kernels: 46 fp16 hi + lo pieces, 47 bf16
+            const bool f16 = naive == 46;
+            const float sc = f16 ? pow2_scale_into_512(pk.data(), pk.size()) : 1.f;
+            unsigned short* dwp = mem.alloc<unsigned short>(2 * pk.size());
+            launch_split_pairs(dw, dwp, (size_t)Cout, KH * KW * (C0 + C1), s, f16, sc);
+            p.w_pair = dwp; p.pair_scale = 1.0f / sc; p.f16 = f16 ? 1 : 0;
+            launch_conv(p, s);
+        } else if (naive == 1) {
+            launch_conv_naive(p, s);
+        } else {   // the direct kernels: 0 production dispatch, 4 / 5 bf16 / fp16 operands, 204 / 26x bf16 activation storage, 100 + v launch_conv tuning variant v
+            unsigned short* ao = nullptr;
+            const bool act = naive == 204 || (naive >= 260 && naive <= 263);  // + bf16 activation storage (IRSDE_FLAG_BF16_ACT)
+            if (naive == 4 || (naive >= 160 && naive <= 163) || act) {  // bf16-MFMA mode (variants 60 / 61: force the 256 / 128 tile; 64 / 65: the 512- / 256-pixel halo kernel)
+                unsigned short* dbf = mem.alloc<unsigned short>(pk.size());
+                launch_f32_to_bf16(dw, dbf, pk.size(), s);
+                p.w_bf = dbf;
+            }
+            const bool f16 = naive == 5 || (naive >= 165 && naive <= 167);  // fp16-MFMA mode: production dispatch / generic 128-row tile / 512- / 256-pixel halo kernel
+            if (f16) {
+                unsigned short* dbf = mem.alloc<unsigned short>(pk.size());
+                launch_f32_to_f16(dw, dbf, pk.size(), s);
+                p.w_bf = dbf;
+                p.f16 = 1;
+            }
+            const size_t npix_in = (size_t)B * Hin * Win, nout = (size_t)B * p.Ho * p.Wo * Cout;
+            if (act) {  // the caller's fp32 tensors are rounded into bf16 copies; the bf16 result is widened back
+                auto to_bf = [&](const float* src, size_t n) {
+                    unsigned short* d = mem.alloc<unsigned short>(n + 32);
+                    launch_f32_to_bf16(src, d, n, s);
+                    return reinterpret_cast<const float*>(d);
+                };
+                p.in0 = to_bf(in0, npix_in * C0);
+                if (in1) p.in1 = to_bf(in1, npix_in * C1);
+                if (res) p.res = to_bf(res, nout);
+                ao = mem.alloc<unsigned short>(nout + 32);
+                p.out = reinterpret_cast<float*>(ao);
+                p.in_bf16 = p.out_bf16 = 1;
+            }
+            {
+                const int halo_v = (naive == 162 || naive == 262 || naive == 166) ? 64 : (naive == 163 || naive == 263 || naive == 167) ? 65 : 0;   // 64 / 65: force the 512- / 256-pixel halo kernel
+                VariantScope vs(halo_v ? halo_v : f16 ? (naive == 165 ? 61 : 0) : act ? (naive == 204 ? 0 : naive - 200) : (naive >= 100 ? naive - 100 : 0));  // tile variants
+                launch_conv(p, s);
+            }
+            if (act) launch_bf16_to_f32(ao, out, nout, s);
+        }
+        IRSDE_HIP_CHECK(hipStreamSynchronize(s));
+    });
+}
+
+int irsde_debug_split_gemm(const float* A, const float* Bm, float* C, int M, int N, int K, int ncomp, int nplanes, void* stream) {
+    return guard([&] {
+        // nplanes 2 / 3: the 128 x 128 plane-major prototype kernel; 42 / 44: the engine's pair-interleaved two-plane kernel
+        if (nplanes != 2 && nplanes != 3 && nplanes != 42 && nplanes != 44) throw HipError("debug_split_gemm: nplanes must be 2, 3, 42 or 44");
+        hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+        conv_global_init();
+        const size_t na = (size_t)ncomp * M * K, nb = (size_t)ncomp * N * K;
+        Scratch mem(s);
+        if (nplanes == 42 || nplanes == 44) {   // the pair-interleaved two-plane kernel (LDS-DMA, 256 x 256 tiles): 42 bf16 pieces, 44 fp16 pieces
+            const bool f16 = nplanes == 44;
+            const float sa = f16 ? 1.0f / 16.0f : 1.f, sb = f16 ? 64.0f : 1.f;   // (any powers of two: the hook exercises the scaling)
+            unsigned short *pa = mem.alloc<unsigned short>(2 * na), *pb = mem.alloc<unsigned short>(2 * nb);
+            launch_split_pairs(A, pa, (size_t)ncomp * M, K, s, f16, sa);
+            launch_split_pairs(Bm, pb, (size_t)ncomp * N, K, s, f16, sb);
+            SplitGemmArgs gp;
+            gp.a = pa; gp.b = pb; gp.out = C;
+            gp.pA = (long long)M * K; gp.pB = (long long)N * K; gp.pO = (long long)M * N;
+            gp.M = M; gp.N = N; gp.K = K; gp.lda = K; gp.ldc = N;
+            gp.out_scale = 1.0f / (sa * sb);
+            launch_gemm_split_pairs(gp, ncomp, s, 0, f16);
+            IRSDE_HIP_CHECK(hipStreamSynchronize(s));
+            return;
+        }
+        unsigned short *da = mem.alloc<unsigned short>(na * nplanes), *db = mem.alloc<unsigned short>(nb * nplanes);
+        launch_split_planes(A, da, na, na, nplanes, s);
+        launch_split_planes(Bm, db, nb, nb, nplanes, s);
+        SplitGemmArgs g;
+        g.a = da; g.b = db; g.out = C;
+        g.plA = (long long)na; g.plB = (long long)nb;
+        g.pA = (long long)M * K; g.pB = (long long)N * K; g.pO = (long long)M * N;
+        g.M = M; g.N = N; g.K = K; g.lda = K; g.ldc = N;
+        g.n_inner = gemm_split_inner(M, N, ncomp);
+        launch_gemm_split(g, nplanes, ncomp, s);
+        IRSDE_HIP_CHECK(hipStreamSynchronize(s));
+    });
+}
+
+int irsde_debug_force_chain_groups(int g) {
+    set_force_chain_groups(g == 1 || g == 2 || g == 4 ? g : 0);
+    return IRSDE_OK;
+}
+
+int irsde_debug_force_subbatches(int n) {
+    set_force_subbatches(n < 0 ? 0 : n);
+    return IRSDE_OK;
+}
+
+int irsde_bench_naf_chain(int variant, int nblocks, int B, int iters, double* ms_out) {
+    return guard([&] {
+        if (!ms_out || nblocks < 1 || nblocks > 64 || B < 1 || iters < 1) throw HipError("bench_naf_chain: bad argument");
+        // 0 / 1 production; 11 (PROBES build) its cycle stamps; r06: 22 / 24 = the kernel with 2 / 4 work-groups per image, 25 (PROBES build) 24 + its cycle
+        // stamps, 26 (PROBES build) 24 with one group per image missing — must report the spin timeout
+        const int G = variant == 22 ? 2 : (variant == 24 || variant == 25 || variant == 26) ? 4 : 1;
+#ifdef IRSDE_PROBES
+        if (variant != 0 && variant != 1 && variant != 11 && G == 1) throw HipError("bench_naf_chain: bad variant");
+#else
+        if (variant != 0 && variant != 1 && G == 1) throw HipError("bench_naf_chain: variant 11 is a measurement twin (make PROBES=1)");   // (before anything is allocated)
+#endif
+        conv_global_init();
+        OwnedStream stream(hipStreamDefault);
+        hipStream_t s = stream.s;
+        Scratch mem(s);
+        const size_t nx = (size_t)B * 64 * 512, nw = naf_chain_weight_halves(nblocks), nv = naf_chain_vec_floats(nblocks);
+        float *dx = mem.alloc<float>(nx), *dout = mem.alloc<float>(nx), *dvec = mem.alloc<float>(nv), *dfilm = mem.alloc<float>((size_t)nblocks * 2048);
+        unsigned short* dw = mem.alloc<unsigned short>(nw);
+        const size_t chunk = (size_t)64 << 20;   // f32 staging of the random weights, converted to fp16 piecewise
+        float* dwf = mem.alloc<float>(chunk);
+        launch_fill_random(dx, nx, 1, 1.0f, s);
+        launch_fill_random(dvec, nv, 2, 0.1f, s);
+        launch_fill_random(dfilm, (size_t)nblocks * 2048, 3, 0.1f, s);
+        for (size_t o = 0; o < nw; o += chunk) {
+            const size_t n = std::min(chunk, nw - o);
+            launch_fill_random(dwf, n, 4 + (unsigned)(o / chunk), 0.04f, s);
+            launch_f32_to_f16(dwf, dw + o, n, s);
+        }
+        unsigned short* dwg = nullptr;
+        void* dscratch = nullptr;
+        if (G > 1) {
+            IRSDE_HIP_CHECK(hipStreamSynchronize(s));
+            dwg = mem.alloc<unsigned short>(nw);
+            naf_chain_build_split_weights(dw, dwg, nblocks, G, s);
+            dscratch = mem.alloc<char>(naf_chain_split_scratch_bytes(B));
+            IRSDE_HIP_CHECK(hipMemset(dscratch, 0, naf_chain_split_scratch_bytes(B)));
+        }
+        auto run = [&]() {
+            if (G > 1) launch_naf_chain_split(dx, dout, dwg, dvec, nblocks, B, dfilm, 0, 0, nullptr, 0, 0, G, dscratch, s);
+            else launch_naf_chain(dx, dout, dw, dvec, nblocks, B, dfilm, 0, 0, nullptr, 0, 0, s, variant == 11 ? 1 : variant);
+        };
+        if (variant == 26) {
+#ifdef IRSDE_PROBES
+            naf_chain_set_sabotage(1);
+#else
+            throw HipError("bench_naf_chain: variant 26 is a PROBES-build test");
+#endif
+        }
+        struct SabotageOff { ~SabotageOff() { naf_chain_set_sabotage(0); } } sabotage_off;
+        run();   // warm
+        if (variant == 25) {
+#ifdef IRSDE_PROBES
+            const int ng = naf_chain_split_groups(B, 4);
+            unsigned long long* dd = mem.alloc<unsigned long long>((size_t)ng * 8 * 16);
+            IRSDE_HIP_CHECK(hipMemsetAsync(dd, 0, (size_t)ng * 8 * 16 * 8, s));
+            naf_chain_set_debug(dd);
+            run();
+            IRSDE_HIP_CHECK(hipStreamSynchronize(s));
+            naf_chain_set_debug(nullptr);
+            std::vector<unsigned long long> hd((size_t)ng * 8 * 16);
+            IRSDE_HIP_CHECK(hipMemcpy(hd.data(), dd, hd.size() * 8, hipMemcpyDeviceToHost));
+            double acc[16] = {0};
+            double nwv = 0;
+            for (size_t w = 0; w < (size_t)ng * 8; ++w) {
+                if (!hd[w * 16 + 15]) continue;   // (a group of an image slot past the batch)
+                for (int k = 0; k < 16; ++k) acc[k] += (double)hd[w * 16 + k];
+                nwv += 1;
+            }
+            static const char* names[12] = {"norm1 (incl. residual-stream fetch)", "conv1 GEMM passes", "depthwise 3x3 + gate + pool", "gated fetch behind barrier (pool)", "sca.1 GEMM", "conv3 GEMM + residual", "norm2 (incl. residual-stream fetch)", "conv4 GEMM + gate", "conv5 GEMM + residual", "scale-vector / gated fetch (sca, conv4)", "group barriers (6 per block)", "publishing (gated slice, residual slice)"};
+            printf("naf_chain stamps, 4 groups per image: %d blocks, B=%d; shader cycles per wave and block (mean over %.0f waves)\n", nblocks, B, nwv);
+            for (int k = 0; k < 12; ++k) printf("  %-42s %9.0f\n", names[k], acc[k] / nwv / nblocks);
+            printf("  %-42s %9.0f\n", "whole kernel / blocks", acc[15] / nwv / nblocks);
+            fflush(stdout);
+#else
+            throw HipError("bench_naf_chain: variant 25 is a measurement twin (make PROBES=1)");
+#endif
+        }
+        if (variant == 11) {   // the stamp twin once: per-phase cycle budget per block, averaged over all waves
+            unsigned long long* dd = mem.alloc<unsigned long long>((size_t)B * 8 * 16);
+            IRSDE_HIP_CHECK(hipMemsetAsync(dd, 0, (size_t)B * 8 * 16 * 8, s));
+            naf_chain_set_debug(dd);
+            launch_naf_chain(dx, dout, dw, dvec, nblocks, B, dfilm, 0, 0, nullptr, 0, 0, s, 11);
+            IRSDE_HIP_CHECK(hipStreamSynchronize(s));
+            naf_chain_set_debug(nullptr);
+            std::vector<unsigned long long> hd((size_t)B * 8 * 16);
+            IRSDE_HIP_CHECK(hipMemcpy(hd.data(), dd, hd.size() * 8, hipMemcpyDeviceToHost));
+            double acc[16] = {0};
+            for (size_t i = 0; i < hd.size(); ++i) acc[i % 16] += (double)hd[i];
+            const double nwv = (double)B * 8, nb = nblocks;
+            static const char* names[10] = {"norm1", "conv1 GEMM passes", "depthwise 3x3 + gate + pool", "barrier (pool)", "sca.1 GEMM", "conv3 GEMM + residual", "norm2", "conv4 GEMM + gate", "conv5 GEMM + residual", "barriers (sca, conv4)"};
+            printf("naf_chain stamps: %d blocks, B=%d; shader cycles per wave and block (mean over %d waves); MFMA floor per wave: conv1 / conv4 512 x 16, conv3 / conv5 256 x 16, sca 64 x 16\n", nblocks, B, B * 8);
+            for (int k = 0; k < 10; ++k) printf("  %-30s %9.0f\n", names[k], acc[k] / nwv / nb);
+            printf("  %-30s %9.0f\n", "whole kernel / blocks", acc[15] / nwv / nb);
+            fflush(stdout);
+        }
+        *ms_out = time_launches(s, iters, run);
+        if (G > 1) {
+            unsigned flag = 0;
+            IRSDE_HIP_CHECK(hipMemcpy(&flag, naf_chain_split_error_flag(dscratch, B), 4, hipMemcpyDeviceToHost));
+            if (flag) throw HipError("bench_naf_chain: the split kernel's groups were not co-resident (spin timeout)");
+        }
+    });
+}
+
+int irsde_bench_conv(int variant, int B, int H, int W, int Cin, int Cout, int K, int stride, int up, int epi, int iters,
+                     double* ms_out) {
+    return guard([&] {
+        if (!ms_out || iters < 1) throw HipError("bad argument");
+        if (!bench_conv_variant_known(variant)) throw HipError("bench_conv: unknown variant " + std::to_string(variant));
+        conv_global_init();
+        OwnedStream stream(hipStreamNonBlocking);
+        hipStream_t s = stream.s;
+        Scratch mem(s);
+        ConvParams p;
+        p.B = B; p.Hin = H; p.Win = W; p.in_shift = up; p.C0 = Cin; p.pix0 = Cin;
+        p.Cout = Cout; p.KH = K; p.KW = K; p.stride = stride; p.pad_y = p.pad_x = (K == 4 ? 1 : K / 2);
+        p.Ho = ((H << up) + 2 * p.pad_y - K) / stride + 1;
+        p.Wo = ((W << up) + 2 * p.pad_x - K) / stride + 1;
+        const size_t nin = (size_t)B * H * W * Cin, nw = (size_t)Cout * K * K * Cin, nout = (size_t)B * p.Ho * p.Wo * Cout;
+        float *din = mem.alloc<float>(nin), *dw = mem.alloc<float>(nw), *dout = mem.alloc<float>(nout), *dres = mem.alloc<float>(nout);
+        float* dfilm = mem.alloc<float>((size_t)2 * Cout + 256);   // + the zero page
+        float* dz = dfilm + 2 * Cout;
+        IRSDE_HIP_CHECK(hipMemset(dz, 0, 1024));
+        p.zeros = dz;
+        launch_fill_random(din, nin, 1, 1.0f, s);
+        launch_fill_random(dw, nw, 2, 1.0f / sqrtf((float)(K * K * Cin)), s);
+        launch_fill_random(dres, nout, 3, 1.0f, s);
+        launch_fill_random(dfilm, (size_t)2 * Cout, 4, 0.3f, s);
+        p.in0 = din; p.w = dw; p.out = dout; p.out_stride = Cout;
+        const int halo_force = (variant == 64 || variant == 66) ? 64 : (variant == 65 || variant == 67) ? 65 : 0;   // r05: 64 / 65 = variant 62 with the 512- / 256-pixel halo kernel forced, 66 / 67 = the same on variant 63
+        if (halo_force) variant = variant <= 65 ? 62 : 63;
+        if (variant >= 60 && variant <= 63) {  // bf16-MFMA mode: 60 = 256x256 tile, 61 = 128x128, 62 = automatic, 63 = automatic + bf16 activations
+            unsigned short* dbf = mem.alloc<unsigned short>(nw);
+            launch_f32_to_bf16(dw, dbf, nw, s);
+            p.w_bf = dbf;
+        }
+        if (epi == 1) { p.film = dfilm; p.silu = 1; }
+        if (epi == 2) { p.silu = 1; p.res = dres; p.res_stride = Cout; }
+        if (variant == 63) {  // bf16 activation storage (the output / residual buffers are simply twice the size needed)
+            unsigned short* dabf = mem.alloc<unsigned short>(nin);
+            launch_f32_to_bf16(din, dabf, nin, s);
+            launch_f32_to_bf16(dout, reinterpret_cast<unsigned short*>(dres), nout / 2, s);
+            p.in0 = reinterpret_cast<const float*>(dabf);
+            p.in_bf16 = 1; p.out_bf16 = 1;
+        }
+        // 80: fused Winograd F(4x4,3x3) kernel; 81: the three-launch Winograd F(4x4,3x3) path (random U: timing only)
+        float* dU = nullptr;
+        WinoPlan wp{};
+        if (variant == 480 || variant == 481 || variant == 482) {   // direct convolution on the PAIR kernels: 480 fp16 pieces, 481 bf16 pieces, 482 = 480 without the 256 x 256 tile
+            unsigned short* dwp = mem.alloc<unsigned short>(2 * nw);
+            launch_split_pairs(dw, dwp, (size_t)Cout, K * K * Cin, s, variant != 481, 64.0f);
+            p.w_pair = dwp; p.pair_scale = 1.0f / 64.0f; p.f16 = variant != 481 ? 1 : 0;
+            variant = variant == 482 ? 61 : 0;
+        }
+        if (variant >= 472 && variant <= 476) {   // the pair-interleaved two-plane component GEMMs alone (v3 kernel): 472 full, 473 no loads, 475 no MFMAs, 476 no output stores
+            if (K != 3 || stride != 1 || !wino_shape_ok(p, 4)) throw HipError("bench_conv: Winograd variants need an eligible 3x3 stride-1 layer");
+            const long long T = (long long)B * (p.Ho / 4) * (p.Wo / 4);
+            float *vf = mem.alloc<float>((size_t)36 * T * Cin), *uf = mem.alloc<float>((size_t)36 * Cout * Cin), *mo = mem.alloc<float>((size_t)36 * T * Cout);
+            unsigned short *vp = mem.alloc<unsigned short>((size_t)36 * T * Cin * 2), *up = mem.alloc<unsigned short>((size_t)36 * Cout * Cin * 2);
+            launch_fill_random(vf, (size_t)36 * T * Cin, 7, 1.0f, s);
+            launch_fill_random(uf, (size_t)36 * Cout * Cin, 8, 0.05f, s);
+            launch_split_pairs(vf, vp, (size_t)36 * T, Cin, s);
+            launch_split_pairs(uf, up, (size_t)36 * Cout, Cin, s);
+            SplitGemmArgs gp;
+            gp.a = vp; gp.b = up; gp.out = mo;
+            gp.pA = T * Cin; gp.pB = (long long)Cout * Cin; gp.pO = T * Cout;
+            gp.M = (int)T; gp.N = Cout; gp.K = Cin; gp.lda = Cin; gp.ldc = Cout;
+            const int abl = variant - 472;
+            for (int i = 0; i < 2; ++i) launch_gemm_split_pairs(gp, 36, s, abl);
+            *ms_out = time_launches(s, iters, [&] { launch_gemm_split_pairs(gp, 36, s, abl); });
+            return;
+        }
+        const bool split_v = variant == 412 || variant == 413 || variant == 422 || variant == 423;  // split-operand GEMMs: 41x whole three-launch layer, 42x the GEMM alone; x = planes
+        WinoSplitPlan sp{};
+        if (variant == 80 || variant == 81 || variant == 421 || split_v || (variant >= 83 && variant <= 82 + 255) || (variant >= 430 && variant <= 469) || variant >= 2000) {
+            if (K != 3 || stride != 1) throw HipError("bench_conv: Winograd variants need a 3x3 stride-1 layer");
+            dU = mem.alloc<float>((size_t)36 * nw / 9);
+            launch_fill_random(dU, (size_t)36 * nw / 9, 5, 1.0f / sqrtf((float)(9 * Cin)), s);
+            if (variant != 81 && variant != 421 && !split_v && !wino_fused_eligible(p)) throw HipError("bench_conv: shape not eligible for the fused Winograd kernel");
+            if (variant >= 400 && !wino_fused64_eligible(p)) throw HipError("bench_conv: shape not eligible for the 64-cout fused Winograd kernel");
+            if (variant == 434) {  // the fp16-pair kernel: the random weights as hi / lo halves
+                float* dUp = mem.alloc<float>((size_t)36 * nw / 9);
+                launch_wino_fused64_split_weights(dU, reinterpret_cast<unsigned short*>(dUp), (size_t)36 * nw / 9, 256.0f, s);
+                dU = dUp;
+                p.pair_scale = 1.0f / (kWinoFused64PairVScale * 256.0f);
+            }
+            if (variant == 81 || variant == 421) {
+                if (!wino_shape_ok(p, 4)) throw HipError("bench_conv: shape not eligible for Winograd F(4x4,3x3)");
+                const long long T = (long long)B * (p.Ho / 4) * (p.Wo / 4);
+                float* dV = mem.alloc<float>((size_t)36 * T * Cin);
+                float* dM = mem.alloc<float>((size_t)36 * T * Cout);
+                wp = make_wino(p, dU, dV, dM, 4);
+                if (variant == 421) launch_wino_input(wp.in, s);
+            }
+            if (split_v) {
+                if (!wino_shape_ok(p, 4)) throw HipError("bench_conv: shape not eligible for Winograd F(4x4,3x3)");
+                const int npl = variant % 10;
+                const long long T = (long long)B * (p.Ho / 4) * (p.Wo / 4);
+                const size_t nu = (size_t)36 * Cout * Cin;
+                unsigned short *dUs = mem.alloc<unsigned short>(nu * npl), *dVs = mem.alloc<unsigned short>((size_t)36 * T * Cin * npl);
+                float* dM = mem.alloc<float>((size_t)36 * T * Cout);
+                launch_split_planes(dU, dUs, nu, nu, npl, s);
+                sp = make_wino_split(p, dUs, dVs, dM, npl);
+                launch_wino_input(sp.in, s);
+            }
+        }
+        if (variant == 82) {  // fused Winograd kernel once, with per-wave phase stamps: prints the averaged timeline
+            dU = mem.alloc<float>((size_t)36 * nw / 9);
+            launch_fill_random(dU, (size_t)36 * nw / 9, 5, 1.0f / sqrtf((float)(9 * Cin)), s);
+            const int nb = wino_fused_num_blocks(p);
+            unsigned long long* dd = mem.alloc<unsigned long long>((size_t)nb * 128);
+            launch_wino_fused(p, dU, s);  // warm
+            IRSDE_HIP_CHECK(hipMemsetAsync(dd, 0, (size_t)nb * 128 * 8, s));
+            launch_wino_fused(p, dU, s, dd);
+            IRSDE_HIP_CHECK(hipStreamSynchronize(s));
+            std::vector<unsigned long long> hd((size_t)nb * 128);
+            IRSDE_HIP_CHECK(hipMemcpy(hd.data(), dd, hd.size() * 8, hipMemcpyDeviceToHost));
+            double ph[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
+            unsigned long long rt_min = ~0ull, rt_max = 0;
+            for (int bi = 0; bi < nb; ++bi)
+                for (int w = 0; w < 8; ++w) {
+                    const unsigned long long* t = &hd[((size_t)bi * 8 + w) * 16];
+                    for (int k = 0; k < 4; ++k) ph[w >= 4][k] += (double)(t[k + 1] - t[k]) / ((double)nb * 4);
+                    rt_min = std::min(rt_min, t[7]);
+                    rt_max = std::max(rt_max, t[7]);
+                }
+            // block start times (100 MHz realtime counter) -> how long the launch kept dispatching new blocks
+            printf("wino_fused timeline B=%d %dx%d Cin=%d Cout=%d: %d blocks, block starts span %.1f us\n", B, p.Ho, p.Wo, Cin, Cout, nb,
+                   (double)(rt_max - rt_min) / 100.0);
+            printf("  MFMA waves     (shader cycles): start->V[0] ready %.0f | K loop %.0f | acc->LDS+barrier %.0f | epilogue %.0f\n", ph[0][0],
+                   ph[0][1], ph[0][2], ph[0][3]);
+            printf("  producer waves (shader cycles): start->chunk 0 done %.0f | K loop rest %.0f | wait MFMA+acc %.0f | epilogue %.0f\n",
+                   ph[1][0], ph[1][1], ph[1][2], ph[1][3]);
+            fflush(stdout);
+            *ms_out = 0.0;
+            return;
+        }
+        if (variant == 465 || (variant >= 4650 && variant <= 4653)) {   // r06: the two-tile-group kernel once with per-wave cycle stamps (4650 / 4651 / 4652: no patch traffic / output stores dropped / residual loads dropped)
+            if (!wino_fused64t_eligible(p)) throw HipError("bench_conv: shape not eligible for the two-tile-group fused Winograd kernel");
+            const int nbp = 256;
+            unsigned long long* dd = mem.alloc<unsigned long long>((size_t)nbp * 64);
+            launch_wino_fused64t(p, dU, s, 0);  // warm
+            IRSDE_HIP_CHECK(hipMemsetAsync(dd, 0, (size_t)nbp * 64 * 8, s));
+            wino_fused64t_set_debug(dd);
+            launch_wino_fused64t(p, dU, s, variant == 465 ? 5 : 12 + (variant - 4650));
+            IRSDE_HIP_CHECK(hipStreamSynchronize(s));
+            wino_fused64t_set_debug(nullptr);
+            std::vector<unsigned long long> hd((size_t)nbp * 64);
+            IRSDE_HIP_CHECK(hipMemcpy(hd.data(), dd, hd.size() * 8, hipMemcpyDeviceToHost));
+            double a5[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+            int nwv = 0;
+            for (int bi = 0; bi < nbp; ++bi)
+                for (int w = 0; w < 8; ++w) {
+                    const unsigned long long* t = &hd[((size_t)bi * 8 + w) * 8];
+                    if (!t[3]) continue;
+                    for (int k = 0; k < 8; ++k) a5[k] += (double)t[k];
+                    nwv++;
+                }
+            const int nst = Cin / 16;
+            const double items = a5[4] / std::max(nwv, 1), chunks = items * nst;
+            printf("wino4_fused64t stamps B=%d %dx%d Cin=%d Cout=%d: %.1f items x %d chunks of 16 channels per block; shader cycles per wave (mean over %d waves)\n", B, p.Ho, p.Wo, Cin,
+                   Cout, items, nst, nwv);
+            printf("  kernel %.0f = K loops incl. transform slices %.0f (%.0f per chunk; MFMA floor per SIMD 9216) + chunk barrier waits %.0f (%.0f per chunk) + epilogue, exchange, first-chunk transform %.0f (%.0f per item)\n",
+                   a5[3] / nwv, a5[0] / nwv, a5[0] / nwv / chunks, a5[1] / nwv, a5[1] / nwv / chunks, (a5[2] + a5[5] + a5[6] + a5[7]) / nwv, (a5[2] + a5[5] + a5[6] + a5[7]) / nwv / items);
+            printf("  per item: first stage + exchange writes + ring %.0f | exchange barriers + reads %.0f | second stage, stores, gathers %.0f | zero, first-chunk transform, barrier %.0f\n",
+                   a5[5] / nwv / items, a5[6] / nwv / items, a5[7] / nwv / items, a5[2] / nwv / items);
+            fflush(stdout);
+            *ms_out = 0.0;
+            return;
+        }
+        if (variant == 435 || (variant >= 2001 && variant <= 2004)) {  // the persistent fused Winograd kernel once with per-wave cycle stamps: prints the averaged budget
+            // 2001 / 2002: the stamp twins without weight / patch traffic (2004 = 435)
+            const int stamp_variant = variant == 2001 ? 28 : variant == 2002 ? 29 : 25;
+            const int nbp = 256;
+            unsigned long long* dd = mem.alloc<unsigned long long>((size_t)nbp * 64);
+            launch_wino_fused64(p, dU, s, 20);  // warm
+            IRSDE_HIP_CHECK(hipMemsetAsync(dd, 0, (size_t)nbp * 64 * 8, s));
+            wino_fused64_set_debug(dd);
+            launch_wino_fused64(p, dU, s, stamp_variant);
+            IRSDE_HIP_CHECK(hipStreamSynchronize(s));
+            wino_fused64_set_debug(nullptr);
+            std::vector<unsigned long long> hd((size_t)nbp * 64);
+            IRSDE_HIP_CHECK(hipMemcpy(hd.data(), dd, hd.size() * 8, hipMemcpyDeviceToHost));
+            double acc[2][5] = {{0, 0, 0, 0, 0}, {0, 0, 0, 0, 0}};
+            int nw[2] = {0, 0};
+            for (int bi = 0; bi < nbp; ++bi)
+                for (int w = 0; w < 8; ++w) {
+                    const unsigned long long* t = &hd[((size_t)bi * 8 + w) * 8];
+                    if (!t[3]) continue;
+                    for (int k = 0; k < 5; ++k) acc[w >= 4][k] += (double)t[k];
+                    nw[w >= 4]++;
+                }
+            const int nchk = Cin / 32;
+            const double items = acc[0][4] / std::max(nw[0], 1), chunks = acc[1][4] / std::max(nw[1], 1);
+            printf("wino4_fused64p stamps B=%d %dx%d Cin=%d Cout=%d: %.1f items x %d chunks per block; shader cycles per wave (mean over %d + %d waves)\n", B, p.Ho, p.Wo,
+                   Cin, Cout, items, nchk, nw[0], nw[1]);
+            printf("  MFMA waves    : kernel %.0f = K-loop compute %.0f (%.0f per chunk; MFMA floor 9216) + barrier wait %.0f (%.0f per chunk) + epilogue %.0f (%.0f per item)\n",
+                   acc[0][3] / nw[0], acc[0][0] / nw[0], acc[0][0] / nw[0] / (items * nchk), acc[0][1] / nw[0], acc[0][1] / nw[0] / (items * nchk), acc[0][2] / nw[0],
+                   acc[0][2] / nw[0] / items);
+            printf("  producer waves: kernel %.0f = load issue %.0f (%.0f per chunk) + data wait, transform, LDS writes %.0f (%.0f per chunk) + barrier wait %.0f (%.0f per chunk)\n",
+                   acc[1][3] / nw[1], acc[1][0] / nw[1], acc[1][0] / nw[1] / chunks, acc[1][1] / nw[1], acc[1][1] / nw[1] / chunks, acc[1][2] / nw[1], acc[1][2] / nw[1] / chunks);
+            fflush(stdout);
+            *ms_out = 0.0;
+            return;
+        }
+        auto run = [&] {
+            if (variant == 80) {
+                launch_wino_fused(p, dU, s);
+            } else if (variant >= 467 && variant <= 469) {  // measurement twins of the two-tile-group kernel: no transform arithmetic / + no gathers / no gathers only
+                launch_wino_fused64t(p, dU, s, variant - 461);
+            } else if (variant >= 460 && variant <= 462) {  // r06 two-tile-group kernel: 460 production, 461 / 462 weight fragments / patch gathers read zeros
+                launch_wino_fused64t(p, dU, s, variant - 460);
+            } else if (variant >= 430 && variant <= 434) {  // r04 persistent kernel: 430 production, 431 / 432 weight fragments / patch loads read zeros, 434 fp16 pairs
+                launch_wino_fused64(p, dU, s, variant - 410);
+            } else if (variant >= 83 && variant <= 82 + 255) {  // tuning aids: dflags = variant - 82 (1 no patch traffic, 2 no weight traffic, 4 / 8 producer / MFMA waves at s_setprio 2)
+                launch_wino_fused(p, dU, s, nullptr, variant - 82);
+            } else if (variant == 81) {
+                launch_wino_input(wp.in, s);
+                launch_conv(wp.gemm, s);
+                launch_wino_output(wp.out, s);
+            } else if (variant == 421) {   // the f32 component GEMMs alone
+                launch_conv(wp.gemm, s);
+            } else if (variant == 412 || variant == 413) {
+                launch_wino_input(sp.in, s);
+                launch_gemm_split(sp.gemm, sp.nplanes, 36, s);
+                launch_wino_output(sp.out, s);
+            } else if (variant == 422 || variant == 423) {   // the split-operand component GEMMs alone
+                launch_gemm_split(sp.gemm, sp.nplanes, 36, s);
+            } else {
+                launch_conv(p, s);
+            }
+        };
+        VariantScope vs(halo_force ? halo_force : variant >= 80 || variant == 63 || variant == 62 ? 0 : variant);
+        for (int i = 0; i < 2; ++i) run();
+        *ms_out = time_launches(s, iters, run);
+    });
+}
+
+}  // extern "C"

@@ -17,7 +17,7 @@ struct Builder {
     bool naive;
     int film_bstride;
     int b0 = 0;   // first image of this plan within the call's batch (sub-batch plans): base of the per-image tables
-    const float* film_base() const { return pl->own_film ? pl->own_film : e->film_cur + (size_t)b0 * film_bstride; }
+    const float* film_base() const { return film_of(e, pl) + (size_t)b0 * film_bstride; }   // (a plan with its own row is a sampler plan: film_bstride == 0)
     const float* cam_base() const { return e->cam_cur + (size_t)b0 * e->cam_row; }
     const float* fused_ln_g = nullptr;  // set around a conv() call: LayerNorm gain applied in that conv's epilogue
 
@@ -833,7 +833,7 @@ void build_naf_plan(irsde_engine* e, Plan* pl, Builder& b, int P) {
     pl->pred = pr.p;
 }
 
-// Sub-batches of a NAFNet sampler step (engine_api.hip: sample_split).  Why: on small latents most of a NAFNet evaluation is per-image latency, not
+// Sub-batches of a NAFNet sampler call (engine_api.hip: irsde_sample).  Why: on small latents most of a NAFNet evaluation is per-image latency, not
 // throughput — naf_chain_kernel keeps ONE CU per image busy for ~45 % of the step (64 of 256 CUs at BASELINE configs[4]'s batch of 64) while the other
 // levels' kernels are bandwidth-bound on all CUs: independent sub-batches on concurrent streams let one part's chain run under the other parts' levels.
 // Only where a level actually runs as a chain, and only as two parts of >= 32 images (measured: smaller or more parts lose what the overlap wins).

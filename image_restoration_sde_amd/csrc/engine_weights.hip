@@ -111,11 +111,7 @@ ConvW pack_conv(irsde_engine* e, const std::string& wname, const std::string& bn
                 IRSDE_HIP_CHECK(hipMalloc(&up, U.size() * 4));
                 e->dev_allocs.push_back(reinterpret_cast<float*>(up));
                 const bool f16 = (e->cfg.flags & IRSDE_FLAG_SPLIT_F16X2) != 0;
-                if (f16) {   // power-of-two scale that brings max |U| to (256, 512]: exact, undone by the GEMM
-                    float mx = 0.f;
-                    for (float v : U) mx = std::max(mx, std::fabs(v));
-                    c.wino_up_scale = mx > 0.f ? std::exp2(std::floor(std::log2(512.0f / mx))) : 1.f;
-                }
+                if (f16) c.wino_up_scale = pow2_scale_into_512(U.data(), U.size());   // exact, undone by the GEMM
                 launch_split_pairs(c.wino_u4, up, (size_t)36 * O, I, e->stream, f16, c.wino_up_scale);
                 IRSDE_HIP_CHECK(hipStreamSynchronize(e->stream));
                 c.wino_up = up;
@@ -132,9 +128,7 @@ ConvW pack_conv(irsde_engine* e, const std::string& wname, const std::string& bn
                 wino_fused64_pack_weights(U.data(), O, I, Uf.data());
                 c.wino_uf64 = e->upload(Uf);
                 if ((e->cfg.flags & IRSDE_FLAG_SPLIT_F16X2) && wino_fused64_pair_enabled()) {   // the fp16-pair twin of the kernel: same fragment order
-                    float mx = 0.f;
-                    for (float v : U) mx = std::max(mx, std::fabs(v));
-                    c.wino_uf64p_scale = mx > 0.f ? std::exp2(std::floor(std::log2(512.0f / mx))) : 1.f;
+                    c.wino_uf64p_scale = pow2_scale_into_512(U.data(), U.size());
                     unsigned short* up = nullptr;
                     IRSDE_HIP_CHECK(hipMalloc(&up, Uf.size() * 4));
                     e->dev_allocs.push_back(reinterpret_cast<float*>(up));

@@ -24,16 +24,21 @@ extern "C" {
  *           staged, three cross products on the 16-bit MFMA): fp16 / bf16 pieces
  *   44 / 45 three-launch Winograd F(4x4,3x3) with the engine's pair GEMM (pair-interleaved operands, LDS-DMA): fp16 / bf16 hi + lo pieces
  *   42 / 43 three-launch Winograd F(4x4,3x3) with split-operand component GEMMs on the bf16 MFMA pipe (csrc/gemm_split.hip): 2 / 3 bf16 planes
- *   34 the 64-cout fused Winograd kernel (r03: Cout and C0 + C1 multiples of 64); 36: with its cout-block-by-XCD block mapping forced wherever legal
- *   35 / 37 the same kernel's fp16-pair twin (IRSDE_FLAG_SPLIT_F16X2; all four hi / lo cross products on v_mfma_f32_16x16x32_f16) / with the mapping forced
+ *   34 the 64-cout fused Winograd kernel (r03: Cout and C0 + C1 multiples of 64); 36: with its cout-block-by-XCD block mapping forced wherever legal;
+ *      55: its production variant selected by number
+ *   35 / 37 the same kernel's fp16-pair twin (IRSDE_FLAG_SPLIT_F16X2; all four hi / lo cross products on v_mfma_f32_16x16x32_f16) / with the mapping forced;
+ *      56: the twin's production variant selected by number
+ *   62 / 63 the two-tile-group fused Winograd kernel (r06, csrc/wino_fused_t.hip) / with the cout-block-by-XCD mapping forced wherever legal
  *   33 the fused Winograd F(4x4,3x3) kernel (csrc/wino_fused.hip; 3x3 s1 p1, H and W multiples of 4, C0, C1 and Cout multiples of 32)
  *   4 bf16-MFMA mode (halo kernel for eligible 3x3 layers); 160 / 161 its generic 256 / 128 tile
  *   5 fp16-MFMA mode (IRSDE_FLAG_FP16; halo kernel for eligible 3x3 layers); 165 its generic 128 tile
  *   204 / 260 / 261 the same three with bf16 activation storage (inputs / residual are rounded, the result widened back)
  *   162 / 262 / 166 (r05) modes 4 / 204 / 5 with the 512-pixel x 128-channel halo kernel forced (conv3x3_halo2_kernel; layers with >= 128 output channels),
  *   163 / 263 / 167 with the 256-pixel halo kernel forced
- *   100 + v: tile variant v of the fp32 kernel (3 = 256x128, 50 = 256x256, 73 = tile-loop kernel for 1x1 layers)
- * splits > 1 forces split-K.  Synchronises `stream`. */
+ *   100 + v: tuning variant v of the fp32 kernel: 0 production dispatch, 3 / 50 the 256x128 / 256x256 tile, 5 one block per CU, 6 generic pointer staging
+ *           instead of buffer descriptors, 7 LDS-transposed instead of direct epilogue, 70 the tile-loop kernel off, 71 / 72 its batch-loop form with all / 2
+ *           components per block, 73 the tile-loop kernel forced for 1x1 layers
+ * Any other code is refused.  splits > 1 forces split-K.  Synchronises `stream`. */
 int irsde_debug_conv(const float* in0, int C0, const float* in1, int C1, int B, int Hin, int Win, int in_shift,
                      const float* w_oihw, int Cout, int KH, int KW, int stride, int pad, const float* bias,
                      const float* film, int film_bstride, int silu, const float* res, float* out, int naive,
@@ -44,14 +49,23 @@ int irsde_debug_conv(const float* in0, int C0, const float* in1, int C1, int B, 
  * pair-interleaved two-piece kernel with bf16 / fp16 pieces), products on v_mfma_f32_32x32x16_bf16, f32 accumulate.  K a multiple of 32.  Synchronises `stream`. */
 int irsde_debug_split_gemm(const float* A, const float* B, float* C, int M, int N, int K, int ncomp, int nplanes, void* stream);
 
-/* Kernel tuning hook: average ms of one KxK convolution (pad K/2, or 4x4 s2 p1) on random NHWC data.
- * variant: 0 production dispatch, 3 / 50 fp32 256x128 / 256x256 tiles, 5 one block per CU, 6 generic pointer staging instead of
- * buffer descriptors, 7 LDS-transposed instead of direct epilogue, 60 / 61 / 62 bf16 mode (256 tile / 128 tile / automatic
- * incl. the halo kernel), 63 = 62 with bf16 activation storage, 64 / 65 = 62 and 66 / 67 = 63 with the 512- / 256-pixel halo kernel forced (r05), 80 / 81 Winograd F(4x4,3x3) fused kernel / three-launch path (3x3 s1 only), 82 the fused kernel once with its
- * phase timeline printed to stdout, 400 the 64-cout fused Winograd kernel (r03; 401 / 402: its weight fragments / patch loads read zeros
- * without memory traffic, 403: 12 instead of 18 weight units in flight, 404 / 405: its fp16-pair twin with 12 / 18 units in flight, 406 / 407 / 408: 18 weight units in flight with the non-temporal hint on the epilogue traffic / also on the patch loads / nowhere, 410: 12 units + the epilogue hint (= 400, production)), 412 / 413 the three-launch Winograd layer with split-operand GEMMs (2 / 3
- * bf16 planes on the 128 x 128 plane-major prototype kernel), 421 / 422 / 423 the component GEMMs alone: native f32 / 2 planes / 3 planes, 480 / 481 / 482 a direct layer on the PAIR kernels (fp16 / bf16 pieces / without the 256 x 256 tile), 472 the
- * engine's pair-interleaved two-plane GEMM alone (473 / 475 / 476: without its global loads / MFMAs / output stores); epi: 0 none, 1 FiLM+SiLU, 2 SiLU+residual. */
+/* Kernel tuning hook: average ms of one KxK convolution (pad K/2, or 4x4 s2 p1) on random NHWC data.  variant (any other code is refused):
+ *   0 production dispatch, 3 / 50 fp32 256x128 / 256x256 tiles, 5 one block per CU, 6 generic pointer staging instead of buffer descriptors,
+ *     7 LDS-transposed instead of direct epilogue, 70 the tile-loop kernel off, 71 / 72 its batch-loop form with all / 2 components per block, 73 forced for 1x1 layers
+ *   60 / 61 / 62 bf16 mode (256 tile / 128 tile / automatic incl. the halo kernel), 63 = 62 with bf16 activation storage,
+ *     64 / 65 = 62 and 66 / 67 = 63 with the 512- / 256-pixel halo kernel forced (r05)
+ *   80 / 81 Winograd F(4x4,3x3) fused kernel / three-launch path (3x3 s1 only), 82 the fused kernel once with its phase timeline printed to stdout,
+ *     82 + f (f in 1..255) the fused kernel with tuning-aid flags f (1 no patch traffic, 2 no weight traffic, 4 / 8 producer / MFMA waves at raised priority)
+ *   412 / 413 the three-launch Winograd layer with split-operand GEMMs (2 / 3 bf16 planes on the 128 x 128 plane-major prototype kernel),
+ *     421 / 422 / 423 the component GEMMs alone: native f32 / 2 planes / 3 planes
+ *   430 the 64-cout fused Winograd kernel (r04 persistent form, production), 431 / 432 its weight fragments / patch loads read zeros, 434 its fp16-pair twin,
+ *     435 (= 2004) the kernel once with its per-wave cycle budget printed to stdout, 2001 / 2002 that stamp run without weight / patch traffic
+ *   460 the two-tile-group fused Winograd kernel (r06, production), 461 / 462 its weight fragments / patch gathers read zeros, 467 / 468 / 469 without
+ *     transform arithmetic / also without gathers / without gathers only, 465 the kernel once with its per-wave cycle stamps printed to stdout,
+ *     4650 / 4651 / 4652 that stamp run without patch traffic / output stores / residual loads, 4653 the stamps of the coalesced-epilogue twin (PROBES build)
+ *   472 the engine's pair-interleaved two-plane GEMM alone, 473 / 475 / 476 without its global loads / MFMAs / output stores (474: no such twin, the launch refuses it)
+ *   480 / 481 / 482 a direct layer on the PAIR kernels (fp16 / bf16 pieces / fp16 without the 256 x 256 tile)
+ * epi: 0 none, 1 FiLM+SiLU, 2 SiLU+residual. */
 int irsde_bench_conv(int variant, int B, int H, int W, int Cin, int Cout, int K, int stride, int up, int epi, int iters,
                      double* ms_out);
 /* Times naf_chain_kernel (csrc/naf_chain.hip) alone on synthetic data: `nblocks` consecutive 512-channel NAFBlocks on B images of 8 x 8 pixels,

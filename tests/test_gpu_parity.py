@@ -1408,8 +1408,9 @@ def test_nafnet_levels_64_32_16_vs_oracle(B):
 
 @pytest.mark.parametrize("nsub", [2, 4])
 def test_nafnet_sampler_concurrent_subbatches(nsub):
-    """ABI 105: irsde_sample splits a chain-bearing ConditionalNAFNet batch into concurrent sub-batches (fork / join inside the captured step graph;
-    engine_api.hip: one_step_split).  Forced here at B = 4 (the heuristic starts at 32 images): the split run must reproduce the un-split one — per-image
+    """ABI 105: irsde_sample splits a chain-bearing ConditionalNAFNet batch into concurrent sub-batches: every part is a complete sampler with its own
+    plan, step state, FiLM row, captured step graph and stream, forked once behind the call's inputs and joined once in front of its outputs
+    (engine_api.hip: irsde_sample).  Forced here at B = 4 (the heuristic starts at 8 images): the split run must reproduce the un-split one — per-image
     lens FiLM rows, injected noise and the Philox streams are all addressed by the call-level image index — up to the tilings the smaller plans choose;
     graph replay and eager launches of the split step are bit-identical."""
     L = _lib.lib()
