@@ -9,7 +9,7 @@ csrc/ -> libirsde_hip.so) with the reference's own Python interface on top:
                        codes/utils/sde_utils.py:373-593, codes/config/denoising-sde/models/{modules/DenoisingUNet_arch.py,
                        modules/DenoisingNAFNet_arch.py, denoising_model.py}, codes/utils/deg_utils.py:13-15
     DenoisingModel     codes/config/deraining/models/denoising_model.py (inference surface)
-    latent.UNet / latent.ConditionalNAFNet / LatentDenoisingModel
+    latent.UNet / latent.ConditionalNAFNet / latent.CNAFNetLocal (also exported as CNAFNetLocal) / LatentDenoisingModel
                        codes/config/latent-dehazing/models/{modules/UNet_arch.py, modules/DenoisingNAFNet_arch.py,
                        latent_denoising_model.py} (encode once, sample in the latent, decode once)
     stereo_sr.ConditionalNAFNet
@@ -28,7 +28,7 @@ from . import metrics  # noqa: F401
 from . import latent  # noqa: F401
 from . import latent_bokeh  # noqa: F401
 from . import stereo_sr  # noqa: F401
-from .latent import LatentDenoisingModel  # noqa: F401
+from .latent import CNAFNetLocal, LatentDenoisingModel  # noqa: F401
 
-__all__ = ["IRSDE", "DenoisingSDE", "denoising_sde", "metrics", "latent", "latent_bokeh", "stereo_sr", "LatentDenoisingModel", "ConditionalUNet", "ConditionalNAFNet", "DenoisingModel", "ReverseSDEDenoisingModel", "create_model", "define_G", "build_library",
+__all__ = ["IRSDE", "DenoisingSDE", "denoising_sde", "metrics", "latent", "latent_bokeh", "stereo_sr", "LatentDenoisingModel", "CNAFNetLocal", "ConditionalUNet", "ConditionalNAFNet", "DenoisingModel", "ReverseSDEDenoisingModel", "create_model", "define_G", "build_library",
            "IrsdeError", "IrsdeLibraryError", "shard_bounds", "gather_batch", "sample_shard", "sample_sharded"]

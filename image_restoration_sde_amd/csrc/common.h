@@ -246,6 +246,10 @@ void launch_dwconv_gate(const float* u, const float* w, const float* bias, float
 // NAFNet SCA: s[b][o] = bias[o] + sum_k W[o][k] * mean_hw(gated)[b][k]
 void launch_sca(const float* partial, int ntiles, const float* W, const float* bias, float* mean, float* s_out, int B,
                 int c, int HW, hipStream_t s);  // mean: scratch [B][c]
+// TLSC local pooling of CNAFNetLocal (tlsc_pool.hip): window means of the gated tensor [B][h][w][c] over k1 x k2 windows -> pooled
+// [B][h - k1 + 1][w - k2 + 1][c] (rowsum: scratch [B][h][w - k2 + 1][c]); gated *= the replicate-padded scale map of the same compact shape
+void launch_tlsc_pool(const float* gated, float* rowsum, float* pooled, int B, int h, int w, int c, int k1, int k2, hipStream_t s);
+void launch_tlsc_scale(float* gated, const float* scale, int B, int h, int w, int c, int k1, int k2, hipStream_t s);
 // out[r][j] = in[r][j] * in[r][j + h]  (SimpleGate on time-embedding rows)
 void launch_row_gate(const float* in, float* out, int rows, int h, hipStream_t s);
 

@@ -347,6 +347,10 @@ struct irsde_engine {
     int cam_rows = 0;           // capacity (images)
     int cam_set = 0;            // images covered by the last irsde_set_lens_info
 
+    // CNAFNetLocal (irsde_nafnet_set_local_pool): every NAFBlock's global average pool becomes a windowed mean (TLSC, local_arch.py:25-72) where the
+    // window frozen at the training size is smaller than the block's map; 0 = the plain ConditionalNAFNet
+    int tlsc_base_h = 0, tlsc_base_w = 0, tlsc_train_h = 0, tlsc_train_w = 0;
+
     // latent UNet (arch == 2): codes/config/latent-dehazing/models/modules/UNet_arch.py
     int lat_in = 0, lat_out = 0, lat_ch = 0, lat_embed = 0;
     std::vector<int> lat_mult;
@@ -454,6 +458,16 @@ inline bool uncond_engine(const irsde_engine* e) {
     return (e->arch == 0 && (e->cfg.flags & IRSDE_FLAG_UNCOND_FULLATTN) != 0) || (e->arch == 1 && (e->cfg.flags & IRSDE_FLAG_NAF_UNCOND) != 0);
 }
 inline int rup32(int c) { return (c + 31) & ~31; }
+// CNAFNetLocal: the pool window (K0, K1) of the NAFBlocks at `level` (encoder i and decoder n_enc - 1 - i: level i; middle: n_enc) — what the reference's
+// conversion forward on rand(train_size) freezes as kernel_size (local_arch.py:26-32): map size there x base_size / train_size.  false: no local pooling
+inline bool tlsc_window(const irsde_engine* e, int level, int* K0, int* K1) {
+    if (e->tlsc_train_h <= 0) return false;
+    const int P = 1 << e->cfg.depth;
+    const int Hp = (e->tlsc_train_h + P - 1) / P * P, Wp = (e->tlsc_train_w + P - 1) / P * P;
+    *K0 = (int)((long long)(Hp >> level) * e->tlsc_base_h / e->tlsc_train_h);
+    *K1 = (int)((long long)(Wp >> level) * e->tlsc_base_w / e->tlsc_train_w);
+    return true;
+}
 // The step counter / coefficient row and the FiLM row a plan's sampler steps run with: a sub-batch plan's own pair, else the engine's
 inline StepState* step_of(const irsde_engine* e, const Plan* pl) { return pl->own_step ? pl->own_step : e->step; }
 inline float* film_of(const irsde_engine* e, const Plan* pl) { return pl->own_film ? pl->own_film : e->film_cur; }

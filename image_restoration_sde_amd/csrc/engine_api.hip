@@ -718,6 +718,35 @@ int irsde_set_lens_info(irsde_engine* e, const float* info, int B) {
     });
 }
 
+int irsde_nafnet_set_local_pool(irsde_engine* e, int base_h, int base_w, int train_h, int train_w) {
+    return guard([&] {
+        if (!e) throw HipError("null argument");
+        if (e->arch != 1 || !(e->cfg.flags & IRSDE_FLAG_NAF_INTRO_SKIP))
+            throw HipError("set_local_pool: CNAFNetLocal is the latent-task ConditionalNAFNet (irsde_create_nafnet with IRSDE_FLAG_NAF_INTRO_SKIP)");
+        const int f = e->cfg.flags;
+        if ((f & (IRSDE_FLAG_NAF_STEREO | IRSDE_FLAG_NAF_LENS | IRSDE_FLAG_NAF_UNCOND | IRSDE_FLAG_SPLIT_BF16X2 | IRSDE_FLAG_SPLIT_F16X2 | IRSDE_FLAG_BF16_ACT |
+                  IRSDE_FLAG_NAIVE_CONV)) || ((f & IRSDE_FLAG_BF16) && !(f & IRSDE_FLAG_FP16)))
+            throw HipError("set_local_pool: local pooling runs in fp32 or with IRSDE_FLAG_FP16 only, and not with IRSDE_FLAG_NAF_STEREO / _NAF_LENS / _NAF_UNCOND / "
+                           "_NAIVE_CONV (not covered)");
+        if (base_h < 1 || base_w < 1 || train_h < 1 || train_w < 1 || base_h > (1 << 20) || base_w > (1 << 20) || train_h > (1 << 20) || train_w > (1 << 20))
+            throw HipError("set_local_pool: base and train sizes must be positive");
+        std::lock_guard<std::mutex> lk(e->mu);
+        const int old[4] = {e->tlsc_base_h, e->tlsc_base_w, e->tlsc_train_h, e->tlsc_train_w};
+        e->tlsc_base_h = base_h; e->tlsc_base_w = base_w; e->tlsc_train_h = train_h; e->tlsc_train_w = train_w;
+        int K0 = 0, K1 = 0;
+        tlsc_window(e, e->cfg.depth, &K0, &K1);   // the smallest window (the middle blocks'): an empty one fails the reference's conversion forward
+        if (K0 < 1 || K1 < 1) {
+            e->tlsc_base_h = old[0]; e->tlsc_base_w = old[1]; e->tlsc_train_h = old[2]; e->tlsc_train_w = old[3];
+            throw HipError("set_local_pool: the window of the deepest level is empty (train size too small for the network's depth)");
+        }
+        if (!e->plans.empty()) {   // plans bake the per-block choice: drop them
+            DeviceScope dev_scope(e->cfg.device);
+            IRSDE_HIP_CHECK(hipDeviceSynchronize());
+            e->plans.clear();
+        }
+    });
+}
+
 int irsde_eval_metrics(const float* out, const float* gt, int B, int C, int H, int W, int crop_border, double* metrics,
                        void* stream) {
     return guard([&] {

@@ -356,7 +356,18 @@ struct Builder {
     }
 
     // NAFBlock.forward — DenoisingNAFNet_arch.py:56-82
-    Tensor nafblock(const NafBlockW& w, const Tensor& x) {
+    // CNAFNetLocal: does the block at `level` pool over a window smaller than its map x (local_arch.py:38-39, 60)?  k1 x k2 = the window clipped to the map
+    bool tlsc_local(const Tensor& x, int level, int* k1 = nullptr, int* k2 = nullptr) const {
+        int K0 = 0, K1 = 0;
+        if (level < 0 || !tlsc_window(e, level, &K0, &K1)) return false;
+        if (K0 >= x.H && K1 >= x.W) return false;   // covered: the global mean, today's path
+        if (k1) *k1 = std::min(x.H, K0);
+        if (k2) *k2 = std::min(x.W, K1);
+        return true;
+    }
+
+    // level >= 0: the block's level in a CNAFNetLocal (see tlsc_local)
+    Tensor nafblock(const NafBlockW& w, const Tensor& x, int level = -1) {
         const int64_t M = (int64_t)x.B * x.H * x.W;
         const int64_t ppi = (int64_t)x.H * x.W;
         const int c = w.c;
@@ -376,6 +387,54 @@ struct Builder {
             tfree(t1);
         }
         Tensor gt = talloc(x.B, x.H, x.W, c);
+        int k1 = 0, k2 = 0;
+        if (tlsc_local(x, level, &k1, &k2)) {
+            // x * sca.1(windowed mean): window means on the compact (h - k1 + 1) x (w - k2 + 1) map (csrc/tlsc_pool.hip), sca.1 on that map through the 1x1 GEMM
+            // (the mode's operand rule), then the replicate pad as a clamped gather times the gated tensor, in place; conv3 takes the scaled tensor as is
+            const int B = x.B, H = x.H, W = x.W, nh = H - k1 + 1, nw = W - k2 + 1;
+            const int nt = dwgate_tiles(H, W, c);
+            float* partial = pl->alloc((size_t)B * nt * c, true);   // (the gate kernel's per-tile sums: not used by this path)
+            float* rowsum = pl->alloc((size_t)B * H * nw * c, true);
+            Tensor pooled = talloc(B, nh, nw, c, 1);
+            float* gp = gt.p;
+            char win[48];
+            snprintf(win, sizeof win, "tlsc %dx%d", k1, k2);
+            {
+                const float *up = u.p, *dw = w.dw_w, *db = w.dw_b;
+                float* pp = pooled.p;
+                push_other(OP_OTHER, [=](hipStream_t s) { launch_dwconv_gate(up, dw, db, gp, partial, B, H, W, c, s); });
+                push_other(OP_OTHER, [=](hipStream_t s) { launch_tlsc_pool(gp, rowsum, pp, B, H, W, c, k1, k2, s); });
+                char buf[160];
+                snprintf(buf, sizeof buf, "%s pool B=%d c=%d hw=%dx%d -> %dx%d window means", win, B, c, H, W, nh, nw);
+                pl->net_ops.back().desc = buf;
+            }
+            tfree(u);
+            ConvW scw;
+            scw.w = w.sca_w; scw.bias = w.sca_b; scw.Cout = scw.Cin = c;
+            Tensor sc = conv_naf(scw, pooled, ConvOpts());
+            pl->net_ops.back().desc = std::string(win) + " sca.1 " + pl->net_ops.back().desc;
+            {
+                const float* sp = sc.p;
+                push_other(OP_OTHER, [=](hipStream_t s) { launch_tlsc_scale(gp, sp, B, H, W, c, k1, k2, s); });
+                char buf[160];
+                snprintf(buf, sizeof buf, "%s scale B=%d c=%d hw=%dx%d (clamped gather of the %dx%d scale map)", win, B, c, H, W, nh, nw);
+                pl->net_ops.back().desc = buf;
+            }
+            pl->release(partial);
+            pl->release(rowsum);
+            tfree(pooled);
+            Tensor y;
+            if (lnconv_ok(w.conv3, gt) && x.C == w.conv3.Cout) {
+                y = pwconv(w.conv3, gt, nullptr, w.beta, x);
+            } else {
+                ConvOpts o3;
+                o3.ch_scale = w.beta; o3.res = &x;
+                y = conv_naf(w.conv3, gt, o3);
+            }
+            tfree(sc);
+            tfree(gt);
+            return nafblock_ffn(w, x, y);
+        }
         const int nt = dwgate_tiles(x.H, x.W, c);
         float* partial = pl->alloc((size_t)x.B * nt * c, true);
         float* sca = pl->alloc((size_t)x.B * c, true);
@@ -402,6 +461,16 @@ struct Builder {
         pl->release(partial);
         pl->release(sca);
         pl->release(mean);
+        return nafblock_ffn(w, x, y);
+    }
+
+    // the FFN half of NAFBlock.forward (:74-82) on y = inp + x * beta; releases y
+    Tensor nafblock_ffn(const NafBlockW& w, const Tensor& x, const Tensor& y) {
+        const int64_t M = (int64_t)x.B * x.H * x.W;
+        const int64_t ppi = (int64_t)x.H * x.W;
+        const int c = w.c;
+        const float* film = film_base() + w.film_off;
+        const int fb = film_bstride;
         Tensor v;
         if (lnconv_ok(w.conv4, y)) {
             v = lnconv(w.conv4, y, w.g2, film + 3 * c, film + 2 * c, 1, naf_lens(e) ? cam_base() + w.cam_off : nullptr);
@@ -728,8 +797,8 @@ void build_naf_plan(irsde_engine* e, Plan* pl, Builder& b, int P) {
     const bool stereo = naf_stereo(e);
     const int B = stereo ? 2 * pl->B : pl->B;   // stereo: the network runs on the 2B views of B pairs
     // NAFBlock (stereo: + fusion = SCAM; taps <path>.fusion.in = the SCAM input, <path> = the block output as in the reference)
-    auto block = [&](const NafBlockW& blk, const Tensor& in, const std::string& path) {
-        Tensor y = b.nafblock(blk, in);
+    auto block = [&](const NafBlockW& blk, const Tensor& in, const std::string& path, int level) {
+        Tensor y = b.nafblock(blk, in, level);
         if (!stereo) return y;
         b.tap(path + ".fusion.in", y);
         Tensor z = b.scam(blk, y);
@@ -758,13 +827,13 @@ void build_naf_plan(irsde_engine* e, Plan* pl, Builder& b, int P) {
     const Tensor intro = x;
     std::vector<Tensor> encs;
     for (size_t i = 0; i < e->naf_enc.size(); ++i) {
-        if (b.naf_chain_ok(e->naf_chain_enc[i], x)) {
+        if (!b.tlsc_local(x, (int)i) && b.naf_chain_ok(e->naf_chain_enc[i], x)) {   // (a block with a local window is never part of a chain)
             Tensor y = b.nafchain(e->naf_chain_enc[i], x);
             if (!(intro_skip && x.p == intro.p)) b.tfree(x);
             x = y;
         } else
         for (size_t j = 0; j < e->naf_enc[i].size(); ++j) {
-            Tensor y = block(e->naf_enc[i][j], x, "encoders." + std::to_string(i) + "." + std::to_string(j));
+            Tensor y = block(e->naf_enc[i][j], x, "encoders." + std::to_string(i) + "." + std::to_string(j), (int)i);
             if (!(intro_skip && x.p == intro.p)) b.tfree(x);
             x = y;
         }
@@ -775,13 +844,14 @@ void build_naf_plan(irsde_engine* e, Plan* pl, Builder& b, int P) {
         x = b.conv_naf(e->naf_downs[i], x, od);  // Conv2d(chan, 2 chan, 2, 2)
         b.tap("downs." + std::to_string(i), x);
     }
-    if (b.naf_chain_ok(e->naf_chain_mid, x)) {
+    const int nlev = (int)e->naf_enc.size();
+    if (!b.tlsc_local(x, nlev) && b.naf_chain_ok(e->naf_chain_mid, x)) {
         Tensor y = b.nafchain(e->naf_chain_mid, x);
         b.tfree(x);
         x = y;
     } else
     for (size_t j = 0; j < e->naf_mid.size(); ++j) {
-        Tensor y = block(e->naf_mid[j], x, "middle_blks." + std::to_string(j));
+        Tensor y = block(e->naf_mid[j], x, "middle_blks." + std::to_string(j), nlev);
         b.tfree(x);
         x = y;
     }
@@ -795,13 +865,13 @@ void build_naf_plan(irsde_engine* e, Plan* pl, Builder& b, int P) {
         b.tfree(skip);
         x = y;
         b.tap("ups." + std::to_string(i), x);
-        if (b.naf_chain_ok(e->naf_chain_dec[i], x)) {
+        if (!b.tlsc_local(x, nlev - 1 - (int)i) && b.naf_chain_ok(e->naf_chain_dec[i], x)) {
             Tensor z = b.nafchain(e->naf_chain_dec[i], x);
             b.tfree(x);
             x = z;
         } else
         for (size_t j = 0; j < e->naf_dec[i].size(); ++j) {
-            Tensor z = block(e->naf_dec[i][j], x, "decoders." + std::to_string(i) + "." + std::to_string(j));
+            Tensor z = block(e->naf_dec[i][j], x, "decoders." + std::to_string(i) + "." + std::to_string(j), nlev - 1 - (int)i);
             b.tfree(x);
             x = z;
         }
@@ -858,7 +928,10 @@ int naf_subbatches(const irsde_engine* e, int B, int H, int W) {
         const int Hp = (H + ps - 1) / ps * ps, Wp = (W + ps - 1) / ps * ps;
         if ((e->cfg.flags & IRSDE_FLAG_FP16) && !(e->cfg.flags & IRSDE_FLAG_NO_NAF_CHAIN))
             for (int i = 0; i < nlev; ++i)
-                if (e->naf_chain_enc[i].nblocks > 0 && naf_chain_shape_ok(Hp >> i, Wp >> i, e->naf_intro.Cout << i)) chain = true;
+                if (e->naf_chain_enc[i].nblocks > 0 && naf_chain_shape_ok(Hp >> i, Wp >> i, e->naf_intro.Cout << i)) {
+                    int K0 = 0, K1 = 0;   // (CNAFNetLocal: a level whose blocks pool over a local window runs no chain)
+                    if (!tlsc_window(e, i, &K0, &K1) || (K0 >= (Hp >> i) && K1 >= (Wp >> i))) chain = true;
+                }
         // r05 (profiles/r05_notes.md section 4): 64 images as 2 x 32: +3 %, smaller parts a loss — with the chain on one CU per image.  r06: the chain runs on 4 groups per
         // image and everything else at these batches is latency-bound on an under-filled GPU: two parts pay from 8 images on (8 / 16 / 24 / 32 / 48 / 64 images:
         // +1.9 / +2.7 / +2.6 / +4.1 / +1.7 / +2 %, profiles/r06_aq_subbatch_ab.txt); 4 parts lose at every batch (two of four streams run, two wait)

@@ -7,7 +7,8 @@ Reference: /root/reference/codes/config/latent-dehazing/
     models/latent_denoising_model.py:40-51,146-152,177-200
     test.py:90-100     latent_LQ, hidden = model.encode(LQ); noisy = sde.noise_state(latent_LQ);
                        model.feed_data(noisy, latent_LQ); model.test(sde, hidden)
-(the latent-bokeh variant additionally threads `lens_info` through every NAFBlock; not built.)
+    models/modules/DenoisingNAFNet_arch.py:190-200 + local_arch.py   CNAFNetLocal: windowed SCA pooling (TLSC)
+(the latent-bokeh variant additionally threads `lens_info` through every NAFBlock: latent_bokeh.py.)
 
 Modules only own parameters under the reference's state_dict names; the arithmetic runs in libirsde_hip.so.
 """
@@ -228,13 +229,58 @@ class ConditionalNAFNet(_ImageNAFNet):
         return super()._create_handle(L, device_index, flags | _lib.FLAG_NAF_INTRO_SKIP)
 
 
+def tlsc_windows(train_size, n_enc, base_size=None):
+    """The pool window (K0, K1) per level 0 .. n_enc that the reference's conversion forward on rand(train_size) freezes as `kernel_size`
+    (local_arch.py:26-32): a block at level l sees the zero-padded train size >> l; encoder i and decoder n_enc - 1 - i are at level i,
+    the middle blocks at level n_enc.  Shapes only: no forward is run."""
+    _, _, H, W = train_size
+    base = base_size or (int(H * 1.5), int(W * 1.5))
+    P = 2 ** n_enc
+    Hp, Wp = (H + P - 1) // P * P, (W + P - 1) // P * P
+    return [((Hp >> l) * base[0] // H, (Wp >> l) * base[1] // W) for l in range(n_enc + 1)]
+
+
+class CNAFNetLocal(ConditionalNAFNet):
+    """CNAFNetLocal (DenoisingNAFNet_arch.py:190-200 with local_arch.py): the latent ConditionalNAFNet whose NAFBlocks pool over a window
+    of 1.5 x the training size instead of the whole map (TLSC), for latents much larger than the training crop.  Same state_dict as
+    ConditionalNAFNet (the pool has no parameters).  The windows follow from the shapes alone (`tlsc_windows`); a block whose window covers
+    its map runs exactly ConditionalNAFNet's launches.  `fast_imp=True`, the reference's self-declared non-equivalent approximation, is
+    not built."""
+
+    def __init__(self, *args, train_size=(1, 3, 128, 128), fast_imp=False, **kwargs):
+        super().__init__(*args, **kwargs)
+        if fast_imp:
+            raise _lib.IrsdeError("CNAFNetLocal: fast_imp=True (the reference's non-equivalent approximation, local_arch.py:41-55) is not built")
+        train_size = tuple(int(v) for v in train_size)
+        if len(train_size) != 4 or min(train_size) < 1:
+            raise _lib.IrsdeError("CNAFNetLocal: train_size must be (N, C, H, W) with positive entries, got %r" % (train_size,))
+        if train_size[1] != self.in_nc:   # the reference's conversion forward fails in `intro`
+            raise _lib.IrsdeError("CNAFNetLocal: train_size has %d channels, the network img_channel=%d" % (train_size[1], self.in_nc))
+        self.train_size = train_size
+        self.base_size = (int(train_size[2] * 1.5), int(train_size[3] * 1.5))
+        self.kernel_sizes = tlsc_windows(train_size, len(self.enc_blk_nums), self.base_size)
+
+    def _create_handle(self, L, device_index, flags):
+        h = super()._create_handle(L, device_index, flags)
+        rc = L.irsde_nafnet_set_local_pool(h, self.base_size[0], self.base_size[1], self.train_size[2], self.train_size[3])
+        if rc != 0:
+            msg = L.irsde_last_error()
+            L.irsde_destroy(h)
+            raise _lib.IrsdeError("libirsde_hip error %d: %s" % (rc, msg.decode() if msg else "?"))
+        return h
+
+
 def define_G(opt):
     """latent-*/models/networks.py: network_G.which_model looked up by name in the task's own modules package — the
     latent-bokeh task (`distortion: bokeh`, options/bokeh/test/refusion.yml:4) has the lens-conditioned ConditionalNAFNet."""
     o = opt["network_G"]
     name = o.get("which_model", o.get("which_model_G"))
-    if name != "ConditionalNAFNet":
-        raise NotImplementedError("latent score network [%s] is not built (ConditionalNAFNet only)" % name)
+    if name not in ("ConditionalNAFNet", "CNAFNetLocal"):
+        raise NotImplementedError("latent score network [%s] is not built (ConditionalNAFNet and CNAFNetLocal only)" % name)
+    if name == "CNAFNetLocal":
+        if opt.get("distortion") == "bokeh":
+            raise NotImplementedError("latent-bokeh CNAFNetLocal (lens-conditioned, with local pooling) is not built")
+        return CNAFNetLocal(**o["setting"])
     if opt.get("distortion") == "bokeh":
         from .latent_bokeh import ConditionalNAFNet as BokehNAFNet
         return BokehNAFNet(**o["setting"])

@@ -34,6 +34,7 @@
  *        call on the engine instead of hanging the GPU.  Debug header: irsde_debug_force_chain_groups; irsde_bench_naf_chain variants 22 / 24.
  *        Additive, same version: IRSDE_FLAG_NAF_STEREO (the stereo-sr ConditionalNAFNet with SCAM); debug header: irsde_debug_scam.
  *        Additive, same version: IRSDE_FLAG_NAF_UNCOND (the denoising-sde ConditionalNAFNet: forward(x, time), DenoisingSDE modes 3 / 4).
+ *        Additive, same version: irsde_nafnet_set_local_pool (CNAFNetLocal: the latent ConditionalNAFNet with windowed SCA pooling, TLSC).
  */
 #ifndef IRSDE_HIP_H
 #define IRSDE_HIP_H
@@ -300,6 +301,25 @@ int irsde_latent_hidden(irsde_engine* e, int B, int H, int W, int k, float* out,
  * info: HOST [B][3] = (src_lens, tgt_lens, disparity) of every image; evaluates cam_mlp and every block's cam_mlp once; the
  * rows stay valid for all following forward / sample calls with batch <= B. */
 int irsde_set_lens_info(irsde_engine* e, const float* info, int B);
+
+/* CNAFNetLocal — replaces Local_Base.convert / AvgPool2d of codes/config/latent-dehazing/models/modules/local_arch.py:6-72,95-102 and
+ * CNAFNetLocal.__init__ (DenoisingNAFNet_arch.py:190-200): every NAFBlock's sca.0 = AdaptiveAvgPool2d(1) becomes the mean over a window
+ * (TLSC, test-time local statistics conversion), for inputs much larger than the training crop.
+ *   base_h, base_w  = int(1.5 * train_h), int(1.5 * train_w) in the reference (:196); train_h, train_w = train_size[2:].
+ * The reference freezes each pool's kernel_size in one forward on rand(train_size); it depends on shapes only and is computed here:
+ * a block at level l (encoder l, decoder n_enc - 1 - l; middle blocks: n_enc), with Hp, Wp = the train size padded to a multiple of
+ * 2^n_enc, has K0 = (Hp >> l) * base_h / train_h, K1 = (Wp >> l) * base_w / train_w (integer division).  At a block whose map is h x w:
+ * K0 >= h and K1 >= w -> the global mean, exactly the plain network's launches (fp16 NAFBlock chain included); otherwise
+ * k1 = min(h, K0), k2 = min(w, K1), m = the (h - k1 + 1) x (w - k2 + 1) window means, replicate-padded back to h x w with
+ * top = (k1 - 1) / 2, left = (k2 - 1) / 2 (:69-70), then x * sca.1(pooled) per pixel.  Such a block is never part of a chain; its rows in
+ * irsde_plan_describe start with "tlsc <k1>x<k2>" (csrc/tlsc_pool.hip; window sums separable and local in fp32, not the reference's
+ * difference of whole-image prefix sums).  The reference's fast_imp=True approximation is not built.
+ * Valid on an irsde_create_nafnet engine with IRSDE_FLAG_NAF_INTRO_SKIP, at any time (cached plans are dropped; synchronises the device
+ * then); fp32 and IRSDE_FLAG_FP16 (pool arithmetic fp32, sca.1 with the mode's fp16 operands).  IRSDE_ERR_INVALID with IRSDE_FLAG_BF16
+ * (without _FP16) / _SPLIT_BF16X2 / _SPLIT_F16X2 / _NAIVE_CONV / _NAF_STEREO / _NAF_LENS / _NAF_UNCOND, on any other engine, for
+ * non-positive sizes, or when the deepest level's window would be empty.  The state_dict is the plain network's (the pool has no
+ * parameters); irsde_nafnet_config is unchanged. */
+int irsde_nafnet_set_local_pool(irsde_engine* e, int base_h, int base_w, int train_h, int train_w);
 
 /* Evaluation tail on the device — replaces, per image of a batch, the metric block of
  * codes/config/deraining/test.py:131-178: util.tensor2img on output and GT (codes/utils/img_utils.py:136-163),
