@@ -246,8 +246,11 @@ void launch_dwconv_gate(const float* u, const float* w, const float* bias, float
 // NAFNet SCA: s[b][o] = bias[o] + sum_k W[o][k] * mean_hw(gated)[b][k]
 void launch_sca(const float* partial, int ntiles, const float* W, const float* bias, float* mean, float* s_out, int B,
                 int c, int HW, hipStream_t s);  // mean: scratch [B][c]
+// the pooled mean alone: mean[b][k] = sum_tiles partial[b][tile][k] / HW (launch_sca's first stage on large maps; the one-launch form forms the same bits in LDS)
+void launch_sca_mean(const float* partial, int ntiles, float* mean, int B, int c, int HW, hipStream_t s);
 // TLSC local pooling of CNAFNetLocal (tlsc_pool.hip): window means of the gated tensor [B][h][w][c] over k1 x k2 windows -> pooled
 // [B][h - k1 + 1][w - k2 + 1][c] (rowsum: scratch [B][h][w - k2 + 1][c]); gated *= the replicate-padded scale map of the same compact shape
+void tlsc_check_shape(int B, int h, int w, int c, int k1, int k2);   // throws HipError: c a positive multiple of 4, 1 <= k1 <= h, 1 <= k2 <= w
 void launch_tlsc_pool(const float* gated, float* rowsum, float* pooled, int B, int h, int w, int c, int k1, int k2, hipStream_t s);
 void launch_tlsc_scale(float* gated, const float* scale, int B, int h, int w, int c, int k1, int k2, hipStream_t s);
 // out[r][j] = in[r][j] * in[r][j + h]  (SimpleGate on time-embedding rows)

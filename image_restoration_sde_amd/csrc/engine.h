@@ -479,6 +479,11 @@ void build_inventory_latent(irsde_engine* e);
 void finalize(irsde_engine* e);
 void compute_film_rows(irsde_engine* e, const float* tvals, int rows, float* dst, hipStream_t s);
 void ensure_film_cur(irsde_engine* e, int rows);
+// the NAFBlock packing steps, shared by pack_nafblock and the kernel-level test hooks (engine_debug.hip)
+void pack_conv_rows(const float* w_oihw, const float* bias, int O, int I, int KH, int KW, const std::vector<int>& perm, std::vector<float>& pw,
+                    std::vector<float>& pb);                          // [O][I][KH][KW] -> [O][KH][KW][I], packed row n' = row perm[n'] (empty: identity)
+std::vector<int> naf_gate_perm(int c);                               // conv4's row order: SimpleGate pairs (j, j + c) adjacent
+std::vector<float> pack_dwconv_taps(const float* w, int c2);         // conv2.weight [2c][1][3][3] -> [9][2c]
 
 // engine_plan.hip: one network evaluation as a static launch list over a static arena
 Plan* get_plan(irsde_engine* e, int B, int H, int W, bool per_sample_film, int slot = 0, int b0 = 0);

@@ -137,6 +137,85 @@ int irsde_debug_scam(const float* x, int B, int H, int W, int C, const float* no
     });
 }
 
+int irsde_debug_naf_gate_sca(const float* u, int B, int H, int W, int c, const float* conv2_w, const float* conv2_b, const float* sca_w, const float* sca_b,
+                             float* gated_out, float* mean_out, float* s_out, void* stream) {
+    return guard([&] {
+        if (!u || !conv2_w || !conv2_b || !sca_w || !sca_b || !gated_out || !s_out) throw HipError("null argument");
+        if (B < 1 || B > 65535 || H < 1 || W < 1 || c < 4 || c % 4 || (long long)H * W >= (1ll << 31)) throw HipError("debug_naf_gate_sca: bad shape");
+        hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+        conv_global_init();
+        Scratch mem(s);
+        float *dw = mem.upload(pack_dwconv_taps(conv2_w, 2 * c)), *db = mem.upload(conv2_b, (size_t)2 * c);
+        float *dsw = mem.upload(sca_w, (size_t)c * c), *dsb = mem.upload(sca_b, c);
+        const int nt = dwgate_tiles(H, W, c);
+        float *partial = mem.alloc<float>((size_t)B * nt * c), *mean = mem.alloc<float>((size_t)B * c);
+        launch_dwconv_gate(u, dw, db, gated_out, partial, B, H, W, c, s);
+        launch_sca(partial, nt, dsw, dsb, mean, s_out, B, c, H * W, s);
+        if (mean_out) launch_sca_mean(partial, nt, mean_out, B, c, H * W, s);   // (the one-launch route keeps its mean in LDS: the same sums from the same partials)
+        IRSDE_HIP_CHECK(hipStreamSynchronize(s));
+    });
+}
+
+int irsde_debug_tlsc(const float* g, int B, int h, int w, int c, int k1, int k2, float* pooled_out, const float* scale_map, float* scaled_out, void* stream) {
+    return guard([&] {
+        if (!g || !pooled_out || !scale_map || !scaled_out) throw HipError("null argument");
+        tlsc_check_shape(B, h, w, c, k1, k2);
+        hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+        conv_global_init();
+        Scratch mem(s);
+        float* rowsum = mem.alloc<float>((size_t)B * h * (w - k2 + 1) * c);
+        launch_tlsc_pool(g, rowsum, pooled_out, B, h, w, c, k1, k2, s);
+        IRSDE_HIP_CHECK(hipMemcpyAsync(scaled_out, g, (size_t)B * h * w * c * sizeof(float), hipMemcpyDeviceToDevice, s));
+        launch_tlsc_scale(scaled_out, scale_map, B, h, w, c, k1, k2, s);
+        IRSDE_HIP_CHECK(hipStreamSynchronize(s));
+    });
+}
+
+int irsde_debug_ln_film(const float* x, long long M, int C, long long ppi, const float* g, const float* fscale, const float* fshift, int film_bstride,
+                        float* out, void* stream) {
+    return guard([&] {
+        if (!x || !g || !fscale || !fshift || !out) throw HipError("null argument");
+        if (M < 1 || ppi < 1 || C < 4 || C % 4 || C > 2048 || film_bstride < 0 || film_bstride % 4) throw HipError("debug_ln_film: bad shape");
+        hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+        conv_global_init();
+        Scratch mem(s);
+        float* dg = mem.upload(g, C);
+        launch_layernorm_film(x, dg, fscale, fshift, film_bstride, ppi, out, M, C, 1e-5f, s);
+        IRSDE_HIP_CHECK(hipStreamSynchronize(s));
+    });
+}
+
+int irsde_debug_naf_lnconv(int mode, const float* x, long long M, int c, int Cout, long long ppi, const float* g, const float* fscale, const float* fshift,
+                           int film_bstride, const float* w, const float* bias, const float* gate_film, int gate_film_bstride, const float* in_scale,
+                           const float* ch_scale, const float* res, float* out, void* stream) {
+    return guard([&] {
+        if (mode < 0 || mode > 3) throw HipError("debug_naf_lnconv: mode must be 0 .. 3");
+        if (!x || !w || !bias || !out) throw HipError("null argument");
+        if (!naf_lnconv_ok(c, Cout, M) || ppi < 1) throw HipError("debug_naf_lnconv: bad shape");
+        const bool ln = mode <= 1;
+        if (ln && (!g || !fscale || !fshift || film_bstride < 0 || film_bstride % 4)) throw HipError("debug_naf_lnconv: modes 0 / 1 need g and the FiLM rows");
+        if (mode == 1 && gate_film && gate_film_bstride < 0) throw HipError("debug_naf_lnconv: bad lens FiLM stride");
+        if (!ln && (!ch_scale || !res || (mode == 2 && !in_scale))) throw HipError("debug_naf_lnconv: modes 2 / 3 need ch_scale and res, mode 2 in_scale");
+        hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+        conv_global_init();
+        std::vector<float> pw, pb;
+        pack_conv_rows(w, bias, Cout, c, 1, 1, mode == 1 ? naf_gate_perm(Cout / 2) : std::vector<int>(), pw, pb);
+        Scratch mem(s);
+        float *dwf = mem.upload(pw), *dbias = mem.upload(pb);
+        unsigned short* w16 = mem.alloc<unsigned short>(pw.size());
+        launch_f32_to_f16(dwf, w16, pw.size(), s);
+        if (ln) {
+            float* dg = mem.upload(g, c);
+            launch_naf_lnconv(x, dg, fscale, fshift, film_bstride, ppi, w16, dbias, out, M, c, Cout, mode, mode == 1 ? gate_film : nullptr,
+                              mode == 1 && gate_film ? gate_film_bstride : 0, s);
+        } else {
+            float* dcs = mem.upload(ch_scale, Cout);
+            launch_naf_pwconv(x, mode == 2 ? in_scale : nullptr, ppi, w16, dbias, dcs, res, out, M, c, Cout, s);
+        }
+        IRSDE_HIP_CHECK(hipStreamSynchronize(s));
+    });
+}
+
 int irsde_debug_conv(const float* in0, int C0, const float* in1, int C1, int B, int Hin, int Win, int in_shift,
                      const float* w_oihw, int Cout, int KH, int KW, int stride, int pad, const float* bias,
                      const float* film, int film_bstride, int silu, const float* res, float* out, int naive,

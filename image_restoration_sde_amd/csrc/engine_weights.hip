@@ -258,28 +258,50 @@ void build_inventory_naf(irsde_engine* e) {
     }
 }
 
-// 1x1 / KxK conv with an output-row permutation: packed row n' = original row perm[n']
-ConvW pack_conv_perm(irsde_engine* e, const std::string& wname, const std::string& bname, const std::vector<int>& perm) {
-    const HostTensor& t = need(e, wname);
-    const int O = (int)t.shape[0], I = (int)t.shape[1], KH = (int)t.shape[2], KW = (int)t.shape[3];
-    std::vector<float> p((size_t)O * KH * KW * I);
+// 1x1 / KxK conv with an output-row permutation: packed row n' = original row perm[n'].  [O][I][KH][KW] -> [O][KH][KW][I]; `bias` may be null
+void pack_conv_rows(const float* w_oihw, const float* bias, int O, int I, int KH, int KW, const std::vector<int>& perm, std::vector<float>& pw,
+                    std::vector<float>& pb) {
+    pw.assign((size_t)O * KH * KW * I, 0.f);
     for (int o = 0; o < O; ++o) {
         const int so = perm.empty() ? o : perm[o];
         for (int i = 0; i < I; ++i)
             for (int ky = 0; ky < KH; ++ky)
                 for (int kx = 0; kx < KW; ++kx)
-                    p[(((size_t)o * KH + ky) * KW + kx) * I + i] = t.data[(((size_t)so * I + i) * KH + ky) * KW + kx];
+                    pw[(((size_t)o * KH + ky) * KW + kx) * I + i] = w_oihw[(((size_t)so * I + i) * KH + ky) * KW + kx];
     }
+    pb.clear();
+    if (bias) {
+        pb.resize(O);
+        for (int o = 0; o < O; ++o) pb[o] = bias[perm.empty() ? o : perm[o]];
+    }
+}
+ConvW pack_conv_perm(irsde_engine* e, const std::string& wname, const std::string& bname, const std::vector<int>& perm) {
+    const HostTensor& t = need(e, wname);
+    const int O = (int)t.shape[0], I = (int)t.shape[1], KH = (int)t.shape[2], KW = (int)t.shape[3];
+    std::vector<float> p, pb;
+    pack_conv_rows(t.data.data(), bname.empty() ? nullptr : need(e, bname).data.data(), O, I, KH, KW, perm, p, pb);
     ConvW c;
     c.w = e->upload(p);
     c.Cout = O; c.Cin = I; c.KH = KH; c.KW = KW;
-    if (!bname.empty()) {
-        const HostTensor& b = need(e, bname);
-        std::vector<float> pb(O);
-        for (int o = 0; o < O; ++o) pb[o] = b.data[perm.empty() ? o : perm[o]];
-        c.bias = e->upload(pb);
-    }
+    if (!bname.empty()) c.bias = e->upload(pb);
     return c;
+}
+
+// SimpleGate pairs (j, j + c) made adjacent: 2j <- j, 2j+1 <- j + c  (the row order of a packed conv4)
+std::vector<int> naf_gate_perm(int c) {
+    std::vector<int> perm(2 * c);
+    for (int j = 0; j < c; ++j) {
+        perm[2 * j] = j;
+        perm[2 * j + 1] = j + c;
+    }
+    return perm;
+}
+// conv2.weight [2c][1][3][3] -> [9][2c]  (tap-major: dwconv_gate_kernel reads one float4 of channels per tap)
+std::vector<float> pack_dwconv_taps(const float* w, int c2) {
+    std::vector<float> p((size_t)9 * c2);
+    for (int ch = 0; ch < c2; ++ch)
+        for (int k = 0; k < 9; ++k) p[(size_t)k * c2 + ch] = w[(size_t)ch * 9 + k];
+    return p;
 }
 
 NafBlockW pack_nafblock(irsde_engine* e, const std::string& p, int c) {
@@ -289,19 +311,12 @@ NafBlockW pack_nafblock(irsde_engine* e, const std::string& p, int c) {
     b.g2 = e->upload(need(e, p + "norm2.g").data);
     b.conv1 = pack_conv_perm(e, p + "conv1.weight", p + "conv1.bias", {});
     b.conv3 = pack_conv_perm(e, p + "conv3.weight", p + "conv3.bias", {});
-    std::vector<int> gate_perm(2 * c);  // SimpleGate pairs (j, j + c) made adjacent: 2j <- j, 2j+1 <- j + c
-    for (int j = 0; j < c; ++j) {
-        gate_perm[2 * j] = j;
-        gate_perm[2 * j + 1] = j + c;
-    }
-    b.conv4 = pack_conv_perm(e, p + "conv4.weight", p + "conv4.bias", gate_perm);
+    b.conv4 = pack_conv_perm(e, p + "conv4.weight", p + "conv4.bias", naf_gate_perm(c));
     b.conv5 = pack_conv_perm(e, p + "conv5.weight", p + "conv5.bias", {});
     {
-        const HostTensor& t = need(e, p + "conv2.weight");  // [2c][1][3][3] -> [9][2c]
-        std::vector<float> w((size_t)9 * 2 * c);
-        for (int ch = 0; ch < 2 * c; ++ch)
-            for (int k = 0; k < 9; ++k) w[(size_t)k * 2 * c + ch] = t.data[(size_t)ch * 9 + k];
-        b.dw_w = e->upload(w);
+        const HostTensor& t = need(e, p + "conv2.weight");
+        if (t.data.size() != (size_t)18 * c) throw HipError("pack_nafblock: unexpected size of " + p + "conv2.weight");
+        b.dw_w = e->upload(pack_dwconv_taps(t.data.data(), 2 * c));
         b.dw_b = e->upload(need(e, p + "conv2.bias").data);
     }
     b.sca_w = e->upload(need(e, p + "sca.1.weight").data);

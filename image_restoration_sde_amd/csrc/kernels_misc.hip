@@ -1993,9 +1993,14 @@ void launch_sca(const float* partial, int ntiles, const float* W, const float* b
     if ((long long)ntiles * c <= 65536 && c <= 4096) {   // small maps: one launch (every block re-sums <= 256 KB of partials from L2)
         hipLaunchKernelGGL(sca_fused_kernel, dim3((c + 3) / 4, B), dim3(256), (size_t)c * 4, s, partial, ntiles, W, bias, s_out, c, 1.0f / (float)HW);
     } else {
-        hipLaunchKernelGGL(sca_mean_kernel, dim3((c + 63) / 64, B), dim3(256), 0, s, partial, ntiles, mean, c, 1.0f / (float)HW);
+        launch_sca_mean(partial, ntiles, mean, B, c, HW, s);
         hipLaunchKernelGGL(sca_kernel, dim3((c + 3) / 4, B), dim3(256), 0, s, mean, W, bias, s_out, c);
     }
+    IRSDE_HIP_CHECK(hipGetLastError());
+}
+
+void launch_sca_mean(const float* partial, int ntiles, float* mean, int B, int c, int HW, hipStream_t s) {
+    hipLaunchKernelGGL(sca_mean_kernel, dim3((c + 63) / 64, B), dim3(256), 0, s, partial, ntiles, mean, c, 1.0f / (float)HW);
     IRSDE_HIP_CHECK(hipGetLastError());
 }
 

@@ -69,11 +69,6 @@ __global__ __launch_bounds__(256) void tlsc_scale_kernel(float4* __restrict__ g,
     g[idx] = v;
 }
 
-void check_tlsc(int B, int h, int w, int c, int k1, int k2) {
-    if (B < 1 || h < 1 || w < 1 || c < 4 || c % 4) throw HipError("tlsc: the channel count must be a positive multiple of 4");
-    if (k1 < 1 || k2 < 1 || k1 > h || k2 > w) throw HipError("tlsc: the window must lie inside the map");
-}
-
 void axis_sum(const float* in, float* out, long long outer, int len, int k, long long inner, float scale, hipStream_t s) {
     const int nout = len - k + 1, nseg = (nout + kTlscSeg - 1) / kTlscSeg;
     const long long inner4 = inner / 4, total = outer * nseg * inner4;
@@ -85,9 +80,14 @@ void axis_sum(const float* in, float* out, long long outer, int len, int k, long
 
 }  // namespace
 
+void tlsc_check_shape(int B, int h, int w, int c, int k1, int k2) {
+    if (B < 1 || h < 1 || w < 1 || c < 4 || c % 4) throw HipError("tlsc: the channel count must be a positive multiple of 4");
+    if (k1 < 1 || k2 < 1 || k1 > h || k2 > w) throw HipError("tlsc: the window must lie inside the map");
+}
+
 // gated [B][h][w][c] -> rowsum (scratch) [B][h][w - k2 + 1][c] -> pooled [B][h - k1 + 1][w - k2 + 1][c] (window means)
 void launch_tlsc_pool(const float* gated, float* rowsum, float* pooled, int B, int h, int w, int c, int k1, int k2, hipStream_t s) {
-    check_tlsc(B, h, w, c, k1, k2);
+    tlsc_check_shape(B, h, w, c, k1, k2);
     const int nw = w - k2 + 1;
     axis_sum(gated, rowsum, (long long)B * h, w, k2, c, 1.0f, s);
     axis_sum(rowsum, pooled, B, h, k1, (long long)nw * c, 1.0f / ((float)k1 * (float)k2), s);
@@ -95,7 +95,7 @@ void launch_tlsc_pool(const float* gated, float* rowsum, float* pooled, int B, i
 
 // gated [B][h][w][c] *= scale [B][h - k1 + 1][w - k2 + 1][c] replicate-padded to h x w (pad top (k1 - 1) / 2, left (k2 - 1) / 2)
 void launch_tlsc_scale(float* gated, const float* scale, int B, int h, int w, int c, int k1, int k2, hipStream_t s) {
-    check_tlsc(B, h, w, c, k1, k2);
+    tlsc_check_shape(B, h, w, c, k1, k2);
     const long long total = (long long)B * h * w * (c / 4);
     if ((total + 255) / 256 >= (1ll << 31)) throw HipError("tlsc: map too large");
     hipLaunchKernelGGL(tlsc_scale_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, reinterpret_cast<float4*>(gated),

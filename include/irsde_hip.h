@@ -35,6 +35,7 @@
  *        Additive, same version: IRSDE_FLAG_NAF_STEREO (the stereo-sr ConditionalNAFNet with SCAM); debug header: irsde_debug_scam.
  *        Additive, same version: IRSDE_FLAG_NAF_UNCOND (the denoising-sde ConditionalNAFNet: forward(x, time), DenoisingSDE modes 3 / 4).
  *        Additive, same version: irsde_nafnet_set_local_pool (CNAFNetLocal: the latent ConditionalNAFNet with windowed SCA pooling, TLSC).
+ *        Debug header only, same version: irsde_debug_naf_gate_sca, irsde_debug_tlsc, irsde_debug_ln_film, irsde_debug_naf_lnconv (NAFBlock glue kernels).
  */
 #ifndef IRSDE_HIP_H
 #define IRSDE_HIP_H

@@ -90,6 +90,37 @@ int irsde_debug_scam(const float* x, int B_pairs, int H, int W, int C, const flo
                      const float* l_proj1_b, const float* r_proj1_w, const float* r_proj1_b, const float* l_proj2_w, const float* l_proj2_b,
                      const float* r_proj2_w, const float* r_proj2_b, const float* beta, const float* gamma, float* out, void* stream);
 
+/* Kernel-level test hooks of the NAFBlock glue kernels (csrc/kernels_misc.hip, csrc/tlsc_pool.hip): each runs the production launchers of ONE
+ * stage on the caller's device tensors (NHWC fp32) and synchronises `stream`.  Weights are HOST pointers in reference layout and go through the engine's own
+ * packing (engine_weights.hip); FiLM / scale rows and activations are DEVICE pointers.  A shape a launcher cannot run is refused before anything is launched.
+ * tests/test_gpu_naf_glue.py compares them with tests/naf_glue_oracle.py.
+ *
+ * conv2 (depthwise 3x3, pad 1) + SimpleGate + SCA: launch_dwconv_gate, then launch_sca (one launch while tiles * c <= 65536, else mean + sca.1 kernels).
+ * u [B][H][W][2c]; conv2_w [2c][1][3][3], conv2_b [2c], sca_w [c][c], sca_b [c]; gated_out [B][H][W][c]; s_out [B][c] = sca.1(mean(gated));
+ * mean_out [B][c] (may be NULL): the pooled mean itself, formed from the gate kernel's tile partials by the mean kernel on either route.
+ * c a multiple of 4, B <= 65535. */
+int irsde_debug_naf_gate_sca(const float* u, int B, int H, int W, int c, const float* conv2_w, const float* conv2_b, const float* sca_w, const float* sca_b,
+                             float* gated_out, float* mean_out, float* s_out, void* stream);
+/* TLSC: launch_tlsc_pool of g [B][h][w][c] over k1 x k2 windows -> pooled_out [B][h - k1 + 1][w - k2 + 1][c] (window means); then scaled_out = g (a copy)
+ * times the caller's scale_map (device, pooled_out's shape) replicate-padded to h x w by launch_tlsc_scale.  c a multiple of 4, 1 <= k1 <= h, 1 <= k2 <= w. */
+int irsde_debug_tlsc(const float* g, int B, int h, int w, int c, int k1, int k2, float* pooled_out, const float* scale_map, float* scaled_out, void* stream);
+/* Channel LayerNorm + FiLM: launch_layernorm_film.  x / out [M][C], image of pixel m = m / ppi; g [C] HOST; fscale / fshift: DEVICE rows of C floats,
+ * row of image b at + b * film_bstride (0: one shared row); out = LN(x) * g * (fscale + 1) + fshift.  C a multiple of 4 in [4, 2048], film_bstride a multiple of 4. */
+int irsde_debug_ln_film(const float* x, long long M, int C, long long ppi, const float* g, const float* fscale, const float* fshift, int film_bstride,
+                        float* out, void* stream);
+/* naf_lnconv_kernel (fp16 operand mode; c in {64, 128, 256}, Cout a multiple of 64) in its three prologues.  x [M][c]; w [Cout][c] and bias [Cout] HOST
+ * (rounded to fp16 on the device like an engine's copy); mode
+ *   0  launch_naf_lnconv: out [M][Cout] = W fp16(LN(x) g (fscale + 1) + fshift) + bias       (norm1 + conv1)
+ *   1  the same with the SimpleGate epilogue (w rows interleaved like a packed conv4): out [M][Cout / 2] = v[j] v[j + Cout / 2], then, with gate_film
+ *      (DEVICE, per image [scale (Cout / 2) | shift (Cout / 2)], row stride gate_film_bstride; may be NULL), * (scale + 1) + shift   (norm2 + conv4)
+ *   2  launch_naf_pwconv: out [M][Cout] = res + (W fp16(x * in_scale[image]) + bias) * ch_scale  (conv3; in_scale DEVICE [images][c])
+ *   3  the same without in_scale (conv5; in_scale is ignored)
+ * g [c] (modes 0 / 1) and ch_scale [Cout] (modes 2 / 3) HOST; fscale / fshift as in irsde_debug_ln_film; res DEVICE [M][Cout].  Arguments a mode does not
+ * use may be NULL. */
+int irsde_debug_naf_lnconv(int mode, const float* x, long long M, int c, int Cout, long long ppi, const float* g, const float* fscale, const float* fshift,
+                           int film_bstride, const float* w, const float* bias, const float* gate_film, int gate_film_bstride, const float* in_scale,
+                           const float* ch_scale, const float* res, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
