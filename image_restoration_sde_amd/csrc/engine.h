@@ -125,6 +125,11 @@ struct NafChainW {
     unsigned short* wsplit[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // [G]: the fragment streams of the G-groups-per-image kernel, built on first use
 };
 
+// the reference-layout tensors of one such block (HOST pointers): what pack_naf_chain_host packs
+struct NafChainHostW {
+    const float *norm1_g, *conv1_w, *conv1_b, *conv2_w, *conv2_b, *sca_w, *sca_b, *conv3_w, *conv3_b, *beta, *norm2_g, *conv4_w, *conv4_b, *conv5_w, *conv5_b, *gamma;
+};
+
 enum OpKind { OP_CONV = 0, OP_LN = 1, OP_ATTN = 2, OP_OTHER = 3, OP_WINO = 4, OP_NKINDS = 5 };
 
 struct Op {
@@ -484,6 +489,8 @@ void pack_conv_rows(const float* w_oihw, const float* bias, int O, int I, int KH
                     std::vector<float>& pb);                          // [O][I][KH][KW] -> [O][KH][KW][I], packed row n' = row perm[n'] (empty: identity)
 std::vector<int> naf_gate_perm(int c);                               // conv4's row order: SimpleGate pairs (j, j + c) adjacent
 std::vector<float> pack_dwconv_taps(const float* w, int c2);         // conv2.weight [2c][1][3][3] -> [9][2c]
+// naf_chain_kernel's fp16 fragment streams (naf_chain_weight_halves) + fp32 vectors (naf_chain_vec_floats) of consecutive 512-channel blocks
+void pack_naf_chain_host(const std::vector<NafChainHostW>& blocks, std::vector<unsigned short>& w, std::vector<float>& vecs);
 
 // engine_plan.hip: one network evaluation as a static launch list over a static arena
 Plan* get_plan(irsde_engine* e, int B, int H, int W, bool per_sample_film, int slot = 0, int b0 = 0);

@@ -216,6 +216,72 @@ int irsde_debug_naf_lnconv(int mode, const float* x, long long M, int c, int Cou
     });
 }
 
+int irsde_debug_naf_chain(const float* x, float* out, int B, int nblocks, const float* norm1_g, const float* conv1_w, const float* conv1_b, const float* conv2_w,
+                          const float* conv2_b, const float* sca_w, const float* sca_b, const float* conv3_w, const float* conv3_b, const float* beta,
+                          const float* norm2_g, const float* conv4_w, const float* conv4_b, const float* conv5_w, const float* conv5_b, const float* gamma,
+                          const float* film, int film_bstride, int film_off, const float* cam, int cam_bstride, int cam_off, int groups, void* stream) {
+    return guard([&] {
+        if (!x || !out || !norm1_g || !conv1_w || !conv1_b || !conv2_w || !conv2_b || !sca_w || !sca_b || !conv3_w || !conv3_b || !beta || !norm2_g || !conv4_w ||
+            !conv4_b || !conv5_w || !conv5_b || !gamma || !film)
+            throw HipError("null argument");
+        // refused before anything is launched: what a launcher cannot run (the kernel reads its rows as aligned float4)
+        if (B < 1 || B > 65535 || nblocks < 1 || nblocks > 64) throw HipError("debug_naf_chain: bad B or nblocks");
+        if (groups != 1 && groups != 2 && groups != 4) throw HipError("debug_naf_chain: groups must be 1, 2 or 4");
+        if (film_bstride < 0 || film_bstride % 4 || film_off < 0 || film_off % 4) throw HipError("debug_naf_chain: bad FiLM stride / offset");
+        if (cam && (cam_bstride < 0 || cam_bstride % 4 || cam_off < 0 || cam_off % 4)) throw HipError("debug_naf_chain: bad lens FiLM stride / offset");
+        hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+        conv_global_init();
+        if (groups > 1 && naf_chain_split_groups(B, groups) > device_cu_count())
+            throw HipError("debug_naf_chain: more work-groups than compute units (they must be co-resident)");
+        constexpr size_t C = 512;
+        std::vector<NafChainHostW> blocks(nblocks);
+        for (int i = 0; i < nblocks; ++i) {
+            NafChainHostW& b = blocks[i];
+            const size_t k = (size_t)i;
+            b.norm1_g = norm1_g + k * C; b.conv1_w = conv1_w + k * 2 * C * C; b.conv1_b = conv1_b + k * 2 * C;
+            b.conv2_w = conv2_w + k * 18 * C; b.conv2_b = conv2_b + k * 2 * C;
+            b.sca_w = sca_w + k * C * C; b.sca_b = sca_b + k * C;
+            b.conv3_w = conv3_w + k * C * C; b.conv3_b = conv3_b + k * C; b.beta = beta + k * C;
+            b.norm2_g = norm2_g + k * C; b.conv4_w = conv4_w + k * 2 * C * C; b.conv4_b = conv4_b + k * 2 * C;
+            b.conv5_w = conv5_w + k * C * C; b.conv5_b = conv5_b + k * C; b.gamma = gamma + k * C;
+        }
+        std::vector<unsigned short> w;
+        std::vector<float> vecs;
+        pack_naf_chain_host(blocks, w, vecs);
+        Scratch mem(s);
+        unsigned short* dw = mem.alloc<unsigned short>(w.size());
+        IRSDE_HIP_CHECK(hipMemcpy(dw, w.data(), w.size() * 2, hipMemcpyHostToDevice));
+        float* dvec = mem.upload(vecs);
+        if (groups == 1) {
+            launch_naf_chain(x, out, dw, dvec, nblocks, B, film, film_bstride, film_off, cam, cam ? cam_bstride : 0, cam ? cam_off : 0, s, 0);
+            IRSDE_HIP_CHECK(hipStreamSynchronize(s));
+            return;
+        }
+        unsigned short* dwg = mem.alloc<unsigned short>(w.size());
+        naf_chain_build_split_weights(dw, dwg, nblocks, groups, s);
+        const size_t sb = naf_chain_split_scratch_bytes(B);
+        char* dscratch = mem.alloc<char>(sb);
+        IRSDE_HIP_CHECK(hipMemset(dscratch, 0, sb));
+        launch_naf_chain_split(x, out, dwg, dvec, nblocks, B, film, film_bstride, film_off, cam, cam ? cam_bstride : 0, cam ? cam_off : 0, groups, dscratch, s);
+        IRSDE_HIP_CHECK(hipStreamSynchronize(s));
+        // one launch, no retry: the error word, then the barrier counters, which the kernel must leave as it found them ([B][4] in front of the error word)
+        std::vector<unsigned> state((size_t)4 * B + 1);
+        IRSDE_HIP_CHECK(hipMemcpy(state.data(), naf_chain_split_error_flag(dscratch, B) - 4 * B, state.size() * 4, hipMemcpyDeviceToHost));
+        if (state[(size_t)4 * B]) throw HipError("debug_naf_chain: the split kernel's groups were not co-resident (spin timeout)");
+        for (size_t i = 0; i < (size_t)4 * B; ++i)
+            if (state[i]) throw HipError("debug_naf_chain: the split kernel left a barrier counter non-zero");
+    });
+}
+
+int irsde_debug_naf_chain_split_order(int nblocks, int groups, int* order_out, long long n) {
+    return guard([&] {
+        if (!order_out || nblocks < 1 || nblocks > 64) throw HipError("debug_naf_chain_split_order: bad argument");
+        const std::vector<int> order = naf_chain_split_order(nblocks, groups);   // (host only; refuses groups other than 2 / 4)
+        if ((long long)order.size() != n) throw HipError("debug_naf_chain_split_order: the order has " + std::to_string(order.size()) + " entries");
+        std::copy(order.begin(), order.end(), order_out);
+    });
+}
+
 int irsde_debug_conv(const float* in0, int C0, const float* in1, int C1, int B, int Hin, int Win, int in_shift,
                      const float* w_oihw, int Cout, int KH, int KW, int stride, int pad, const float* bias,
                      const float* film, int film_bstride, int silu, const float* res, float* out, int naive,

@@ -351,14 +351,15 @@ NafBlockW pack_nafblock(irsde_engine* e, const std::string& p, int c) {
 }
 
 
-// The fp16 weight streams + fp32 vectors of naf_chain_kernel (csrc/naf_chain.hip) for the blocks `prefixes` (consecutive 512-channel NAFBlocks).
+// The fp16 weight streams + fp32 vectors of naf_chain_kernel (csrc/naf_chain.hip) for the consecutive 512-channel NAFBlocks `blocks` (host tensors in
+// reference layout): the packing both pack_naf_chain (tensors looked up by name) and the test hook irsde_debug_naf_chain (engine_debug.hip) run.
 // Stream of wave w, block i: [conv1: 4 passes x 16 k steps x (lo tile, hi tile)] [sca.1: 16 k steps x 4 tiles] [conv3: 2 passes x 16 x 2 tiles] [conv4: as conv1]
 // [conv5: as conv3]; a fragment = 64 lanes x 8 halves: lane l holds W[tile channel base + (l & 15)][32 ks + 8 (l >> 4) + 0 .. 7].
-NafChainW pack_naf_chain(irsde_engine* e, const std::vector<std::string>& prefixes, const NafBlockW& first) {
+void pack_naf_chain_host(const std::vector<NafChainHostW>& blocks, std::vector<unsigned short>& w, std::vector<float>& vecs) {
     constexpr int C = 512, FR = 448;
-    const int nb = (int)prefixes.size();
-    std::vector<unsigned short> w(naf_chain_weight_halves(nb));
-    std::vector<float> vecs(naf_chain_vec_floats(nb));
+    const int nb = (int)blocks.size();
+    w.assign(naf_chain_weight_halves(nb), 0);
+    vecs.assign(naf_chain_vec_floats(nb), 0.f);
     const size_t NV = vecs.size() / nb;
     auto h16 = [](float v) {
         const _Float16 h = (_Float16)v;   // round to nearest even
@@ -367,12 +368,8 @@ NafChainW pack_naf_chain(irsde_engine* e, const std::vector<std::string>& prefix
         return u;
     };
     for (int i = 0; i < nb; ++i) {
-        const std::string& p = prefixes[i];
-        const float* w1 = need(e, p + "conv1.weight").data.data();
-        const float* ws = need(e, p + "sca.1.weight").data.data();
-        const float* w3 = need(e, p + "conv3.weight").data.data();
-        const float* w4 = need(e, p + "conv4.weight").data.data();
-        const float* w5 = need(e, p + "conv5.weight").data.data();
+        const NafChainHostW& b = blocks[i];
+        const float *w1 = b.conv1_w, *ws = b.sca_w, *w3 = b.conv3_w, *w4 = b.conv4_w, *w5 = b.conv5_w;
         for (int wave = 0; wave < 8; ++wave) {
             unsigned short* dst = w.data() + ((size_t)wave * nb + i) * FR * 512;
             auto frag = [&](const float* W, int chbase, int ks) {
@@ -402,29 +399,46 @@ NafChainW pack_naf_chain(irsde_engine* e, const std::vector<std::string>& prefix
             if (dst != w.data() + ((size_t)wave * nb + i + 1) * FR * 512) throw HipError("pack_naf_chain: stream length mismatch");
         }
         float* v = vecs.data() + (size_t)i * NV;
-        auto put = [&](int off, const std::string& name, size_t nexp) {
-            const HostTensor& t = need(e, p + name);
-            if (t.data.size() != nexp) throw HipError("pack_naf_chain: unexpected size of " + p + name);
-            std::copy(t.data.begin(), t.data.end(), v + off);
-        };
+        auto put = [&](int off, const float* src, size_t n) { std::copy(src, src + n, v + off); };
         // offsets: naf_chain.hip NV_*
-        put(0, "norm1.g", C); put(512, "norm2.g", C); put(1024, "conv1.bias", 2 * C); put(2048, "conv2.bias", 2 * C);
+        put(0, b.norm1_g, C); put(512, b.norm2_g, C); put(1024, b.conv1_b, 2 * C); put(2048, b.conv2_b, 2 * C);
         {   // NV_TAP = 3072: conv2.weight [2c][1][3][3] as fp16 rows of 16 halves per channel (taps 0 .. 8, then zeros)
-            const HostTensor& t = need(e, p + "conv2.weight");
-            if (t.data.size() != (size_t)18 * C) throw HipError("pack_naf_chain: unexpected conv2.weight size");
             unsigned short* hd = reinterpret_cast<unsigned short*>(v + 3072);
             for (int ch = 0; ch < 2 * C; ++ch)
-                for (int k = 0; k < 16; ++k) hd[ch * 16 + k] = k < 9 ? h16(t.data[(size_t)ch * 9 + k]) : (unsigned short)0;
+                for (int k = 0; k < 16; ++k) hd[ch * 16 + k] = k < 9 ? h16(b.conv2_w[(size_t)ch * 9 + k]) : (unsigned short)0;
         }
-        put(11264, "sca.1.bias", C); put(11776, "conv3.bias", C); put(12288, "beta", C); put(12800, "conv4.bias", 2 * C); put(13824, "conv5.bias", C);
-        put(14336, "gamma", C);
+        put(11264, b.sca_b, C); put(11776, b.conv3_b, C); put(12288, b.beta, C); put(12800, b.conv4_b, 2 * C); put(13824, b.conv5_b, C);
+        put(14336, b.gamma, C);
     }
+}
+
+NafChainW pack_naf_chain(irsde_engine* e, const std::vector<std::string>& prefixes, const NafBlockW& first) {
+    constexpr size_t C = 512;
+    std::vector<NafChainHostW> blocks;
+    for (const std::string& p : prefixes) {
+        auto get = [&](const char* name, size_t nexp) {
+            const HostTensor& t = need(e, p + name);
+            if (t.data.size() != nexp) throw HipError("pack_naf_chain: unexpected size of " + p + name);
+            return t.data.data();
+        };
+        NafChainHostW b;
+        b.norm1_g = get("norm1.g", C); b.conv1_w = get("conv1.weight", 2 * C * C); b.conv1_b = get("conv1.bias", 2 * C);
+        b.conv2_w = get("conv2.weight", 18 * C); b.conv2_b = get("conv2.bias", 2 * C);
+        b.sca_w = get("sca.1.weight", C * C); b.sca_b = get("sca.1.bias", C);
+        b.conv3_w = get("conv3.weight", C * C); b.conv3_b = get("conv3.bias", C); b.beta = get("beta", C);
+        b.norm2_g = get("norm2.g", C); b.conv4_w = get("conv4.weight", 2 * C * C); b.conv4_b = get("conv4.bias", 2 * C);
+        b.conv5_w = get("conv5.weight", C * C); b.conv5_b = get("conv5.bias", C); b.gamma = get("gamma", C);
+        blocks.push_back(b);
+    }
+    std::vector<unsigned short> w;
+    std::vector<float> vecs;
+    pack_naf_chain_host(blocks, w, vecs);
     NafChainW cw;
     unsigned short* dw = reinterpret_cast<unsigned short*>(e->dmalloc((w.size() + 1) / 2));
     IRSDE_HIP_CHECK(hipMemcpy(dw, w.data(), w.size() * 2, hipMemcpyHostToDevice));
     cw.w = dw;
     cw.vecs = e->upload(vecs);
-    cw.nblocks = nb;
+    cw.nblocks = (int)blocks.size();
     cw.film_off = first.film_off;
     cw.cam_off = first.cam_off;
     return cw;

@@ -121,6 +121,25 @@ int irsde_debug_naf_lnconv(int mode, const float* x, long long M, int c, int Cou
                            int film_bstride, const float* w, const float* bias, const float* gate_film, int gate_film_bstride, const float* in_scale,
                            const float* ch_scale, const float* res, float* out, void* stream);
 
+/* naf_chain_kernel (csrc/naf_chain.hip): `nblocks` consecutive 512-channel NAFBlocks on B images of 8 x 8 pixels as ONE launch of the production launcher —
+ * groups == 1: launch_naf_chain; groups == 2 / 4: naf_chain_build_split_weights + launch_naf_chain_split on a freshly zeroed scratch buffer.
+ * x / out: DEVICE [B][64][512] fp32 (NHWC).  The sixteen weight arguments are HOST pointers in reference layout, each holding `nblocks` consecutive tensors
+ * (norm1.g [512], conv1.weight [1024][512], conv1.bias [1024], conv2.weight [1024][1][3][3], conv2.bias [1024], sca.1.weight [512][512], sca.1.bias [512],
+ * conv3.weight [512][512], conv3.bias [512], beta [512], norm2.g [512], conv4.weight [1024][512], conv4.bias [1024], conv5.weight [512][512], conv5.bias [512],
+ * gamma [512]); they go through the engine's own packing (pack_naf_chain_host).  film: DEVICE, the row of image b at + b * film_bstride (0: one shared row),
+ * block i at + film_off + i * 2048 = [shift_att | scale_att | shift_ffn | scale_ffn]; cam: DEVICE or NULL, row b at + b * cam_bstride, block i at
+ * + cam_off + i * 1024 = [scale | shift].  Strides and offsets are multiples of 4.  Refused before anything is launched: groups other than 1 / 2 / 4,
+ * more work-groups (8 ceil(B / 8) groups) than compute units, nblocks < 1.  groups > 1: the call launches ONCE; if the kernel raised its error word the
+ * call fails naming the co-residency (spin) timeout, and it fails if a barrier counter was not restored to zero.  Synchronises `stream`.
+ * tests/test_gpu_naf_chain.py compares it with tests/naf_chain_oracle.py. */
+int irsde_debug_naf_chain(const float* x, float* out, int B, int nblocks, const float* norm1_g, const float* conv1_w, const float* conv1_b, const float* conv2_w,
+                          const float* conv2_b, const float* sca_w, const float* sca_b, const float* conv3_w, const float* conv3_b, const float* beta,
+                          const float* norm2_g, const float* conv4_w, const float* conv4_b, const float* conv5_w, const float* conv5_b, const float* gamma,
+                          const float* film, int film_bstride, int film_off, const float* cam, int cam_bstride, int cam_off, int groups, void* stream);
+/* Host only: naf_chain_split_order(nblocks, groups) — for every 1 KB fragment of the groups-per-image weight streams its position in the one-group
+ * streams — into order_out[n], n = 8 * nblocks * 448 (any other n is refused). */
+int irsde_debug_naf_chain_split_order(int nblocks, int groups, int* order_out, long long n);
+
 #ifdef __cplusplus
 }
 #endif
