@@ -14,6 +14,8 @@ csrc/ -> libirsde_hip.so) with the reference's own Python interface on top:
                        latent_denoising_model.py} (encode once, sample in the latent, decode once)
     stereo_sr.ConditionalNAFNet
                        codes/config/stereo-sr/models/modules/DenoisingNAFNet_arch.py (NAFBlocks + SCAM on stereo pairs)
+    stereo_sr.ConditionalUNet
+                       codes/config/stereo-sr/models/modules/DenoisingUNet_arch.py (the IR-SDE UNet with a full-resolution SCAM on every level)
     metrics            codes/utils/img_utils.py:136-234 + codes/data/util.py:177-198 (tensor2img / PSNR / SSIM / Y channel)
 """
 from ._lib import IrsdeError, IrsdeLibraryError, build_library  # noqa: F401

@@ -34,6 +34,7 @@ FLAG_SPLIT_BF16X2 = 16384
 FLAG_SPLIT_F16X2 = 32768
 FLAG_NAF_STEREO = 65536
 FLAG_NAF_UNCOND = 131072
+FLAG_UNET_STEREO = 262144
 SAMPLE_GRAPH = 1
 SAMPLE_PROFILE = 2
 
@@ -42,7 +43,7 @@ SYMBOLS = [
     "irsde_last_error", "irsde_version", "irsde_create", "irsde_create_nafnet", "irsde_destroy", "irsde_num_weights",
     "irsde_weight_name", "irsde_weight_shape", "irsde_load_weight", "irsde_finalize_weights",
     "irsde_set_schedule", "irsde_unet_forward", "irsde_sample", "irsde_sde_step", "irsde_philox_normal",
-    "irsde_get_profile", "irsde_debug_tap", "irsde_work_model", "irsde_debug_conv", "irsde_plan_describe", "irsde_bench_conv", "irsde_op_profile", "irsde_debug_split_gemm", "irsde_bench_naf_chain", "irsde_debug_force_subbatches", "irsde_debug_force_chain_groups", "irsde_debug_scam",
+    "irsde_get_profile", "irsde_debug_tap", "irsde_work_model", "irsde_debug_conv", "irsde_plan_describe", "irsde_bench_conv", "irsde_op_profile", "irsde_debug_split_gemm", "irsde_bench_naf_chain", "irsde_debug_force_subbatches", "irsde_debug_force_chain_groups", "irsde_debug_scam", "irsde_debug_scam_full",
     "irsde_debug_naf_gate_sca", "irsde_debug_tlsc", "irsde_debug_ln_film", "irsde_debug_naf_lnconv", "irsde_debug_naf_chain", "irsde_debug_naf_chain_split_order",
     "irsde_eval_metrics", "irsde_tensor2img",
     "irsde_set_lens_info", "irsde_nafnet_set_local_pool", "irsde_create_latent_unet", "irsde_latent_shapes", "irsde_latent_encode", "irsde_latent_decode", "irsde_latent_hidden",
@@ -131,6 +132,7 @@ def _declare(lib):
     lib.irsde_debug_force_subbatches.argtypes = [c.c_int]
     lib.irsde_debug_force_chain_groups.argtypes = [c.c_int]
     lib.irsde_debug_scam.argtypes = [P, c.c_int, c.c_int, c.c_int, c.c_int] + [P] * 12 + [P, P]
+    lib.irsde_debug_scam_full.argtypes = [P, c.c_int, c.c_int, c.c_int, c.c_int] + [P] * 12 + [P, P]
     lib.irsde_debug_naf_gate_sca.argtypes = [P, c.c_int, c.c_int, c.c_int, c.c_int] + [P] * 8
     lib.irsde_debug_tlsc.argtypes = [P] + [c.c_int] * 6 + [P] * 4
     lib.irsde_debug_ln_film.argtypes = [P, c.c_int64, c.c_int, c.c_int64, P, P, P, c.c_int, P, P]

@@ -296,9 +296,23 @@ void launch_scam_prologue(const float* x, const float* g_l, const float* g_r, fl
 void launch_scam_core(const float* qv, float* F, int B, int H, int W, int c, hipStream_t s);
 void launch_scam_epilogue(const float* x, const float* F, const float* beta, const float* gamma, float* out, int B, int H, int W, int c, hipStream_t s);
 void scam_pack_proj(const float* w1, const float* b1, const float* w2, const float* b2, int c, std::vector<float>& w, std::vector<float>& bias);
+// Full-resolution SCAM of the stereo-sr ConditionalUNet (scam.hip; DenoisingUNet_arch.py:18-56): no downsample, no upsample, H' = H, W' = W.
+//   prologue  x2 [2B][H][W][LN(x) (norm_l / norm_r gain) | x]
+//   core      qv [2B][H][W][Q | V] -> F [2B][H][W][c]
+//   epilogue  x += (beta | gamma)[ch] * F, in place
+constexpr int kScamFullMaxW = 1024;   // widest row: the 16 x W score strip (and nothing else of S) lives in LDS
+constexpr int kScamFullMaxC = 2048;
+void scam_full_check_shape(int H, int W, int c);   // throws HipError for shapes the kernels do not cover
+void launch_scam_full_prologue(const float* x, const float* g_l, const float* g_r, float* x2, int B, int H, int W, int c, hipStream_t s);
+void launch_scam_full_core(const float* qv, float* F, int B, int H, int W, int c, hipStream_t s);
+void launch_scam_full_epilogue(float* x, const float* F, const float* beta, const float* gamma, int B, int H, int W, int c, hipStream_t s);
 // stereo network glue: 6-channel pair tensors <-> the 2B-view network batch
 void launch_stereo_prep(const float* xt, const float* cond, float* x0, int B, int ic, int P, int H, int W, int Hp, int Wp, hipStream_t s);
 void launch_stereo_pack_pred(const float* in, float* out, int B, int ic, int Hp, int Wp, int in_stride, int out_stride, hipStream_t s);
+// the stereo UNet's forms: cat(xt_v, cond_v) with the reflect pad, and eps_hat = xt + cat(x_l, x_r) (xt: the pair state [B][2 ic][H][W])
+void launch_stereo_unet_prep(const float* xt, const float* cond, float* x0, int B, int ic, int P, int H, int W, int Hp, int Wp, hipStream_t s);
+void launch_stereo_unet_pack_pred(const float* in, const float* xt, float* out, int B, int ic, int H, int W, int Hp, int Wp, int in_stride, int out_stride,
+                                  hipStream_t s);
 
 // Full softmax attention over N tokens (denoising-sde bottleneck): qkv [B][N][384] -> out [B][N][128].
 void launch_full_attention(const float* qkv, float* out, int B, int N, hipStream_t s);

@@ -92,6 +92,13 @@ struct ResW {
     int film_off = 0;
     int Cout = 0;
 };
+// SCAM(c) of the stereo-sr ConditionalUNet (IRSDE_FLAG_UNET_STEREO; stereo-sr DenoisingUNet_arch.py:18-35)
+struct ScamW {
+    int c = 0;
+    float *gl = nullptr, *gr = nullptr;   // norm_l.g / norm_r.g
+    ConvW l, r;                           // [[proj1, 0], [0, proj2]] per view: [LN(x) | x] (2c) -> [Q | V] (2c), bias [b1 | b2]
+    float *beta = nullptr, *gamma = nullptr;
+};
 struct AttnW {
     float* g1 = nullptr;
     ConvW qkv, out;
@@ -326,6 +333,8 @@ struct irsde_engine {
     std::vector<ConvW> down_conv;
     ResW mid1, mid2;
     AttnW mid_attn;
+    std::vector<ScamW> down_scam, up_scam;   // IRSDE_FLAG_UNET_STEREO: downs.i.3 / ups.j.3
+    ScamW mid_scam;                          // mid_fusion
     std::vector<ResW> up_res;
     std::vector<AttnW> up_attn;
     std::vector<ConvW> up_conv;
@@ -335,7 +344,7 @@ struct irsde_engine {
 
     // ConditionalNAFNet (arch == 1)
     int arch = 0;
-    int naf_ic = 0;   // the network's img_channel (cfg.in_nc is the sampler state's channel count: 2 naf_ic for IRSDE_FLAG_NAF_STEREO)
+    int naf_ic = 0;   // the network's img_channel (cfg.in_nc is the sampler state's channel count: 2 naf_ic for IRSDE_FLAG_NAF_STEREO / _UNET_STEREO)
     std::vector<int> naf_enc_nums, naf_dec_nums;
     int naf_mid_num = 0;
     std::vector<std::vector<NafBlockW>> naf_enc, naf_dec;
@@ -458,6 +467,8 @@ namespace irsde {
 
 inline bool naf_lens(const irsde_engine* e) { return (e->cfg.flags & IRSDE_FLAG_NAF_LENS) != 0; }
 inline bool naf_stereo(const irsde_engine* e) { return e->arch == 1 && (e->cfg.flags & IRSDE_FLAG_NAF_STEREO) != 0; }
+inline bool unet_stereo(const irsde_engine* e) { return e->arch == 0 && (e->cfg.flags & IRSDE_FLAG_UNET_STEREO) != 0; }
+inline bool stereo_engine(const irsde_engine* e) { return naf_stereo(e) || unet_stereo(e); }   // pair state, the network on the 2B views
 // The networks without a condition input (denoising-sde): forward(x, time), DenoisingSDE sampler modes 3 / 4, cond / mu may be NULL
 inline bool uncond_engine(const irsde_engine* e) {
     return (e->arch == 0 && (e->cfg.flags & IRSDE_FLAG_UNCOND_FULLATTN) != 0) || (e->arch == 1 && (e->cfg.flags & IRSDE_FLAG_NAF_UNCOND) != 0);

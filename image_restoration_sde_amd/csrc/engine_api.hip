@@ -126,10 +126,20 @@ int irsde_create(const irsde_config* cfg, irsde_engine** out) {
             throw HipError("in_nc/out_nc must be in 1..4");
         if (cfg->in_nc != cfg->out_nc) throw HipError("sampler needs in_nc == out_nc");
         if ((cfg->nf << cfg->depth) > 2048) throw HipError("nf * 2^depth must be <= 2048");
+        const bool stereo = (cfg->flags & IRSDE_FLAG_UNET_STEREO) != 0;
+        if (stereo) {
+            if (cfg->flags & (IRSDE_FLAG_BF16 | IRSDE_FLAG_BF16_ACT | IRSDE_FLAG_FP16 | IRSDE_FLAG_SPLIT_BF16X2 | IRSDE_FLAG_SPLIT_F16X2))
+                throw HipError("IRSDE_FLAG_UNET_STEREO runs in fp32 only (the 16-bit and split-operand modes are not covered for the full-resolution SCAM network)");
+            if (cfg->flags & IRSDE_FLAG_UNCOND_FULLATTN) throw HipError("IRSDE_FLAG_UNET_STEREO cannot be combined with IRSDE_FLAG_UNCOND_FULLATTN");
+        }
         if (cfg->flags & IRSDE_FLAG_NAF_STEREO) throw HipError("IRSDE_FLAG_NAF_STEREO: the stereo network is a ConditionalNAFNet (irsde_create_nafnet)");
         if (cfg->flags & IRSDE_FLAG_NAF_UNCOND) throw HipError("IRSDE_FLAG_NAF_UNCOND: irsde_create_nafnet only (the unconditional UNet is IRSDE_FLAG_UNCOND_FULLATTN)");
         auto* e = new irsde_engine();
         e->cfg = *cfg;
+        if (stereo) {   // the sampler state holds [L | R] per pair
+            e->naf_ic = cfg->in_nc;
+            e->cfg.in_nc = e->cfg.out_nc = 2 * cfg->in_nc;
+        }
         if (cfg->flags & IRSDE_FLAG_BF16_ACT) {
             if (cfg->flags & (IRSDE_FLAG_UNCOND_FULLATTN | IRSDE_FLAG_NAIVE_CONV)) {
                 delete e;
@@ -152,6 +162,7 @@ int irsde_create_nafnet(const irsde_nafnet_config* cfg, irsde_engine** out) {
         if (cfg->n_enc < 1 || cfg->n_enc > 6 || cfg->n_dec != cfg->n_enc) throw HipError("need 1..6 encoder stages and as many decoder stages");
         if ((cfg->width << cfg->n_enc) > 2048) throw HipError("width * 2^stages must be <= 2048");
         if (cfg->flags & IRSDE_FLAG_BF16_ACT) throw HipError("IRSDE_FLAG_BF16_ACT: conditional UNet only");
+        if (cfg->flags & IRSDE_FLAG_UNET_STEREO) throw HipError("IRSDE_FLAG_UNET_STEREO: the stereo UNet is a ConditionalUNet (irsde_create)");
         const bool stereo = (cfg->flags & IRSDE_FLAG_NAF_STEREO) != 0;
         if (stereo) {
             if (cfg->flags & (IRSDE_FLAG_NAF_LENS | IRSDE_FLAG_NAF_INTRO_SKIP))
@@ -302,7 +313,7 @@ int irsde_unet_forward(irsde_engine* e, const float* xt, const float* cond, cons
                                            (size_t)e->film_row * 4, hipMemcpyDeviceToDevice, s));
         } else {
             // stereo with per-pair times: one row per view v B + b (time = torch.cat([time, time], 0), stereo-sr DenoisingNAFNet_arch.py:213)
-            const int rows = (naf_stereo(e) && nt > 1 ? 2 : 1) * nt;
+            const int rows = (stereo_engine(e) && nt > 1 ? 2 : 1) * nt;
             std::vector<float> tv(rows);
             for (int i = 0; i < rows; ++i) tv[i] = (float)t_host[i % nt];
             float* dtv = nullptr;

@@ -137,6 +137,50 @@ int irsde_debug_scam(const float* x, int B, int H, int W, int C, const float* no
     });
 }
 
+int irsde_debug_scam_full(const float* x, int B, int H, int W, int C, const float* norm_l_g, const float* norm_r_g, const float* l_proj1_w,
+                          const float* l_proj1_b, const float* r_proj1_w, const float* r_proj1_b, const float* l_proj2_w, const float* l_proj2_b,
+                          const float* r_proj2_w, const float* r_proj2_b, const float* beta, const float* gamma, float* out, void* stream) {
+    return guard([&] {
+        if (!x || !out || !norm_l_g || !norm_r_g || !l_proj1_w || !l_proj1_b || !r_proj1_w || !r_proj1_b || !l_proj2_w || !l_proj2_b || !r_proj2_w ||
+            !r_proj2_b || !beta || !gamma)
+            throw HipError("null argument");
+        if (B < 1 || (long long)B * H > 65535) throw HipError("debug_scam_full: bad shape");
+        scam_full_check_shape(H, W, C);
+        hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+        conv_global_init();
+        std::vector<float> wl, bl, wr, br;
+        scam_pack_proj(l_proj1_w, l_proj1_b, l_proj2_w, l_proj2_b, C, wl, bl);
+        scam_pack_proj(r_proj1_w, r_proj1_b, r_proj2_w, r_proj2_b, C, wr, br);
+        Scratch mem(s);
+        auto up = [&](const float* h, size_t n) {
+            float* d = mem.alloc<float>(std::max<size_t>(n, 16));
+            if (h) IRSDE_HIP_CHECK(hipMemcpy(d, h, n * 4, hipMemcpyHostToDevice));
+            return d;
+        };
+        float *dgl = up(norm_l_g, C), *dgr = up(norm_r_g, C), *dbe = up(beta, C), *dga = up(gamma, C);
+        float *dwl = up(wl.data(), wl.size()), *dbl = up(bl.data(), bl.size()), *dwr = up(wr.data(), wr.size()), *dbr = up(br.data(), br.size());
+        const size_t vsz = (size_t)B * H * W * 2 * C;
+        float *x2 = up(nullptr, 2 * vsz), *qv = up(nullptr, 2 * vsz), *F = up(nullptr, vsz), *dz = up(nullptr, 256);
+        IRSDE_HIP_CHECK(hipMemset(dz, 0, 1024));
+        launch_scam_full_prologue(x, dgl, dgr, x2, B, H, W, C, s);
+        for (int v = 0; v < 2; ++v) {
+            ConvParams p;
+            p.in0 = x2 + v * vsz; p.C0 = 2 * C; p.pix0 = 2 * C;
+            p.Hin = H; p.Win = W;
+            p.w = v ? dwr : dwl; p.Cout = 2 * C; p.KH = p.KW = 1; p.stride = 1;
+            p.B = B; p.Ho = H; p.Wo = W;
+            p.out = qv + v * vsz; p.out_stride = 2 * C;
+            p.bias = v ? dbr : dbl;
+            p.zeros = dz;
+            launch_conv(p, s);
+        }
+        launch_scam_full_core(qv, F, B, H, W, C, s);
+        if (out != x) IRSDE_HIP_CHECK(hipMemcpyAsync(out, x, vsz * sizeof(float), hipMemcpyDeviceToDevice, s));   // (vsz = 2 B H W C: the whole tensor)
+        launch_scam_full_epilogue(out, F, dbe, dga, B, H, W, C, s);
+        IRSDE_HIP_CHECK(hipStreamSynchronize(s));
+    });
+}
+
 int irsde_debug_naf_gate_sca(const float* u, int B, int H, int W, int c, const float* conv2_w, const float* conv2_b, const float* sca_w, const float* sca_b,
                              float* gated_out, float* mean_out, float* s_out, void* stream) {
     return guard([&] {

@@ -600,6 +600,65 @@ struct Builder {
         return out;
     }
 
+    // SCAM.forward of the stereo-sr ConditionalUNet — DenoisingUNet_arch.py:37-56 (csrc/scam.hip, the *_full kernels): x holds the 2 B views [L | R]
+    // of B pairs and is updated IN PLACE (x += scale * F) unless activations are kept for taps.  Takes over x: the caller uses the returned tensor.
+    Tensor scam_full(const ScamW& w, const Tensor& x) {
+        const int c = x.C, Bp = x.B / 2, H = x.H, W = x.W;
+        if (x.bf16 || c != w.c || (x.B & 1)) throw HipError("internal: SCAM input");
+        scam_full_check_shape(H, W, c);
+        const size_t vsz = (size_t)Bp * H * W * 2 * c;   // one view's [LN(x) | x] / [Q | V]
+        float* x2 = pl->alloc(2 * vsz, reuse);
+        float* qv = pl->alloc(2 * vsz, reuse);
+        float* F = pl->alloc(vsz, reuse);
+        char buf[160];
+        auto name = [&](const char* what) {
+            snprintf(buf, sizeof buf, "scam_full_%s B=%d c=%d hw=%dx%d", what, x.B, c, H, W);
+            pl->net_ops.back().desc = buf;
+        };
+        {
+            const float *xp = x.p, *gl = w.gl, *gr = w.gr;
+            push_other(OP_LN, [=](hipStream_t s) { launch_scam_full_prologue(xp, gl, gr, x2, Bp, H, W, c, s); });
+            name("prologue(LayerNorm -> [LN(x) | x])");
+        }
+        for (int v = 0; v < 2; ++v) {   // [Q | V] = [[proj1, 0], [0, proj2]] [LN(x) | x] + [b1 | b2]: one GEMM per view (its weights)
+            const ConvW& cw = v ? w.r : w.l;
+            ConvParams p;
+            p.in0 = x2 + v * vsz; p.C0 = 2 * c; p.pix0 = 2 * c;
+            p.Hin = H; p.Win = W;
+            p.w = cw.w; p.Cout = 2 * c; p.KH = p.KW = 1; p.stride = 1;
+            p.B = Bp; p.Ho = H; p.Wo = W;
+            p.out = qv + v * vsz; p.out_stride = 2 * c;
+            p.bias = cw.bias;
+            push_conv(p);
+            pl->net_ops.back().desc = std::string(v ? "scam_full_proj(r) " : "scam_full_proj(l) ") + pl->net_ops.back().desc;
+        }
+        {
+            push_other(OP_ATTN, [=](hipStream_t s) { launch_scam_full_core(qv, F, Bp, H, W, c, s); });
+            name("core(S strips + softmax + PV, fp32 MFMA)");
+        }
+        Tensor out = x;
+        if (!reuse) {   // IRSDE_FLAG_KEEP_ACTIVATIONS: the SCAM input stays readable as a tap
+            out = talloc(x.B, H, W, c);
+            const float* src = x.p;
+            float* dst = out.p;
+            const size_t bytes = x.numel() * sizeof(float);
+            push_other(OP_OTHER, [=](hipStream_t s) { IRSDE_HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s)); });
+            name("copy(kept activations)");
+        }
+        {
+            const float *be = w.beta, *ga = w.gamma;
+            float* op = out.p;
+            push_other(OP_OTHER, [=](hipStream_t s) { launch_scam_full_epilogue(op, F, be, ga, Bp, H, W, c, s); });
+            name("epilogue(scale + residual, in place)");
+        }
+        if (reuse) {
+            pl->release(x2);
+            pl->release(qv);
+            pl->release(F);
+        }
+        return out;
+    }
+
     // ResBlock.forward — module_util.py:136-146
     Tensor resblock(const ResW& w, const Tensor& in0, const Tensor* in1) {
         Tensor R;
@@ -915,7 +974,7 @@ int forced_chain_groups() { return g_force_chain_groups.load(std::memory_order_r
 static std::atomic<int> g_force_subbatches{0};
 void set_force_subbatches(int n) { g_force_subbatches.store(n, std::memory_order_relaxed); }
 int naf_subbatches(const irsde_engine* e, int B, int H, int W) {
-    if (e->arch == 2 || naf_stereo(e) || (e->cfg.flags & (IRSDE_FLAG_NAIVE_CONV | IRSDE_FLAG_KEEP_ACTIVATIONS))) return 1;
+    if (e->arch == 2 || stereo_engine(e) || (e->cfg.flags & (IRSDE_FLAG_NAIVE_CONV | IRSDE_FLAG_KEEP_ACTIVATIONS))) return 1;
     int n = g_force_subbatches.load(std::memory_order_relaxed);
     if (n <= 0) {
         static const int env = tuning_env_int("IRSDE_SUBBATCHES", 0);
@@ -980,7 +1039,8 @@ Plan* get_plan(irsde_engine* e, int B, int H, int W, bool per_sample_film, int s
 }
 
 static Plan* build_plan(irsde_engine* e, int B, int H, int W, bool per_sample_film, int slot, int b0) {
-    const bool stereo = naf_stereo(e);
+    const bool stereo = stereo_engine(e), ustereo = unet_stereo(e);
+    if (stereo && slot > 0) throw HipError("internal: a stereo batch is never split into sub-batches");
     ensure_film_cur(e, per_sample_film ? (stereo ? 2 : 1) * (b0 + B) : 1);   // stereo: rows of views v B + b (both rows of pair b hold its time)
     if (naf_lens(e)) {
         if (e->cam_set < b0 + B) throw HipError("latent-bokeh ConditionalNAFNet: irsde_set_lens_info must cover the batch first");
@@ -1023,7 +1083,11 @@ static Plan* build_plan(irsde_engine* e, int B, int H, int W, bool per_sample_fi
         float* x0 = pl->x0;
         const int Hp = pl->Hp, Wp = pl->Wp;
         const int reflect = e->arch == 1 ? 0 : 1;  // NAFNet zero-pads (DenoisingNAFNet_arch.py:189-194)
-        if (stereo) {   // stereo-sr forward :203-212: views prepared as cat(x_v - cond_v, cond_v) and stacked on the batch axis
+        if (ustereo) {   // stereo-sr DenoisingUNet_arch.py:143-153: views as cat(xt_v, cond_v), stacked on the batch axis, reflect pad
+            const int ic = e->naf_ic;
+            b.push_other(OP_OTHER, [=](hipStream_t s) { launch_stereo_unet_prep(xi, ci, x0, B, ic, P, H, W, Hp, Wp, s); });
+            pl->net_ops.back().desc = "stereo_unet_prep";
+        } else if (stereo) {   // stereo-sr forward :203-212: views prepared as cat(x_v - cond_v, cond_v) and stacked on the batch axis
             const int ic = e->naf_ic;
             b.push_other(OP_OTHER, [=](hipStream_t s) { launch_stereo_prep(xi, ci, x0, B, ic, P, H, W, Hp, Wp, s); });
         } else
@@ -1035,18 +1099,22 @@ static Plan* build_plan(irsde_engine* e, int B, int H, int W, bool per_sample_fi
         return pl;
     }
     // init_conv 7x7 (DenoisingUNet_arch.py:96) as 7 row taps over the zero-bordered input
+    // (stereo-sr: 3x3 as 3 row taps — border 3, so the first tap row / column is +2 — on the NB = 2B views)
+    const int NB = ustereo ? 2 * B : B;
     Tensor x;
     {
         ConvParams p;
         p.in0 = pl->x0; p.C0 = e->init_conv.Cin; p.pix0 = P;
         p.Hin = pl->Hp + 6; p.Win = pl->Wp + 6;
         p.w = e->init_conv.w; p.Cout = nf; p.KH = 7; p.KW = 1; p.stride = 1; p.pad_y = 0; p.pad_x = 0;
-        p.B = B; p.Ho = pl->Hp; p.Wo = pl->Wp;
-        x = b.talloc(B, pl->Hp, pl->Wp, nf);
+        if (ustereo) { p.KH = 3; p.pad_y = -2; p.pad_x = -2; }
+        p.B = NB; p.Ho = pl->Hp; p.Wo = pl->Wp;
+        x = b.talloc(NB, pl->Hp, pl->Wp, nf);
         p.out = x.p; p.out_stride = nf; p.out_bf16 = x.bf16;  // the prepped input x0 stays fp32
         b.push_conv(p);
         // algorithmic accounting: 7x7 x (2*in_nc) real MACs, not the padded 7 x 64
-        const double real = 2.0 * (double)B * pl->Hp * pl->Wp * nf * 49.0 * ((uncond ? 1.0 : 2.0) * in_nc);
+        const double real = ustereo ? 2.0 * (double)NB * pl->Hp * pl->Wp * nf * 9.0 * (2.0 * e->naf_ic)
+                                    : 2.0 * (double)B * pl->Hp * pl->Wp * nf * 49.0 * ((uncond ? 1.0 : 2.0) * in_nc);
         pl->conv_flops += real - pl->net_ops.back().flops;
         pl->net_ops.back().flops = real;  // (exec_flops keeps the padded 7 x 64 K that is actually issued)
     }
@@ -1064,12 +1132,16 @@ static Plan* build_plan(irsde_engine* e, int B, int H, int W, bool per_sample_fi
         Tensor g = b.attn(e->down_attn[i], c);
         b.tfree(c);
         b.tap(d + "2", g);
+        if (ustereo) {   // fusion(x) before h.append(x): the second skip is the SCAM output (stereo-sr DenoisingUNet_arch.py:167-169)
+            g = b.scam_full(e->down_scam[i], g);
+            b.tap(d + "3", g);
+        }
         hs.push_back(g);
         if (i != depth - 1)
             x = b.conv(e->down_conv[i], g, nullptr, 2, 1, 0, nullptr, 0, nullptr);  // Downsample 4x4 s2 p1
         else
             x = b.conv(e->down_conv[i], g, nullptr, 1, 1, 0, nullptr, 0, nullptr);
-        b.tap(d + "3", x);
+        b.tap(d + (ustereo ? "4" : "3"), x);
     }
     {
         Tensor a = b.resblock(e->mid1, x, nullptr);
@@ -1078,6 +1150,10 @@ static Plan* build_plan(irsde_engine* e, int B, int H, int W, bool per_sample_fi
         Tensor g = b.attn(e->mid_attn, a);
         b.tfree(a);
         b.tap("mid_attn", g);
+        if (ustereo) {
+            g = b.scam_full(e->mid_scam, g);
+            b.tap("mid_fusion", g);
+        }
         x = b.resblock(e->mid2, g, nullptr);
         b.tfree(g);
         b.tap("mid_block2", x);
@@ -1095,20 +1171,32 @@ static Plan* build_plan(irsde_engine* e, int B, int H, int W, bool per_sample_fi
         Tensor g = b.attn(e->up_attn[j], c);
         b.tfree(c);
         b.tap(u + "2", g);
+        if (ustereo) {
+            g = b.scam_full(e->up_scam[j], g);
+            b.tap(u + "3", g);
+        }
         if (j != depth - 1)
             x = b.conv(e->up_conv[j], g, nullptr, 1, 1, 1, nullptr, 0, nullptr);  // nearest x2 fused into the 3x3
         else
             x = b.conv(e->up_conv[j], g, nullptr, 1, 1, 0, nullptr, 0, nullptr);
         b.tfree(g);
-        b.tap(u + "3", x);
+        b.tap(u + (ustereo ? "4" : "3"), x);
     }
     {
         Tensor f = b.resblock(e->final_res, x, &x_init);
         b.tfree(x); b.tfree(x_init);
         b.tap("final_res_block", f);
-        Tensor pr = b.conv(e->final_conv, f, nullptr, 1, 1, 0, nullptr, 0, nullptr, pl->pred_stride);
+        Tensor pr = b.conv(e->final_conv, f, nullptr, 1, 1, 0, nullptr, 0, nullptr, ustereo ? (e->naf_ic + 3) & ~3 : pl->pred_stride);
         b.tfree(f);
         pl->pred = pr.p;
+        if (ustereo) {   // the network's output is xt + cat(x_l, x_r) (:193-194): that sum is what the reverse step reads as eps_hat
+            float* pred = pl->alloc((size_t)B * pl->Hp * pl->Wp * pl->pred_stride, false);
+            const float *src = pr.p, *xi = pl->xin;
+            const int ic = e->naf_ic, Hp = pl->Hp, Wp = pl->Wp, is = pr.C, os = pl->pred_stride;
+            b.push_other(OP_OTHER, [=](hipStream_t s) { launch_stereo_unet_pack_pred(src, xi, pred, B, ic, H, W, Hp, Wp, is, os, s); });
+            pl->net_ops.back().desc = "stereo_unet_pack_pred(xt + cat(x_l, x_r))";
+            pl->pred = pred;
+        }
     }
     e->plans.push_back(std::move(plan));
     return pl;

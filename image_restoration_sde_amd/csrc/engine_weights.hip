@@ -32,9 +32,25 @@ void inv_attn(irsde_engine* e, const std::string& p, int c) {
     add_w(e, p + "fn.fn.to_out.0.bias", {c});
     add_w(e, p + "fn.fn.to_out.1.g", {1, c, 1, 1});
 }
+// SCAM(c) of the stereo-sr ConditionalUNet (DenoisingUNet_arch.py:22-35)
+void inv_scam(irsde_engine* e, const std::string& f, int c) {
+    add_w(e, f + "norm_l.g", {1, c, 1, 1});
+    add_w(e, f + "norm_r.g", {1, c, 1, 1});
+    for (const char* pr : {"l_proj1.", "r_proj1.", "l_proj2.", "r_proj2."}) {
+        add_w(e, f + pr + "weight", {c, c, 1, 1});
+        add_w(e, f + pr + "bias", {c});
+    }
+    add_w(e, f + "beta", {1, c, 1, 1});
+    add_w(e, f + "gamma", {1, c, 1, 1});
+}
 void build_inventory(irsde_engine* e) {
     const int nf = e->cfg.nf, depth = e->cfg.depth;
     const bool uncond = (e->cfg.flags & IRSDE_FLAG_UNCOND_FULLATTN) != 0;  // denoising-sde variant
+    const bool stereo = unet_stereo(e);   // stereo-sr: init_conv 3x3 on one view's cat(xt, cond), a SCAM at index 3 of every level
+    const int vnc = stereo ? e->naf_ic : e->cfg.in_nc, vout = stereo ? e->naf_ic : e->cfg.out_nc;
+    const std::string conv_idx = stereo ? "4" : "3";
+    if (stereo) add_w(e, "init_conv.weight", {nf, 2 * vnc, 3, 3});
+    else
     add_w(e, "init_conv.weight", {nf, (uncond ? 1 : 2) * e->cfg.in_nc, 7, 7});
     add_w(e, "time_mlp.1.weight", {e->time_dim, nf});
     add_w(e, "time_mlp.1.bias", {e->time_dim});
@@ -46,24 +62,27 @@ void build_inventory(irsde_engine* e) {
         inv_resblock(e, d + "0.", di, di);
         inv_resblock(e, d + "1.", di, di);
         inv_attn(e, d + "2.", di);
+        if (stereo) inv_scam(e, d + "3.", di);
         if (i != depth - 1) {
-            add_w(e, d + "3.weight", {dout, di, 4, 4});
-            add_w(e, d + "3.bias", {dout});
+            add_w(e, d + conv_idx + ".weight", {dout, di, 4, 4});
+            add_w(e, d + conv_idx + ".bias", {dout});
         } else {
-            add_w(e, d + "3.weight", {dout, di, 3, 3});
+            add_w(e, d + conv_idx + ".weight", {dout, di, 3, 3});
         }
         const std::string u = "ups." + std::to_string(depth - 1 - i) + ".";
         inv_resblock(e, u + "0.", dout + di, dout);
         inv_resblock(e, u + "1.", dout + di, dout);
         inv_attn(e, u + "2.", dout);
+        if (stereo) inv_scam(e, u + "3.", dout);
         if (i != 0) {
-            add_w(e, u + "3.1.weight", {di, dout, 3, 3});
-            add_w(e, u + "3.1.bias", {di});
+            add_w(e, u + conv_idx + ".1.weight", {di, dout, 3, 3});
+            add_w(e, u + conv_idx + ".1.bias", {di});
         } else {
-            add_w(e, u + "3.weight", {di, dout, 3, 3});
+            add_w(e, u + conv_idx + ".weight", {di, dout, 3, 3});
         }
     }
     const int mid = nf << depth;
+    if (stereo) inv_scam(e, "mid_fusion.", mid);
     inv_resblock(e, "mid_block1.", mid, mid);
     if (uncond) {  // full Attention: to_out is a bare Conv2d, no LayerNorm (module_util.py:182-191)
         add_w(e, "mid_attn.fn.norm.g", {1, mid, 1, 1});
@@ -75,8 +94,8 @@ void build_inventory(irsde_engine* e) {
     }
     inv_resblock(e, "mid_block2.", mid, mid);
     inv_resblock(e, "final_res_block.", 2 * nf, nf);
-    add_w(e, "final_conv.weight", {e->cfg.out_nc, nf, 3, 3});
-    add_w(e, "final_conv.bias", {e->cfg.out_nc});
+    add_w(e, "final_conv.weight", {vout, nf, 3, 3});
+    add_w(e, "final_conv.bias", {vout});
 }
 
 const HostTensor& need(irsde_engine* e, const std::string& n) {
@@ -144,20 +163,21 @@ ConvW pack_conv(irsde_engine* e, const std::string& wname, const std::string& bn
 
 // init 7x7 conv as a 7-tap (ky) conv over rows of 7 pixels x P channels: weight [O][7][CK], CK = roundup(7*P,32),
 // element (kx, c) at kx*P + c, zeros elsewhere (the kernel over-reads into the next pixels; zero weights).
+// (stereo-sr: the same form for its 3x3 init_conv, K = 3)
 ConvW pack_init_conv(irsde_engine* e) {
     const HostTensor& t = need(e, "init_conv.weight");
-    const int O = (int)t.shape[0], I = (int)t.shape[1];
+    const int O = (int)t.shape[0], I = (int)t.shape[1], K = (int)t.shape[2];
     const int P = (I + 3) & ~3;
-    const int CK = (7 * P + 31) & ~31;
-    std::vector<float> p((size_t)O * 7 * CK, 0.f);
+    const int CK = (K * P + 31) & ~31;
+    std::vector<float> p((size_t)O * K * CK, 0.f);
     for (int o = 0; o < O; ++o)
         for (int i = 0; i < I; ++i)
-            for (int ky = 0; ky < 7; ++ky)
-                for (int kx = 0; kx < 7; ++kx)
-                    p[((size_t)o * 7 + ky) * CK + kx * P + i] = t.data[(((size_t)o * I + i) * 7 + ky) * 7 + kx];
+            for (int ky = 0; ky < K; ++ky)
+                for (int kx = 0; kx < K; ++kx)
+                    p[((size_t)o * K + ky) * CK + kx * P + i] = t.data[(((size_t)o * I + i) * K + ky) * K + kx];
     ConvW c;
     c.w = e->upload(p);
-    c.Cout = O; c.Cin = CK; c.KH = 7; c.KW = 1;
+    c.Cout = O; c.Cin = CK; c.KH = K; c.KW = 1;
     return c;
 }
 
@@ -171,6 +191,25 @@ ResW pack_res(irsde_engine* e, const std::string& p) {
     r.mlp_w = e->upload(need(e, p + "mlp.1.weight").data);
     r.mlp_b = e->upload(need(e, p + "mlp.1.bias").data);
     return r;
+}
+ScamW pack_scam(irsde_engine* e, const std::string& f) {
+    ScamW w;
+    w.c = (int)need(e, f + "beta").data.size();
+    w.gl = e->upload(need(e, f + "norm_l.g").data);
+    w.gr = e->upload(need(e, f + "norm_r.g").data);
+    for (int v = 0; v < 2; ++v) {
+        const std::string s1 = f + (v ? "r_proj1." : "l_proj1."), s2 = f + (v ? "r_proj2." : "l_proj2.");
+        std::vector<float> wt, bias;
+        scam_pack_proj(need(e, s1 + "weight").data.data(), need(e, s1 + "bias").data.data(), need(e, s2 + "weight").data.data(),
+                       need(e, s2 + "bias").data.data(), w.c, wt, bias);
+        ConvW& cw = v ? w.r : w.l;
+        cw.w = e->upload(wt);
+        cw.bias = e->upload(bias);
+        cw.Cout = cw.Cin = 2 * w.c;
+    }
+    w.beta = e->upload(need(e, f + "beta").data);
+    w.gamma = e->upload(need(e, f + "gamma").data);
+    return w;
 }
 AttnW pack_attn(irsde_engine* e, const std::string& p) {
     AttnW a;
@@ -669,6 +708,8 @@ void finalize(irsde_engine* e) {
         return;
     }
     const int depth = e->cfg.depth;
+    const bool stereo = unet_stereo(e);
+    const std::string ci = stereo ? "4" : "3";   // stereo-sr: index 3 of a level is its SCAM
     e->init_conv = pack_init_conv(e);
     e->tm_w1 = e->upload(need(e, "time_mlp.1.weight").data);
     e->tm_b1 = e->upload(need(e, "time_mlp.1.bias").data);
@@ -689,8 +730,10 @@ void finalize(irsde_engine* e) {
         e->down_res.push_back(pack_res(e, d + "0."));
         e->down_res.push_back(pack_res(e, d + "1."));
         e->down_attn.push_back(pack_attn(e, d + "2."));
-        e->down_conv.push_back(pack_conv(e, d + "3.weight", i != depth - 1 ? d + "3.bias" : ""));
+        if (stereo) e->down_scam.push_back(pack_scam(e, d + "3."));
+        e->down_conv.push_back(pack_conv(e, d + ci + ".weight", i != depth - 1 ? d + ci + ".bias" : ""));
     }
+    if (stereo) e->mid_scam = pack_scam(e, "mid_fusion.");
     e->mid1 = pack_res(e, "mid_block1.");
     if (e->cfg.flags & IRSDE_FLAG_UNCOND_FULLATTN) {
         AttnW a;
@@ -708,10 +751,11 @@ void finalize(irsde_engine* e) {
         e->up_res.push_back(pack_res(e, u + "0."));
         e->up_res.push_back(pack_res(e, u + "1."));
         e->up_attn.push_back(pack_attn(e, u + "2."));
+        if (stereo) e->up_scam.push_back(pack_scam(e, u + "3."));
         if (j != depth - 1)
-            e->up_conv.push_back(pack_conv(e, u + "3.1.weight", u + "3.1.bias"));
+            e->up_conv.push_back(pack_conv(e, u + ci + ".1.weight", u + ci + ".1.bias"));
         else
-            e->up_conv.push_back(pack_conv(e, u + "3.weight", ""));
+            e->up_conv.push_back(pack_conv(e, u + ci + ".weight", ""));
     }
     e->final_res = pack_res(e, "final_res_block.");
     e->final_conv = pack_conv(e, "final_conv.weight", "final_conv.bias");

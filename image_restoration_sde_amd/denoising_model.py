@@ -26,9 +26,9 @@ def define_G(opt, task="deraining"):
     name = opt_net["which_model_G"]
     if task == "stereo-sr":
         from . import stereo_sr
-        if name != "ConditionalNAFNet":
-            raise NotImplementedError("stereo-sr: only ConditionalNAFNet (with SCAM) is provided, not %s" % name)
-        return stereo_sr.ConditionalNAFNet(**opt_net["setting"])
+        if name not in ("ConditionalNAFNet", "ConditionalUNet"):   # what stereo-sr/models/modules/__init__.py exports with a live forward graph here
+            raise NotImplementedError("stereo-sr: ConditionalNAFNet and ConditionalUNet (both with SCAM) are provided, not %s" % name)
+        return getattr(stereo_sr, name)(**opt_net["setting"])
     if task == "denoising-sde":   # that task directory's own models.modules: forward(x, time), no condition input
         from . import denoising_sde
         if name not in ("ConditionalUNet", "ConditionalNAFNet"):

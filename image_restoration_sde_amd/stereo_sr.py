@@ -1,4 +1,5 @@
-"""stereo-sr score network: `ConditionalNAFNet` whose NAFBlocks end in a stereo cross-attention module (SCAM).
+"""stereo-sr score networks: `ConditionalNAFNet` whose NAFBlocks end in a stereo cross-attention module (SCAM), and `ConditionalUNet`
+(below) with a full-resolution SCAM on every level.  The NAFNet:
 
 Reference: codes/config/stereo-sr/models/modules/DenoisingNAFNet_arch.py
     :15-60   SCAM(c): bicubic quarter-downsample, LayerNorm + 1x1 projections per view, one W' x W' score matrix per image row,
@@ -20,7 +21,7 @@ import torch.nn as nn
 from . import _lib
 from .denoising_model import DenoisingModel
 from .nafnet import ConditionalNAFNet as _ImageNAFNet, _NAFBlock
-from .unet import _Gain
+from .unet import ConditionalUNet as _ImageUNet, _Gain, _ResBlock, _Residual, _upsample
 
 
 class _SCAM(nn.Module):  # DenoisingNAFNet_arch.py:15-31 (parameter container)
@@ -90,6 +91,65 @@ class ConditionalNAFNet(_ImageNAFNet):
         if inp.dim() != 4 or inp.shape[1] != self.in_nc or tuple(cond.shape) != tuple(inp.shape):
             raise _lib.IrsdeError("stereo ConditionalNAFNet.forward needs inp and cond of shape [B, %d, H, W]" % self.in_nc)
         return super().forward(inp, cond, time)
+
+
+class ConditionalUNet(_ImageUNet):
+    """The IR-SDE (UNet) score network of stereo-sr: codes/config/stereo-sr/models/modules/DenoisingUNet_arch.py
+        :18-56   SCAM(c) WITHOUT the quarter-downsample / upsample of the NAFNet's: one W x W score matrix per image row at full resolution
+        :59-196  ConditionalUNet(in_nc, out_nc, nf, depth=4, upscale=1, fusion=False): init_conv 3x3 on cat(xt_v, cond_v) (no xt - cond);
+                 every level is ResBlock, ResBlock, Residual(PreNorm(LinearAttention)), SCAM, down / up-sample; mid_fusion between
+                 mid_attn and mid_block2; output xt + cat(x_l, x_r).
+    Parameter container under the reference's state_dict names; the arithmetic runs on the HIP engine (IRSDE_FLAG_UNET_STEREO, fp32 only;
+    padded width <= 1024).  xt / cond are [B, 2 in_nc, H, W] pairs; an int `time` is shared by every pair, a [B] tensor gives each its own."""
+
+    def __init__(self, in_nc, out_nc, nf, depth=4, upscale=1, fusion=False):
+        nn.Module.__init__(self)
+        if in_nc != out_nc:
+            raise _lib.IrsdeError("stereo ConditionalUNet: in_nc must equal out_nc (the output is a residual on the state)")
+        self.view_nc, self.nf, self.depth = in_nc, nf, depth
+        self.in_nc = self.out_nc = 2 * in_nc   # a stereo pair: [left | right]
+        self.upscale, self.fusion = upscale, fusion   # stored and unused, as in the reference (:63-64)
+        time_dim = nf * 4
+        self.init_conv = nn.Conv2d(in_nc * 2, nf, 3, padding=1, bias=False)
+        self.time_mlp = nn.Sequential(nn.Identity(), nn.Linear(nf, time_dim), nn.GELU(), nn.Linear(time_dim, time_dim))
+        self.downs = nn.ModuleList([])
+        self.ups = nn.ModuleList([])
+        for i in range(depth):
+            di, do = nf * 2 ** i, nf * 2 ** (i + 1)
+            self.downs.append(nn.ModuleList([
+                _ResBlock(di, di, time_dim), _ResBlock(di, di, time_dim), _Residual(di), _SCAM(di),
+                nn.Conv2d(di, do, 4, 2, 1) if i != depth - 1 else nn.Conv2d(di, do, 3, padding=1, bias=False)]))
+            self.ups.insert(0, nn.ModuleList([
+                _ResBlock(do + di, do, time_dim), _ResBlock(do + di, do, time_dim), _Residual(do), _SCAM(do),
+                _upsample(do, di) if i != 0 else nn.Conv2d(do, di, 3, padding=1, bias=False)]))
+        mid = nf * 2 ** depth
+        self.mid_block1 = _ResBlock(mid, mid, time_dim)
+        self.mid_attn = _Residual(mid)
+        self.mid_fusion = _SCAM(mid)
+        self.mid_block2 = _ResBlock(mid, mid, time_dim)
+        self.final_res_block = _ResBlock(nf * 2, nf, time_dim)
+        self.final_conv = nn.Conv2d(nf, out_nc, 3, 1, 1)
+        self._engine = None
+        self._engine_key = None
+        self.engine_flags = 0
+
+    def _create_handle(self, L, device_index, flags):
+        cfg = _lib.Config(self.view_nc, self.view_nc, self.nf, self.depth, device_index, flags | _lib.FLAG_UNET_STEREO)
+        h = ctypes.c_void_p()
+        _lib.check(L.irsde_create(ctypes.byref(cfg), ctypes.byref(h)))
+        return h
+
+    def set_compute_dtype(self, dtype):
+        """fp32 only: the other operand modes are not covered for the full-resolution SCAM network (the engine refuses them too)."""
+        if dtype not in ("fp32", "f32", torch.float32):
+            raise _lib.IrsdeError("stereo ConditionalUNet runs in fp32 only, not %r" % (dtype,))
+        return _ImageUNet.set_compute_dtype(self, dtype)
+
+    def forward(self, xt, cond, time):
+        """out = model(xt, cond, time) on stereo pairs [B, 2 in_nc, H, W] — DenoisingUNet_arch.py:136-196."""
+        if xt.dim() != 4 or xt.shape[1] != self.in_nc or tuple(cond.shape) != tuple(xt.shape):
+            raise _lib.IrsdeError("stereo ConditionalUNet.forward needs xt and cond of shape [B, %d, H, W]" % self.in_nc)
+        return super().forward(xt, cond, time)
 
 
 class StereoDenoisingModel(DenoisingModel):

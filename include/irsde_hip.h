@@ -36,6 +36,8 @@
  *        Additive, same version: IRSDE_FLAG_NAF_UNCOND (the denoising-sde ConditionalNAFNet: forward(x, time), DenoisingSDE modes 3 / 4).
  *        Additive, same version: irsde_nafnet_set_local_pool (CNAFNetLocal: the latent ConditionalNAFNet with windowed SCA pooling, TLSC).
  *        Debug header only, same version: irsde_debug_naf_gate_sca, irsde_debug_tlsc, irsde_debug_ln_film, irsde_debug_naf_lnconv (NAFBlock glue kernels).
+ *        Additive, same version: IRSDE_FLAG_UNET_STEREO (the stereo-sr ConditionalUNet with a full-resolution SCAM on every level); debug header:
+ *        irsde_debug_scam_full.
  */
 #ifndef IRSDE_HIP_H
 #define IRSDE_HIP_H
@@ -142,6 +144,20 @@ enum {
                                         0 - 2.  Everything behind the intro (NAFBlocks, time MLP, zero pad, every operand mode, the fp16 NAFBlock
                                         chain, concurrent sub-batches) is the conditional network's, on the same kernels.  Refused together with
                                         IRSDE_FLAG_NAF_STEREO / _NAF_LENS / _NAF_INTRO_SKIP */
+    IRSDE_FLAG_UNET_STEREO = 262144, /* irsde_create only: the ConditionalUNet of stereo-sr (codes/config/stereo-sr/models/modules/
+                                        DenoisingUNet_arch.py:59-196), the IR-SDE counterpart of IRSDE_FLAG_NAF_STEREO.  irsde_config.in_nc / out_nc
+                                        are the channels of ONE view (1..4); xt / cond / out / sampler state / noise are [B][2 in_nc][H][W] stereo
+                                        pairs (channels [0, in_nc) the left view) and the network runs on the 2B views [L_0..L_{B-1}, R_0..R_{B-1}].
+                                        It differs from the deraining UNet in: init_conv 3x3 on cat(xt_v, cond_v) (no xt - cond); a SCAM(c) behind the
+                                        LinearAttention of every down level (c = nf 2^i, the second skip is taken behind it), every up level
+                                        (c = nf 2^(i+1)) and the bottleneck (mid_fusion); the output is xt + cat(x_l, x_r), which is what the
+                                        sampler's reverse step reads as the noise prediction.  That SCAM has no quarter-downsample and no
+                                        upsample: one W x W score matrix per image row at the level's full resolution (csrc/scam.hip, the *_full
+                                        kernels; never in HBM, both softmaxes exact, fp32 statistics, no atomics).  Limits: c a multiple of 32 up to
+                                        2048; padded width of level 0 <= 1024 (wider inputs: IRSDE_ERR_INVALID).  fp32 only: IRSDE_FLAG_BF16 /
+                                        _BF16_ACT / _FP16 / _SPLIT_BF16X2 / _SPLIT_F16X2 and IRSDE_FLAG_UNCOND_FULLATTN are refused with
+                                        IRSDE_ERR_INVALID.  A pair is never split: no concurrent sub-batches (irsde_debug_force_subbatches is
+                                        ignored).  An int time is shared by every pair; B times give each pair its own */
     IRSDE_FLAG_NO_WINOGRAD_F43 = 8   /* Winograd F(2x2,3x3) only (>= 256 channels); default also uses F(4x4,3x3) from 128
                                         channels up where H, W are multiples of 4 */
 };

@@ -140,6 +140,14 @@ int irsde_debug_naf_chain(const float* x, float* out, int B, int nblocks, const 
  * streams — into order_out[n], n = 8 * nblocks * 448 (any other n is refused). */
 int irsde_debug_naf_chain_split_order(int nblocks, int groups, int* order_out, long long n);
 
+/* Kernel-level test hook: ONE full-resolution SCAM of the stereo-sr ConditionalUNet (csrc/scam.hip *_full kernels + the projection GEMM on the
+ * implicit-GEMM kernel, fp32) — the counterpart of irsde_debug_scam, same argument order.  x / out: device NHWC [2 B_pairs][H][W][C], views stacked
+ * [L_0..L_{B-1}, R_0..R_{B-1}]; every weight is a HOST pointer in reference layout.  C a multiple of 32 in [32, 2048], H, W >= 1, W <= 1024
+ * (wider: IRSDE_ERR_INVALID).  Synchronises `stream`. */
+int irsde_debug_scam_full(const float* x, int B_pairs, int H, int W, int C, const float* norm_l_g, const float* norm_r_g, const float* l_proj1_w,
+                          const float* l_proj1_b, const float* r_proj1_w, const float* r_proj1_b, const float* l_proj2_w, const float* l_proj2_b,
+                          const float* r_proj2_w, const float* r_proj2_b, const float* beta, const float* gamma, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
