@@ -316,6 +316,9 @@ void launch_stereo_unet_pack_pred(const float* in, const float* xt, float* out, 
 
 // Full softmax attention over N tokens (denoising-sde bottleneck): qkv [B][N][384] -> out [B][N][128].
 void launch_full_attention(const float* qkv, float* out, int B, int N, hipStream_t s);
+// The same on bf16 tensors (IRSDE_FLAG_BF16_ACT; full_attn16.hip): qkv bf16 [B][N][384] -> out bf16 [B][N][128], both 16-byte aligned.  Flash form on the bf16
+// MFMA: q, k, v as stored, fp32 scores / max / exponent / rescale, P rounded to bf16 for P.V, O / l rounded once on the store.
+void launch_full_attention16(const unsigned short* qkv, unsigned short* out, int B, int N, hipStream_t s);
 
 // xt, cond: NCHW [B][3][H][W] (cond may be null: unconditional variant, channels = xt only).  x0: [B][Hp+6][Wp+6][8] (+8 floats slack), zero border of 3,
 // channels {xt-cond (3), cond (3), 0, 0}, reflect-padded right/bottom from (H,W) to (Hp,Wp).

@@ -141,7 +141,7 @@ int irsde_create(const irsde_config* cfg, irsde_engine** out) {
             e->cfg.in_nc = e->cfg.out_nc = 2 * cfg->in_nc;
         }
         if (cfg->flags & IRSDE_FLAG_BF16_ACT) {
-            if (cfg->flags & (IRSDE_FLAG_UNCOND_FULLATTN | IRSDE_FLAG_NAIVE_CONV)) {
+            if (cfg->flags & IRSDE_FLAG_NAIVE_CONV) {
                 delete e;
                 throw HipError("IRSDE_FLAG_BF16_ACT: only the conditional UNet on the MFMA kernels stores bf16 activations");
             }

@@ -229,6 +229,15 @@ int irsde_debug_ln_film(const float* x, long long M, int C, long long ppi, const
     });
 }
 
+int irsde_debug_full_attention16(const void* qkv_bf16, int B, int N, void* out_bf16, void* stream) {
+    return guard([&] {
+        if (!qkv_bf16 || !out_bf16) throw HipError("null argument");
+        hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+        launch_full_attention16(static_cast<const unsigned short*>(qkv_bf16), static_cast<unsigned short*>(out_bf16), B, N, s);
+        IRSDE_HIP_CHECK(hipStreamSynchronize(s));
+    });
+}
+
 int irsde_debug_naf_lnconv(int mode, const float* x, long long M, int c, int Cout, long long ppi, const float* g, const float* fscale, const float* fshift,
                            int film_bstride, const float* w, const float* bias, const float* gate_film, int gate_film_bstride, const float* in_scale,
                            const float* ch_scale, const float* res, float* out, void* stream) {

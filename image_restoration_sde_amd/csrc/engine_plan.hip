@@ -795,7 +795,16 @@ struct Builder {
             const float* q = qkv.p;
             float* o = a.p;
             const int B = x.B;
-            push_other(OP_ATTN, [=](hipStream_t s) { launch_full_attention(q, o, B, N, s); });
+            if (x.bf16) {
+                // IRSDE_FLAG_BF16_ACT: LayerNorm, q | k | v and the attention output are bf16 tensors; the core runs on the bf16 MFMA (full_attn16.hip)
+                if (!qkv.bf16 || !a.bf16) throw HipError("attention: mixed activation storage types");
+                push_other(OP_ATTN, [=](hipStream_t s) {
+                    launch_full_attention16(reinterpret_cast<const unsigned short*>(q), reinterpret_cast<unsigned short*>(o), B, N, s);
+                });
+                pl->net_ops.back().desc = "full_attention (bf16 operands + storage)";
+            } else {
+                push_other(OP_ATTN, [=](hipStream_t s) { launch_full_attention(q, o, B, N, s); });
+            }
             tfree(qkv);
             Tensor y = conv(w.out, a, nullptr, 1, 0, 0, nullptr, 0, &x);
             tfree(a);

@@ -5,7 +5,10 @@
                      name as the reference's (that task directory resolves `which_model_G: ConditionalUNet` inside its
                      own `models.modules`): `forward(x, time)`, no condition input, full softmax `Attention` at the
                      bottleneck (module_util.py:182-204) — the one place the N x N QK^T / AV contractions exist; they run
-                     as a flash-style fp32-MFMA kernel (csrc/kernels_misc.hip: full_attn_kernel).
+                     as a flash-style fp32-MFMA kernel (csrc/kernels_misc.hip: full_attn_kernel) in the fp32 mode and in the
+                     operand-only 16-bit modes ('bf16', 'fp16': fp32 storage), and as a flash-style bf16-MFMA kernel on bf16
+                     tensors (csrc/full_attn16.hip) in the 'bf16_act' mode.  `set_compute_dtype` takes every mode of the
+                     deraining ConditionalUNet.
 
   `ConditionalNAFNet` codes/config/denoising-sde/models/modules/DenoisingNAFNet_arch.py:85-183 — the Refusion
                      network of that task (options/test/refusion.yml): the deraining NAFNet with an `img_channel`-input
@@ -54,7 +57,9 @@ class _ResidualFull(nn.Module):
 
 
 class ConditionalUNet(_CondUNet):
-    """denoising-sde ConditionalUNet(in_nc, out_nc, nf, depth=4); forward(x, time)."""
+    """denoising-sde ConditionalUNet(in_nc, out_nc, nf, depth=4); forward(x, time).  Compute modes as for the deraining network (`set_compute_dtype`:
+    'fp32', 'fp32_split', 'fp32_split_f16', 'bf16', 'bf16_act', 'fp16'); in 'bf16_act' the LayerNorm output, q | k | v and the attention output of the
+    bottleneck are bf16 tensors and the softmax attention runs on the bf16 MFMA with fp32 scores, softmax statistics and accumulation."""
 
     def __init__(self, in_nc, out_nc, nf, depth=4):
         nn.Module.__init__(self)

@@ -160,7 +160,7 @@ class ConditionalUNet(nn.Module):
             self.engine_flags |= _lib.FLAG_SPLIT_F16X2
         elif dtype in ("bf16", torch.bfloat16):
             self.engine_flags |= _lib.FLAG_BF16
-        elif dtype == "bf16_act":  # + bf16 storage of the activation tensors (conditional UNet only)
+        elif dtype == "bf16_act":  # + bf16 storage of the activation tensors (this UNet and the denoising-sde one; not the NAFNets)
             self.engine_flags |= _lib.FLAG_BF16 | _lib.FLAG_BF16_ACT
         elif dtype in ("fp16", "f16", torch.float16):
             self.engine_flags |= _lib.FLAG_FP16

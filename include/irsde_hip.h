@@ -38,6 +38,8 @@
  *        Debug header only, same version: irsde_debug_naf_gate_sca, irsde_debug_tlsc, irsde_debug_ln_film, irsde_debug_naf_lnconv (NAFBlock glue kernels).
  *        Additive, same version: IRSDE_FLAG_UNET_STEREO (the stereo-sr ConditionalUNet with a full-resolution SCAM on every level); debug header:
  *        irsde_debug_scam_full.
+ *        Additive, same version: IRSDE_FLAG_BF16_ACT is accepted together with IRSDE_FLAG_UNCOND_FULLATTN (the denoising-sde ConditionalUNet with bf16
+ *        activation storage; its full softmax attention runs on the bf16 MFMA, csrc/full_attn16.hip); debug header: irsde_debug_full_attention16.
  */
 #ifndef IRSDE_HIP_H
 #define IRSDE_HIP_H
@@ -69,7 +71,9 @@ enum {
     IRSDE_FLAG_NO_WINOGRAD = 4,      /* run every 3x3 layer as a direct implicit GEMM (no Winograd) */
     IRSDE_FLAG_UNCOND_FULLATTN = 16, /* the denoising-sde variant of ConditionalUNet (codes/config/denoising-sde/models/modules/
                                         DenoisingUNet_arch.py:20-130): forward(x, time) without a condition input (init_conv takes
-                                        in_nc channels) and full softmax Attention at the bottleneck (module_util.py:182-204) */
+                                        in_nc channels) and full softmax Attention at the bottleneck (module_util.py:182-204).  Every operand mode of
+                                        the conditional UNet applies; IRSDE_FLAG_BF16 / _FP16 keep the attention core on the fp32 MFMA, with
+                                        IRSDE_FLAG_BF16_ACT it reads and writes bf16 tensors on the bf16 MFMA (fp32 softmax and accumulation) */
     IRSDE_FLAG_BF16 = 32,            /* reduced-precision mode (BASELINE configs[2]; the reference is fp32 only): every convolution
                                         runs on v_mfma_f32_32x32x16_bf16 with operands rounded to bf16 (RNE) and fp32
                                         accumulation; no Winograd; everything else (state, LayerNorm, attention, FiLM,
@@ -79,7 +83,8 @@ enum {
                                         q | k | v and the attention output are no longer rounded to a stored tensor.
                                         IRSDE_FLAG_NO_FUSED_ATTN restores the to_qkv convolution + q | k | v tensor */
     IRSDE_FLAG_BF16_ACT = 128,       /* IRSDE_FLAG_BF16 plus bf16 storage of every activation tensor between the prepped input
-                                        and eps_hat (conditional ConditionalUNet only): halves the HBM/L2 traffic of the
+                                        and eps_hat (the ConditionalUNet, conditional or IRSDE_FLAG_UNCOND_FULLATTN, on the MFMA kernels:
+                                        refused with IRSDE_FLAG_NAIVE_CONV and for the NAFNets): halves the HBM/L2 traffic of the
                                         bandwidth-bound layers; LayerNorm / attention / epilogue arithmetic stays fp32 */
     IRSDE_FLAG_NO_FUSED_LN = 256,    /* keep LinearAttention.to_out's LayerNorm + residual as a separate kernel (default: fused into the
                                         1x1 conv's epilogue when the channel row fits one tile, C = 64 or 128) */

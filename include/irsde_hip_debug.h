@@ -140,6 +140,12 @@ int irsde_debug_naf_chain(const float* x, float* out, int B, int nblocks, const 
  * streams — into order_out[n], n = 8 * nblocks * 448 (any other n is refused). */
 int irsde_debug_naf_chain_split_order(int nblocks, int groups, int* order_out, long long n);
 
+/* Kernel-level test hook: the full softmax attention core of the denoising-sde bottleneck on bf16 tensors (csrc/full_attn16.hip, IRSDE_FLAG_BF16_ACT) —
+ * ONE launch of the production launcher on the caller's device tensors: qkv_bf16 [B][N][384] (rows q | k | v, 4 heads x 32) -> out_bf16 [B][N][128], both
+ * bf16 and 16-byte aligned.  B, N >= 1, 4 B <= 65535.  Rows behind row N of `out` are not written.  Synchronises `stream`.
+ * tests/test_gpu_dsde_unet16.py compares it with tests/dsde_unet16_oracle.py. */
+int irsde_debug_full_attention16(const void* qkv_bf16, int B, int N, void* out_bf16, void* stream);
+
 /* Kernel-level test hook: ONE full-resolution SCAM of the stereo-sr ConditionalUNet (csrc/scam.hip *_full kernels + the projection GEMM on the
  * implicit-GEMM kernel, fp32) — the counterpart of irsde_debug_scam, same argument order.  x / out: device NHWC [2 B_pairs][H][W][C], views stacked
  * [L_0..L_{B-1}, R_0..R_{B-1}]; every weight is a HOST pointer in reference layout.  C a multiple of 32 in [32, 2048], H, W >= 1, W <= 1024
