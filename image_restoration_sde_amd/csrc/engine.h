@@ -40,9 +40,9 @@ inline int wino_fused64_max_cout() { return tuning_env_int("IRSDE_WINO_FUSED64_M
 inline long long wino_fused64_min_tiles() { return tuning_env_int("IRSDE_WINO_FUSED64_MINT", 1024); }
 // r06: the two-tile-group kernel (wino_fused_t.hip) on the layers it measured faster on: 0 never, 1 by the rule of Plan::push_wino_fused, 2 wherever eligible
 inline int wino_fused64t_mode() { return tuning_env_int("IRSDE_WINO_FUSED64T", 1); }
-// r06: work-groups per image of the NAFBlock chain kernel: 0 = as many (4, 2) as fit the compute units next to the call's other sub-batches, 1 = the one-group kernel, 2 / 4 forced (if they fit)
 // r06: NAFBlock norm + 1x1 convolution as one launch on the small-channel levels of the fp16 operand mode (1; 0 = LayerNorm kernel + convolution kernel)
 inline bool naf_lnconv_enabled() { return tuning_env_int("IRSDE_NAF_LNCONV", 1) != 0; }
+// r06: work-groups per image of the NAFBlock chain kernel: 0 = as many (4, 2) as fit the compute units next to the call's other sub-batches, 1 = the one-group kernel, 2 / 4 forced (if they fit)
 inline int naf_chain_split_mode() { return tuning_env_int("IRSDE_NAF_CHAIN_SPLIT", 0); }
 
 inline int wino_min_c(int tile) {
@@ -92,7 +92,8 @@ struct ResW {
     int film_off = 0;
     int Cout = 0;
 };
-// SCAM(c) of the stereo-sr ConditionalUNet (IRSDE_FLAG_UNET_STEREO; stereo-sr DenoisingUNet_arch.py:18-35)
+// SCAM(c): the fusion after every NAFBlock of the stereo-sr NAFNet (IRSDE_FLAG_NAF_STEREO; stereo-sr DenoisingNAFNet_arch.py:15-60, 131, on the quarter-resolution
+// xs) and of the stereo-sr ConditionalUNet (IRSDE_FLAG_UNET_STEREO; stereo-sr DenoisingUNet_arch.py:18-35, at full resolution)
 struct ScamW {
     int c = 0;
     float *gl = nullptr, *gr = nullptr;   // norm_l.g / norm_r.g
@@ -118,10 +119,7 @@ struct NafBlockW {
     int film_off = 0;                            // [shift_att | scale_att | shift_ffn | scale_ffn]
     float *cam_w = nullptr, *cam_b = nullptr;    // latent-bokeh: cam_mlp.1: Linear(time_dim/2, 2c)
     int cam_off = 0;                             // [cam_scale | cam_shift] inside a row of the lens table
-    // stereo-sr (IRSDE_FLAG_NAF_STEREO): fusion = SCAM(c) after the block (stereo-sr DenoisingNAFNet_arch.py:15-60, 131)
-    float *scam_gl = nullptr, *scam_gr = nullptr;  // fusion.norm_l.g / norm_r.g
-    ConvW scam_l, scam_r;                          // [[proj1, 0], [0, proj2]] per view: [LN(xs) | xs] (2c) -> [Q | V] (2c), bias [b1 | b2]
-    float *scam_beta = nullptr, *scam_gamma = nullptr;
+    ScamW fusion;                                // stereo-sr (IRSDE_FLAG_NAF_STEREO): SCAM(c) after the block
 };
 
 // a run of consecutive 512-channel NAFBlocks packed for naf_chain_kernel (fp16 mode): fragment streams + fp32 vectors

@@ -88,6 +88,59 @@ bool bench_conv_variant_known(int v) {
            (v >= 472 && v <= 476);         // the pair GEMM's ablation twins (launch_gemm_split_pairs refuses the ones it lacks)
 }
 
+// What irsde_debug_scam and irsde_debug_scam_full share; the projections run on the B x Hs x Ws map of each view.  In order: the argument check, the hook's own
+// check_shape(), the two views' packed projection weights, the uploads and the [in2 | qv | F] scratch, the hook's prologue(dev, s), the two [LN(x) | x] -> [Q | V]
+// GEMMs, the hook's tail(dev, s) = its core + epilogue
+struct ScamHookArgs {   // the hooks' pointers, in their parameter order
+    const float* x;
+    float* out;
+    const float *norm_l_g, *norm_r_g, *l_proj1_w, *l_proj1_b, *r_proj1_w, *r_proj1_b, *l_proj2_w, *l_proj2_b, *r_proj2_w, *r_proj2_b, *beta, *gamma;
+};
+struct ScamHookDev {
+    float *gl, *gr, *beta, *gamma;   // device copies of norm_l.g / norm_r.g / beta / gamma
+    float *in2, *qv, *F;
+    size_t vsz;                      // one view's [LN(x) | x] / [Q | V]: B Hs Ws 2C floats
+};
+template <class ShapeCheck, class Prologue, class Tail>
+void scam_hook(const ScamHookArgs& a, int B, int Hs, int Ws, int C, void* stream, ShapeCheck check_shape, Prologue prologue, Tail tail) {
+    if (!a.x || !a.out || !a.norm_l_g || !a.norm_r_g || !a.l_proj1_w || !a.l_proj1_b || !a.r_proj1_w || !a.r_proj1_b || !a.l_proj2_w || !a.l_proj2_b ||
+        !a.r_proj2_w || !a.r_proj2_b || !a.beta || !a.gamma)
+        throw HipError("null argument");
+    check_shape();
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    conv_global_init();
+    std::vector<float> wl, bl, wr, br;
+    scam_pack_proj(a.l_proj1_w, a.l_proj1_b, a.l_proj2_w, a.l_proj2_b, C, wl, bl);
+    scam_pack_proj(a.r_proj1_w, a.r_proj1_b, a.r_proj2_w, a.r_proj2_b, C, wr, br);
+    Scratch mem(s);
+    auto up = [&](const float* h, size_t n) {
+        float* d = mem.alloc<float>(std::max<size_t>(n, 16));
+        if (h) IRSDE_HIP_CHECK(hipMemcpy(d, h, n * 4, hipMemcpyHostToDevice));
+        return d;
+    };
+    ScamHookDev d;
+    d.gl = up(a.norm_l_g, C); d.gr = up(a.norm_r_g, C); d.beta = up(a.beta, C); d.gamma = up(a.gamma, C);
+    float *dwl = up(wl.data(), wl.size()), *dbl = up(bl.data(), bl.size()), *dwr = up(wr.data(), wr.size()), *dbr = up(br.data(), br.size());
+    d.vsz = (size_t)B * Hs * Ws * 2 * C;
+    d.in2 = up(nullptr, 2 * d.vsz); d.qv = up(nullptr, 2 * d.vsz); d.F = up(nullptr, d.vsz);
+    float* dz = up(nullptr, 256);
+    IRSDE_HIP_CHECK(hipMemset(dz, 0, 1024));
+    prologue(d, s);
+    for (int v = 0; v < 2; ++v) {
+        ConvParams p;
+        p.in0 = d.in2 + v * d.vsz; p.C0 = 2 * C; p.pix0 = 2 * C;
+        p.Hin = Hs; p.Win = Ws;
+        p.w = v ? dwr : dwl; p.Cout = 2 * C; p.KH = p.KW = 1; p.stride = 1;
+        p.B = B; p.Ho = Hs; p.Wo = Ws;
+        p.out = d.qv + v * d.vsz; p.out_stride = 2 * C;
+        p.bias = v ? dbr : dbl;
+        p.zeros = dz;
+        launch_conv(p, s);
+    }
+    tail(d, s);
+    IRSDE_HIP_CHECK(hipStreamSynchronize(s));
+}
+
 }  // namespace
 }  // namespace irsde
 
@@ -97,43 +150,17 @@ int irsde_debug_scam(const float* x, int B, int H, int W, int C, const float* no
                      const float* l_proj1_b, const float* r_proj1_w, const float* r_proj1_b, const float* l_proj2_w, const float* l_proj2_b,
                      const float* r_proj2_w, const float* r_proj2_b, const float* beta, const float* gamma, float* out, void* stream) {
     return guard([&] {
-        if (!x || !out || !norm_l_g || !norm_r_g || !l_proj1_w || !l_proj1_b || !r_proj1_w || !r_proj1_b || !l_proj2_w || !l_proj2_b || !r_proj2_w ||
-            !r_proj2_b || !beta || !gamma)
-            throw HipError("null argument");
-        if (B < 1) throw HipError("debug_scam: bad shape");
-        scam_check_shape(H, W, C);
-        hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-        conv_global_init();
-        const int Hs = H / 4, Ws = W / 4;
-        std::vector<float> wl, bl, wr, br;
-        scam_pack_proj(l_proj1_w, l_proj1_b, l_proj2_w, l_proj2_b, C, wl, bl);
-        scam_pack_proj(r_proj1_w, r_proj1_b, r_proj2_w, r_proj2_b, C, wr, br);
-        Scratch mem(s);
-        auto up = [&](const float* h, size_t n) {
-            float* d = mem.alloc<float>(std::max<size_t>(n, 16));
-            if (h) IRSDE_HIP_CHECK(hipMemcpy(d, h, n * 4, hipMemcpyHostToDevice));
-            return d;
-        };
-        float *dgl = up(norm_l_g, C), *dgr = up(norm_r_g, C), *dbe = up(beta, C), *dga = up(gamma, C);
-        float *dwl = up(wl.data(), wl.size()), *dbl = up(bl.data(), bl.size()), *dwr = up(wr.data(), wr.size()), *dbr = up(br.data(), br.size());
-        const size_t vsz = (size_t)B * Hs * Ws * 2 * C;
-        float *xs2 = up(nullptr, 2 * vsz), *qv = up(nullptr, 2 * vsz), *F = up(nullptr, vsz), *dz = up(nullptr, 256);
-        IRSDE_HIP_CHECK(hipMemset(dz, 0, 1024));
-        launch_scam_prologue(x, dgl, dgr, xs2, B, H, W, C, s);
-        for (int v = 0; v < 2; ++v) {
-            ConvParams p;
-            p.in0 = xs2 + v * vsz; p.C0 = 2 * C; p.pix0 = 2 * C;
-            p.Hin = Hs; p.Win = Ws;
-            p.w = v ? dwr : dwl; p.Cout = 2 * C; p.KH = p.KW = 1; p.stride = 1;
-            p.B = B; p.Ho = Hs; p.Wo = Ws;
-            p.out = qv + v * vsz; p.out_stride = 2 * C;
-            p.bias = v ? dbr : dbl;
-            p.zeros = dz;
-            launch_conv(p, s);
-        }
-        launch_scam_core(qv, F, B, H, W, C, s);
-        launch_scam_epilogue(x, F, dbe, dga, out, B, H, W, C, s);
-        IRSDE_HIP_CHECK(hipStreamSynchronize(s));
+        scam_hook(
+            {x, out, norm_l_g, norm_r_g, l_proj1_w, l_proj1_b, r_proj1_w, r_proj1_b, l_proj2_w, l_proj2_b, r_proj2_w, r_proj2_b, beta, gamma}, B, H / 4, W / 4, C, stream,
+            [&] {
+                if (B < 1) throw HipError("debug_scam: bad shape");
+                scam_check_shape(H, W, C);
+            },
+            [&](const ScamHookDev& d, hipStream_t s) { launch_scam_prologue(x, d.gl, d.gr, d.in2, B, H, W, C, s); },
+            [&](const ScamHookDev& d, hipStream_t s) {
+                launch_scam_core(d.qv, d.F, B, H, W, C, s);
+                launch_scam_epilogue(x, d.F, d.beta, d.gamma, out, B, H, W, C, s);
+            });
     });
 }
 
@@ -141,43 +168,18 @@ int irsde_debug_scam_full(const float* x, int B, int H, int W, int C, const floa
                           const float* l_proj1_b, const float* r_proj1_w, const float* r_proj1_b, const float* l_proj2_w, const float* l_proj2_b,
                           const float* r_proj2_w, const float* r_proj2_b, const float* beta, const float* gamma, float* out, void* stream) {
     return guard([&] {
-        if (!x || !out || !norm_l_g || !norm_r_g || !l_proj1_w || !l_proj1_b || !r_proj1_w || !r_proj1_b || !l_proj2_w || !l_proj2_b || !r_proj2_w ||
-            !r_proj2_b || !beta || !gamma)
-            throw HipError("null argument");
-        if (B < 1 || (long long)B * H > 65535) throw HipError("debug_scam_full: bad shape");
-        scam_full_check_shape(H, W, C);
-        hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-        conv_global_init();
-        std::vector<float> wl, bl, wr, br;
-        scam_pack_proj(l_proj1_w, l_proj1_b, l_proj2_w, l_proj2_b, C, wl, bl);
-        scam_pack_proj(r_proj1_w, r_proj1_b, r_proj2_w, r_proj2_b, C, wr, br);
-        Scratch mem(s);
-        auto up = [&](const float* h, size_t n) {
-            float* d = mem.alloc<float>(std::max<size_t>(n, 16));
-            if (h) IRSDE_HIP_CHECK(hipMemcpy(d, h, n * 4, hipMemcpyHostToDevice));
-            return d;
-        };
-        float *dgl = up(norm_l_g, C), *dgr = up(norm_r_g, C), *dbe = up(beta, C), *dga = up(gamma, C);
-        float *dwl = up(wl.data(), wl.size()), *dbl = up(bl.data(), bl.size()), *dwr = up(wr.data(), wr.size()), *dbr = up(br.data(), br.size());
-        const size_t vsz = (size_t)B * H * W * 2 * C;
-        float *x2 = up(nullptr, 2 * vsz), *qv = up(nullptr, 2 * vsz), *F = up(nullptr, vsz), *dz = up(nullptr, 256);
-        IRSDE_HIP_CHECK(hipMemset(dz, 0, 1024));
-        launch_scam_full_prologue(x, dgl, dgr, x2, B, H, W, C, s);
-        for (int v = 0; v < 2; ++v) {
-            ConvParams p;
-            p.in0 = x2 + v * vsz; p.C0 = 2 * C; p.pix0 = 2 * C;
-            p.Hin = H; p.Win = W;
-            p.w = v ? dwr : dwl; p.Cout = 2 * C; p.KH = p.KW = 1; p.stride = 1;
-            p.B = B; p.Ho = H; p.Wo = W;
-            p.out = qv + v * vsz; p.out_stride = 2 * C;
-            p.bias = v ? dbr : dbl;
-            p.zeros = dz;
-            launch_conv(p, s);
-        }
-        launch_scam_full_core(qv, F, B, H, W, C, s);
-        if (out != x) IRSDE_HIP_CHECK(hipMemcpyAsync(out, x, vsz * sizeof(float), hipMemcpyDeviceToDevice, s));   // (vsz = 2 B H W C: the whole tensor)
-        launch_scam_full_epilogue(out, F, dbe, dga, B, H, W, C, s);
-        IRSDE_HIP_CHECK(hipStreamSynchronize(s));
+        scam_hook(
+            {x, out, norm_l_g, norm_r_g, l_proj1_w, l_proj1_b, r_proj1_w, r_proj1_b, l_proj2_w, l_proj2_b, r_proj2_w, r_proj2_b, beta, gamma}, B, H, W, C, stream,
+            [&] {
+                if (B < 1 || (long long)B * H > 65535) throw HipError("debug_scam_full: bad shape");
+                scam_full_check_shape(H, W, C);
+            },
+            [&](const ScamHookDev& d, hipStream_t s) { launch_scam_full_prologue(x, d.gl, d.gr, d.in2, B, H, W, C, s); },
+            [&](const ScamHookDev& d, hipStream_t s) {
+                launch_scam_full_core(d.qv, d.F, B, H, W, C, s);
+                if (out != x) IRSDE_HIP_CHECK(hipMemcpyAsync(out, x, d.vsz * sizeof(float), hipMemcpyDeviceToDevice, s));   // (vsz = 2 B H W C: the whole tensor)
+                launch_scam_full_epilogue(out, d.F, d.beta, d.gamma, B, H, W, C, s);
+            });
     });
 }
 

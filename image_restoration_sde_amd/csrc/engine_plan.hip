@@ -34,6 +34,14 @@ struct Builder {
     }
     void tap(const std::string& name, const Tensor& t) { pl->taps[name] = t; }
 
+    // Every launch group that carries work goes into the plan through here: irsde_work_model (bench.py's roofline) reads the totals
+    void push_op(Op op) {
+        pl->conv_flops += op.flops;
+        pl->conv_exec_flops += op.exec_flops;
+        pl->conv_bytes += op.bytes;
+        pl->net_ops.push_back(std::move(op));
+    }
+
     void push_conv(ConvParams p) {
         const int M = p.B * p.Ho * p.Wo;
         // split-K for under-filled grids (small batch / deep levels)
@@ -58,9 +66,7 @@ struct Builder {
             // (!ln_g: the fused LayerNorm epilogue normalises over the tile's BN columns and needs BN == Cout, which the PAIR tile
             //  choice does not guarantee — to_out layers of the IRSDE_FLAG_NO_FUSED_ATTN plan stay on the f32 kernel)
             // split-operand arithmetic for the direct layers too (PAIR kernels): fp32 storage, 16-bit hi + lo operand pairs
-            const size_t nw = (size_t)p.Cout * p.KH * p.KW * (p.C0 + p.C1);
             const auto pc = e->pair_copy_il(p.w, (size_t)p.Cout, p.KH * p.KW * (p.C0 + p.C1));
-            (void)nw;
             p.w_pair = pc.p; p.pair_scale = pc.inv_scale;
             p.f16 = (e->cfg.flags & IRSDE_FLAG_SPLIT_F16X2) ? 1 : 0;
         }
@@ -71,9 +77,6 @@ struct Builder {
         op.bytes = in_bytes + (p.out_bf16 ? 2.0 : 4.0) * (double)M * p.Cout +
                    (p.w_bf ? 2.0 : 4.0) * (double)p.Cout * p.KH * p.KW * (p.C0 + p.C1);
         op.exec_flops = op.flops;
-        pl->conv_flops += op.flops;
-        pl->conv_exec_flops += op.exec_flops;
-        pl->conv_bytes += op.bytes;
         {
             char buf[256];
             snprintf(buf, sizeof buf, "conv%s M=%d Cout=%d Cin=%d k=%dx%d s=%d up=%d splits=%d blocks=%d flops=%.4g",
@@ -89,7 +92,7 @@ struct Builder {
             else
                 launch_conv(p, s);
         };
-        pl->net_ops.push_back(std::move(op));
+        push_op(std::move(op));
         // the split-K scratch is dead once this op's reduce kernel has run (same stream): recycle it
         if (p.partial) pl->release(p.partial);
     }
@@ -170,9 +173,6 @@ struct Builder {
         op.flops = conv_flops(d);
         op.exec_flops = 36 * 2.0 * (double)T * parts * Ctot * d.Cout;
         op.bytes = 4.0 * (double)d.B * d.Hin * d.Win * Ctot + 4.0 * (double)d.B * d.Ho * d.Wo * d.Cout + 4.0 * 9.0 * (double)d.Cout * Ctot;
-        pl->conv_flops += op.flops;
-        pl->conv_exec_flops += op.exec_flops;
-        pl->conv_bytes += op.bytes;
         char buf[256];
         const bool pair = pair_uscale != 0.f;
         snprintf(buf, sizeof buf, "conv(%swinograd F4 fused) %s T=%lld Cout=%d Cin=%d up=%d blocks=%lld flops=%.4g exec=%.4g%s", pair ? "split f16x2 " : "",
@@ -196,7 +196,7 @@ struct Builder {
             op.fn = [slices, Uf, pair](hipStream_t s) { for (const auto& q : slices) launch_wino_fused64(q, Uf, s, pair ? 4 : 0); };
         else
             op.fn = [slices, Uf](hipStream_t s) { for (const auto& q : slices) launch_wino_fused(q, Uf, s); };
-        pl->net_ops.push_back(std::move(op));
+        push_op(std::move(op));
         return true;
     }
 
@@ -237,9 +237,6 @@ struct Builder {
             op.exec_flops = ncomp * 2.0 * (double)T * Ctot * d.Cout;
             const double in_bytes = 4.0 * (double)d.B * d.Hin * d.Win * Ctot;
             op.bytes = in_bytes + 4.0 * (double)d.B * d.Ho * d.Wo * d.Cout + 4.0 * 9.0 * (double)d.Cout * Ctot;
-            pl->conv_flops += op.flops;
-            pl->conv_exec_flops += op.exec_flops;
-            pl->conv_bytes += op.bytes;
             char buf[256];
             snprintf(buf, sizeof buf, "conv(%s F%d gemm x%d) T=%lld Cout=%d Cin=%d flops=%.4g exec=%.4g", Up ? (sp.f16 ? "split f16x2 winograd" : "split bf16x2 winograd") : "winograd", tile, ncomp, T,
                      d.Cout, Ctot, op.flops, op.exec_flops);
@@ -252,7 +249,7 @@ struct Builder {
                 const ConvParams g = wp.gemm;
                 op.fn = [g](hipStream_t s) { launch_conv(g, s); };
             }
-            pl->net_ops.push_back(std::move(op));
+            push_op(std::move(op));
         }
         {
             Op op;
@@ -301,58 +298,77 @@ struct Builder {
         return out;
     }
 
+    // What lnconv and pwconv (below) share: the output tensor of out_c channels, the fp16 weight copy, the work accounting (out_bytes per output element next to the
+    // input and the weights) and the desc with the variant's text `what`; launch(w16, out, M, ppi, stream) runs the variant's kernel
+    template <class Launch>
+    Tensor fused_1x1(const ConvW& cw, const Tensor& x, int out_c, double out_bytes, const char* what, Launch launch) {
+        const int64_t M = (int64_t)x.B * x.H * x.W, ppi = (int64_t)x.H * x.W;
+        const int c = x.C, Cout = cw.Cout;
+        Tensor out = talloc(x.B, x.H, x.W, out_c);
+        const unsigned short* w16 = e->bf16_copy(cw.w, (size_t)Cout * c);   // (IRSDE_FLAG_FP16: the copy holds IEEE fp16)
+        float* op = out.p;
+        Op o;
+        o.kind = OP_CONV;
+        o.flops = 2.0 * (double)M * c * Cout;
+        o.exec_flops = o.flops;
+        o.bytes = 4.0 * (double)M * c + out_bytes * (double)M * out_c + 2.0 * (double)Cout * c;
+        char buf[200];
+        snprintf(buf, sizeof buf, "conv(fp16, %s) M=%lld Cout=%d Cin=%d k=1x1 blocks=%lld flops=%.4g", what, (long long)M, Cout, c,
+                 (long long)((M + 63) / 64) * (Cout / 64), o.flops);
+        o.desc = buf;
+        o.fn = [=](hipStream_t s) { launch(w16, op, M, ppi, s); };
+        push_op(std::move(o));
+        return out;
+    }
+
     // r06: norm + FiLM + 1x1 convolution (+ SimpleGate) as one launch (naf_lnconv_kernel, kernels_misc.hip): fp16 operand mode, c = 64 / 128 / 256
     bool lnconv_ok(const ConvW& cw, const Tensor& x) const {
         return !naive && (e->cfg.flags & IRSDE_FLAG_FP16) && naf_lnconv_enabled() && cw.KH == 1 && cw.KW == 1 &&
                naf_lnconv_ok(x.C, cw.Cout, (long long)x.B * x.H * x.W);
     }
     Tensor lnconv(const ConvW& cw, const Tensor& x, const float* g, const float* fscale, const float* fshift, int gate, const float* gate_film) {
-        const int64_t M = (int64_t)x.B * x.H * x.W, ppi = (int64_t)x.H * x.W;
         const int c = x.C, Cout = cw.Cout, fb = film_bstride, gfb = gate_film ? e->cam_row : 0;
-        Tensor out = talloc(x.B, x.H, x.W, gate ? Cout / 2 : Cout);
-        const unsigned short* w16 = e->bf16_copy(cw.w, (size_t)Cout * c);   // (IRSDE_FLAG_FP16: the copy holds IEEE fp16)
         const float *xp = x.p, *bias = cw.bias;
-        float* op = out.p;
-        Op o;
-        o.kind = OP_CONV;
-        o.flops = 2.0 * (double)M * c * Cout;
-        o.exec_flops = o.flops;
-        o.bytes = 4.0 * (double)M * c + 4.0 * (double)M * (gate ? Cout / 2 : Cout) + 2.0 * (double)Cout * c;
-        pl->conv_flops += o.flops;
-        pl->conv_exec_flops += o.exec_flops;
-        pl->conv_bytes += o.bytes;
-        char buf[200];
-        snprintf(buf, sizeof buf, "conv(fp16, LayerNorm + FiLM fused%s) M=%lld Cout=%d Cin=%d k=1x1 blocks=%lld flops=%.4g", gate ? ", gate" : "", (long long)M, Cout, c,
-                 (long long)((M + 63) / 64) * (Cout / 64), o.flops);
-        o.desc = buf;
-        o.fn = [=](hipStream_t s) { launch_naf_lnconv(xp, g, fscale, fshift, fb, ppi, w16, bias, op, M, c, Cout, gate, gate_film, gfb, s); };
-        pl->net_ops.push_back(std::move(o));
-        return out;
+        return fused_1x1(cw, x, gate ? Cout / 2 : Cout, 4.0, gate ? "LayerNorm + FiLM fused, gate" : "LayerNorm + FiLM fused",
+                         [=](const unsigned short* w16, float* op, int64_t M, int64_t ppi, hipStream_t s) {
+                             launch_naf_lnconv(xp, g, fscale, fshift, fb, ppi, w16, bias, op, M, c, Cout, gate, gate_film, gfb, s);
+                         });
     }
 
     // conv3 / conv5 on the same kernel (no LayerNorm): out = res + (W (in * in_scale) + bias) * ch_scale
     Tensor pwconv(const ConvW& cw, const Tensor& in, const float* in_scale, const float* ch_scale, const Tensor& res) {
-        const int64_t M = (int64_t)in.B * in.H * in.W, ppi = (int64_t)in.H * in.W;
         const int c = in.C, Cout = cw.Cout;
-        Tensor out = talloc(in.B, in.H, in.W, Cout);
-        const unsigned short* w16 = e->bf16_copy(cw.w, (size_t)Cout * c);
         const float *xp = in.p, *bias = cw.bias, *rp = res.p;
-        float* op = out.p;
-        Op o;
-        o.kind = OP_CONV;
-        o.flops = 2.0 * (double)M * c * Cout;
-        o.exec_flops = o.flops;
-        o.bytes = 4.0 * (double)M * c + 8.0 * (double)M * Cout + 2.0 * (double)Cout * c;
-        pl->conv_flops += o.flops;
-        pl->conv_exec_flops += o.exec_flops;
-        pl->conv_bytes += o.bytes;
-        char buf[200];
-        snprintf(buf, sizeof buf, "conv(fp16, one-piece K%s) M=%lld Cout=%d Cin=%d k=1x1 blocks=%lld flops=%.4g", in_scale ? ", SCA scale" : "", (long long)M, Cout, c,
-                 (long long)((M + 63) / 64) * (Cout / 64), o.flops);
-        o.desc = buf;
-        o.fn = [=](hipStream_t s) { launch_naf_pwconv(xp, in_scale, ppi, w16, bias, ch_scale, rp, op, M, c, Cout, s); };
-        pl->net_ops.push_back(std::move(o));
+        return fused_1x1(cw, in, Cout, 8.0, in_scale ? "one-piece K, SCA scale" : "one-piece K",   // (8 bytes per output element: the residual read + the store)
+                         [=](const unsigned short* w16, float* op, int64_t M, int64_t ppi, hipStream_t s) {
+                             launch_naf_pwconv(xp, in_scale, ppi, w16, bias, ch_scale, rp, op, M, c, Cout, s);
+                         });
+    }
+
+    // The two choices every NAFBlock makes twice or more.  norm + FiLM + 1x1 (+ SimpleGate, + the lens FiLM after the gate): one launch where lnconv_ok, else the
+    // LayerNorm kernel and the convolution kernel
+    Tensor norm_conv(const ConvW& cw, const Tensor& x, const float* g, const float* fscale, const float* fshift, int gate, const float* gate_film) {
+        if (lnconv_ok(cw, x)) return lnconv(cw, x, g, fscale, fshift, gate, gate_film);
+        const int64_t M = (int64_t)x.B * x.H * x.W, ppi = (int64_t)x.H * x.W;
+        Tensor t = talloc(x.B, x.H, x.W, x.C);
+        {
+            const float* xp = x.p;
+            float* o = t.p;
+            const int c = x.C, fb = film_bstride;
+            push_other(OP_LN, [=](hipStream_t s) { launch_layernorm_film(xp, g, fscale, fshift, fb, ppi, o, M, c, 1e-5f, s); });
+        }
+        ConvOpts o;
+        o.gate = gate; o.gate_film = gate_film;
+        Tensor out = conv_naf(cw, t, o);
+        tfree(t);
         return out;
+    }
+    // 1x1 + channel scale + residual (+ the SCA scale on the input): out = res + (W (in * in_scale) + bias) * ch_scale, on the lnconv kernel where eligible
+    Tensor scale_res_conv(const ConvW& cw, const Tensor& in, const float* in_scale, const float* ch_scale, const Tensor& res) {
+        if (lnconv_ok(cw, in) && res.C == cw.Cout) return pwconv(cw, in, in_scale, ch_scale, res);
+        ConvOpts o;
+        o.in_scale = in_scale; o.ch_scale = ch_scale; o.res = &res;
+        return conv_naf(cw, in, o);
     }
 
     // NAFBlock.forward — DenoisingNAFNet_arch.py:56-82
@@ -368,24 +384,9 @@ struct Builder {
 
     // level >= 0: the block's level in a CNAFNetLocal (see tlsc_local)
     Tensor nafblock(const NafBlockW& w, const Tensor& x, int level = -1) {
-        const int64_t M = (int64_t)x.B * x.H * x.W;
-        const int64_t ppi = (int64_t)x.H * x.W;
         const int c = w.c;
         const float* film = film_base() + w.film_off;  // [shift_att | scale_att | shift_ffn | scale_ffn]
-        const int fb = film_bstride;
-        Tensor u;
-        if (lnconv_ok(w.conv1, x)) {
-            u = lnconv(w.conv1, x, w.g1, film + c, film, 0, nullptr);
-        } else {
-            Tensor t1 = talloc(x.B, x.H, x.W, c);
-            {
-                const float *xp = x.p, *g = w.g1;
-                float* o = t1.p;
-                push_other(OP_LN, [=](hipStream_t s) { launch_layernorm_film(xp, g, film + c, film, fb, ppi, o, M, c, 1e-5f, s); });
-            }
-            u = conv_naf(w.conv1, t1, ConvOpts());
-            tfree(t1);
-        }
+        Tensor u = norm_conv(w.conv1, x, w.g1, film + c, film, 0, nullptr);
         Tensor gt = talloc(x.B, x.H, x.W, c);
         int k1 = 0, k2 = 0;
         if (tlsc_local(x, level, &k1, &k2)) {
@@ -423,14 +424,7 @@ struct Builder {
             pl->release(partial);
             pl->release(rowsum);
             tfree(pooled);
-            Tensor y;
-            if (lnconv_ok(w.conv3, gt) && x.C == w.conv3.Cout) {
-                y = pwconv(w.conv3, gt, nullptr, w.beta, x);
-            } else {
-                ConvOpts o3;
-                o3.ch_scale = w.beta; o3.res = &x;
-                y = conv_naf(w.conv3, gt, o3);
-            }
+            Tensor y = scale_res_conv(w.conv3, gt, nullptr, w.beta, x);   // (gt is scaled already)
             tfree(sc);
             tfree(gt);
             return nafblock_ffn(w, x, y);
@@ -449,14 +443,7 @@ struct Builder {
             });
         }
         tfree(u);
-        Tensor y;
-        if (lnconv_ok(w.conv3, gt) && x.C == w.conv3.Cout) {
-            y = pwconv(w.conv3, gt, sca, w.beta, x);
-        } else {
-            ConvOpts o3;
-            o3.in_scale = sca; o3.ch_scale = w.beta; o3.res = &x;
-            y = conv_naf(w.conv3, gt, o3);
-        }
+        Tensor y = scale_res_conv(w.conv3, gt, sca, w.beta, x);
         tfree(gt);
         pl->release(partial);
         pl->release(sca);
@@ -466,35 +453,11 @@ struct Builder {
 
     // the FFN half of NAFBlock.forward (:74-82) on y = inp + x * beta; releases y
     Tensor nafblock_ffn(const NafBlockW& w, const Tensor& x, const Tensor& y) {
-        const int64_t M = (int64_t)x.B * x.H * x.W;
-        const int64_t ppi = (int64_t)x.H * x.W;
         const int c = w.c;
         const float* film = film_base() + w.film_off;
-        const int fb = film_bstride;
-        Tensor v;
-        if (lnconv_ok(w.conv4, y)) {
-            v = lnconv(w.conv4, y, w.g2, film + 3 * c, film + 2 * c, 1, naf_lens(e) ? cam_base() + w.cam_off : nullptr);
-        } else {
-            Tensor t2 = talloc(x.B, x.H, x.W, c);
-            {
-                const float *yp = y.p, *g = w.g2;
-                float* o = t2.p;
-                push_other(OP_LN, [=](hipStream_t s) { launch_layernorm_film(yp, g, film + 3 * c, film + 2 * c, fb, ppi, o, M, c, 1e-5f, s); });
-            }
-            ConvOpts o4;
-            o4.gate = 1;
-            if (naf_lens(e)) o4.gate_film = cam_base() + w.cam_off;  // x * (cam_scale + 1) + cam_shift after the gate (:82-83)
-            v = conv_naf(w.conv4, t2, o4);
-            tfree(t2);
-        }
-        Tensor out;
-        if (lnconv_ok(w.conv5, v) && y.C == w.conv5.Cout) {
-            out = pwconv(w.conv5, v, nullptr, w.gamma, y);
-        } else {
-            ConvOpts o5;
-            o5.ch_scale = w.gamma; o5.res = &y;
-            out = conv_naf(w.conv5, v, o5);
-        }
+        const float* lens = naf_lens(e) ? cam_base() + w.cam_off : nullptr;  // x * (cam_scale + 1) + cam_shift after the gate (:82-83)
+        Tensor v = norm_conv(w.conv4, y, w.g2, film + 3 * c, film + 2 * c, 1, lens);
+        Tensor out = scale_res_conv(w.conv5, v, nullptr, w.gamma, y);
         tfree(v);
         tfree(y);
         return out;
@@ -532,9 +495,6 @@ struct Builder {
         o.flops = 2.0 * (double)c.nblocks * B * ((double)x.H * x.W * 512.0 * (1024.0 + 512.0 + 1024.0 + 512.0) + 512.0 * 512.0);
         o.exec_flops = o.flops;
         o.bytes = (double)c.nblocks * (3.5 * 1024 * 1024 + 4.0 * (double)naf_chain_vec_floats(1)) + 2.0 * 4.0 * (double)x.numel();
-        pl->conv_flops += o.flops;
-        pl->conv_exec_flops += o.exec_flops;
-        pl->conv_bytes += o.bytes;
         char buf[200];
         snprintf(buf, sizeof buf, "naf_chain(fp16) blocks=%d B=%d c=%d hw=%dx%d groups=%d flops=%.4g", c.nblocks, B, x.C, x.H, x.W, G, o.flops);
         o.desc = buf;
@@ -547,18 +507,49 @@ struct Builder {
         } else {
             o.fn = [=](hipStream_t s) { launch_naf_chain(xp, op, c.w, c.vecs, c.nblocks, B, film, fb, c.film_off, cam, cb, c.cam_off, s); };
         }
-        pl->net_ops.push_back(std::move(o));
+        push_op(std::move(o));
         return out;
     }
 
+    // The scratch of one SCAM, back in the arena when it leaves scope: both views' [LN(x) | x] (in2) and [Q | V] (qv), and F; vsz = one view's 2c-channel tensor
+    struct ScamScratch {
+        Builder& b;
+        const size_t vsz;
+        float *in2, *qv, *F;
+        ScamScratch(Builder& b_, size_t vsz_)
+            : b(b_), vsz(vsz_), in2(b.pl->alloc(2 * vsz, b.reuse)), qv(b.pl->alloc(2 * vsz, b.reuse)), F(b.pl->alloc(vsz, b.reuse)) {}
+        ~ScamScratch() {
+            if (!b.reuse) return;
+            b.pl->release(in2);
+            b.pl->release(qv);
+            b.pl->release(F);
+        }
+        ScamScratch(const ScamScratch&) = delete;
+        ScamScratch& operator=(const ScamScratch&) = delete;
+    };
+    // [Q | V] = [[proj1, 0], [0, proj2]] [LN(x) | x] + [b1 | b2] on the Bp x H x W map of each view: one GEMM per view (its weights)
+    void scam_proj(const ScamW& w, const ScamScratch& ws, int Bp, int H, int W, const char* desc_prefix) {
+        const int c = w.c;
+        for (int v = 0; v < 2; ++v) {
+            const ConvW& cw = v ? w.r : w.l;
+            ConvParams p;
+            p.in0 = ws.in2 + v * ws.vsz; p.C0 = 2 * c; p.pix0 = 2 * c;
+            p.Hin = H; p.Win = W;
+            p.w = cw.w; p.Cout = 2 * c; p.KH = p.KW = 1; p.stride = 1;
+            p.B = Bp; p.Ho = H; p.Wo = W;
+            p.out = ws.qv + v * ws.vsz; p.out_stride = 2 * c;
+            p.bias = cw.bias;
+            push_conv(p);
+            pl->net_ops.back().desc = desc_prefix + std::string(v ? "(r) " : "(l) ") + pl->net_ops.back().desc;
+        }
+    }
+
     // SCAM.forward — stereo-sr DenoisingNAFNet_arch.py:33-60 (csrc/scam.hip): x holds the 2 B views [L | R] of B pairs
-    Tensor scam(const NafBlockW& w, const Tensor& x) {
+    Tensor scam(const ScamW& w, const Tensor& x) {
         const int c = x.C, Bp = x.B / 2, Hs = x.H / 4, Ws = x.W / 4, H = x.H, W = x.W;
         scam_check_shape(x.H, x.W, c);
-        const size_t vsz = (size_t)Bp * Hs * Ws * 2 * c;   // one view's [LN(xs) | xs] / [Q | V]
-        float* xs2 = pl->alloc(2 * vsz, reuse);
-        float* qv = pl->alloc(2 * vsz, reuse);
-        float* F = pl->alloc(vsz, reuse);
+        ScamScratch ws(*this, (size_t)Bp * Hs * Ws * 2 * c);   // one view's [LN(xs) | xs] / [Q | V]
+        float *xs2 = ws.in2, *qv = ws.qv, *F = ws.F;
         Tensor out = talloc(x.B, x.H, x.W, c);
         char buf[160];
         auto name = [&](const char* what) {
@@ -566,36 +557,20 @@ struct Builder {
             pl->net_ops.back().desc = buf;
         };
         {
-            const float *xp = x.p, *gl = w.scam_gl, *gr = w.scam_gr;
+            const float *xp = x.p, *gl = w.gl, *gr = w.gr;
             push_other(OP_LN, [=](hipStream_t s) { launch_scam_prologue(xp, gl, gr, xs2, Bp, H, W, c, s); });
             name("prologue(bicubic/4 + LayerNorm)");
         }
-        for (int v = 0; v < 2; ++v) {   // [Q | V] = [[proj1, 0], [0, proj2]] [LN(xs) | xs] + [b1 | b2]: one GEMM per view (its weights)
-            const ConvW& cw = v ? w.scam_r : w.scam_l;
-            ConvParams p;
-            p.in0 = xs2 + v * vsz; p.C0 = 2 * c; p.pix0 = 2 * c;
-            p.Hin = Hs; p.Win = Ws;
-            p.w = cw.w; p.Cout = 2 * c; p.KH = p.KW = 1; p.stride = 1;
-            p.B = Bp; p.Ho = Hs; p.Wo = Ws;
-            p.out = qv + v * vsz; p.out_stride = 2 * c;
-            p.bias = cw.bias;
-            push_conv(p);
-            pl->net_ops.back().desc = std::string(v ? "scam_proj(r) " : "scam_proj(l) ") + pl->net_ops.back().desc;
-        }
+        scam_proj(w, ws, Bp, Hs, Ws, "scam_proj");
         {
             push_other(OP_ATTN, [=](hipStream_t s) { launch_scam_core(qv, F, Bp, H, W, c, s); });
             name("core(S strips + softmax + PV, fp32 MFMA)");
         }
         {
-            const float *xp = x.p, *be = w.scam_beta, *ga = w.scam_gamma;
+            const float *xp = x.p, *be = w.beta, *ga = w.gamma;
             float* op = out.p;
             push_other(OP_OTHER, [=](hipStream_t s) { launch_scam_epilogue(xp, F, be, ga, op, Bp, H, W, c, s); });
             name("epilogue(scale + nearest up + residual)");
-        }
-        if (reuse) {
-            pl->release(xs2);
-            pl->release(qv);
-            pl->release(F);
         }
         return out;
     }
@@ -606,10 +581,8 @@ struct Builder {
         const int c = x.C, Bp = x.B / 2, H = x.H, W = x.W;
         if (x.bf16 || c != w.c || (x.B & 1)) throw HipError("internal: SCAM input");
         scam_full_check_shape(H, W, c);
-        const size_t vsz = (size_t)Bp * H * W * 2 * c;   // one view's [LN(x) | x] / [Q | V]
-        float* x2 = pl->alloc(2 * vsz, reuse);
-        float* qv = pl->alloc(2 * vsz, reuse);
-        float* F = pl->alloc(vsz, reuse);
+        ScamScratch ws(*this, (size_t)Bp * H * W * 2 * c);   // one view's [LN(x) | x] / [Q | V]
+        float *x2 = ws.in2, *qv = ws.qv, *F = ws.F;
         char buf[160];
         auto name = [&](const char* what) {
             snprintf(buf, sizeof buf, "scam_full_%s B=%d c=%d hw=%dx%d", what, x.B, c, H, W);
@@ -620,18 +593,7 @@ struct Builder {
             push_other(OP_LN, [=](hipStream_t s) { launch_scam_full_prologue(xp, gl, gr, x2, Bp, H, W, c, s); });
             name("prologue(LayerNorm -> [LN(x) | x])");
         }
-        for (int v = 0; v < 2; ++v) {   // [Q | V] = [[proj1, 0], [0, proj2]] [LN(x) | x] + [b1 | b2]: one GEMM per view (its weights)
-            const ConvW& cw = v ? w.r : w.l;
-            ConvParams p;
-            p.in0 = x2 + v * vsz; p.C0 = 2 * c; p.pix0 = 2 * c;
-            p.Hin = H; p.Win = W;
-            p.w = cw.w; p.Cout = 2 * c; p.KH = p.KW = 1; p.stride = 1;
-            p.B = Bp; p.Ho = H; p.Wo = W;
-            p.out = qv + v * vsz; p.out_stride = 2 * c;
-            p.bias = cw.bias;
-            push_conv(p);
-            pl->net_ops.back().desc = std::string(v ? "scam_full_proj(r) " : "scam_full_proj(l) ") + pl->net_ops.back().desc;
-        }
+        scam_proj(w, ws, Bp, H, W, "scam_full_proj");
         {
             push_other(OP_ATTN, [=](hipStream_t s) { launch_scam_full_core(qv, F, Bp, H, W, c, s); });
             name("core(S strips + softmax + PV, fp32 MFMA)");
@@ -651,11 +613,6 @@ struct Builder {
             push_other(OP_OTHER, [=](hipStream_t s) { launch_scam_full_epilogue(op, F, be, ga, Bp, H, W, c, s); });
             name("epilogue(scale + residual, in place)");
         }
-        if (reuse) {
-            pl->release(x2);
-            pl->release(qv);
-            pl->release(F);
-        }
         return out;
     }
 
@@ -674,6 +631,17 @@ struct Builder {
         return out;
     }
 
+    // The scratch of the linear-attention kernels (kernels_misc.hip sizes it the same way): per-chunk maxima, contexts and sums of the pixel chunks, and the merged context
+    AttnWorkspace attn_workspace(int B, int N) {
+        AttnWorkspace ws;
+        ws.nch = attn_num_chunks(N, B);
+        ws.pmax = pl->alloc((size_t)B * ws.nch * 128, false);
+        ws.pctx = pl->alloc((size_t)B * 4 * ws.nch * 1024, false);
+        ws.psum = pl->alloc((size_t)B * 4 * ws.nch * 32, false);
+        ws.ctx = pl->alloc((size_t)B * 4 * 1024, false);
+        return ws;
+    }
+
     // Residual(PreNorm(dim, LinearAttention(dim))) — module_util.py:20-26,82-90,150-178
     Tensor attn(const AttnW& w, const Tensor& x) {
         const int64_t M = (int64_t)x.B * x.H * x.W;
@@ -686,12 +654,7 @@ struct Builder {
         const bool fused_16 = w.g2 && !naive && (e->cfg.flags & IRSDE_FLAG_BF16) && !(e->cfg.flags & (IRSDE_FLAG_NO_FUSED_ATTN | IRSDE_FLAG_NO_FUSED_LN)) &&
                               (x.C == 64 || x.C == 128 || x.C == 256) && x.bf16 == act_bf16();
         if (fused_16) {
-            AttnWorkspace ws;
-            ws.nch = attn_num_chunks(N, x.B);
-            ws.pmax = pl->alloc((size_t)x.B * ws.nch * 128, false);
-            ws.pctx = pl->alloc((size_t)x.B * 4 * ws.nch * 1024, false);
-            ws.psum = pl->alloc((size_t)x.B * 4 * ws.nch * 32, false);
-            ws.ctx = pl->alloc((size_t)x.B * 4 * 1024, false);
+            const AttnWorkspace ws = attn_workspace(x.B, N);
             Tensor y = talloc(x.B, x.H, x.W, x.C);
             if (y.bf16 != x.bf16) throw HipError("attention: mixed activation storage types");
             const float *xp = x.p, *wqkv = w.qkv.w, *wo = w.out.w, *bo = w.out.bias, *g1 = w.g1, *g2 = w.g2;
@@ -718,12 +681,7 @@ struct Builder {
         if (fused_all) {
             // whole Residual(PreNorm(LinearAttention)) block in two kernels + the context merge: PreNorm's LayerNorm runs on
             // the tiles both kernels stage, so no normalised copy of x, no q / k / v, no attention output reach HBM
-            AttnWorkspace ws;
-            ws.nch = attn_num_chunks(N, x.B);
-            ws.pmax = pl->alloc((size_t)x.B * ws.nch * 128, false);
-            ws.pctx = pl->alloc((size_t)x.B * 4 * ws.nch * 1024, false);
-            ws.psum = pl->alloc((size_t)x.B * 4 * ws.nch * 32, false);
-            ws.ctx = pl->alloc((size_t)x.B * 4 * 1024, false);
+            const AttnWorkspace ws = attn_workspace(x.B, N);
             Tensor y = talloc(x.B, x.H, x.W, x.C);
             const float *xp = x.p, *wq = w.qkv.w, *wkv = w.qkv.w + (size_t)128 * x.C, *wo = w.out.w, *bo = w.out.bias, *g1 = w.g1, *g2 = w.g2;
             float* yp = y.p;
@@ -762,12 +720,7 @@ struct Builder {
         if (fused_kv) {
             // fp32 fused form: the k and v thirds of to_qkv never reach HBM — their projection, the softmax over the pixels and
             // the context run in one kernel on the LayerNorm output; only q (rows 0..127 of to_qkv.weight) is a convolution
-            AttnWorkspace ws;
-            ws.nch = attn_num_chunks(N, x.B);
-            ws.pmax = pl->alloc((size_t)x.B * ws.nch * 128, false);
-            ws.pctx = pl->alloc((size_t)x.B * 4 * ws.nch * 1024, false);
-            ws.psum = pl->alloc((size_t)x.B * 4 * ws.nch * 32, false);
-            ws.ctx = pl->alloc((size_t)x.B * 4 * 1024, false);
+            const AttnWorkspace ws = attn_workspace(x.B, N);
             {
                 const float *xp = xn.p, *wkv = w.qkv.w + (size_t)128 * x.C;
                 const int B = x.B, C = x.C;
@@ -811,12 +764,7 @@ struct Builder {
             return y;
         }
         {
-            AttnWorkspace ws;
-            ws.nch = attn_num_chunks(N, x.B);
-            ws.pmax = pl->alloc((size_t)x.B * ws.nch * 128, false);
-            ws.pctx = pl->alloc((size_t)x.B * 4 * ws.nch * 1024, false);
-            ws.psum = pl->alloc((size_t)x.B * 4 * ws.nch * 32, false);
-            ws.ctx = pl->alloc((size_t)x.B * 4 * 1024, false);
+            const AttnWorkspace ws = attn_workspace(x.B, N);
             const float* q = qkv.p;
             float* o = a.p;
             const int B = x.B;
@@ -869,7 +817,7 @@ void build_naf_plan(irsde_engine* e, Plan* pl, Builder& b, int P) {
         Tensor y = b.nafblock(blk, in, level);
         if (!stereo) return y;
         b.tap(path + ".fusion.in", y);
-        Tensor z = b.scam(blk, y);
+        Tensor z = b.scam(blk.fusion, y);
         b.tfree(y);
         b.tap(path, z);
         return z;
@@ -893,18 +841,22 @@ void build_naf_plan(irsde_engine* e, Plan* pl, Builder& b, int P) {
     // latent variant (latent-dehazing/models/modules/DenoisingNAFNet_arch.py:162-176): ending(x + intro output)
     const bool intro_skip = (e->cfg.flags & IRSDE_FLAG_NAF_INTRO_SKIP) != 0;
     const Tensor intro = x;
+    // x through the blocks `path`0, `path`1, ... of one level: a chain launch where the level qualifies (a block with a local window is never part of a chain),
+    // else block by block.  Every input is recycled but the intro output that the latent variant adds back at the end.  Below the first encoder level
+    // x is a downs / ups output, so the guard only matters there; it also keeps the intro output alive in a net without encoder levels
+    auto run_level = [&](NafChainW& chain, const std::vector<NafBlockW>& blks, const std::string& path, int level) {
+        auto advance = [&](const Tensor& y) {
+            if (!(intro_skip && x.p == intro.p)) b.tfree(x);
+            x = y;
+        };
+        if (!b.tlsc_local(x, level) && b.naf_chain_ok(chain, x))
+            advance(b.nafchain(chain, x));
+        else
+            for (size_t j = 0; j < blks.size(); ++j) advance(block(blks[j], x, path + std::to_string(j), level));
+    };
     std::vector<Tensor> encs;
     for (size_t i = 0; i < e->naf_enc.size(); ++i) {
-        if (!b.tlsc_local(x, (int)i) && b.naf_chain_ok(e->naf_chain_enc[i], x)) {   // (a block with a local window is never part of a chain)
-            Tensor y = b.nafchain(e->naf_chain_enc[i], x);
-            if (!(intro_skip && x.p == intro.p)) b.tfree(x);
-            x = y;
-        } else
-        for (size_t j = 0; j < e->naf_enc[i].size(); ++j) {
-            Tensor y = block(e->naf_enc[i][j], x, "encoders." + std::to_string(i) + "." + std::to_string(j), (int)i);
-            if (!(intro_skip && x.p == intro.p)) b.tfree(x);
-            x = y;
-        }
+        run_level(e->naf_chain_enc[i], e->naf_enc[i], "encoders." + std::to_string(i) + ".", (int)i);
         b.tap("encoders." + std::to_string(i), x);
         encs.push_back(x);
         Builder::ConvOpts od;
@@ -913,16 +865,7 @@ void build_naf_plan(irsde_engine* e, Plan* pl, Builder& b, int P) {
         b.tap("downs." + std::to_string(i), x);
     }
     const int nlev = (int)e->naf_enc.size();
-    if (!b.tlsc_local(x, nlev) && b.naf_chain_ok(e->naf_chain_mid, x)) {
-        Tensor y = b.nafchain(e->naf_chain_mid, x);
-        b.tfree(x);
-        x = y;
-    } else
-    for (size_t j = 0; j < e->naf_mid.size(); ++j) {
-        Tensor y = block(e->naf_mid[j], x, "middle_blks." + std::to_string(j), nlev);
-        b.tfree(x);
-        x = y;
-    }
+    run_level(e->naf_chain_mid, e->naf_mid, "middle_blks.", nlev);
     b.tap("middle", x);
     for (size_t i = 0; i < e->naf_dec.size(); ++i) {
         Tensor skip = encs[encs.size() - 1 - i];
@@ -933,16 +876,7 @@ void build_naf_plan(irsde_engine* e, Plan* pl, Builder& b, int P) {
         b.tfree(skip);
         x = y;
         b.tap("ups." + std::to_string(i), x);
-        if (!b.tlsc_local(x, nlev - 1 - (int)i) && b.naf_chain_ok(e->naf_chain_dec[i], x)) {
-            Tensor z = b.nafchain(e->naf_chain_dec[i], x);
-            b.tfree(x);
-            x = z;
-        } else
-        for (size_t j = 0; j < e->naf_dec[i].size(); ++j) {
-            Tensor z = block(e->naf_dec[i][j], x, "decoders." + std::to_string(i) + "." + std::to_string(j), nlev - 1 - (int)i);
-            b.tfree(x);
-            x = z;
-        }
+        run_level(e->naf_chain_dec[i], e->naf_dec[i], "decoders." + std::to_string(i) + ".", nlev - 1 - (int)i);
         b.tap("decoders." + std::to_string(i), x);
     }
     if (intro_skip) {
@@ -1027,6 +961,16 @@ static bool evict_lru_plan(irsde_engine* e) {
 
 static Plan* build_plan(irsde_engine* e, int B, int H, int W, bool per_sample_film, int slot, int b0);
 
+// The geometry of a new plan: the image size padded to multiples of sdiv, and its first LRU stamp
+static void init_plan_geometry(irsde_engine* e, Plan* pl, int B, int H, int W, int sdiv) {
+    pl->B = B; pl->H = H; pl->W = W;
+    pl->Hp = (H + sdiv - 1) / sdiv * sdiv;
+    pl->Wp = (W + sdiv - 1) / sdiv * sdiv;
+    pl->last_use = ++e->use_counter;
+    // F.pad 'reflect' needs pad < dim (DenoisingUNet_arch.py:82); NAFNet zero-pads (DenoisingNAFNet_arch.py:189-194)
+    if (e->arch != 1 && (pl->Hp - H >= H || pl->Wp - W >= W)) throw HipError("image too small for reflect padding");
+}
+
 // Cached plans are bounded by count (8: a split batch holds up to four sub-batch plans) AND by device memory: every plan owns its activation arena
 // (16 x 512^2: several GiB), so a build that runs out of memory drops the least recently used plans and tries again instead of failing the sampler call
 // (ADVICE r05).
@@ -1057,18 +1001,12 @@ static Plan* build_plan(irsde_engine* e, int B, int H, int W, bool per_sample_fi
     }
 
     const int depth = e->cfg.depth, nf = e->cfg.nf, in_nc = e->cfg.in_nc;
-    const int sdiv = 1 << depth;
     std::unique_ptr<Plan> plan(new Plan());
     Plan* pl = plan.get();
-    pl->B = B; pl->H = H; pl->W = W;
-    pl->Hp = (H + sdiv - 1) / sdiv * sdiv;
-    pl->Wp = (W + sdiv - 1) / sdiv * sdiv;
+    init_plan_geometry(e, pl, B, H, W, 1 << depth);
     pl->per_sample_film = per_sample_film;
     pl->slot = slot; pl->b0 = b0;
     pl->pred_stride = (e->cfg.out_nc + 3) & ~3;
-    pl->last_use = ++e->use_counter;
-    // F.pad 'reflect' needs pad < dim (DenoisingUNet_arch.py:82)
-    if (e->arch != 1 && (pl->Hp - H >= H || pl->Wp - W >= W)) throw HipError("image too small for reflect padding");
 
     if (slot > 0) {
         if (per_sample_film) throw HipError("internal: sub-batch plans are sampler plans (one time step for the whole part)");
@@ -1248,16 +1186,11 @@ LatentPlan* get_latent_plan(irsde_engine* e, int B, int H, int W, bool decode) {
     }
     const int depth = (int)e->lat_mult.size(), ch = e->lat_ch;
     auto dim = [&](int i) { return i == 0 ? ch : ch * e->lat_mult[i - 1]; };
-    const int sdiv = 1 << depth;  // check_image_size pads to 2^depth although only depth-1 levels downsample (:52-57)
     std::unique_ptr<LatentPlan> lp(new LatentPlan());
     lp->decode = decode;
     lp->plan.reset(new Plan());
     Plan* pl = lp->plan.get();
-    pl->B = B; pl->H = H; pl->W = W;
-    pl->Hp = (H + sdiv - 1) / sdiv * sdiv;
-    pl->Wp = (W + sdiv - 1) / sdiv * sdiv;
-    pl->last_use = ++e->use_counter;
-    if (pl->Hp - H >= H || pl->Wp - W >= W) throw HipError("image too small for reflect padding");
+    init_plan_geometry(e, pl, B, H, W, 1 << depth);  // check_image_size pads to 2^depth although only depth-1 levels downsample (:52-57)
     // skips never alias anything else: they cross the encode/decode boundary (decode: they are inputs)
     Builder b{e, pl, false, (e->cfg.flags & IRSDE_FLAG_NAIVE_CONV) != 0, 0};
     // hidden list geometry: h[0] = init_conv output, then two entries per level

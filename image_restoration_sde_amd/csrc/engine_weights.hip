@@ -369,23 +369,7 @@ NafBlockW pack_nafblock(irsde_engine* e, const std::string& p, int c) {
         b.cam_w = e->upload(need(e, p + "cam_mlp.1.weight").data);
         b.cam_b = e->upload(need(e, p + "cam_mlp.1.bias").data);
     }
-    if (naf_stereo(e)) {
-        const std::string f = p + "fusion.";
-        b.scam_gl = e->upload(need(e, f + "norm_l.g").data);
-        b.scam_gr = e->upload(need(e, f + "norm_r.g").data);
-        for (int v = 0; v < 2; ++v) {
-            const std::string s1 = f + (v ? "r_proj1." : "l_proj1."), s2 = f + (v ? "r_proj2." : "l_proj2.");
-            std::vector<float> w, bias;
-            scam_pack_proj(need(e, s1 + "weight").data.data(), need(e, s1 + "bias").data.data(), need(e, s2 + "weight").data.data(),
-                           need(e, s2 + "bias").data.data(), c, w, bias);
-            ConvW& cw = v ? b.scam_r : b.scam_l;
-            cw.w = e->upload(w);
-            cw.bias = e->upload(bias);
-            cw.Cout = cw.Cin = 2 * c;
-        }
-        b.scam_beta = e->upload(need(e, f + "beta").data);
-        b.scam_gamma = e->upload(need(e, f + "gamma").data);
-    }
+    if (naf_stereo(e)) b.fusion = pack_scam(e, p + "fusion.");
     return b;
 }
 
