@@ -35,6 +35,7 @@ FLAG_SPLIT_F16X2 = 32768
 FLAG_NAF_STEREO = 65536
 FLAG_NAF_UNCOND = 131072
 FLAG_UNET_STEREO = 262144
+FLAG_F16_ACT = 524288
 SAMPLE_GRAPH = 1
 SAMPLE_PROFILE = 2
 

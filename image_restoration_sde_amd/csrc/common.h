@@ -90,6 +90,9 @@ struct ConvParams {
     // bf16 activation storage (IRSDE_FLAG_BF16_ACT, bf16-MFMA kernels only): in0/in1 resp. out/res point at bf16 tensors
     // (strides in elements); accumulation and the epilogue arithmetic stay fp32
     int in_bf16 = 0, out_bf16 = 0;
+    // IEEE fp16 activation storage (IRSDE_FLAG_F16_ACT, fp16-MFMA implicit-GEMM kernels only): in0/in1 resp. out/res point at fp16 tensors (strides in
+    // elements).  The two sides are independent: the NAFNet's intro reads the fp32 prepped input, its ending writes the fp32 eps_hat
+    int in_f16 = 0, out_f16 = 0;
     // channel LayerNorm fused into the epilogue (LinearAttention.to_out = Conv2d + LayerNorm, module_util.py:158-161, then the
     // Residual add): v = (v - mean_n v) * rsqrt(var_n v + eps) * ln_g[n], applied after bias and before +res.  Needs the
     // whole output row in one tile: Cout == 64 or 128, no split-K.
@@ -229,20 +232,22 @@ void launch_layernorm(const float* x, const float* g, const float* res, float* o
                       float eps, hipStream_t s, bool bf16 = false);
 // NAFNet: y = LN(x) * g * (scale + 1) + shift with per-channel FiLM rows (row stride film_bstride per batch item, 0 = shared)
 void launch_layernorm_film(const float* x, const float* g, const float* scale, const float* shift, int film_bstride,
-                           int64_t pixels_per_image, float* out, int64_t M, int C, float eps, hipStream_t s);
+                           int64_t pixels_per_image, float* out, int64_t M, int C, float eps, hipStream_t s,
+                           bool f16 = false);   // f16: x and out are IEEE fp16 tensors behind the float* (IRSDE_FLAG_F16_ACT)
 // NAFNet: depthwise 3x3 (pad 1, bias) over u [B][H][W][2c] fused with SimpleGate -> out [B][H][W][c], plus per-tile
 // channel sums partial[b][tile][c] (deterministic two-stage global average pool).  w: [9][2c], bias: [2c].
 int dwgate_tiles(int H, int W, int c);
 // r06: NAFBlock norm + FiLM + 1x1 convolution (+ SimpleGate) in one launch, fp16 operand mode, c = 64 / 128 / 256 (kernels_misc.hip)
 bool naf_lnconv_ok(int c, int Cout, long long M);
 void launch_naf_pwconv(const float* x, const float* in_scale, int64_t pixels_per_image, const unsigned short* w16, const float* bias, const float* ch_scale,
-                       const float* res, float* out, int64_t M, int c, int Cout, hipStream_t s);
+                       const float* res, float* out, int64_t M, int c, int Cout, hipStream_t s, bool f16 = false);   // f16: x, res and out are fp16 tensors
 void naf_lnconv_global_init();
 void launch_naf_lnconv(const float* x, const float* g, const float* fscale, const float* fshift, int film_bstride, int64_t pixels_per_image,
                        const unsigned short* w16, const float* bias, float* out, int64_t M, int c, int Cout, int gate, const float* gate_film,
-                       int gate_film_bstride, hipStream_t s);  // tiles of launch_dwconv_gate = rows of its `partial` buffer per image
+                       int gate_film_bstride, hipStream_t s, bool f16 = false);  // f16: x and out are fp16 tensors
+// tiles of launch_dwconv_gate = rows of its `partial` buffer per image
 void launch_dwconv_gate(const float* u, const float* w, const float* bias, float* out, float* partial, int B, int H, int W,
-                        int c, hipStream_t s);
+                        int c, hipStream_t s, bool f16 = false);   // f16: u and out are fp16 tensors; partial stays fp32, summed before the store rounding
 // NAFNet SCA: s[b][o] = bias[o] + sum_k W[o][k] * mean_hw(gated)[b][k]
 void launch_sca(const float* partial, int ntiles, const float* W, const float* bias, float* mean, float* s_out, int B,
                 int c, int HW, hipStream_t s);  // mean: scratch [B][c]
@@ -364,7 +369,7 @@ void launch_add(const float* a, const float* b, float* out, size_t n, hipStream_
 void launch_nchw_to_nhwc_pad(const float* in, float* out, int B, int C, int H, int W, int Hp, int Wp, int Cp, int reflect,
                              hipStream_t s);
 // NHWC [B][H][W][C] -> NCHW (debug taps)
-void launch_nhwc_to_nchw(const float* in, float* out, int B, int C, int H, int W, hipStream_t s, bool bf16 = false);
+void launch_nhwc_to_nchw(const float* in, float* out, int B, int C, int H, int W, hipStream_t s, bool bf16 = false, bool f16 = false);   // bf16 / f16: `in` is a 16-bit tensor
 
 // Reverse-step update x <- f(x, mu, eps_hat, z) on NCHW state; eps_hat addressed by strides.
 struct UpdateParams {

@@ -36,10 +36,14 @@ namespace irsde {
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 typedef float floatx4 __attribute__((ext_vector_type(4)));
+typedef float floatx2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef float floatx8 __attribute__((ext_vector_type(8)));
 
 namespace {
 
@@ -49,12 +53,16 @@ template <bool F16>
 struct Op16 {
     using x8 = bf16x8;
     using x4 = bf16x4;
+    using x2 = bf16x2;
+    using x1 = __bf16;
     static __device__ __forceinline__ floatx16 mfma(x8 a, x8 b, floatx16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
 };
 template <>
 struct Op16<true> {
     using x8 = f16x8;
     using x4 = f16x4;
+    using x2 = f16x2;
+    using x1 = _Float16;
     static __device__ __forceinline__ floatx16 mfma(x8 a, x8 b, floatx16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
 };
 
@@ -66,7 +74,7 @@ struct Cfg {
     static constexpr int ROW_BYTES = BK * (BF16 ? 2 : 4) + 16;  // LDS tile row: 32 k + 16-B pad
     static constexpr int TM = BM / WAVES_M / 32;
     static constexpr int TN = BN / WAVES_N / 32;
-    // A (activations): fp32 in HBM = 8 x 16-B loads per row of 32 k; bf16 in HBM (ABF, IRSDE_FLAG_BF16_ACT) = 4
+    // A (activations): fp32 in HBM = 8 x 16-B loads per row of 32 k; bf16 / fp16 in HBM (ABF: IRSDE_FLAG_BF16_ACT, or the kernel's AF16: IRSDE_FLAG_F16_ACT) = 4
     static constexpr int A_CHUNKS = ABF ? 4 : 8;
     static constexpr int A_ROWS = NT / A_CHUNKS;
     static constexpr int A_PASSES = BM / A_ROWS;
@@ -111,16 +119,21 @@ __device__ __forceinline__ void static_for(F&& f) {
 // 16-bit MFMA — the arithmetic of gemm_split.hip for the direct (implicit-GEMM) layers.  Activations are split while they are
 // staged (two LDS planes per operand), the weights come pre-split (p.w_pair: two planes); fp16 pieces carry 22+ significand
 // bits (fp32-equivalent), their weight plane is scaled by a power of two that p.pair_scale undoes on the accumulators.
+// AF16 (IRSDE_FLAG_F16_ACT): the fp16-operand kernel on IEEE fp16 activation tensors — a staged piece is 8 halves that go to LDS as they are; with INSCALE they are
+// widened, multiplied by the fp32 SCA scale and rounded once more (the operand is round_f16(stored * scale)).  The output side is a run-time
+// switch of the epilogue (p.out_f16, like p.out_bf16): intro reads fp32 and writes fp16, ending reads fp16 and writes fp32.
 template <int BM, int BN, int WAVES_M, int WAVES_N, int MIN_WAVES_PER_SIMD, bool BF16, bool INSCALE, bool ABF = false, bool F16 = false,
-          bool BUFA = false, bool PAIR = false>
+          bool BUFA = false, bool PAIR = false, bool AF16 = false>
 __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, MIN_WAVES_PER_SIMD) void conv_igemm_kernel(
     const ConvParams pin, const int nblk_n, const int M, const int nk_total) {
-    using C = Cfg<BM, BN, WAVES_M, WAVES_N, BF16, ABF, PAIR ? 2 : 1>;
+    using C = Cfg<BM, BN, WAVES_M, WAVES_N, BF16, ABF || AF16, PAIR ? 2 : 1>;
     using H16 = Op16<F16>;
     static_assert(!PAIR || (BF16 && !ABF && !BUFA), "PAIR: 16-bit MFMA on fp32 activation storage, generic staging");
     constexpr int PL = PAIR ? 2 : 1;
     static_assert(!ABF || (BF16 && !INSCALE), "bf16 activation storage belongs to the bf16-MFMA mode");
-    static_assert(!F16 || (BF16 && !ABF), "fp16 operands: the 16-bit MFMA mode with fp32 activation storage");
+    static_assert(!F16 || (BF16 && !ABF), "fp16 operands: the 16-bit MFMA mode with fp32 or fp16 activation storage");
+    static_assert(!AF16 || (F16 && !PAIR && !BUFA), "fp16 activation storage belongs to the fp16-MFMA mode");
+    constexpr bool A16 = ABF || AF16;   // 16-bit activation tensors: 8 elements per staged piece
     // XCD-aware block remap (bijective): each XCD (linear block id % 8) walks a contiguous range of tiles so
     // that neighbouring tiles (same activation rows, other Cout slices / halo rows) share one L2.  Batched launches (Winograd
     // components, blockIdx.z) fold the component into the walk: an XCD then owns WHOLE components (A and B of a component are
@@ -173,7 +186,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, MIN_WAVES_PER_SIMD) void co
     const int Wv = p.Win << p.in_shift;
 
     // ---- per-thread staging coordinates (fixed for the whole K loop) ----
-    const int chunk = tid % C::A_CHUNKS;  // A: 16-B chunk (4 fp32 / 8 bf16 k) of the 32-k slice
+    const int chunk = tid % C::A_CHUNKS;  // A: 16-B chunk (4 fp32 / 8 bf16 or fp16 k) of the 32-k slice
     const int row0 = tid / C::A_CHUNKS;   // A: first staged row
     const int bchunk = tid % C::B_CHUNKS;
     const int brow0 = tid / C::B_CHUNKS;
@@ -258,7 +271,8 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, MIN_WAVES_PER_SIMD) void co
     constexpr int NP = C::A_PASSES + C::B_PASSES;   // (the PAIR kernels stage through their own lambdas further down)
     floatx4 rs[NP];  // (ext_vector: HIP's float4 struct copies become memcpys that can pin the array to scratch)
     floatx4 rscale[INSCALE ? C::A_PASSES : 1];  // NAFNet SCA: the per-(image, channel) scales of the A pieces in flight
-    constexpr int AESZ = ABF ? 2 : 4;        // bytes per activation element in HBM
+    floatx4 rscale_hi[INSCALE && AF16 ? C::A_PASSES : 1];   // AF16: a piece is 8 channels — the scales of its second four
+    constexpr int AESZ = A16 ? 2 : 4;        // bytes per activation element in HBM
     constexpr int ACE = 16 / AESZ;           // elements per 16-byte chunk
     const char* cur_src = nullptr;  // source pointer (+channel +chunk) of the K-step being staged
     int cur_pix = 0;                // bytes between consecutive pixels of that source
@@ -297,7 +311,11 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, MIN_WAVES_PER_SIMD) void co
             // branch-free: out-of-image taps (zero padding, rows past M) read the zero page instead
             const char* g = a_poff[q] >= 0 ? cur_src + (size_t)a_poff[q] * cur_pix : reinterpret_cast<const char*>(p.zeros);
             rs[q] = *reinterpret_cast<const floatx4*>(g);
-            if constexpr (INSCALE)  // single source (C1 == 0); multiplied when the piece is written to LDS (store_piece)
+            if constexpr (INSCALE && AF16) {
+                const float* sp = p.in_scale + (size_t)a_b[q] * p.C0 + cc + chunk * 8;
+                rscale[q < C::A_PASSES ? q : 0] = *reinterpret_cast<const floatx4*>(sp);
+                rscale_hi[q < C::A_PASSES ? q : 0] = *reinterpret_cast<const floatx4*>(sp + 4);
+            } else if constexpr (INSCALE)  // single source (C1 == 0); multiplied when the piece is written to LDS (store_piece)
                 rscale[q < C::A_PASSES ? q : 0] = *reinterpret_cast<const floatx4*>(p.in_scale + (size_t)a_b[q] * p.C0 + cc + chunk * 4);
         } else {
             rs[q] = *reinterpret_cast<const floatx4*>(wrow[q - C::A_PASSES] + cur_wk);
@@ -306,8 +324,13 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, MIN_WAVES_PER_SIMD) void co
     auto store_piece = [&](int q, int buf) {
         if (q < C::A_PASSES) {
             char* dst = As + (buf * BM + row0 + q * C::A_ROWS) * C::ROW_BYTES;
-            if (ABF) {
-                *reinterpret_cast<floatx4*>(dst + chunk * 16) = rs[q];  // already bf16: 8 k per piece
+            if constexpr (AF16 && INSCALE) {   // fp16 storage under the SCA scale: widen, fp32 product, one rounding (RNE)
+                const floatx8 f = __builtin_convertvector(__builtin_bit_cast(f16x8, rs[q]), floatx8);
+                const floatx4 s0 = rscale[q < C::A_PASSES ? q : 0], s1 = rscale_hi[q < C::A_PASSES ? q : 0];
+                const floatx8 sc = {s0[0], s0[1], s0[2], s0[3], s1[0], s1[1], s1[2], s1[3]};
+                *reinterpret_cast<f16x8*>(dst + chunk * 16) = __builtin_convertvector(f * sc, f16x8);
+            } else if (A16) {
+                *reinterpret_cast<floatx4*>(dst + chunk * 16) = rs[q];  // already bf16 / fp16: 8 k per piece
             } else if (BF16) {
                 floatx4 v = rs[q];
                 if constexpr (INSCALE) v *= rscale[q < C::A_PASSES ? q : 0];
@@ -578,7 +601,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, MIN_WAVES_PER_SIMD) void co
     // per output instead of ~10 (vector instructions are paid in f32-MFMA time on gfx950).
     // (PAIR kernels too, late r03: their LDS-transposed epilogue was 26 % of a 512 -> 1024 NAFNet layer; the descriptors here only concern out / res)
     if constexpr (BUFA || PAIR) {
-        if (p.splits == 1 && !p.ln_g && !p.gate && !p.shuffle && !(p.film && p.film_bstride != 0) && !p.out_bf16 && !p.no_direct_epi) {
+        if (p.splits == 1 && !p.ln_g && !p.gate && !p.shuffle && !(p.film && p.film_bstride != 0) && !p.out_bf16 && !p.out_f16 && !p.no_direct_epi) {
             const int wm_s = __builtin_amdgcn_readfirstlane(wm), wn_s = __builtin_amdgcn_readfirstlane(wn);
             const int rowb = m0 + wm_s * C::TM * 32, colb = n0 + wn_s * C::TN * 32;
             const int rows = M - rowb;
@@ -632,6 +655,10 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, MIN_WAVES_PER_SIMD) void co
     // ---- epilogue: transpose the accumulators through LDS (A/B buffers are dead after the last barrier) ----
     // C/D layout of the 32x32 MFMA: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
     float* Cs = smem;
+    using O16 = typename H16::x1;         // 16-bit output storage: bf16 (p.out_bf16) in the bf16 kernels, IEEE fp16 (p.out_f16) in the fp16 kernels
+    using O16x4 = typename H16::x4;
+    using O16x2 = typename H16::x2;
+    const bool out16 = BF16 && (F16 ? p.out_f16 != 0 : p.out_bf16 != 0);
     constexpr int NV = BN / 4;            // float4 columns of the tile
     constexpr int RSTEP = C::NT / NV;     // rows covered per sweep
     const int c4 = tid % NV;
@@ -705,13 +732,13 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, MIN_WAVES_PER_SIMD) void co
                     const float rstd = 1.0f / sqrtf(sq[u] * (1.0f / (float)BN) + p.ln_eps);
                     float o4[4] = {v[u][0] * rstd * g4.x, v[u][1] * rstd * g4.y, v[u][2] * rstd * g4.z, v[u][3] * rstd * g4.w};
                     const size_t off = (size_t)mrow[u];
-                    if (BF16 && p.out_bf16) {
+                    if (out16) {
                         if (p.res) {
-                            const bf16x4 t4 = *reinterpret_cast<const bf16x4*>(reinterpret_cast<const __bf16*>(p.res) + off * p.res_stride + n);
+                            const O16x4 t4 = *reinterpret_cast<const O16x4*>(reinterpret_cast<const O16*>(p.res) + off * p.res_stride + n);
                             o4[0] += (float)t4[0]; o4[1] += (float)t4[1]; o4[2] += (float)t4[2]; o4[3] += (float)t4[3];
                         }
                         const floatx4 fv = {o4[0], o4[1], o4[2], o4[3]};
-                        *reinterpret_cast<bf16x4*>(reinterpret_cast<__bf16*>(p.out) + off * p.out_stride + n) = __builtin_convertvector(fv, bf16x4);
+                        *reinterpret_cast<O16x4*>(reinterpret_cast<O16*>(p.out) + off * p.out_stride + n) = __builtin_convertvector(fv, O16x4);
                     } else {
                         if (p.res) {
                             const float4 t4 = *reinterpret_cast<const float4*>(p.res + off * p.res_stride + n);
@@ -781,14 +808,19 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, MIN_WAVES_PER_SIMD) void co
                     g0 = g0 * (f[ocol] + 1.0f) + f[ch + ocol];
                     g1 = g1 * (f[ocol + 1] + 1.0f) + f[ch + ocol + 1];
                 }
+                if (out16) {   // (16-bit storage: the two products as one 4-byte store)
+                    const floatx2 gv = {g0, g1};
+                    *reinterpret_cast<O16x2*>(reinterpret_cast<O16*>(p.out) + opix * p.out_stride + ocol) = __builtin_convertvector(gv, O16x2);
+                    continue;
+                }
                 *reinterpret_cast<float2*>(dst) = make_float2(g0, g1);
                 continue;
             }
-            if (BF16 && p.out_bf16) {  // bf16 activation storage: residual and output tensors are bf16
+            if (out16) {  // bf16 / fp16 activation storage: residual and output tensors are 16-bit
                 if (p.res) {
-                    const __bf16* rp = reinterpret_cast<const __bf16*>(p.res) + opix * p.res_stride + ocol;
+                    const O16* rp = reinterpret_cast<const O16*>(p.res) + opix * p.res_stride + ocol;
                     if (n + 3 < p.Cout && (p.res_stride & 3) == 0) {
-                        const bf16x4 t4 = *reinterpret_cast<const bf16x4*>(rp);
+                        const O16x4 t4 = *reinterpret_cast<const O16x4*>(rp);
                         v[0] += (float)t4[0]; v[1] += (float)t4[1]; v[2] += (float)t4[2]; v[3] += (float)t4[3];
                     } else {
 #pragma unroll
@@ -796,14 +828,14 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, MIN_WAVES_PER_SIMD) void co
                             if (n + e < p.Cout) v[e] += (float)rp[e];
                     }
                 }
-                __bf16* dst = reinterpret_cast<__bf16*>(p.out) + opix * p.out_stride + ocol;
+                O16* dst = reinterpret_cast<O16*>(p.out) + opix * p.out_stride + ocol;
                 if (vec_ok) {
                     const floatx4 fv = {v[0], v[1], v[2], v[3]};
-                    *reinterpret_cast<bf16x4*>(dst) = __builtin_convertvector(fv, bf16x4);
+                    *reinterpret_cast<O16x4*>(dst) = __builtin_convertvector(fv, O16x4);
                 } else {
 #pragma unroll
                     for (int e = 0; e < 4; ++e)
-                        if (n + e < p.Cout) dst[e] = (__bf16)v[e];
+                        if (n + e < p.Cout) dst[e] = (O16)v[e];
                 }
                 continue;
             }
@@ -1128,6 +1160,11 @@ __global__ void conv_splitk_reduce(const ConvParams p, const int M) {
         reinterpret_cast<__bf16*>(p.out)[(size_t)m * p.out_stride + n] = (__bf16)v;
         return;
     }
+    if (p.out_f16) {
+        if (p.res) v += (float)reinterpret_cast<const _Float16*>(p.res)[(size_t)m * p.res_stride + n];
+        reinterpret_cast<_Float16*>(p.out)[(size_t)m * p.out_stride + n] = (_Float16)v;
+        return;
+    }
     if (p.res) v += p.res[(size_t)m * p.res_stride + n];
     p.out[(size_t)m * p.out_stride + n] = v;
 }
@@ -1193,13 +1230,14 @@ void init_cfg_pair() {
         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
 }
 
-template <int BM, int BN, int WAVES_M, int WAVES_N, int MINW, bool BF16, bool INSCALE = false, bool ABF = false, bool F16 = false>
+template <int BM, int BN, int WAVES_M, int WAVES_N, int MINW, bool BF16, bool INSCALE = false, bool ABF = false, bool F16 = false, bool AF16 = false>
 void launch_cfg(const ConvParams& p, int M, int nk_total, hipStream_t s, int lds_override = 0) {
-    using C = Cfg<BM, BN, WAVES_M, WAVES_N, BF16, ABF>;
+    using C = Cfg<BM, BN, WAVES_M, WAVES_N, BF16, ABF || AF16>;
     if constexpr (BF16 && !ABF && !F16) {
+        if (p.f16 && p.in_f16) return launch_cfg<BM, BN, WAVES_M, WAVES_N, MINW, true, INSCALE, false, true, true>(p, M, nk_total, s, lds_override);
         if (p.f16) return launch_cfg<BM, BN, WAVES_M, WAVES_N, MINW, true, INSCALE, false, true>(p, M, nk_total, s, lds_override);
     }
-    auto kern = conv_igemm_kernel<BM, BN, WAVES_M, WAVES_N, MINW, BF16, INSCALE, ABF, F16>;
+    auto kern = conv_igemm_kernel<BM, BN, WAVES_M, WAVES_N, MINW, BF16, INSCALE, ABF, F16, false, false, AF16>;
     if constexpr (!BF16) {  // f32: the buffer-descriptor staging when every operand tensor is below 2 GiB
         const long long npix = (long long)p.B * p.Hin * p.Win;
         const long long e0 = ((npix - 1) * p.pix0 + p.C0) * 4, e1 = p.C1 ? ((npix - 1) * p.pix1 + p.C1) * 4 : 0;
@@ -1223,10 +1261,14 @@ void init_cfg() {
     IRSDE_HIP_CHECK(hipFuncSetAttribute(
         reinterpret_cast<const void*>(conv_igemm_kernel<BM, BN, WAVES_M, WAVES_N, MINW, BF16, INSCALE, ABF>),
         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    if constexpr (BF16 && !ABF)  // the fp16 twin of every bf16-operand kernel
+    if constexpr (BF16 && !ABF) {  // the fp16 twin of every bf16-operand kernel, and its fp16-storage twin
         IRSDE_HIP_CHECK(hipFuncSetAttribute(
             reinterpret_cast<const void*>(conv_igemm_kernel<BM, BN, WAVES_M, WAVES_N, MINW, true, INSCALE, false, true>),
             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        IRSDE_HIP_CHECK(hipFuncSetAttribute(
+            reinterpret_cast<const void*>(conv_igemm_kernel<BM, BN, WAVES_M, WAVES_N, MINW, true, INSCALE, false, true, false, false, true>),
+            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    }
     if constexpr (!BF16)  // the buffer-descriptor twin of every f32 kernel
         IRSDE_HIP_CHECK(hipFuncSetAttribute(
             reinterpret_cast<const void*>(conv_igemm_kernel<BM, BN, WAVES_M, WAVES_N, MINW, false, INSCALE, false, false, true>),
@@ -1392,7 +1434,7 @@ void launch_conv(const ConvParams& p, hipStream_t s) {
         throw HipError("launch_conv: fused LayerNorm needs Cout == 64 or 128 in one tile, no split-K");
     if (!p.zeros) throw HipError("launch_conv: ConvParams::zeros (zero page for out-of-image taps) is not set");
     if (p.w_pair) {   // split-operand arithmetic (IRSDE_FLAG_SPLIT_BF16X2 / _F16X2): the PAIR kernels on fp32 storage
-        if (p.w_bf || p.in_bf16 || p.out_bf16 || p.nz != 1) throw HipError("launch_conv: split-operand pairs go with fp32 storage, one component");
+        if (p.w_bf || p.in_bf16 || p.out_bf16 || p.in_f16 || p.out_f16 || p.nz != 1) throw HipError("launch_conv: split-operand pairs go with fp32 storage, one component");
         if (p.in_scale && p.C1) throw HipError("launch_conv: in_scale needs a single source");
         if (p.ln_g) throw HipError("launch_conv: the fused LayerNorm epilogue (BN == Cout) is not available on the PAIR tiles");
         const int nk = p.KH * p.KW * (Ctot / 32);
@@ -1481,7 +1523,9 @@ void launch_conv(const ConvParams& p, hipStream_t s) {
     const int nk_total = p.KH * p.KW * (Ctot / 32);
     if ((p.in_bf16 || p.out_bf16) && !p.w_bf) throw HipError("launch_conv: bf16 activation storage needs the bf16-MFMA mode");
     if (p.f16 && (!p.w_bf || p.in_bf16 || p.out_bf16)) throw HipError("launch_conv: fp16 operands go with fp32 activation storage");
-    if (p.in_bf16 && (p.in_scale || p.gate || p.shuffle)) throw HipError("launch_conv: NAFNet fusions are fp32-storage only");
+    if ((p.in_f16 || p.out_f16) && (!p.w_bf || !p.f16 || p.in_bf16 || p.out_bf16 || p.ln_g || p.nz != 1))
+        throw HipError("launch_conv: fp16 activation storage needs the fp16-MFMA mode (one component, no fused LayerNorm)");
+    if (p.in_bf16 && (p.in_scale || p.gate || p.shuffle)) throw HipError("launch_conv: NAFNet fusions are fp32- or fp16-storage only");
     if (p.in_scale) {  // NAFNet SCA fused into the staging (128-row tiles only)
         if (p.C1) throw HipError("launch_conv: in_scale needs a single source");
         if (p.w_bf) {

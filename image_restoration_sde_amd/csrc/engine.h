@@ -231,9 +231,10 @@ inline float pow2_scale_into_512(const float* host, size_t n) {
 }
 
 struct Tensor {
-    float* p = nullptr;  // bf16 == true: really a bf16 tensor (IRSDE_FLAG_BF16_ACT)
+    float* p = nullptr;  // bf16 == true: really a bf16 tensor (IRSDE_FLAG_BF16_ACT); f16 == true: an IEEE fp16 tensor (IRSDE_FLAG_F16_ACT)
     int B = 0, H = 0, W = 0, C = 0;
-    bool bf16 = false;
+    bool bf16 = false, f16 = false;   // storage kind: at most one is set
+    bool half() const { return bf16 || f16; }
     size_t numel() const { return (size_t)B * H * W * C; }
 };
 

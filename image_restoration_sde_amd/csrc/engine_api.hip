@@ -132,6 +132,7 @@ int irsde_create(const irsde_config* cfg, irsde_engine** out) {
                 throw HipError("IRSDE_FLAG_UNET_STEREO runs in fp32 only (the 16-bit and split-operand modes are not covered for the full-resolution SCAM network)");
             if (cfg->flags & IRSDE_FLAG_UNCOND_FULLATTN) throw HipError("IRSDE_FLAG_UNET_STEREO cannot be combined with IRSDE_FLAG_UNCOND_FULLATTN");
         }
+        if (cfg->flags & IRSDE_FLAG_F16_ACT) throw HipError("IRSDE_FLAG_F16_ACT: the image-space ConditionalNAFNet only (irsde_create_nafnet)");
         if (cfg->flags & IRSDE_FLAG_NAF_STEREO) throw HipError("IRSDE_FLAG_NAF_STEREO: the stereo network is a ConditionalNAFNet (irsde_create_nafnet)");
         if (cfg->flags & IRSDE_FLAG_NAF_UNCOND) throw HipError("IRSDE_FLAG_NAF_UNCOND: irsde_create_nafnet only (the unconditional UNet is IRSDE_FLAG_UNCOND_FULLATTN)");
         auto* e = new irsde_engine();
@@ -161,6 +162,17 @@ int irsde_create_nafnet(const irsde_nafnet_config* cfg, irsde_engine** out) {
         if (cfg->img_channel < 1 || cfg->img_channel > 8) throw HipError("img_channel must be in 1..8");
         if (cfg->n_enc < 1 || cfg->n_enc > 6 || cfg->n_dec != cfg->n_enc) throw HipError("need 1..6 encoder stages and as many decoder stages");
         if ((cfg->width << cfg->n_enc) > 2048) throw HipError("width * 2^stages must be <= 2048");
+        if (cfg->flags & IRSDE_FLAG_F16_ACT) {   // fp16 activation storage: the image-space networks on the fp16 MFMA kernels
+            const int f = cfg->flags;
+            if (f & (IRSDE_FLAG_NAF_INTRO_SKIP | IRSDE_FLAG_NAF_LENS | IRSDE_FLAG_NAF_STEREO))
+                throw HipError("IRSDE_FLAG_F16_ACT cannot be combined with IRSDE_FLAG_NAF_INTRO_SKIP / IRSDE_FLAG_NAF_LENS / IRSDE_FLAG_NAF_STEREO (the image-space "
+                               "ConditionalNAFNet only: the latent networks' hot level is the per-image chain kernel)");
+            if ((f & IRSDE_FLAG_BF16) && !(f & IRSDE_FLAG_FP16)) throw HipError("IRSDE_FLAG_F16_ACT implies IRSDE_FLAG_FP16: it cannot be combined with IRSDE_FLAG_BF16 alone");
+            if (f & IRSDE_FLAG_BF16_ACT) throw HipError("IRSDE_FLAG_F16_ACT cannot be combined with IRSDE_FLAG_BF16_ACT (one storage type per engine)");
+            if (f & (IRSDE_FLAG_SPLIT_BF16X2 | IRSDE_FLAG_SPLIT_F16X2))
+                throw HipError("IRSDE_FLAG_F16_ACT cannot be combined with IRSDE_FLAG_SPLIT_BF16X2 / IRSDE_FLAG_SPLIT_F16X2 (split operands go with fp32 storage)");
+            if (f & IRSDE_FLAG_NAIVE_CONV) throw HipError("IRSDE_FLAG_F16_ACT: only the MFMA kernels store fp16 activations (not IRSDE_FLAG_NAIVE_CONV)");
+        }
         if (cfg->flags & IRSDE_FLAG_BF16_ACT) throw HipError("IRSDE_FLAG_BF16_ACT: conditional UNet only");
         if (cfg->flags & IRSDE_FLAG_UNET_STEREO) throw HipError("IRSDE_FLAG_UNET_STEREO: the stereo UNet is a ConditionalUNet (irsde_create)");
         const bool stereo = (cfg->flags & IRSDE_FLAG_NAF_STEREO) != 0;
@@ -181,6 +193,7 @@ int irsde_create_nafnet(const irsde_nafnet_config* cfg, irsde_engine** out) {
         e->cfg.depth = cfg->n_enc;  // pad multiple 2^stages (padder_size, DenoisingNAFNet_arch.py:147)
         e->cfg.device = cfg->device;
         e->cfg.flags = cfg->flags;
+        if (e->cfg.flags & IRSDE_FLAG_F16_ACT) e->cfg.flags |= IRSDE_FLAG_FP16;
         apply_fp16_flag(e);
         e->time_dim = cfg->width * 4;
         for (int i = 0; i < cfg->n_enc; ++i) {
@@ -517,7 +530,7 @@ int irsde_debug_tap(irsde_engine* e, const char* name, float* dst, int64_t dims[
         IRSDE_HIP_CHECK(hipDeviceSynchronize());
         float* tmp = nullptr;
         IRSDE_HIP_CHECK(hipMalloc(&tmp, t.numel() * 4));
-        launch_nhwc_to_nchw(t.p, tmp, t.B, t.C, t.H, t.W, e->stream, t.bf16);
+        launch_nhwc_to_nchw(t.p, tmp, t.B, t.C, t.H, t.W, e->stream, t.bf16, t.f16);
         IRSDE_HIP_CHECK(hipStreamSynchronize(e->stream));
         IRSDE_HIP_CHECK(hipMemcpy(dst, tmp, t.numel() * 4, hipMemcpyDeviceToHost));
         (void)hipFree(tmp);
@@ -577,6 +590,7 @@ int irsde_create_latent_unet(const irsde_latent_unet_config* cfg, irsde_engine**
         if (cfg->ch < 1 || cfg->n_mult < 1 || cfg->n_mult > 6) throw HipError("ch / ch_mult out of range");
         if (cfg->embed_dim < 1 || cfg->embed_dim > 32) throw HipError("embed_dim must be in 1..32");
         if (cfg->flags & IRSDE_FLAG_BF16_ACT) throw HipError("IRSDE_FLAG_BF16_ACT: conditional UNet only");
+        if (cfg->flags & IRSDE_FLAG_F16_ACT) throw HipError("IRSDE_FLAG_F16_ACT: the image-space ConditionalNAFNet only (irsde_create_nafnet)");
         auto* e = new irsde_engine();
         e->arch = 2;
         e->cfg.in_nc = cfg->in_ch; e->cfg.out_nc = cfg->out_ch; e->cfg.nf = cfg->ch; e->cfg.depth = cfg->n_mult;
@@ -732,6 +746,7 @@ int irsde_set_lens_info(irsde_engine* e, const float* info, int B) {
 int irsde_nafnet_set_local_pool(irsde_engine* e, int base_h, int base_w, int train_h, int train_w) {
     return guard([&] {
         if (!e) throw HipError("null argument");
+        if (e->cfg.flags & IRSDE_FLAG_F16_ACT) throw HipError("set_local_pool: not with IRSDE_FLAG_F16_ACT (fp16 activation storage covers the image-space ConditionalNAFNet only)");
         if (e->arch != 1 || !(e->cfg.flags & IRSDE_FLAG_NAF_INTRO_SKIP))
             throw HipError("set_local_pool: CNAFNetLocal is the latent-task ConditionalNAFNet (irsde_create_nafnet with IRSDE_FLAG_NAF_INTRO_SKIP)");
         const int f = e->cfg.flags;

@@ -22,11 +22,13 @@ struct Builder {
     const float* fused_ln_g = nullptr;  // set around a conv() call: LayerNorm gain applied in that conv's epilogue
 
     bool act_bf16() const { return (e->cfg.flags & IRSDE_FLAG_BF16_ACT) != 0; }
+    bool act_f16() const { return (e->cfg.flags & IRSDE_FLAG_F16_ACT) != 0; }
     Tensor talloc(int B, int H, int W, int C, int force_f32 = 0) {
         Tensor t;
         t.B = B; t.H = H; t.W = W; t.C = C;
         t.bf16 = act_bf16() && !force_f32;
-        t.p = pl->alloc(t.bf16 ? (t.numel() + 1) / 2 : t.numel(), reuse);
+        t.f16 = act_f16() && !force_f32;
+        t.p = pl->alloc(t.half() ? (t.numel() + 1) / 2 : t.numel(), reuse);
         return t;
     }
     void tfree(const Tensor& t) {
@@ -73,14 +75,14 @@ struct Builder {
         Op op;
         op.kind = OP_CONV;
         op.flops = conv_flops(p);
-        const double in_bytes = (p.in_bf16 ? 2.0 : 4.0) * (double)p.B * (p.Hin) * (p.Win) * (double)(p.C0 + p.C1);
-        op.bytes = in_bytes + (p.out_bf16 ? 2.0 : 4.0) * (double)M * p.Cout +
+        const double in_bytes = (p.in_bf16 || p.in_f16 ? 2.0 : 4.0) * (double)p.B * (p.Hin) * (p.Win) * (double)(p.C0 + p.C1);
+        op.bytes = in_bytes + (p.out_bf16 || p.out_f16 ? 2.0 : 4.0) * (double)M * p.Cout +
                    (p.w_bf ? 2.0 : 4.0) * (double)p.Cout * p.KH * p.KW * (p.C0 + p.C1);
         op.exec_flops = op.flops;
         {
             char buf[256];
             snprintf(buf, sizeof buf, "conv%s M=%d Cout=%d Cin=%d k=%dx%d s=%d up=%d splits=%d blocks=%d flops=%.4g",
-                     p.w_pair ? (p.f16 ? "(split f16x2)" : "(split bf16x2)") : p.w_bf ? (p.f16 ? "(fp16)" : "(bf16)") : "", M, p.Cout, p.C0 + p.C1, p.KH, p.KW, p.stride, p.in_shift, splits, blocks, op.flops);
+                     p.w_pair ? (p.f16 ? "(split f16x2)" : "(split bf16x2)") : p.w_bf ? (p.f16 ? (p.in_f16 || p.out_f16 ? "(fp16 operands + storage)" : "(fp16)") : "(bf16)") : "", M, p.Cout, p.C0 + p.C1, p.KH, p.KW, p.stride, p.in_shift, splits, blocks, op.flops);
             op.desc = buf;
             // r06: which 3x3 kernel a 16-bit layer runs on (launch_conv's own choice, conv_igemm.hip) — the plan tests pin the benchmarked plan's kernel mix with it
             if (!naive && p.w_bf && conv_halo_eligible(p)) op.desc += conv_halo2_wanted(p, 0) ? " kernel=halo512" : " kernel=halo256";
@@ -288,8 +290,10 @@ struct Builder {
         else if (o.gate)
             out = talloc(p.B, p.Ho, p.Wo, w.Cout / 2);
         else
-            out = talloc(p.B, p.Ho, p.Wo, o.out_stride ? o.out_stride : w.Cout);
+            out = talloc(p.B, p.Ho, p.Wo, o.out_stride ? o.out_stride : w.Cout, o.out_stride != 0);   // an explicit stride = the fp32 eps_hat tensor
         p.out = out.p; p.out_stride = out.C;
+        p.in_f16 = in.f16; p.out_f16 = out.f16;
+        if (in.bf16 || out.bf16 || (o.res && o.res->f16 != out.f16)) throw HipError("conv_naf: mixed activation storage types");
         p.bias = w.bias;
         p.ch_scale = o.ch_scale; p.in_scale = o.in_scale; p.gate = o.gate; p.shuffle = o.shuffle;
         p.gate_film = o.gate_film; p.gate_film_bstride = o.gate_film ? e->cam_row : 0;
@@ -305,15 +309,18 @@ struct Builder {
         const int64_t M = (int64_t)x.B * x.H * x.W, ppi = (int64_t)x.H * x.W;
         const int c = x.C, Cout = cw.Cout;
         Tensor out = talloc(x.B, x.H, x.W, out_c);
+        if (x.f16 != out.f16 || x.bf16) throw HipError("fused_1x1: mixed activation storage types");
+        const double esz = x.f16 ? 2.0 : 4.0;   // bytes per activation element (IRSDE_FLAG_F16_ACT: fp16 tensors)
+        out_bytes *= esz / 4.0;
         const unsigned short* w16 = e->bf16_copy(cw.w, (size_t)Cout * c);   // (IRSDE_FLAG_FP16: the copy holds IEEE fp16)
         float* op = out.p;
         Op o;
         o.kind = OP_CONV;
         o.flops = 2.0 * (double)M * c * Cout;
         o.exec_flops = o.flops;
-        o.bytes = 4.0 * (double)M * c + out_bytes * (double)M * out_c + 2.0 * (double)Cout * c;
+        o.bytes = esz * (double)M * c + out_bytes * (double)M * out_c + 2.0 * (double)Cout * c;
         char buf[200];
-        snprintf(buf, sizeof buf, "conv(fp16, %s) M=%lld Cout=%d Cin=%d k=1x1 blocks=%lld flops=%.4g", what, (long long)M, Cout, c,
+        snprintf(buf, sizeof buf, x.f16 ? "conv(fp16 operands + storage, %s) M=%lld Cout=%d Cin=%d k=1x1 blocks=%lld flops=%.4g" : "conv(fp16, %s) M=%lld Cout=%d Cin=%d k=1x1 blocks=%lld flops=%.4g", what, (long long)M, Cout, c,
                  (long long)((M + 63) / 64) * (Cout / 64), o.flops);
         o.desc = buf;
         o.fn = [=](hipStream_t s) { launch(w16, op, M, ppi, s); };
@@ -329,9 +336,10 @@ struct Builder {
     Tensor lnconv(const ConvW& cw, const Tensor& x, const float* g, const float* fscale, const float* fshift, int gate, const float* gate_film) {
         const int c = x.C, Cout = cw.Cout, fb = film_bstride, gfb = gate_film ? e->cam_row : 0;
         const float *xp = x.p, *bias = cw.bias;
+        const bool h16 = x.f16;
         return fused_1x1(cw, x, gate ? Cout / 2 : Cout, 4.0, gate ? "LayerNorm + FiLM fused, gate" : "LayerNorm + FiLM fused",
                          [=](const unsigned short* w16, float* op, int64_t M, int64_t ppi, hipStream_t s) {
-                             launch_naf_lnconv(xp, g, fscale, fshift, fb, ppi, w16, bias, op, M, c, Cout, gate, gate_film, gfb, s);
+                             launch_naf_lnconv(xp, g, fscale, fshift, fb, ppi, w16, bias, op, M, c, Cout, gate, gate_film, gfb, s, h16);
                          });
     }
 
@@ -339,9 +347,11 @@ struct Builder {
     Tensor pwconv(const ConvW& cw, const Tensor& in, const float* in_scale, const float* ch_scale, const Tensor& res) {
         const int c = in.C, Cout = cw.Cout;
         const float *xp = in.p, *bias = cw.bias, *rp = res.p;
+        const bool h16 = in.f16;
+        if (res.f16 != in.f16) throw HipError("pwconv: mixed activation storage types");
         return fused_1x1(cw, in, Cout, 8.0, in_scale ? "one-piece K, SCA scale" : "one-piece K",   // (8 bytes per output element: the residual read + the store)
                          [=](const unsigned short* w16, float* op, int64_t M, int64_t ppi, hipStream_t s) {
-                             launch_naf_pwconv(xp, in_scale, ppi, w16, bias, ch_scale, rp, op, M, c, Cout, s);
+                             launch_naf_pwconv(xp, in_scale, ppi, w16, bias, ch_scale, rp, op, M, c, Cout, s, h16);
                          });
     }
 
@@ -355,7 +365,9 @@ struct Builder {
             const float* xp = x.p;
             float* o = t.p;
             const int c = x.C, fb = film_bstride;
-            push_other(OP_LN, [=](hipStream_t s) { launch_layernorm_film(xp, g, fscale, fshift, fb, ppi, o, M, c, 1e-5f, s); });
+            const bool h16 = x.f16;
+            if (t.f16 != x.f16) throw HipError("norm_conv: mixed activation storage types");
+            push_other(OP_LN, [=](hipStream_t s) { launch_layernorm_film(xp, g, fscale, fshift, fb, ppi, o, M, c, 1e-5f, s, h16); });
         }
         ConvOpts o;
         o.gate = gate; o.gate_film = gate_film;
@@ -390,6 +402,7 @@ struct Builder {
         Tensor gt = talloc(x.B, x.H, x.W, c);
         int k1 = 0, k2 = 0;
         if (tlsc_local(x, level, &k1, &k2)) {
+            if (x.f16) throw HipError("internal: local pooling with fp16 activation storage");
             // x * sca.1(windowed mean): window means on the compact (h - k1 + 1) x (w - k2 + 1) map (csrc/tlsc_pool.hip), sca.1 on that map through the 1x1 GEMM
             // (the mode's operand rule), then the replicate pad as a clamped gather times the gated tensor, in place; conv3 takes the scaled tensor as is
             const int B = x.B, H = x.H, W = x.W, nh = H - k1 + 1, nw = W - k2 + 1;
@@ -437,8 +450,10 @@ struct Builder {
             const float *up = u.p, *dw = w.dw_w, *db = w.dw_b, *sw = w.sca_w, *sb = w.sca_b;
             float* gp = gt.p;
             const int B = x.B, H = x.H, W = x.W;
+            const bool h16 = u.f16;
+            if (gt.f16 != u.f16) throw HipError("nafblock: mixed activation storage types");
             push_other(OP_OTHER, [=](hipStream_t s) {
-                launch_dwconv_gate(up, dw, db, gp, partial, B, H, W, c, s);
+                launch_dwconv_gate(up, dw, db, gp, partial, B, H, W, c, s, h16);
                 launch_sca(partial, nt, sw, sb, mean, sca, B, c, H * W, s);
             });
         }
@@ -466,7 +481,7 @@ struct Builder {
     // a run of NAFBlocks as one launch (naf_chain.hip): one work-group per image walks the whole run
     bool naf_chain_ok(const NafChainW& cw, const Tensor& x) const {
         // (stereo: the SCAM after every block couples the two views of a pair — no per-image chain)
-        return cw.nblocks > 0 && !naive && !x.bf16 && !naf_stereo(e) && naf_chain_shape_ok(x.H, x.W, x.C);
+        return cw.nblocks > 0 && !naive && !x.half() && !naf_stereo(e) && naf_chain_shape_ok(x.H, x.W, x.C);
     }
     // r06: G work-groups per image where they all fit the compute units at the same time (a spinning group holds its CU): the batch's groups next to
     // those of the call's other concurrent sub-batches
@@ -831,7 +846,7 @@ void build_naf_plan(irsde_engine* e, Plan* pl, Builder& b, int P) {
         p.B = B; p.Ho = pl->Hp; p.Wo = pl->Wp;
         p.bias = e->naf_intro.bias;
         x = b.talloc(B, pl->Hp, pl->Wp, p.Cout);
-        p.out = x.p; p.out_stride = p.Cout;
+        p.out = x.p; p.out_stride = p.Cout; p.out_f16 = x.f16;   // (the prepped input x0 stays fp32)
         b.push_conv(p);
         const double real = 2.0 * (double)B * pl->Hp * pl->Wp * p.Cout * 9.0 * ((uncond_engine(e) ? 1.0 : 2.0) * e->naf_ic);
         pl->conv_flops += real - pl->net_ops.back().flops;
@@ -928,7 +943,7 @@ int naf_subbatches(const irsde_engine* e, int B, int H, int W) {
         bool chain = false;
         const int nlev = (int)e->naf_enc.size(), ps = 1 << nlev;
         const int Hp = (H + ps - 1) / ps * ps, Wp = (W + ps - 1) / ps * ps;
-        if ((e->cfg.flags & IRSDE_FLAG_FP16) && !(e->cfg.flags & IRSDE_FLAG_NO_NAF_CHAIN))
+        if ((e->cfg.flags & IRSDE_FLAG_FP16) && !(e->cfg.flags & (IRSDE_FLAG_NO_NAF_CHAIN | IRSDE_FLAG_F16_ACT)))   // (fp16 activation storage: no chain in the plan)
             for (int i = 0; i < nlev; ++i)
                 if (e->naf_chain_enc[i].nblocks > 0 && naf_chain_shape_ok(Hp >> i, Wp >> i, e->naf_intro.Cout << i)) {
                     int K0 = 0, K1 = 0;   // (CNAFNetLocal: a level whose blocks pool over a local window runs no chain)

@@ -13,6 +13,7 @@ namespace irsde {
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 typedef float floatx4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16_t;
+typedef _Float16 f16_t;
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
@@ -36,13 +37,23 @@ struct Mf16<true> {
     static __device__ __forceinline__ floatx16 mfma(x8 a, x8 b, floatx16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
 };
 
-// Activation storage type T (fp32, or bf16 under IRSDE_FLAG_BF16_ACT): arithmetic is fp32 either way.
+// Activation storage type T (fp32, bf16 under IRSDE_FLAG_BF16_ACT, IEEE fp16 under IRSDE_FLAG_F16_ACT): arithmetic is fp32 either way.
 __device__ __forceinline__ float ld1(const float* p) { return *p; }
 __device__ __forceinline__ float ld1(const bf16_t* p) { return (float)*p; }
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ float4 ld4(const bf16_t* p) {
     const bf16x4 v = *reinterpret_cast<const bf16x4*>(p);
     return make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);
+}
+__device__ __forceinline__ float ld1(const f16_t* p) { return (float)*p; }
+__device__ __forceinline__ float4 ld4(const f16_t* p) {
+    const f16x4 v = *reinterpret_cast<const f16x4*>(p);
+    return make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);
+}
+__device__ __forceinline__ void st1(f16_t* p, float v) { *p = (f16_t)v; }  // RNE
+__device__ __forceinline__ void st4(f16_t* p, float4 v) {
+    const floatx4 f = {v.x, v.y, v.z, v.w};
+    *reinterpret_cast<f16x4*>(p) = __builtin_convertvector(f, f16x4);  // RNE
 }
 __device__ __forceinline__ void st1(float* p, float v) { *p = v; }
 __device__ __forceinline__ void st1(bf16_t* p, float v) { *p = (bf16_t)v; }
@@ -1578,12 +1589,19 @@ static inline DwGeom dw_geom(int H, int W, int c) {
     return g;
 }
 
-__global__ __launch_bounds__(256) void dwconv_gate_kernel(const float* __restrict__ u, const float* __restrict__ w,
-                                                          const float* __restrict__ bias, float* __restrict__ out,
+__device__ __forceinline__ float4 dw_widen(const float4 v) { return v; }
+__device__ __forceinline__ float4 dw_widen(const f16x4 v) { return make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]); }
+
+// T = the storage type of u and out (fp32, or IEEE fp16 under IRSDE_FLAG_F16_ACT: the window loads widen, the gated product is rounded once on the store);
+// the weights, the window, the accumulation and the per-tile sums — taken from the fp32 products, before the store rounding — are fp32 either way
+template <typename T>
+__global__ __launch_bounds__(256) void dwconv_gate_kernel(const T* __restrict__ u, const float* __restrict__ w,
+                                                          const float* __restrict__ bias, T* __restrict__ out,
                                                           float* __restrict__ partial, const int H, const int W,
                                                           const int c, const int tiles_x, const int ntiles, const int run) {
     __shared__ float4 red[256];
     constexpr int R = kDwRows;
+    using Win = std::conditional_t<std::is_same<T, float>::value, float4, f16x4>;   // a window entry: 4 channels as stored
     const int tile = blockIdx.x, b = blockIdx.y;
     const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
     const int HW = H * W;
@@ -1606,13 +1624,15 @@ __global__ __launch_bounds__(256) void dwconv_gate_kernel(const float* __restric
                 w1[k] = *reinterpret_cast<const float4*>(w + k * C2 + ch);
                 w2[k] = *reinterpret_cast<const float4*>(w + k * C2 + c + ch);
             }
-            const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
-            const float* ub = u + (size_t)b * HW * C2 + ch;
-            auto ld = [&](int iy, int ix, int half) -> float4 {
+            const T* ub = u + (size_t)b * HW * C2 + ch;
+            // fp16 storage: the window holds the loaded halves as they are (half the registers of the fp32 window) and a tap widens its operand inside the
+            // multiply-add.  (Widening at the load, inside the bounds branch, made every load wait for the one before: 1.6 x slower than the fp32 kernel.)
+            const Win zero = {};
+            auto ld = [&](int iy, int ix, int half) -> Win {
                 if ((unsigned)iy >= (unsigned)H || (unsigned)ix >= (unsigned)W) return zero;
-                return *reinterpret_cast<const float4*>(ub + ((size_t)iy * W + ix) * C2 + half * c);
+                return *reinterpret_cast<const Win*>(ub + ((size_t)iy * W + ix) * C2 + half * c);
             };
-            float4 win1[R + 2][3], win2[R + 2][3];  // [row y0 - 1 + r][column slot] of the two gate halves
+            Win win1[R + 2][3], win2[R + 2][3];  // [row y0 - 1 + r][column slot] of the two gate halves
             // one step: the new column x + 1 goes to slot CN (the oldest), the outputs of column x use slots (CL, CM, CN)
             auto step = [&](const int x, auto cl, auto cm, auto cn) {
                 constexpr int CL = decltype(cl)::value, CM = decltype(cm)::value, CN = decltype(cn)::value;
@@ -1631,7 +1651,7 @@ __global__ __launch_bounds__(256) void dwconv_gate_kernel(const float* __restric
                         const int slot[3] = {CL, CM, CN};
 #pragma unroll
                         for (int kx = 0; kx < 3; ++kx) {
-                            const float4 v1 = win1[ro + ky][slot[kx]], v2 = win2[ro + ky][slot[kx]];
+                            const float4 v1 = dw_widen(win1[ro + ky][slot[kx]]), v2 = dw_widen(win2[ro + ky][slot[kx]]);
                             const float4 q1 = w1[ky * 3 + kx], q2 = w2[ky * 3 + kx];
                             a1.x = fmaf(v1.x, q1.x, a1.x); a1.y = fmaf(v1.y, q1.y, a1.y);
                             a1.z = fmaf(v1.z, q1.z, a1.z); a1.w = fmaf(v1.w, q1.w, a1.w);
@@ -1640,7 +1660,7 @@ __global__ __launch_bounds__(256) void dwconv_gate_kernel(const float* __restric
                         }
                     }
                     const float4 o = make_float4(a1.x * a2.x, a1.y * a2.y, a1.z * a2.z, a1.w * a2.w);
-                    *reinterpret_cast<float4*>(out + ((size_t)b * HW + (size_t)y * W + x) * c + ch) = o;
+                    st4(out + ((size_t)b * HW + (size_t)y * W + x) * c + ch, o);
                     sum.x += o.x; sum.y += o.y; sum.z += o.z; sum.w += o.w;
                 }
             };
@@ -1758,8 +1778,13 @@ struct NafLnConvArgs {
 };
 
 // PRO: 0 LayerNorm + FiLM, 1 per-image channel scale, 2 plain
-template <int C, int PRO = 0>
+// T: the storage type of x, res and out (fp32, or IEEE fp16 under IRSDE_FLAG_F16_ACT: behind the float pointers of the argument block); the lane layout, the fp32
+// LayerNorm arithmetic and its summation order are the same for both, the epilogues round once on the store
+template <int C, int PRO = 0, typename T = float>
 __global__ __launch_bounds__(256, 2) void naf_lnconv_kernel(const NafLnConvArgs a) {
+    const T* const xT = reinterpret_cast<const T*>(a.x);
+    const T* const resT = reinterpret_cast<const T*>(a.res);
+    T* const outT = reinterpret_cast<T*>(a.out);
     constexpr int L = C / 4;                 // lanes per pixel (16 / 32 / 64)
     constexpr int RPP = 256 / L;             // pixels per pass of the block
     constexpr int NPASS = 64 / RPP;          // passes (4 / 8 / 16): one float4 per lane and pass
@@ -1784,7 +1809,7 @@ __global__ __launch_bounds__(256, 2) void naf_lnconv_kernel(const NafLnConvArgs 
 #pragma unroll
     for (int ps = 0; ps < NPASS; ++ps) {
         const int m = m0 + ps * RPP + sub;
-        v[ps] = *reinterpret_cast<const float4*>(a.x + (size_t)(m < a.M ? m : a.M - 1) * C + 4 * li);
+        v[ps] = ld4(xT + (size_t)(m < a.M ? m : a.M - 1) * C + 4 * li);
     }
     constexpr int BCH = (64 * C * 2 / 16) / 256;   // 16-byte chunks of the weight tile per thread (2 / 4 / 8)
     floatx4 wv[BCH];
@@ -1856,15 +1881,15 @@ __global__ __launch_bounds__(256, 2) void naf_lnconv_kernel(const NafLnConvArgs 
             const int m = m0 + wm * 32 + 8 * (r >> 2) + 4 * h + (r & 3);
             if (m < a.M) {
                 float t = (acc[r] + bn) * cs;
-                t += a.res[(size_t)m * a.Cout + n];
-                a.out[(size_t)m * a.Cout + n] = t;
+                t += ld1(resT + (size_t)m * a.Cout + n);
+                st1(outT + (size_t)m * a.Cout + n, t);
             }
         }
     } else if (!a.gate) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int m = m0 + wm * 32 + 8 * (r >> 2) + 4 * h + (r & 3);
-            if (m < a.M) a.out[(size_t)m * a.Cout + n] = acc[r] + bn;
+            if (m < a.M) st1(outT + (size_t)m * a.Cout + n, acc[r] + bn);
         }
     } else {   // SimpleGate: the packed weight rows pair columns (2 j, 2 j + 1); product j, then the per-image lens FiLM
         const int ch = a.Cout >> 1, oc = n >> 1;
@@ -1878,7 +1903,7 @@ __global__ __launch_bounds__(256, 2) void naf_lnconv_kernel(const NafLnConvArgs 
                 const float* f = a.gate_film + (size_t)((m < a.M ? m : a.M - 1) / a.ppi) * a.gate_film_bstride;
                 gv = gv * (f[oc] + 1.0f) + f[ch + oc];
             }
-            if (!(lane & 1) && m < a.M) a.out[(size_t)m * ch + oc] = gv;
+            if (!(lane & 1) && m < a.M) st1(outT + (size_t)m * ch + oc, gv);
         }
     }
 }
@@ -1925,8 +1950,12 @@ void launch_layernorm(const float* x, const float* g, const float* res, float* o
 }
 
 void launch_layernorm_film(const float* x, const float* g, const float* scale, const float* shift, int film_bstride,
-                           int64_t pixels_per_image, float* out, int64_t M, int C, float eps, hipStream_t s) {
-    launch_ln_t(x, g, (const float*)nullptr, out, M, C, eps, scale, shift, film_bstride, pixels_per_image, s);
+                           int64_t pixels_per_image, float* out, int64_t M, int C, float eps, hipStream_t s, bool f16) {
+    if (f16)
+        launch_ln_t(reinterpret_cast<const f16_t*>(x), g, (const f16_t*)nullptr, reinterpret_cast<f16_t*>(out), M, C, eps, scale, shift, film_bstride,
+                    pixels_per_image, s);
+    else
+        launch_ln_t(x, g, (const float*)nullptr, out, M, C, eps, scale, shift, film_bstride, pixels_per_image, s);
 }
 
 int dwgate_tiles(int H, int W, int c) {
@@ -1942,12 +1971,15 @@ void naf_lnconv_global_init() {
     IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(naf_lnconv_kernel<256>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(naf_lnconv_kernel<256, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(naf_lnconv_kernel<256, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(naf_lnconv_kernel<256, 0, f16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(naf_lnconv_kernel<256, 1, f16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(naf_lnconv_kernel<256, 2, f16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
 }
 
 // norm + FiLM + 1x1 convolution (fp16 operands: w16 = the layer's fp16 weight copy [Cout][c]) in one launch; gate: SimpleGate epilogue (+ gate_film)
 void launch_naf_lnconv(const float* x, const float* g, const float* fscale, const float* fshift, int film_bstride, int64_t pixels_per_image,
                        const unsigned short* w16, const float* bias, float* out, int64_t M, int c, int Cout, int gate, const float* gate_film,
-                       int gate_film_bstride, hipStream_t s) {
+                       int gate_film_bstride, hipStream_t s, bool f16) {
     if (!naf_lnconv_ok(c, Cout, M)) throw HipError("naf_lnconv: unsupported shape");
     NafLnConvArgs a;
     a.x = x; a.g = g; a.fscale = fscale; a.fshift = fshift; a.film_bstride = film_bstride; a.ppi = pixels_per_image;
@@ -1956,7 +1988,11 @@ void launch_naf_lnconv(const float* x, const float* g, const float* fscale, cons
     a.in_scale = nullptr; a.ch_scale = nullptr; a.res = nullptr;
     const dim3 grid((unsigned)(((M + 63) / 64) * (Cout / 64)));
     const size_t lds = (size_t)128 * (c * 2 + 16);
-    if (c == 64) hipLaunchKernelGGL(naf_lnconv_kernel<64>, grid, dim3(256), lds, s, a);
+    if (f16) {
+        if (c == 64) hipLaunchKernelGGL((naf_lnconv_kernel<64, 0, f16_t>), grid, dim3(256), lds, s, a);
+        else if (c == 128) hipLaunchKernelGGL((naf_lnconv_kernel<128, 0, f16_t>), grid, dim3(256), lds, s, a);
+        else hipLaunchKernelGGL((naf_lnconv_kernel<256, 0, f16_t>), grid, dim3(256), lds, s, a);
+    } else if (c == 64) hipLaunchKernelGGL(naf_lnconv_kernel<64>, grid, dim3(256), lds, s, a);
     else if (c == 128) hipLaunchKernelGGL(naf_lnconv_kernel<128>, grid, dim3(256), lds, s, a);
     else hipLaunchKernelGGL(naf_lnconv_kernel<256>, grid, dim3(256), lds, s, a);
     IRSDE_HIP_CHECK(hipGetLastError());
@@ -1964,7 +2000,7 @@ void launch_naf_lnconv(const float* x, const float* g, const float* fscale, cons
 
 // conv3 / conv5 of a NAFBlock on the same kernel: out = res + (W (x * in_scale) + bias) * ch_scale, in_scale (per image and input channel) optional
 void launch_naf_pwconv(const float* x, const float* in_scale, int64_t pixels_per_image, const unsigned short* w16, const float* bias, const float* ch_scale,
-                       const float* res, float* out, int64_t M, int c, int Cout, hipStream_t s) {
+                       const float* res, float* out, int64_t M, int c, int Cout, hipStream_t s, bool f16) {
     if (!naf_lnconv_ok(c, Cout, M) || !ch_scale || !res) throw HipError("naf_pwconv: unsupported shape");
     NafLnConvArgs a;
     a.x = x; a.g = nullptr; a.fscale = nullptr; a.fshift = nullptr; a.film_bstride = 0; a.ppi = pixels_per_image;
@@ -1973,18 +2009,26 @@ void launch_naf_pwconv(const float* x, const float* in_scale, int64_t pixels_per
     a.in_scale = in_scale; a.ch_scale = ch_scale; a.res = res;
     const dim3 grid((unsigned)(((M + 63) / 64) * (Cout / 64)));
     const size_t lds = (size_t)128 * (c * 2 + 16);
-#define IRSDE_PW(CC) do { if (in_scale) hipLaunchKernelGGL((naf_lnconv_kernel<CC, 1>), grid, dim3(256), lds, s, a); else hipLaunchKernelGGL((naf_lnconv_kernel<CC, 2>), grid, dim3(256), lds, s, a); } while (0)
-    if (c == 64) IRSDE_PW(64); else if (c == 128) IRSDE_PW(128); else IRSDE_PW(256);
+#define IRSDE_PW(CC, TT) do { if (in_scale) hipLaunchKernelGGL((naf_lnconv_kernel<CC, 1, TT>), grid, dim3(256), lds, s, a); else hipLaunchKernelGGL((naf_lnconv_kernel<CC, 2, TT>), grid, dim3(256), lds, s, a); } while (0)
+    if (f16) {
+        if (c == 64) IRSDE_PW(64, f16_t); else if (c == 128) IRSDE_PW(128, f16_t); else IRSDE_PW(256, f16_t);
+    } else {
+        if (c == 64) IRSDE_PW(64, float); else if (c == 128) IRSDE_PW(128, float); else IRSDE_PW(256, float);
+    }
 #undef IRSDE_PW
     IRSDE_HIP_CHECK(hipGetLastError());
 }
 
 void launch_dwconv_gate(const float* u, const float* w, const float* bias, float* out, float* partial, int B, int H, int W,
-                        int c, hipStream_t s) {
+                        int c, hipStream_t s, bool f16) {
     if (c % 4) throw HipError("dwconv_gate: channel count must be a multiple of 4");
     const DwGeom g = dw_geom(H, W, c);
     const int nt = g.tiles_x * g.tiles_y;
-    hipLaunchKernelGGL(dwconv_gate_kernel, dim3(nt, B), dim3(256), 0, s, u, w, bias, out, partial, H, W, c, g.tiles_x, nt, g.run);
+    if (f16)
+        hipLaunchKernelGGL(dwconv_gate_kernel<f16_t>, dim3(nt, B), dim3(256), 0, s, reinterpret_cast<const f16_t*>(u), w, bias, reinterpret_cast<f16_t*>(out), partial,
+                           H, W, c, g.tiles_x, nt, g.run);
+    else
+        hipLaunchKernelGGL(dwconv_gate_kernel<float>, dim3(nt, B), dim3(256), 0, s, u, w, bias, out, partial, H, W, c, g.tiles_x, nt, g.run);
     IRSDE_HIP_CHECK(hipGetLastError());
 }
 
@@ -2242,9 +2286,12 @@ void launch_unpack_pred(const float* pred, float* out, int B, int C, int H, int 
     IRSDE_HIP_CHECK(hipGetLastError());
 }
 
-void launch_nhwc_to_nchw(const float* in, float* out, int B, int C, int H, int W, hipStream_t s, bool bf16) {
+void launch_nhwc_to_nchw(const float* in, float* out, int B, int C, int H, int W, hipStream_t s, bool bf16, bool f16) {
     const size_t total = (size_t)B * C * H * W;
-    if (bf16)
+    if (f16)
+        hipLaunchKernelGGL(nhwc_to_nchw_kernel<f16_t>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s,
+                           reinterpret_cast<const f16_t*>(in), out, B, C, H, W);
+    else if (bf16)
         hipLaunchKernelGGL(nhwc_to_nchw_kernel<bf16_t>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s,
                            reinterpret_cast<const bf16_t*>(in), out, B, C, H, W);
     else

@@ -224,6 +224,7 @@ class UNet(nn.Module):
 class ConditionalNAFNet(_ImageNAFNet):
     """latent-dehazing ConditionalNAFNet: same parameters as the image-space one (668 tensors for nasde.yml), but
     `ending(x + intro(x))` (DenoisingNAFNet_arch.py:162-176) and typically img_channel = the latent's embed_dim (<= 8)."""
+    _fp16_act = False   # fp16 activation storage covers the image-space network only (the engine refuses it here too)
 
     def _create_handle(self, L, device_index, flags):
         return super()._create_handle(L, device_index, flags | _lib.FLAG_NAF_INTRO_SKIP)

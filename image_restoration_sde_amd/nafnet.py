@@ -34,6 +34,7 @@ class _NAFBlock(nn.Module):  # DenoisingNAFNet_arch.py:15-49 (parameter containe
 
 class ConditionalNAFNet(ConditionalUNet):
     """Shares engine management / forward with ConditionalUNet (same C entry points after creation)."""
+    _fp16_act = True   # set_compute_dtype("fp16_act"): the 'fp16' mode with IEEE fp16 storage of every activation tensor (IRSDE_FLAG_F16_ACT)
 
     def __init__(self, img_channel=3, width=16, middle_blk_num=1, enc_blk_nums=[], dec_blk_nums=[], upscale=1):
         nn.Module.__init__(self)

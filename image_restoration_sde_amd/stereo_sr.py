@@ -45,6 +45,8 @@ class _StereoNAFBlock(_NAFBlock):
 
 
 class ConditionalNAFNet(_ImageNAFNet):
+    _fp16_act = False   # fp16 activation storage covers the image-space network only (the engine refuses it here too)
+
     def __init__(self, img_channel=3, width=16, middle_blk_num=1, enc_blk_nums=[], dec_blk_nums=[], upscale=1):
         nn.Module.__init__(self)
         self.upscale = upscale

@@ -145,13 +145,16 @@ class ConditionalUNet(nn.Module):
             self._engine_key = key
         return self._engine
 
+    _fp16_act = False   # does set_compute_dtype take 'fp16_act' (fp16 activation storage: the image-space ConditionalNAFNets)
+
     def set_compute_dtype(self, dtype):
         """'fp32' (default: exact-fp32 MFMA + Winograd), 'bf16' (BASELINE configs[2]: conv operands rounded to bf16,
         fp32 accumulation, everything else fp32), 'bf16_act' (+ bf16 activation storage) or 'fp16' (BASELINE configs[4]:
         the 'bf16' mode with IEEE fp16 operands), or 'fp32_split' (r03: fp32 everywhere, but the deep Winograd component GEMMs
         multiply bf16 hi + lo pairs of their fp32 operands on the bf16 MFMA pipe, IRSDE_FLAG_SPLIT_BF16X2; 'fp32_split_f16': fp16 pairs).  New behaviour — the
-        reference is fp32 only."""
-        self.engine_flags &= ~(_lib.FLAG_BF16 | _lib.FLAG_BF16_ACT | _lib.FLAG_FP16 | _lib.FLAG_SPLIT_BF16X2 | _lib.FLAG_SPLIT_F16X2)
+        reference is fp32 only.  The image-space ConditionalNAFNets (`_fp16_act`) also take 'fp16_act': the 'fp16' mode plus IEEE fp16
+        storage of every activation tensor between kernels."""
+        self.engine_flags &= ~(_lib.FLAG_BF16 | _lib.FLAG_BF16_ACT | _lib.FLAG_FP16 | _lib.FLAG_SPLIT_BF16X2 | _lib.FLAG_SPLIT_F16X2 | _lib.FLAG_F16_ACT)
         if dtype in ("fp32", "f32", torch.float32):
             pass
         elif dtype == "fp32_split":
@@ -164,6 +167,10 @@ class ConditionalUNet(nn.Module):
             self.engine_flags |= _lib.FLAG_BF16 | _lib.FLAG_BF16_ACT
         elif dtype in ("fp16", "f16", torch.float16):
             self.engine_flags |= _lib.FLAG_FP16
+        elif dtype == "fp16_act" and self._fp16_act:  # + fp16 storage of the activation tensors (both bits: the fp16 bit is what marks the operand mode)
+            self.engine_flags |= _lib.FLAG_FP16 | _lib.FLAG_F16_ACT
+        elif self._fp16_act:
+            raise _lib.IrsdeError("compute dtype must be 'fp32', 'fp32_split', 'fp32_split_f16', 'bf16', 'bf16_act', 'fp16' or 'fp16_act'")
         else:
             raise _lib.IrsdeError("compute dtype must be 'fp32', 'fp32_split', 'fp32_split_f16', 'bf16', 'bf16_act' or 'fp16'")
         return self

@@ -40,6 +40,8 @@
  *        irsde_debug_scam_full.
  *        Additive, same version: IRSDE_FLAG_BF16_ACT is accepted together with IRSDE_FLAG_UNCOND_FULLATTN (the denoising-sde ConditionalUNet with bf16
  *        activation storage; its full softmax attention runs on the bf16 MFMA, csrc/full_attn16.hip); debug header: irsde_debug_full_attention16.
+ *        Additive, same version: IRSDE_FLAG_F16_ACT (irsde_create_nafnet only: IEEE fp16 storage of every activation tensor of the image-space
+ *        ConditionalNAFNet, on fp16-storage variants of its implicit-GEMM, LayerNorm, depthwise-gate and norm + 1x1 kernels).
  */
 #ifndef IRSDE_HIP_H
 #define IRSDE_HIP_H
@@ -163,6 +165,15 @@ enum {
                                         _BF16_ACT / _FP16 / _SPLIT_BF16X2 / _SPLIT_F16X2 and IRSDE_FLAG_UNCOND_FULLATTN are refused with
                                         IRSDE_ERR_INVALID.  A pair is never split: no concurrent sub-batches (irsde_debug_force_subbatches is
                                         ignored).  An int time is shared by every pair; B times give each pair its own */
+    IRSDE_FLAG_F16_ACT = 524288,     /* irsde_create_nafnet only: IEEE fp16 storage of every activation tensor between kernels (the intro output, per NAFBlock
+                                        conv1's output, the gated depthwise output, y = x + conv3(.) beta, the gated conv4 output and the block output,
+                                        the downs outputs, the ups outputs after pixel-shuffle and skip add), rounded to nearest-even once, on the store.
+                                        Implies IRSDE_FLAG_FP16.  The sampler state, the prepped input, eps_hat, the FiLM rows, the SCA pooled sums / mean /
+                                        scale vector (the sums are taken from the fp32 products before the store rounding; conv3's operand is
+                                        round_f16(stored x scale)), biases, beta, gamma, the LayerNorm gains and all arithmetic stay fp32.  Refused with
+                                        IRSDE_ERR_INVALID together with IRSDE_FLAG_NAF_INTRO_SKIP / _NAF_LENS / _NAF_STEREO, IRSDE_FLAG_BF16 without _FP16,
+                                        IRSDE_FLAG_BF16_ACT, _SPLIT_BF16X2 / _SPLIT_F16X2 and _NAIVE_CONV; by irsde_create and irsde_create_latent_unet; and
+                                        by irsde_nafnet_set_local_pool.  The per-image NAFBlock chain is not part of this mode's plans */
     IRSDE_FLAG_NO_WINOGRAD_F43 = 8   /* Winograd F(2x2,3x3) only (>= 256 channels); default also uses F(4x4,3x3) from 128
                                         channels up where H, W are multiples of 4 */
 };

@@ -7,7 +7,7 @@ time of the FiLM table of the T = 1000 schedule, and the plan-build time per sha
 same shapes: the yardstick (the unconditional network does the same work minus half of the intro's K).  IRSDE_LIB_PATH selects the
 library build, so the yardstick can be another build's in the same session.
 
-Usage:  python tools/dsde_naf_bench.py [--network uncond|cond] [--shapes 1x512x512 8x512x512 1x481x321] [--dtypes fp32 fp16] [--reps 3]
+Usage:  python tools/dsde_naf_bench.py [--network uncond|cond] [--shapes 1x512x512 8x512x512 1x481x321] [--dtypes fp32 fp16 fp16_act] [--reps 3]
 Prints one JSON line per (dtype, shape)."""
 import argparse
 import ctypes

@@ -198,10 +198,10 @@ def main(argv=None):
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16", "bf16_act", "fp16"],
+    ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16", "bf16_act", "fp16", "fp16_act"],
                     help="compute mode (set_compute_dtype): bf16 / fp16 = 16-bit MFMA operands with fp32 storage; bf16_act = bf16 operands + bf16 activation "
                     "storage, for both UNets (deraining --arch unet and --task denoising --arch unet, whose bottleneck attention then runs on the bf16 MFMA); "
-                    "the NAFNets take fp32 / bf16 / fp16")
+                    "the NAFNets take fp32 / bf16 / fp16, and the image-space ones fp16_act (fp16 operands + fp16 activation storage)")
     a = ap.parse_args(argv)
     if a.task is None and a.lq is None:
         ap.error("the following arguments are required: --lq")
