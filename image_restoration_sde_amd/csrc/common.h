@@ -128,6 +128,28 @@ struct WinoParams {
     int res_stride = 0;
 };
 void launch_wino_input(const WinoParams& p, hipStream_t s);
+// Polyphase Winograd F(4x4,2x2) for the resampling convolutions (wino.hip): 25 products per 16 outputs and phase.
+//   down (up = 0): Conv2d 4x4 stride 2 pad 1 = the sum over the four input pixel phases (p, q) of a 2x2 correlation with taps w[2a+p][2b+q]; the phases join
+//                  Cin in the K walk: V [25][T][4 Cin] (K index = (2p+q) Cin + c), U [25][Cout][4 Cin], M [25][T][Cout]; tile = 4x4 output pixels
+//   up   (up = 1): nearest x2 + Conv2d 3x3 pad 1 = four OUTPUT phases (py, px), each a 2x2 correlation over the low-resolution map with phase-summed taps:
+//                  V [4][25][T][Cin], U [4][25][Cout][Cin], M [4][25][T][Cout] (z = (2py+px) 25 + component); tile = 4x4 low-resolution = 8x8 output pixels
+// T = B * TH * TW, TH / TW = ceil(tiled extent / 4); ragged edges are masked.  Epilogue: + bias.
+struct WinoPolyParams {
+    int up = 0;
+    const float* in = nullptr;  // [B][Hin][Win][C]
+    int C = 0, Hin = 0, Win = 0;
+    int B = 0, TH = 0, TW = 0, T = 0;
+    float* V = nullptr;
+    const float* M = nullptr;
+    int Cout = 0, Ho = 0, Wo = 0;
+    float* out = nullptr;       // [B][Ho][Wo][out_stride]
+    int out_stride = 0;
+    const float* bias = nullptr;
+};
+void launch_wino_poly_input(const WinoPolyParams& p, hipStream_t s);
+void launch_wino_poly_output(const WinoPolyParams& p, hipStream_t s);
+// host: U of the layouts above from the packed weights [Cout][KH][KW][Cin] (up = 0: 4x4, 25 * Cout * 4 Cin floats; up = 1: 3x3, 100 * Cout * Cin floats)
+void wino_poly_transform_weights(const float* w_packed, int Cout, int Cin, float* U, int up);
 // fp32-equivalent GEMMs on the bf16 MFMA pipe (gemm_split.hip): C_z[m][n] = sum_k A_z[m][k] B_z[n][k] with both operands given
 // as 2 or 3 bf16 planes (hi / mid / lo pieces of the f32 value), f32 accumulate, z = 0 .. ncomp-1.
 struct SplitGemmArgs {

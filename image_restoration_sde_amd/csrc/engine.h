@@ -45,6 +45,15 @@ inline bool naf_lnconv_enabled() { return tuning_env_int("IRSDE_NAF_LNCONV", 1) 
 // r06: work-groups per image of the NAFBlock chain kernel: 0 = as many (4, 2) as fit the compute units next to the call's other sub-batches, 1 = the one-group kernel, 2 / 4 forced (if they fit)
 inline int naf_chain_split_mode() { return tuning_env_int("IRSDE_NAF_CHAIN_SPLIT", 0); }
 
+// polyphase F(4x4,2x2) for the resampling convolutions of the exact-fp32 plans (wino.hip): 0 never, 1 by the rule of Builder::push_wino_poly, 2 wherever eligible
+// (irsde_debug_force_wino_poly overrides the knob for engines created afterwards)
+int wino_poly_mode();
+void set_force_wino_poly(int mode);   // irsde_debug_force_wino_poly
+// the rule's side that is known at weight-load time: every 4x4 stride-2 layer; nearest-x2 + 3x3 layers from 512 input channels (below that V and M, which the
+// fused F(4x4,3x3) kernel keeps out of HBM, cost what the saved products gain: 256 -> 128 at 16 x 128^2 measured 1.45 against 1.47 ms, profiles/wino_poly.md)
+constexpr int kWinoPolyUpMinCin = 512;
+inline bool wino_poly_wants_weights(int mode, bool up, int Cin) { return mode >= 2 || (mode == 1 && (!up || Cin >= kWinoPolyUpMinCin)); }
+
 inline int wino_min_c(int tile) {
     return tuning_env_int(tile == 4 ? "IRSDE_WINO4_MINC" : "IRSDE_WINO2_MINC", tile == 4 ? 64 : 256);
 }
@@ -83,6 +92,7 @@ struct ConvW {
     float wino_uf64p_scale = 1.f;
     unsigned short* wino_up = nullptr;  // IRSDE_FLAG_SPLIT_BF16X2 / _F16X2: the F(4x4,3x3) weights as hi / lo pairs, [36][Cout][Cin / 32][2][32]
     float wino_up_scale = 1.f;          // fp16 pairs: the power of two U was multiplied by (max |U| * scale <= 512)
+    float* wino_poly = nullptr;  // polyphase F(4x4,2x2) weights (exact fp32 mode): 4x4 stride-2 layers [25][Cout][4 Cin], nearest-x2 + 3x3 layers [100][Cout][Cin]
 };
 struct ResW {
     ConvW b1, b2, res;
@@ -167,6 +177,40 @@ inline WinoPlan make_wino(const ConvParams& d, const float* U, float* V, float* 
     g.KH = g.KW = 1; g.stride = 1; g.pad_y = g.pad_x = 0; g.B = 1; g.Ho = 1; g.Wo = T;
     g.out = Mb; g.out_stride = d.Cout; g.zeros = d.zeros;
     g.nz = ncomp; g.z_in = (long long)T * Ctot; g.z_w = (long long)d.Cout * Ctot; g.z_out = (long long)T * d.Cout;
+    return w;
+}
+// Polyphase F(4x4,2x2) launch triple (wino.hip) of a 4x4 stride-2 pad-1 convolution (down) or a 3x3 pad-1 convolution behind the nearest x2 upsample (up)
+inline bool wino_poly_down_shape(const ConvParams& d) {
+    return d.KH == 4 && d.KW == 4 && d.stride == 2 && d.pad_y == 1 && d.pad_x == 1 && !d.in_shift && d.Hin >= 2 && d.Win >= 2;
+}
+inline bool wino_poly_up_shape(const ConvParams& d) { return d.KH == 3 && d.KW == 3 && d.stride == 1 && d.pad_y == 1 && d.pad_x == 1 && d.in_shift == 1; }
+// single fp32 source, bias-only epilogue
+inline bool wino_poly_eligible(const ConvParams& d) {
+    return (wino_poly_down_shape(d) || wino_poly_up_shape(d)) && !d.in1 && !d.C1 && d.C0 % 32 == 0 && d.pix0 == d.C0 && d.Cout % 4 == 0 && d.out_stride % 4 == 0 &&
+           !d.film && !d.silu && !d.res && !d.ln_g && !d.ch_scale && !d.in_scale && !d.gate && !d.shuffle && !d.in_bf16 && !d.out_bf16 && !d.in_f16 && !d.out_f16;
+}
+struct WinoPolyPlan {
+    WinoPolyParams in, out;
+    ConvParams gemm;
+    int ncomp = 0;      // component GEMMs: 25 (down) / 100 (up)
+    long long T = 0;
+    int K = 0;          // 4 Cin (down) / Cin (up)
+};
+inline WinoPolyPlan make_wino_poly(const ConvParams& d, const float* U, float* V, float* Mb) {
+    WinoPolyPlan w;
+    const int up = d.in_shift ? 1 : 0;
+    WinoPolyParams& q = w.in;
+    q.up = up; q.in = d.in0; q.C = d.C0; q.Hin = d.Hin; q.Win = d.Win; q.B = d.B;
+    q.Ho = d.Ho; q.Wo = d.Wo;
+    q.TH = ((up ? d.Hin : d.Ho) + 3) / 4; q.TW = ((up ? d.Win : d.Wo) + 3) / 4; q.T = d.B * q.TH * q.TW;
+    q.V = V; q.M = Mb; q.Cout = d.Cout; q.out = d.out; q.out_stride = d.out_stride; q.bias = d.bias;
+    w.out = q;
+    w.ncomp = up ? 100 : 25; w.T = q.T; w.K = up ? d.C0 : 4 * d.C0;
+    ConvParams& g = w.gemm;
+    g.in0 = V; g.C0 = w.K; g.pix0 = w.K; g.Hin = 1; g.Win = q.T; g.w = U; g.Cout = d.Cout;
+    g.KH = g.KW = 1; g.stride = 1; g.pad_y = g.pad_x = 0; g.B = 1; g.Ho = 1; g.Wo = q.T;
+    g.out = Mb; g.out_stride = d.Cout; g.zeros = d.zeros;
+    g.nz = w.ncomp; g.z_in = (long long)q.T * w.K; g.z_w = (long long)d.Cout * w.K; g.z_out = (long long)q.T * d.Cout;
     return w;
 }
 // Split-operand variant (gemm_split.hip): V as `nplanes` bf16 planes (Vs: nplanes * 36 * T * Ctot elements), Us the weights'

@@ -77,7 +77,7 @@ struct VariantScope {
 // The selector codes irsde_debug_conv / irsde_bench_conv know (see their branches): any other code is refused, never run as the production dispatch.
 bool code_in(const std::initializer_list<int>& codes, int c) { return std::find(codes.begin(), codes.end(), c) != codes.end(); }
 bool debug_conv_code_known(int c) {
-    return code_in({0, 1, 2, 3, 4, 5, 12, 13, 22, 23, 33, 34, 35, 36, 37, 42, 43, 44, 45, 46, 47, 55, 56, 62, 63, 204, 260, 261, 262, 263}, c) ||
+    return code_in({0, 1, 2, 3, 4, 5, 12, 13, 22, 23, 24, 25, 33, 34, 35, 36, 37, 42, 43, 44, 45, 46, 47, 55, 56, 62, 63, 204, 260, 261, 262, 263}, c) ||
            code_in({100, 103, 105, 106, 107, 150, 160, 161, 162, 163, 165, 166, 167, 170, 171, 172, 173}, c);   // 100 + a launch_conv tuning variant
 }
 bool bench_conv_variant_known(int v) {
@@ -373,7 +373,22 @@ int irsde_debug_conv(const float* in0, int C0, const float* in1, int C1, int B, 
             p.splits = splits;
             p.partial = mem.alloc<float>((size_t)splits * B * p.Ho * p.Wo * Cout);
         }
-        if (naive == 44 || naive == 45) {  // three-launch Winograd F(4x4,3x3) with the engine's pair GEMM: 44 fp16 pairs, 45 bf16 pairs
+        if (naive == 24 || naive == 25) {   // polyphase Winograd F(4x4,2x2): 24 a 4x4 stride-2 pad-1 layer, 25 a 3x3 pad-1 layer behind the nearest x2 upsample
+            if (!(naive == 24 ? wino_poly_down_shape(p) : wino_poly_up_shape(p)) || !wino_poly_eligible(p) || splits > 1)
+                throw HipError(naive == 24 ? "debug_conv: selector 24 runs a 4x4 stride-2 pad-1 convolution (single source, channels a multiple of 32, bias only)"
+                                           : "debug_conv: selector 25 runs a 3x3 stride-1 pad-1 convolution with in_shift = 1 (single source, channels a multiple of 32, bias only)");
+            const int up = naive == 25;
+            std::vector<float> U((size_t)100 * Cout * Cin);   // 25 x Cout x 4 Cin resp. 100 x Cout x Cin
+            wino_poly_transform_weights(pk.data(), Cout, Cin, U.data(), up);
+            float* dU = mem.upload(U);
+            WinoPolyPlan wp = make_wino_poly(p, dU, nullptr, nullptr);
+            float* dV = mem.alloc<float>((size_t)wp.ncomp * wp.T * wp.K);
+            float* dM = mem.alloc<float>((size_t)wp.ncomp * wp.T * Cout);
+            wp = make_wino_poly(p, dU, dV, dM);
+            launch_wino_poly_input(wp.in, s);
+            launch_conv(wp.gemm, s);
+            launch_wino_poly_output(wp.out, s);
+        } else if (naive == 44 || naive == 45) {  // three-launch Winograd F(4x4,3x3) with the engine's pair GEMM: 44 fp16 pairs, 45 bf16 pairs
             const bool f16 = naive == 44;
             if (!wino_shape_ok(p, 4) || Cin % 32) throw HipError("debug_conv: shape not eligible for the pair GEMM");
             std::vector<float> U((size_t)36 * Cout * Cin);
@@ -532,6 +547,11 @@ int irsde_debug_split_gemm(const float* A, const float* Bm, float* C, int M, int
 
 int irsde_debug_force_chain_groups(int g) {
     set_force_chain_groups(g == 1 || g == 2 || g == 4 ? g : 0);
+    return IRSDE_OK;
+}
+
+int irsde_debug_force_wino_poly(int mode) {
+    set_force_wino_poly(mode >= 0 && mode <= 2 ? mode : -1);
     return IRSDE_OK;
 }
 

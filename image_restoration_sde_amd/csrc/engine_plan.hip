@@ -123,6 +123,7 @@ struct Builder {
         p.silu = silu;
         if (res) { p.res = res->p; p.res_stride = res->C; }
         if (!naive) {  // prefer F(4x4,3x3), then F(2x2,3x3), then the direct implicit GEMM
+            if (w.wino_poly && push_wino_poly(p, w.wino_poly)) return out;   // the resampling layers: polyphase F(4x4,2x2)
             if (w.wino_up && wino_shape_ok(p, 4) && push_wino(p, w.wino_u4, 4, w.wino_up, w.wino_up_scale)) return out;
             if (w.wino_uf64p && push_wino_fused(p, reinterpret_cast<const float*>(w.wino_uf64p), true, w.wino_uf64p_scale)) return out;
             if (w.wino_uf64 && push_wino_fused(p, w.wino_uf64, true)) return out;
@@ -199,6 +200,62 @@ struct Builder {
         else
             op.fn = [slices, Uf](hipStream_t s) { for (const auto& q : slices) launch_wino_fused(q, Uf, s); };
         push_op(std::move(op));
+        return true;
+    }
+
+    // Polyphase Winograd F(4x4,2x2) of a resampling layer (wino.hip): a 4x4 stride-2 Downsample as 25 component GEMMs with K = 4 Cin (6.25 products per
+    // output instead of 16), a nearest-x2 + 3x3 Upsample as 4 x 25 component GEMMs over the low-resolution map (1.5625 instead of F(4x4,3x3)'s 2.25).
+    // Rule (IRSDE_WINO_POLY = 1; measured per layer, profiles/wino_poly.md): the component GEMMs fill the block slots at least once and execute >= 2e10 FLOP
+    // (0.13 ms at the f32 MFMA roof) — below that the two extra launches and the V / M round trip through HBM cost what the saved products gain (B = 4 at 256^2:
+    // Downsample 0.137 against 0.139 ms; B = 2: Upsample 512 -> 256 0.189 against 0.183 ms).  An Upsample needs >= 512 input channels (ConvW::wino_poly exists
+    // only then): below, the fused F(4x4,3x3) kernel, which keeps V and M out of HBM, is as fast.
+    bool push_wino_poly(const ConvParams& d, const float* U) {
+        const int mode = wino_poly_mode();
+        if (mode <= 0 || !wino_poly_eligible(d)) return false;
+        ConvParams dd = d;
+        dd.zeros = e->zeros;
+        WinoPolyPlan wp = make_wino_poly(dd, U, nullptr, nullptr);
+        const long long T = wp.T;
+        const long long gemm_blocks = wp.ncomp * ((T + 127) / 128) * ((d.Cout + 127) / 128);
+        const double exec_flops = wp.ncomp * 2.0 * (double)T * wp.K * d.Cout;
+        if (mode == 1 && (gemm_blocks < 2ll * device_cu_count() || exec_flops < 2e10)) return false;
+        if ((unsigned long long)T * std::max(wp.K, d.Cout) * 4ull >= 0x7fffffffull) return false;   // a component's V / M slice stays below 2 GiB (32-bit buffer offsets in the GEMM)
+        float* V = pl->alloc((size_t)wp.ncomp * T * wp.K, true);
+        float* Mb = pl->alloc((size_t)wp.ncomp * T * d.Cout, true);
+        wp = make_wino_poly(dd, U, V, Mb);
+        const char* what = wp.in.up ? "up" : "down";
+        {
+            Op op;
+            op.kind = OP_WINO;
+            op.desc = std::string("wino_poly_input(") + what + ") T=" + std::to_string(T) + " C=" + std::to_string(d.C0);
+            const WinoPolyParams ip = wp.in;
+            op.fn = [ip](hipStream_t s) { launch_wino_poly_input(ip, s); };
+            pl->net_ops.push_back(std::move(op));
+        }
+        {
+            Op op;
+            op.kind = OP_CONV;
+            op.flops = conv_flops(d);
+            op.exec_flops = exec_flops;
+            op.bytes = 4.0 * (double)d.B * d.Hin * d.Win * d.C0 + 4.0 * (double)d.B * d.Ho * d.Wo * d.Cout + 4.0 * (double)d.KH * d.KW * d.Cout * d.C0;
+            char buf[256];
+            snprintf(buf, sizeof buf, "conv(winograd F4x2 poly %s gemm x%d) T=%lld Cout=%d Cin=%d K=%d flops=%.4g exec=%.4g", what, wp.ncomp, T, d.Cout, d.C0, wp.K,
+                     op.flops, op.exec_flops);
+            op.desc = buf;
+            const ConvParams g = wp.gemm;
+            op.fn = [g](hipStream_t s) { launch_conv(g, s); };
+            push_op(std::move(op));
+        }
+        {
+            Op op;
+            op.kind = OP_WINO;
+            op.desc = std::string("wino_poly_output(") + what + ") T=" + std::to_string(T) + " Cout=" + std::to_string(d.Cout);
+            const WinoPolyParams oparm = wp.out;
+            op.fn = [oparm](hipStream_t s) { launch_wino_poly_output(oparm, s); };
+            pl->net_ops.push_back(std::move(op));
+        }
+        pl->release(V);
+        pl->release(Mb);
         return true;
     }
 
@@ -929,6 +986,12 @@ void build_naf_plan(irsde_engine* e, Plan* pl, Builder& b, int P) {
 static std::atomic<int> g_force_chain_groups{0};   // irsde_debug_force_chain_groups: 0 = the rule (Builder::chain_groups)
 void set_force_chain_groups(int g) { g_force_chain_groups.store(g, std::memory_order_relaxed); }
 int forced_chain_groups() { return g_force_chain_groups.load(std::memory_order_relaxed); }
+static std::atomic<int> g_force_wino_poly{-1};   // irsde_debug_force_wino_poly: -1 = the IRSDE_WINO_POLY knob
+void set_force_wino_poly(int mode) { g_force_wino_poly.store(mode, std::memory_order_relaxed); }
+int wino_poly_mode() {
+    const int f = g_force_wino_poly.load(std::memory_order_relaxed);
+    return f >= 0 ? f : tuning_env_int("IRSDE_WINO_POLY", 1);
+}
 static std::atomic<int> g_force_subbatches{0};
 void set_force_subbatches(int n) { g_force_subbatches.store(n, std::memory_order_relaxed); }
 int naf_subbatches(const irsde_engine* e, int B, int H, int W) {

@@ -105,7 +105,8 @@ const HostTensor& need(irsde_engine* e, const std::string& n) {
 }
 
 // OIHW -> [O][KH][KW][I]
-ConvW pack_conv(irsde_engine* e, const std::string& wname, const std::string& bname) {
+// resample: 0 = plain layer, 1 = the layer reads its input through the nearest x2 upsample (a 4x4 layer is a stride-2 Downsample)
+ConvW pack_conv(irsde_engine* e, const std::string& wname, const std::string& bname, int resample = 0) {
     const HostTensor& t = need(e, wname);
     const int O = (int)t.shape[0], I = (int)t.shape[1], KH = (int)t.shape[2], KW = (int)t.shape[3];
     std::vector<float> p((size_t)O * KH * KW * I);
@@ -118,6 +119,16 @@ ConvW pack_conv(irsde_engine* e, const std::string& wname, const std::string& bn
     c.w = e->upload(p);
     c.Cout = O; c.Cin = I; c.KH = KH; c.KW = KW;
     if (!bname.empty()) c.bias = e->upload(need(e, bname).data);
+    // polyphase F(4x4,2x2) of the resampling layers: exact fp32 only (the 16-bit and split modes keep their paths)
+    constexpr int kNotExactF32 = IRSDE_FLAG_NO_WINOGRAD | IRSDE_FLAG_NAIVE_CONV | IRSDE_FLAG_BF16 | IRSDE_FLAG_BF16_ACT | IRSDE_FLAG_FP16 | IRSDE_FLAG_F16_ACT |
+                                 IRSDE_FLAG_SPLIT_BF16X2 | IRSDE_FLAG_SPLIT_F16X2 | IRSDE_FLAG_NO_WINO_POLY;
+    const bool poly_up = resample && KH == 3 && KW == 3, poly_down = KH == 4 && KW == 4;
+    if ((poly_up || poly_down) && I % 32 == 0 && O % 4 == 0 && !bname.empty() && !(e->cfg.flags & kNotExactF32) &&
+        wino_poly_wants_weights(wino_poly_mode(), poly_up, I)) {
+        std::vector<float> U((size_t)(poly_up ? 100 : 25 * 4) * O * I);
+        wino_poly_transform_weights(p.data(), O, I, U.data(), poly_up ? 1 : 0);
+        c.wino_poly = e->upload(U);
+    }
     if (KH == 3 && KW == 3 && I % 32 == 0 && !(e->cfg.flags & (IRSDE_FLAG_NO_WINOGRAD | IRSDE_FLAG_BF16))) {
         for (int tile : {2, 4}) {
             if (tile == 4 && (e->cfg.flags & IRSDE_FLAG_NO_WINOGRAD_F43)) continue;
@@ -737,7 +748,7 @@ void finalize(irsde_engine* e) {
         e->up_attn.push_back(pack_attn(e, u + "2."));
         if (stereo) e->up_scam.push_back(pack_scam(e, u + "3."));
         if (j != depth - 1)
-            e->up_conv.push_back(pack_conv(e, u + ci + ".1.weight", u + ci + ".1.bias"));
+            e->up_conv.push_back(pack_conv(e, u + ci + ".1.weight", u + ci + ".1.bias", 1));
         else
             e->up_conv.push_back(pack_conv(e, u + ci + ".weight", ""));
     }

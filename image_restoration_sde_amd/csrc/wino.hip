@@ -11,6 +11,8 @@
 //                                         the fp32 MFMA pipe — the same kernel as the direct path, run as a 1x1 conv
 //   wino_output_kernel  y = A^T M A (m x m pixels per tile) + bias / FiLM / SiLU / residual            (HBM bound)
 // U = G g G^T is computed once at weight-load time (engine_weights.hip).
+// Polyphase F(4x4,2x2) for the resampling convolutions (4x4 stride 2; nearest x2 + 3x3): wino_poly_input_kernel / wino_poly_output_kernel below, the same
+// component GEMMs with 25 / 100 components (WinoPolyParams, common.h).
 #include "common.h"
 
 namespace irsde {
@@ -279,7 +281,200 @@ __global__ __launch_bounds__(256) void wino_output_kernel(const WinoParams p) {
     }
 }
 
+// ---- polyphase F(4x4,2x2) (points 0, 1, -1, 2, inf): the stride-2 4x4 and the nearest-x2 + 3x3 convolutions, see WinoPolyParams ----
+// B^T = [2 -1 -2 1 0; 0 -2 -1 1 0; 0 2 -3 1 0; 0 -1 0 1 0; 0 2 -1 -2 1]
+__device__ __forceinline__ void bt5_apply(const float4* d, float4* t) {
+    t[0] = 2.0f * (d[0] - d[2]) + (d[3] - d[1]);
+    t[1] = (d[3] - d[2]) - 2.0f * d[1];
+    t[2] = 2.0f * d[1] - 3.0f * d[2] + d[3];
+    t[3] = d[3] - d[1];
+    t[4] = 2.0f * (d[1] - d[3]) + (d[4] - d[2]);
+}
+// A^T = [1 1 1 1 0; 0 1 -1 2 0; 0 1 1 4 0; 0 1 -1 8 1]
+__device__ __forceinline__ void at5_apply(const float4* m, float4* y) {
+    const float4 s12 = m[1] + m[2], d12 = m[1] - m[2];
+    y[0] = m[0] + s12 + m[3];
+    y[1] = d12 + 2.0f * m[3];
+    y[2] = s12 + 4.0f * m[3];
+    y[3] = d12 + 8.0f * m[3] + m[4];
+}
+
+// one thread = (tile, phase, 4 channels): the phase's 5x5 patch (down: every second pixel from (8 ty - 1 + p, 8 tx - 1 + q); up: from (4 ty - 1 + py, 4 tx - 1 + px))
+template <bool UP>
+__global__ __launch_bounds__(256) void wino_poly_input_kernel(const WinoPolyParams p) {
+    const int C4 = p.C / 4;
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long total = (long long)p.T * 4 * C4;
+    if (idx >= total) return;
+    const int c = (int)(idx % C4) * 4;
+    const long long i1 = idx / C4;
+    const int ph = (int)(i1 & 3);
+    const int t = (int)(i1 >> 2);
+    const int tx = t % p.TW;
+    const int t1 = t / p.TW;
+    const int ty = t1 % p.TH;
+    const int b = t1 / p.TH;
+    constexpr int STEP = UP ? 1 : 2;
+    const int y0 = 4 * STEP * ty - 1 + (ph >> 1), x0 = 4 * STEP * tx - 1 + (ph & 1);
+    const float* src = p.in + c;
+    float4 w[5][5];  // after the row pass: w[r][s] = (B^T d)[r][s]
+    {
+        float4 d[5][5];
+#pragma unroll
+        for (int r = 0; r < 5; ++r) {
+            const int iy = y0 + STEP * r;
+#pragma unroll
+            for (int s = 0; s < 5; ++s) {
+                const int ix = x0 + STEP * s;
+                const bool ok = (unsigned)iy < (unsigned)p.Hin && (unsigned)ix < (unsigned)p.Win;
+                const size_t pixel = (size_t)b * p.Hin * p.Win + (size_t)(ok ? iy : 0) * p.Win + (ok ? ix : 0);
+                const float4 v = *reinterpret_cast<const float4*>(src + pixel * p.C);
+                d[r][s] = ok ? v : make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+        }
+#pragma unroll
+        for (int s = 0; s < 5; ++s) {
+            float4 col[5], tc[5];
+#pragma unroll
+            for (int r = 0; r < 5; ++r) col[r] = d[r][s];
+            bt5_apply(col, tc);
+#pragma unroll
+            for (int r = 0; r < 5; ++r) w[r][s] = tc[r];
+        }
+    }
+    const size_t K = UP ? (size_t)p.C : (size_t)4 * p.C;
+    const size_t kstride = (size_t)p.T * K;
+    float* vp = UP ? p.V + (size_t)ph * 25 * kstride + (size_t)t * K + c : p.V + (size_t)t * K + (size_t)ph * p.C + c;
+#pragma unroll
+    for (int r = 0; r < 5; ++r) {
+        float4 o[5];
+        bt5_apply(w[r], o);
+#pragma unroll
+        for (int s = 0; s < 5; ++s) *reinterpret_cast<float4*>(vp + (size_t)(r * 5 + s) * kstride) = o[s];
+    }
+}
+
+// one thread = (tile, [up: output phase,] 4 output channels): y = A^T m A + bias, 4x4 pixels (up: of the phase's pixel lattice)
+template <bool UP>
+__global__ __launch_bounds__(256) void wino_poly_output_kernel(const WinoPolyParams p) {
+    const int N4 = p.Cout / 4;
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long total = (long long)p.T * (UP ? 4 : 1) * N4;
+    if (idx >= total) return;
+    const int n = (int)(idx % N4) * 4;
+    const long long i1 = idx / N4;
+    const int ph = UP ? (int)(i1 & 3) : 0;
+    const int t = UP ? (int)(i1 >> 2) : (int)i1;
+    const int tx = t % p.TW;
+    const int t1 = t / p.TW;
+    const int ty = t1 % p.TH;
+    const int b = t1 / p.TH;
+    const size_t kstride = (size_t)p.T * p.Cout;
+    const float* mp = p.M + (size_t)ph * 25 * kstride + (size_t)t * p.Cout + n;
+    float4 u[4][5];  // u = A^T m (row pass)
+    {
+        float4 m[5][5];
+#pragma unroll
+        for (int r = 0; r < 5; ++r)
+#pragma unroll
+            for (int s = 0; s < 5; ++s) m[r][s] = *reinterpret_cast<const float4*>(mp + (size_t)(r * 5 + s) * kstride);
+#pragma unroll
+        for (int s = 0; s < 5; ++s) {
+            float4 col[5], yc[4];
+#pragma unroll
+            for (int r = 0; r < 5; ++r) col[r] = m[r][s];
+            at5_apply(col, yc);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) u[i][s] = yc[i];
+        }
+    }
+    float4 bias = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (p.bias) bias = *reinterpret_cast<const float4*>(p.bias + n);
+    const int LH = UP ? p.Hin : p.Ho, LW = UP ? p.Win : p.Wo;   // extent of the tiled lattice
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        float4 y[4];
+        at5_apply(u[i], y);
+        const int ly = 4 * ty + i;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int lx = 4 * tx + j;
+            if (ly >= LH || lx >= LW) continue;
+            const int oy = UP ? 2 * ly + (ph >> 1) : ly, ox = UP ? 2 * lx + (ph & 1) : lx;
+            const size_t pixel = ((size_t)b * p.Ho + oy) * p.Wo + ox;
+            *reinterpret_cast<float4*>(p.out + pixel * p.out_stride + n) = y[j] + bias;
+        }
+    }
+}
+
 }  // namespace
+
+static void wino_poly_check(const WinoPolyParams& p, bool output) {
+    const int LH = p.up ? p.Hin : p.Ho, LW = p.up ? p.Win : p.Wo;
+    if (p.C <= 0 || p.C % 4 || p.B <= 0 || p.Hin <= 0 || p.Win <= 0 || p.TH != (LH + 3) / 4 || p.TW != (LW + 3) / 4 || p.T != p.B * p.TH * p.TW)
+        throw HipError("wino_poly: inconsistent tiling");
+    if (p.up ? (p.Ho != 2 * p.Hin || p.Wo != 2 * p.Win) : (p.Ho != (p.Hin - 2) / 2 + 1 || p.Wo != (p.Win - 2) / 2 + 1 || p.Hin < 2 || p.Win < 2))
+        throw HipError("wino_poly: output size does not belong to the input size");
+    if (output && (p.Cout <= 0 || p.Cout % 4 || p.out_stride % 4 || p.out_stride < p.Cout)) throw HipError("wino_poly_output: channels must be multiples of 4");
+}
+
+void launch_wino_poly_input(const WinoPolyParams& p, hipStream_t s) {
+    wino_poly_check(p, false);
+    const long long total = (long long)p.T * p.C;   // T * 4 phases * C / 4
+    const dim3 grid((unsigned)((total + 255) / 256));
+    if (p.up) hipLaunchKernelGGL((wino_poly_input_kernel<true>), grid, dim3(256), 0, s, p);
+    else hipLaunchKernelGGL((wino_poly_input_kernel<false>), grid, dim3(256), 0, s, p);
+    IRSDE_HIP_CHECK(hipGetLastError());
+}
+
+void launch_wino_poly_output(const WinoPolyParams& p, hipStream_t s) {
+    wino_poly_check(p, true);
+    const long long total = (long long)p.T * (p.up ? 4 : 1) * (p.Cout / 4);
+    const dim3 grid((unsigned)((total + 255) / 256));
+    if (p.up) hipLaunchKernelGGL((wino_poly_output_kernel<true>), grid, dim3(256), 0, s, p);
+    else hipLaunchKernelGGL((wino_poly_output_kernel<false>), grid, dim3(256), 0, s, p);
+    IRSDE_HIP_CHECK(hipGetLastError());
+}
+
+// U = G g G^T of F(4x4,2x2), G = [1/2 0; -1/2 -1/2; -1/6 1/6; 1/6 1/3; 0 1], per phase, in double, rounded once (host, at weight load)
+void wino_poly_transform_weights(const float* w_packed, int Cout, int Cin, float* U, int up) {
+    static const double G[5][2] = {{0.5, 0.0}, {-0.5, -0.5}, {-1.0 / 6, 1.0 / 6}, {1.0 / 6, 1.0 / 3}, {0.0, 1.0}};
+    const int KW = up ? 3 : 4;
+    const size_t K = up ? (size_t)Cin : (size_t)4 * Cin;
+    const size_t kstride = (size_t)Cout * K;
+    for (int n = 0; n < Cout; ++n)
+        for (int c = 0; c < Cin; ++c) {
+            double w[4][4];
+            for (int ky = 0; ky < KW; ++ky)
+                for (int kx = 0; kx < KW; ++kx) w[ky][kx] = w_packed[(((size_t)n * KW + ky) * KW + kx) * Cin + c];
+            for (int ph = 0; ph < 4; ++ph) {
+                const int p = ph >> 1, q = ph & 1;
+                double g[2][2];
+                for (int a = 0; a < 2; ++a)
+                    for (int b = 0; b < 2; ++b) {
+                        if (!up) {
+                            g[a][b] = w[2 * a + p][2 * b + q];
+                        } else {   // rows: phase 0 taps {w0, w1 + w2} on rows {i - 1, i}; phase 1 taps {w0 + w1, w2} on rows {i, i + 1}; columns alike
+                            const int y0 = p == 0 ? (a == 0 ? 0 : 1) : (a == 0 ? 0 : 2), y1 = p == 0 ? (a == 0 ? 0 : 2) : (a == 0 ? 1 : 2);
+                            const int x0 = q == 0 ? (b == 0 ? 0 : 1) : (b == 0 ? 0 : 2), x1 = q == 0 ? (b == 0 ? 0 : 2) : (b == 0 ? 1 : 2);
+                            double sum = 0.0;
+                            for (int ky = y0; ky <= y1; ++ky)
+                                for (int kx = x0; kx <= x1; ++kx) sum += w[ky][kx];
+                            g[a][b] = sum;
+                        }
+                    }
+                double tmp[5][2];
+                for (int r = 0; r < 5; ++r)
+                    for (int b = 0; b < 2; ++b) tmp[r][b] = G[r][0] * g[0][b] + G[r][1] * g[1][b];
+                for (int r = 0; r < 5; ++r)
+                    for (int s = 0; s < 5; ++s) {
+                        const float v = (float)(tmp[r][0] * G[s][0] + tmp[r][1] * G[s][1]);
+                        if (up) U[((size_t)ph * 25 + r * 5 + s) * kstride + (size_t)n * K + c] = v;
+                        else U[(size_t)(r * 5 + s) * kstride + (size_t)n * K + (size_t)ph * Cin + c] = v;
+                    }
+            }
+        }
+}
 
 // IRSDE_WINO_VEC=1 (experiment): one channel per thread instead of four
 static int wino_vec() {

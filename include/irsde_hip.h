@@ -42,6 +42,9 @@
  *        activation storage; its full softmax attention runs on the bf16 MFMA, csrc/full_attn16.hip); debug header: irsde_debug_full_attention16.
  *        Additive, same version: IRSDE_FLAG_F16_ACT (irsde_create_nafnet only: IEEE fp16 storage of every activation tensor of the image-space
  *        ConditionalNAFNet, on fp16-storage variants of its implicit-GEMM, LayerNorm, depthwise-gate and norm + 1x1 kernels).
+ *        Additive, same version: IRSDE_FLAG_NO_WINO_POLY (the exact-fp32 ConditionalUNet runs its 4x4 stride-2 Downsample convolutions and the
+ *        nearest-x2 + 3x3 Upsample convolutions from 512 input channels as polyphase Winograd F(4x4,2x2) by default: same results up to fp32 rounding; the flag keeps the old paths).
+ *        Debug header: irsde_debug_conv selectors 24 / 25.
  */
 #ifndef IRSDE_HIP_H
 #define IRSDE_HIP_H
@@ -174,6 +177,9 @@ enum {
                                         IRSDE_ERR_INVALID together with IRSDE_FLAG_NAF_INTRO_SKIP / _NAF_LENS / _NAF_STEREO, IRSDE_FLAG_BF16 without _FP16,
                                         IRSDE_FLAG_BF16_ACT, _SPLIT_BF16X2 / _SPLIT_F16X2 and _NAIVE_CONV; by irsde_create and irsde_create_latent_unet; and
                                         by irsde_nafnet_set_local_pool.  The per-image NAFBlock chain is not part of this mode's plans */
+    IRSDE_FLAG_NO_WINO_POLY = 1048576, /* measurement only: keep the resampling convolutions of the exact-fp32 ConditionalUNet (Downsample 4x4 stride 2; nearest x2 +
+                                        3x3 of the two deepest Upsamples) on the direct / F(4x4,3x3) paths.  Default: polyphase Winograd F(4x4,2x2) where the plan's rule
+                                        adopts it (csrc/wino.hip, profiles/wino_poly.md); no effect in the other operand modes, which never use it */
     IRSDE_FLAG_NO_WINOGRAD_F43 = 8   /* Winograd F(2x2,3x3) only (>= 256 channels); default also uses F(4x4,3x3) from 128
                                         channels up where H, W are multiples of 4 */
 };

@@ -20,6 +20,9 @@ extern "C" {
  *   0 production dispatch      1 VALU cross-check kernel
  *   2 / 3 Winograd F(2x2,3x3) / F(4x4,3x3) (3x3 s1 p1 only); 12 / 13 and 22 / 23: the same with the component GEMMs forced
  *         onto the tile-loop kernel (all / 2 components per block)
+ *   24 / 25 polyphase Winograd F(4x4,2x2) (csrc/wino.hip: wino_poly_input_kernel, the component GEMMs, wino_poly_output_kernel): 24 a 4x4 stride-2 pad-1
+ *           layer (25 components, K = 4 C0), 25 a 3x3 stride-1 pad-1 layer with in_shift = 1 (4 output phases x 25 components); single source, C0 a multiple
+ *           of 32, Cout of 4, bias only — anything else (film, silu, res, in1, splits > 1, another geometry) is refused
  *   46 / 47 the direct implicit GEMM on the PAIR kernels (conv_igemm.hip: fp32 storage, activations split into 16-bit hi + lo pieces while
  *           staged, three cross products on the 16-bit MFMA): fp16 / bf16 pieces
  *   44 / 45 three-launch Winograd F(4x4,3x3) with the engine's pair GEMM (pair-interleaved operands, LDS-DMA): fp16 / bf16 hi + lo pieces
@@ -81,6 +84,10 @@ int irsde_debug_force_subbatches(int n);
  * forced (where 8 ceil(B / 8) g groups fit the compute units next to the call's other sub-batches, else fewer), 0 returns to the rule (as many as fit).
  * Plans already built keep their choice: use a fresh engine (or another batch shape) per setting. */
 int irsde_debug_force_chain_groups(int g);
+/* Test / measurement hook (process-wide): the polyphase Winograd F(4x4,2x2) path of the resampling convolutions in engines CREATED from now on (the
+ * weights are transformed at irsde_finalize_weights) — 0 never, 1 by the plan's rule, 2 wherever eligible (exact fp32, single source, bias only);
+ * any other value returns to the default (the rule; the IRSDE_WINO_POLY tuning knob). */
+int irsde_debug_force_wino_poly(int mode);
 
 /* Kernel-level test hook: ONE SCAM of the stereo-sr NAFBlock (csrc/scam.hip + the projection GEMM on the implicit-GEMM kernel, the engine's
  * fp32 path).  x / out: device NHWC [2 B_pairs][H][W][C] (views stacked [L_0..L_{B-1}, R_0..R_{B-1}] as inside the reference network);
