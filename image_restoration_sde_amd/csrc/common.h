@@ -318,7 +318,8 @@ void launch_attention_q_out_fused(const float* xn, const float* x, const float* 
 //   prologue  xs2 [2B][H'][W'][LN(xs) (norm_l / norm_r gain) | xs], xs = bicubic quarter-downsample of x
 //   core      qv [2B][H'][W'][Q | V] -> F [2B][H'][W'][c]: F_r2l in the left images, F_l2r in the right ones
 //   epilogue  out = x + (beta | gamma)[ch] * F[nearest]
-void scam_check_shape(int H, int W, int c);   // throws HipError for maps the reference cannot run (H or W < 4) or the kernels do not cover
+void scam_check_shape(int H, int W, int c, bool any_width = false);   // throws HipError for maps the reference cannot run (H or W < 4) or the kernels do not cover
+                                                                      // (any_width: the core is the streaming one, the strip limit W / 4 <= 512 does not apply)
 void launch_scam_prologue(const float* x, const float* g_l, const float* g_r, float* xs2, int B, int H, int W, int c, hipStream_t s);
 void launch_scam_core(const float* qv, float* F, int B, int H, int W, int c, hipStream_t s);
 void launch_scam_epilogue(const float* x, const float* F, const float* beta, const float* gamma, float* out, int B, int H, int W, int c, hipStream_t s);
@@ -329,10 +330,17 @@ void scam_pack_proj(const float* w1, const float* b1, const float* w2, const flo
 //   epilogue  x += (beta | gamma)[ch] * F, in place
 constexpr int kScamFullMaxW = 1024;   // widest row: the 16 x W score strip (and nothing else of S) lives in LDS
 constexpr int kScamFullMaxC = 2048;
-void scam_full_check_shape(int H, int W, int c);   // throws HipError for shapes the kernels do not cover
+void scam_full_check_shape(int H, int W, int c, bool any_width = false);   // throws HipError for shapes the kernels do not cover (any_width: as above, W <= 1024 dropped)
 void launch_scam_full_prologue(const float* x, const float* g_l, const float* g_r, float* x2, int B, int H, int W, int c, hipStream_t s);
 void launch_scam_full_core(const float* qv, float* F, int B, int H, int W, int c, hipStream_t s);
 void launch_scam_full_epilogue(float* x, const float* F, const float* beta, const float* gamma, int B, int H, int W, int c, hipStream_t s);
+// Streaming core of both SCAMs (scam_stream.hip, IRSDE_FLAG_SCAM_STREAM): the strip cores' contract on the H' x W' map of each view, any W', the other view's
+// row walked in column blocks of block_w (a multiple of 16 up to kScamStreamMaxBlockW; 0 = that maximum) with an online softmax.  Throws HipError for c outside
+// [32, 2048] / not a multiple of 32, B * H' > 65535 and a bad block_w.
+constexpr int kScamMaxWs = 512;               // widest quarter-map row of scam_core_kernel
+constexpr int kScamStreamMaxBlockW = 512;     // a 33 KB score tile
+bool scam_stream_block_ok(int block_w);       // a multiple of 16 in [16, kScamStreamMaxBlockW]
+void launch_scam_stream_core(const float* qv, float* F, int B, int Hs, int Ws, int c, int block_w, hipStream_t s);
 // stereo network glue: 6-channel pair tensors <-> the 2B-view network batch
 void launch_stereo_prep(const float* xt, const float* cond, float* x0, int B, int ic, int P, int H, int W, int Hp, int Wp, hipStream_t s);
 void launch_stereo_pack_pred(const float* in, float* out, int B, int ic, int Hp, int Wp, int in_stride, int out_stride, hipStream_t s);

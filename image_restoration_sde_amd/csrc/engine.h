@@ -550,7 +550,9 @@ void pack_naf_chain_host(const std::vector<NafChainHostW>& blocks, std::vector<u
 Plan* get_plan(irsde_engine* e, int B, int H, int W, bool per_sample_film, int slot = 0, int b0 = 0);
 int naf_subbatches(const irsde_engine* e, int B, int H, int W);
 void set_force_chain_groups(int g);   // irsde_debug_force_chain_groups
+void set_force_scam_stream(int block_w);   // irsde_debug_force_scam_stream (0 = the rule)
 int forced_chain_groups();
+int forced_scam_stream();
 void set_force_subbatches(int n);                                 // irsde_debug_force_subbatches   // how many concurrent sub-batches the sampler splits a NAFNet batch into (1 = none)
 LatentPlan* get_latent_plan(irsde_engine* e, int B, int H, int W, bool decode);
 

@@ -132,6 +132,8 @@ int irsde_create(const irsde_config* cfg, irsde_engine** out) {
                 throw HipError("IRSDE_FLAG_UNET_STEREO runs in fp32 only (the 16-bit and split-operand modes are not covered for the full-resolution SCAM network)");
             if (cfg->flags & IRSDE_FLAG_UNCOND_FULLATTN) throw HipError("IRSDE_FLAG_UNET_STEREO cannot be combined with IRSDE_FLAG_UNCOND_FULLATTN");
         }
+        if ((cfg->flags & IRSDE_FLAG_SCAM_STREAM) && !stereo)
+            throw HipError("IRSDE_FLAG_SCAM_STREAM: the stereo networks only (with IRSDE_FLAG_UNET_STEREO here, with IRSDE_FLAG_NAF_STEREO in irsde_create_nafnet)");
         if (cfg->flags & IRSDE_FLAG_F16_ACT) throw HipError("IRSDE_FLAG_F16_ACT: the image-space ConditionalNAFNet only (irsde_create_nafnet)");
         if (cfg->flags & IRSDE_FLAG_NAF_STEREO) throw HipError("IRSDE_FLAG_NAF_STEREO: the stereo network is a ConditionalNAFNet (irsde_create_nafnet)");
         if (cfg->flags & IRSDE_FLAG_NAF_UNCOND) throw HipError("IRSDE_FLAG_NAF_UNCOND: irsde_create_nafnet only (the unconditional UNet is IRSDE_FLAG_UNCOND_FULLATTN)");
@@ -176,6 +178,8 @@ int irsde_create_nafnet(const irsde_nafnet_config* cfg, irsde_engine** out) {
         if (cfg->flags & IRSDE_FLAG_BF16_ACT) throw HipError("IRSDE_FLAG_BF16_ACT: conditional UNet only");
         if (cfg->flags & IRSDE_FLAG_UNET_STEREO) throw HipError("IRSDE_FLAG_UNET_STEREO: the stereo UNet is a ConditionalUNet (irsde_create)");
         const bool stereo = (cfg->flags & IRSDE_FLAG_NAF_STEREO) != 0;
+        if ((cfg->flags & IRSDE_FLAG_SCAM_STREAM) && !stereo)
+            throw HipError("IRSDE_FLAG_SCAM_STREAM: the stereo networks only (with IRSDE_FLAG_NAF_STEREO here, with IRSDE_FLAG_UNET_STEREO in irsde_create)");
         if (stereo) {
             if (cfg->flags & (IRSDE_FLAG_NAF_LENS | IRSDE_FLAG_NAF_INTRO_SKIP))
                 throw HipError("IRSDE_FLAG_NAF_STEREO cannot be combined with IRSDE_FLAG_NAF_LENS / IRSDE_FLAG_NAF_INTRO_SKIP");
@@ -591,6 +595,7 @@ int irsde_create_latent_unet(const irsde_latent_unet_config* cfg, irsde_engine**
         if (cfg->embed_dim < 1 || cfg->embed_dim > 32) throw HipError("embed_dim must be in 1..32");
         if (cfg->flags & IRSDE_FLAG_BF16_ACT) throw HipError("IRSDE_FLAG_BF16_ACT: conditional UNet only");
         if (cfg->flags & IRSDE_FLAG_F16_ACT) throw HipError("IRSDE_FLAG_F16_ACT: the image-space ConditionalNAFNet only (irsde_create_nafnet)");
+        if (cfg->flags & IRSDE_FLAG_SCAM_STREAM) throw HipError("IRSDE_FLAG_SCAM_STREAM: the stereo networks only (irsde_create / irsde_create_nafnet)");
         auto* e = new irsde_engine();
         e->arch = 2;
         e->cfg.in_nc = cfg->in_ch; e->cfg.out_nc = cfg->out_ch; e->cfg.nf = cfg->ch; e->cfg.depth = cfg->n_mult;

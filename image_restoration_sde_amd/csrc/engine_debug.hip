@@ -183,6 +183,52 @@ int irsde_debug_scam_full(const float* x, int B, int H, int W, int C, const floa
     });
 }
 
+int irsde_debug_scam_stream(const float* x, int B, int H, int W, int C, const float* norm_l_g, const float* norm_r_g, const float* l_proj1_w,
+                            const float* l_proj1_b, const float* r_proj1_w, const float* r_proj1_b, const float* l_proj2_w, const float* l_proj2_b,
+                            const float* r_proj2_w, const float* r_proj2_b, const float* beta, const float* gamma, int block_w, float* out, void* stream) {
+    return guard([&] {
+        scam_hook(
+            {x, out, norm_l_g, norm_r_g, l_proj1_w, l_proj1_b, r_proj1_w, r_proj1_b, l_proj2_w, l_proj2_b, r_proj2_w, r_proj2_b, beta, gamma}, B, H / 4, W / 4, C, stream,
+            [&] {
+                if (B < 1 || (long long)B * (H / 4) > 65535) throw HipError("debug_scam_stream: bad shape");
+                if (block_w != 0 && !scam_stream_block_ok(block_w)) throw HipError("debug_scam_stream: block_w must be 0 or a multiple of 16 in [16, 512]");
+                scam_check_shape(H, W, C, true);
+            },
+            [&](const ScamHookDev& d, hipStream_t s) { launch_scam_prologue(x, d.gl, d.gr, d.in2, B, H, W, C, s); },
+            [&](const ScamHookDev& d, hipStream_t s) {
+                launch_scam_stream_core(d.qv, d.F, B, H / 4, W / 4, C, block_w, s);
+                launch_scam_epilogue(x, d.F, d.beta, d.gamma, out, B, H, W, C, s);
+            });
+    });
+}
+
+int irsde_debug_scam_full_stream(const float* x, int B, int H, int W, int C, const float* norm_l_g, const float* norm_r_g, const float* l_proj1_w,
+                                 const float* l_proj1_b, const float* r_proj1_w, const float* r_proj1_b, const float* l_proj2_w, const float* l_proj2_b,
+                                 const float* r_proj2_w, const float* r_proj2_b, const float* beta, const float* gamma, int block_w, float* out,
+                                 void* stream) {
+    return guard([&] {
+        scam_hook(
+            {x, out, norm_l_g, norm_r_g, l_proj1_w, l_proj1_b, r_proj1_w, r_proj1_b, l_proj2_w, l_proj2_b, r_proj2_w, r_proj2_b, beta, gamma}, B, H, W, C, stream,
+            [&] {
+                if (B < 1 || (long long)B * H > 65535) throw HipError("debug_scam_full_stream: bad shape");
+                if (block_w != 0 && !scam_stream_block_ok(block_w)) throw HipError("debug_scam_full_stream: block_w must be 0 or a multiple of 16 in [16, 512]");
+                scam_full_check_shape(H, W, C, true);
+            },
+            [&](const ScamHookDev& d, hipStream_t s) { launch_scam_full_prologue(x, d.gl, d.gr, d.in2, B, H, W, C, s); },
+            [&](const ScamHookDev& d, hipStream_t s) {
+                launch_scam_stream_core(d.qv, d.F, B, H, W, C, block_w, s);
+                if (out != x) IRSDE_HIP_CHECK(hipMemcpyAsync(out, x, d.vsz * sizeof(float), hipMemcpyDeviceToDevice, s));   // (vsz = 2 B H W C: the whole tensor)
+                launch_scam_full_epilogue(out, d.F, d.beta, d.gamma, B, H, W, C, s);
+            });
+    });
+}
+
+int irsde_debug_force_scam_stream(int block_w) {
+    if (block_w != 0 && !scam_stream_block_ok(block_w)) return guard([&] { throw HipError("debug_force_scam_stream: block_w must be 0 or a multiple of 16 in [16, 512]"); });
+    set_force_scam_stream(block_w);
+    return IRSDE_OK;
+}
+
 int irsde_debug_naf_gate_sca(const float* u, int B, int H, int W, int c, const float* conv2_w, const float* conv2_b, const float* sca_w, const float* sca_b,
                              float* gated_out, float* mean_out, float* s_out, void* stream) {
     return guard([&] {

@@ -616,10 +616,19 @@ struct Builder {
         }
     }
 
+    // The core of one SCAM whose score rows are Ws wide (strip_max: what the strip kernel holds): -1 = the strip kernel, otherwise the streaming kernel
+    // (csrc/scam_stream.hip) with that block_w.  The rule: IRSDE_FLAG_SCAM_STREAM and a row beyond the strip limit; irsde_debug_force_scam_stream: every core.
+    int scam_stream_bw(int Ws, int strip_max) const {
+        if (const int f = forced_scam_stream()) return f;
+        return (e->cfg.flags & IRSDE_FLAG_SCAM_STREAM) && Ws > strip_max ? kScamStreamMaxBlockW : -1;
+    }
+    bool scam_any_width() const { return forced_scam_stream() || (e->cfg.flags & IRSDE_FLAG_SCAM_STREAM); }
+
     // SCAM.forward — stereo-sr DenoisingNAFNet_arch.py:33-60 (csrc/scam.hip): x holds the 2 B views [L | R] of B pairs
     Tensor scam(const ScamW& w, const Tensor& x) {
         const int c = x.C, Bp = x.B / 2, Hs = x.H / 4, Ws = x.W / 4, H = x.H, W = x.W;
-        scam_check_shape(x.H, x.W, c);
+        scam_check_shape(x.H, x.W, c, scam_any_width());
+        const int bw = scam_stream_bw(Ws, kScamMaxWs);
         ScamScratch ws(*this, (size_t)Bp * Hs * Ws * 2 * c);   // one view's [LN(xs) | xs] / [Q | V]
         float *xs2 = ws.in2, *qv = ws.qv, *F = ws.F;
         Tensor out = talloc(x.B, x.H, x.W, c);
@@ -634,9 +643,13 @@ struct Builder {
             name("prologue(bicubic/4 + LayerNorm)");
         }
         scam_proj(w, ws, Bp, Hs, Ws, "scam_proj");
-        {
+        if (bw < 0) {
             push_other(OP_ATTN, [=](hipStream_t s) { launch_scam_core(qv, F, Bp, H, W, c, s); });
             name("core(S strips + softmax + PV, fp32 MFMA)");
+        } else {
+            push_other(OP_ATTN, [=](hipStream_t s) { launch_scam_stream_core(qv, F, Bp, Hs, Ws, c, bw, s); });
+            snprintf(buf, sizeof buf, "scam_stream_core(S blocks + online softmax + PV, fp32 MFMA) B=%d c=%d hw=%dx%d W'=%d H'=%d bw=%d", x.B, c, H, W, Ws, Hs, bw);
+            pl->net_ops.back().desc = buf;
         }
         {
             const float *xp = x.p, *be = w.beta, *ga = w.gamma;
@@ -652,7 +665,8 @@ struct Builder {
     Tensor scam_full(const ScamW& w, const Tensor& x) {
         const int c = x.C, Bp = x.B / 2, H = x.H, W = x.W;
         if (x.bf16 || c != w.c || (x.B & 1)) throw HipError("internal: SCAM input");
-        scam_full_check_shape(H, W, c);
+        scam_full_check_shape(H, W, c, scam_any_width());
+        const int bw = scam_stream_bw(W, kScamFullMaxW);
         ScamScratch ws(*this, (size_t)Bp * H * W * 2 * c);   // one view's [LN(x) | x] / [Q | V]
         float *x2 = ws.in2, *qv = ws.qv, *F = ws.F;
         char buf[160];
@@ -666,9 +680,13 @@ struct Builder {
             name("prologue(LayerNorm -> [LN(x) | x])");
         }
         scam_proj(w, ws, Bp, H, W, "scam_full_proj");
-        {
+        if (bw < 0) {
             push_other(OP_ATTN, [=](hipStream_t s) { launch_scam_full_core(qv, F, Bp, H, W, c, s); });
             name("core(S strips + softmax + PV, fp32 MFMA)");
+        } else {
+            push_other(OP_ATTN, [=](hipStream_t s) { launch_scam_stream_core(qv, F, Bp, H, W, c, bw, s); });
+            snprintf(buf, sizeof buf, "scam_full_stream_core(S blocks + online softmax + PV, fp32 MFMA) B=%d c=%d hw=%dx%d bw=%d", x.B, c, H, W, bw);
+            pl->net_ops.back().desc = buf;
         }
         Tensor out = x;
         if (!reuse) {   // IRSDE_FLAG_KEEP_ACTIVATIONS: the SCAM input stays readable as a tap
@@ -986,6 +1004,9 @@ void build_naf_plan(irsde_engine* e, Plan* pl, Builder& b, int P) {
 static std::atomic<int> g_force_chain_groups{0};   // irsde_debug_force_chain_groups: 0 = the rule (Builder::chain_groups)
 void set_force_chain_groups(int g) { g_force_chain_groups.store(g, std::memory_order_relaxed); }
 int forced_chain_groups() { return g_force_chain_groups.load(std::memory_order_relaxed); }
+static std::atomic<int> g_force_scam_stream{0};   // irsde_debug_force_scam_stream: 0 = the rule (Builder::scam_stream_bw), else the block width of every SCAM core
+void set_force_scam_stream(int block_w) { g_force_scam_stream.store(block_w, std::memory_order_relaxed); }
+int forced_scam_stream() { return g_force_scam_stream.load(std::memory_order_relaxed); }
 static std::atomic<int> g_force_wino_poly{-1};   // irsde_debug_force_wino_poly: -1 = the IRSDE_WINO_POLY knob
 void set_force_wino_poly(int mode) { g_force_wino_poly.store(mode, std::memory_order_relaxed); }
 int wino_poly_mode() {

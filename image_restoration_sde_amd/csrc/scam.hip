@@ -460,11 +460,12 @@ __global__ void stereo_unet_pack_pred_kernel(const float* __restrict__ in, const
 
 }  // namespace
 
-void scam_full_check_shape(int H, int W, int c) {
+void scam_full_check_shape(int H, int W, int c, bool any_width) {
     if (H < 1 || W < 1) throw HipError("SCAM (full resolution): empty feature map");
     if (c % 32 || c < 32 || c > kScamFullMaxC) throw HipError("SCAM (full resolution): channel count must be a multiple of 32 in [32, 2048]");
-    if (W > kScamFullMaxW)
-        throw HipError("SCAM (full resolution): feature maps wider than 1024 pixels are not supported (the 16 x W score strip must fit LDS)");
+    if (W > kScamFullMaxW && !any_width)
+        throw HipError("SCAM (full resolution): feature maps wider than 1024 pixels are not supported (the 16 x W score strip must fit LDS; "
+                       "IRSDE_FLAG_SCAM_STREAM runs them on the streaming core)");
 }
 
 void launch_scam_full_prologue(const float* x, const float* g_l, const float* g_r, float* x2, int B, int H, int W, int c, hipStream_t s) {
@@ -513,11 +514,12 @@ void launch_stereo_unet_pack_pred(const float* in, const float* xt, float* out, 
     IRSDE_HIP_CHECK(hipGetLastError());
 }
 
-void scam_check_shape(int H, int W, int c) {
+void scam_check_shape(int H, int W, int c, bool any_width) {
     if (H < 4 || W < 4) throw HipError("SCAM: the feature map must have at least 4 rows and columns (the bicubic quarter-downsample of the reference "
                                        "is empty below that): pad the stereo input to a larger size");
     if (c % 32 || c < 32 || c > 1024) throw HipError("SCAM: channel count must be a multiple of 32 in [32, 1024]");
-    if (W / 4 > 512) throw HipError("SCAM: feature maps wider than 2051 pixels are not supported (W / 4 <= 512)");
+    if (W / 4 > kScamMaxWs && !any_width)
+        throw HipError("SCAM: feature maps wider than 2051 pixels are not supported (W / 4 <= 512; IRSDE_FLAG_SCAM_STREAM runs them on the streaming core)");
 }
 
 void launch_scam_prologue(const float* x, const float* g_l, const float* g_r, float* xs2, int B, int H, int W, int c, hipStream_t s) {

@@ -44,7 +44,19 @@ class _StereoNAFBlock(_NAFBlock):
         self.fusion = _SCAM(c)
 
 
-class ConditionalNAFNet(_ImageNAFNet):
+class _WideRows:
+    def set_wide_rows(self, enable=True):
+        """Lift the width limit (IRSDE_FLAG_SCAM_STREAM): SCAMs whose score rows are wider than the strip kernels hold in LDS (ConditionalUNet: padded
+        width > 1024; ConditionalNAFNet: > 2051) run the streaming online-softmax core of csrc/scam_stream.hip; narrower inputs compute exactly what
+        they compute without it.  The next call builds a fresh engine."""
+        if enable:
+            self.engine_flags |= _lib.FLAG_SCAM_STREAM
+        else:
+            self.engine_flags &= ~_lib.FLAG_SCAM_STREAM
+        return self
+
+
+class ConditionalNAFNet(_WideRows, _ImageNAFNet):
     _fp16_act = False   # fp16 activation storage covers the image-space network only (the engine refuses it here too)
 
     def __init__(self, img_channel=3, width=16, middle_blk_num=1, enc_blk_nums=[], dec_blk_nums=[], upscale=1):
@@ -95,14 +107,14 @@ class ConditionalNAFNet(_ImageNAFNet):
         return super().forward(inp, cond, time)
 
 
-class ConditionalUNet(_ImageUNet):
+class ConditionalUNet(_WideRows, _ImageUNet):
     """The IR-SDE (UNet) score network of stereo-sr: codes/config/stereo-sr/models/modules/DenoisingUNet_arch.py
         :18-56   SCAM(c) WITHOUT the quarter-downsample / upsample of the NAFNet's: one W x W score matrix per image row at full resolution
         :59-196  ConditionalUNet(in_nc, out_nc, nf, depth=4, upscale=1, fusion=False): init_conv 3x3 on cat(xt_v, cond_v) (no xt - cond);
                  every level is ResBlock, ResBlock, Residual(PreNorm(LinearAttention)), SCAM, down / up-sample; mid_fusion between
                  mid_attn and mid_block2; output xt + cat(x_l, x_r).
     Parameter container under the reference's state_dict names; the arithmetic runs on the HIP engine (IRSDE_FLAG_UNET_STEREO, fp32 only;
-    padded width <= 1024).  xt / cond are [B, 2 in_nc, H, W] pairs; an int `time` is shared by every pair, a [B] tensor gives each its own."""
+    padded width <= 1024 unless `set_wide_rows()`).  xt / cond are [B, 2 in_nc, H, W] pairs; an int `time` is shared by every pair, a [B] tensor gives each its own."""
 
     def __init__(self, in_nc, out_nc, nf, depth=4, upscale=1, fusion=False):
         nn.Module.__init__(self)

@@ -45,6 +45,9 @@
  *        Additive, same version: IRSDE_FLAG_NO_WINO_POLY (the exact-fp32 ConditionalUNet runs its 4x4 stride-2 Downsample convolutions and the
  *        nearest-x2 + 3x3 Upsample convolutions from 512 input channels as polyphase Winograd F(4x4,2x2) by default: same results up to fp32 rounding; the flag keeps the old paths).
  *        Debug header: irsde_debug_conv selectors 24 / 25.
+ *        Additive, same version: IRSDE_FLAG_SCAM_STREAM (the stereo networks on rows of any width: SCAMs beyond the strip kernels' width run a streaming
+ *        online-softmax core, csrc/scam_stream.hip; narrower ones and engines without the flag are unchanged); debug header: irsde_debug_scam_stream,
+ *        irsde_debug_scam_full_stream, irsde_debug_force_scam_stream.
  */
 #ifndef IRSDE_HIP_H
 #define IRSDE_HIP_H
@@ -164,7 +167,7 @@ enum {
                                         sampler's reverse step reads as the noise prediction.  That SCAM has no quarter-downsample and no
                                         upsample: one W x W score matrix per image row at the level's full resolution (csrc/scam.hip, the *_full
                                         kernels; never in HBM, both softmaxes exact, fp32 statistics, no atomics).  Limits: c a multiple of 32 up to
-                                        2048; padded width of level 0 <= 1024 (wider inputs: IRSDE_ERR_INVALID).  fp32 only: IRSDE_FLAG_BF16 /
+                                        2048; padded width of level 0 <= 1024 (wider inputs: IRSDE_ERR_INVALID unless IRSDE_FLAG_SCAM_STREAM is set).  fp32 only: IRSDE_FLAG_BF16 /
                                         _BF16_ACT / _FP16 / _SPLIT_BF16X2 / _SPLIT_F16X2 and IRSDE_FLAG_UNCOND_FULLATTN are refused with
                                         IRSDE_ERR_INVALID.  A pair is never split: no concurrent sub-batches (irsde_debug_force_subbatches is
                                         ignored).  An int time is shared by every pair; B times give each pair its own */
@@ -180,6 +183,14 @@ enum {
     IRSDE_FLAG_NO_WINO_POLY = 1048576, /* measurement only: keep the resampling convolutions of the exact-fp32 ConditionalUNet (Downsample 4x4 stride 2; nearest x2 +
                                         3x3 of the two deepest Upsamples) on the direct / F(4x4,3x3) paths.  Default: polyphase Winograd F(4x4,2x2) where the plan's rule
                                         adopts it (csrc/wino.hip, profiles/wino_poly.md); no effect in the other operand modes, which never use it */
+    IRSDE_FLAG_SCAM_STREAM = 2097152, /* with IRSDE_FLAG_UNET_STEREO (irsde_create) or IRSDE_FLAG_NAF_STEREO (irsde_create_nafnet) only, refused everywhere else: lifts the
+                                        width limit of the stereo networks.  A SCAM whose score rows are wider than its strip kernel holds in LDS (ConditionalUNet: a
+                                        level wider than 1024; ConditionalNAFNet: W / 4 > 512, i.e. wider than 2051) runs the streaming core of csrc/scam_stream.hip:
+                                        the other view's row in column blocks of 512 with a running maximum and rescale (online softmax; fp32 statistics and
+                                        products, no atomics, no scratch in HBM; fp32 rounding differs from the exact two-pass softmax in the order of the sums only).
+                                        Every narrower SCAM keeps its strip kernel, so on inputs inside the old limits the results are bit-identical to an engine
+                                        without the flag.  Limits under the flag: any width; at most 65535 image rows per SCAM launch (B * H' <= 65535, H' the
+                                        level's height, / 4 for the NAFNet); the channel limits above */
     IRSDE_FLAG_NO_WINOGRAD_F43 = 8   /* Winograd F(2x2,3x3) only (>= 256 channels); default also uses F(4x4,3x3) from 128
                                         channels up where H, W are multiples of 4 */
 };

@@ -161,6 +161,23 @@ int irsde_debug_scam_full(const float* x, int B_pairs, int H, int W, int C, cons
                           const float* l_proj1_b, const float* r_proj1_w, const float* r_proj1_b, const float* l_proj2_w, const float* l_proj2_b,
                           const float* r_proj2_w, const float* r_proj2_b, const float* beta, const float* gamma, float* out, void* stream);
 
+/* Kernel-level test hooks: irsde_debug_scam / irsde_debug_scam_full with the streaming core (csrc/scam_stream.hip, what IRSDE_FLAG_SCAM_STREAM runs on rows
+ * beyond the strip kernels' width) between the same prologue, projections and epilogue — same arguments plus block_w before `out`: the column block of the
+ * online softmax, a multiple of 16 in [16, 512], or 0 for the default (512).  Any width; B_pairs * H' <= 65535 (H' = H / 4 for irsde_debug_scam_stream,
+ * H for irsde_debug_scam_full_stream); the channel limits of their counterparts.  Synchronise `stream`.  tests/test_gpu_scam_stream.py. */
+int irsde_debug_scam_stream(const float* x, int B_pairs, int H, int W, int C, const float* norm_l_g, const float* norm_r_g, const float* l_proj1_w,
+                            const float* l_proj1_b, const float* r_proj1_w, const float* r_proj1_b, const float* l_proj2_w, const float* l_proj2_b,
+                            const float* r_proj2_w, const float* r_proj2_b, const float* beta, const float* gamma, int block_w, float* out, void* stream);
+int irsde_debug_scam_full_stream(const float* x, int B_pairs, int H, int W, int C, const float* norm_l_g, const float* norm_r_g, const float* l_proj1_w,
+                                 const float* l_proj1_b, const float* r_proj1_w, const float* r_proj1_b, const float* l_proj2_w, const float* l_proj2_b,
+                                 const float* r_proj2_w, const float* r_proj2_b, const float* beta, const float* gamma, int block_w, float* out,
+                                 void* stream);
+/* Test / measurement hook (process-wide): block_w a multiple of 16 in [16, 512] — plans built from now on run EVERY SCAM core of the stereo networks on the
+ * streaming kernel with that block width, whatever the row width and the engine's flags (how small networks exercise several blocks per row); 0 returns to the
+ * rule (IRSDE_FLAG_SCAM_STREAM and a row beyond the strip limit).  Any other value: IRSDE_ERR_INVALID, nothing changes.  Plans already built keep their
+ * choice: use a fresh engine per setting. */
+int irsde_debug_force_scam_stream(int block_w);
+
 #ifdef __cplusplus
 }
 #endif
