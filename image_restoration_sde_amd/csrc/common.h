@@ -7,6 +7,7 @@
 #include <stdexcept>
 #include <string>
 #include <vector>
+#include "split3_layout.h"
 
 namespace irsde {
 
@@ -116,6 +117,8 @@ struct WinoParams {
     int v_f16 = 0;              // pairs only: 1 = IEEE fp16 pieces of V * v_scale (v_scale a power of two), 0 = bf16 pieces of V
     float v_scale = 1.f;
     int v_pairs = 0;            // 1: two planes, pair-interleaved: element (k, t, c, p) at Vs + ((k * T + t) * (Ctot / 32) + c / 32) * 64 + p * 32 + c % 32
+    int v_triples = 0;          // 1: three bf16 planes in the row-pair-interleaved layout of split3_layout.h: element (k, t, c, p) at
+                                //    Vs + k * split3_comp_elems(T, Ctot) + split3_index(t, c, p, Ctot / 32)
     const float* M = nullptr;   // [(m+2)^2][T][Cout]
     int Cout = 0;
     float* out = nullptr;
@@ -140,6 +143,7 @@ struct WinoPolyParams {
     int C = 0, Hin = 0, Win = 0;
     int B = 0, TH = 0, TW = 0, T = 0;
     float* V = nullptr;
+    unsigned short* Vs = nullptr;   // != nullptr: V as three bf16 planes in the layout of split3_layout.h instead (component z, row t, K index as above)
     const float* M = nullptr;
     int Cout = 0, Ho = 0, Wo = 0;
     float* out = nullptr;       // [B][Ho][Wo][out_stride]
@@ -172,6 +176,12 @@ void launch_gemm_split_pairs(const SplitGemmArgs& a, int ncomp, hipStream_t s, i
 void launch_split_pairs(const float* in, unsigned short* out, size_t rows, int K, hipStream_t s, bool f16 = false,
                         float scale = 1.0f);  // f32 [rows][K] -> pair-interleaved hi / lo (f16: of in * scale)
 void launch_gemm_split(const SplitGemmArgs& a, int nplanes, int ncomp, hipStream_t s);
+// three bf16 planes in the row-pair-interleaved layout of split3_layout.h (gemm_split3i_kernel: six products, LDS-DMA, 256 x 128 tiles): the default path of
+// the exact-fp32 engine's deep component GEMMs.  pA / pB = unsigned shorts per component (split3_comp_elems), plA / plB / lda unused.
+// abl: the measurement twins of the PROBES build (1 no global loads in the K loop, 3 no MFMAs, 4 no output stores)
+void launch_gemm_split_triples(const SplitGemmArgs& a, int ncomp, hipStream_t s, int abl = 0);
+bool gemm_split_triples_fits(long long M, long long N, long long K, long long ldc);   // K % 32 == 0 and every component slice inside the 32-bit offset range
+void launch_split_triples(const float* in, unsigned short* out, int ncomp, size_t rows, int K, hipStream_t s);   // f32 [ncomp][rows][K] -> that layout
 void launch_split_planes(const float* in, unsigned short* out, size_t n, size_t plane, int nplanes, hipStream_t s, bool f16 = false,
                          float scale = 1.0f);  // f32 -> bf16 pieces (f16: two IEEE fp16 pieces of in * scale), plane-major
 void launch_wino_output(const WinoParams& p, hipStream_t s);

@@ -54,6 +54,18 @@ void set_force_wino_poly(int mode);   // irsde_debug_force_wino_poly
 constexpr int kWinoPolyUpMinCin = 512;
 inline bool wino_poly_wants_weights(int mode, bool up, int Cin) { return mode >= 2 || (mode == 1 && (!up || Cin >= kWinoPolyUpMinCin)); }
 
+// The exact-fp32 engine's deep component GEMMs on three bf16 pieces per operand and six products (gemm_split3i_kernel, gemm_split.hip): 0 never, 1 by the rule
+// of Builder::split3_adopts, 2 wherever eligible (irsde_debug_force_split3 overrides the knob for engines created afterwards); IRSDE_FLAG_NO_SPLIT3 = never
+int split3_mode();
+void set_force_split3(int mode);   // irsde_debug_force_split3
+// the rule's side that is known at weight-load time (profiles/split3.md): F(4x4,3x3) layers beyond the fused kernels' reach (Cin > 512; mode 2: every layer),
+// every polyphase layer
+constexpr int kSplit3WinoMinCin = 513;
+// every mode whose arithmetic is not the exact-fp32 engine's: the three-piece operands are never built there
+constexpr int kSplit3NotExactF32 = IRSDE_FLAG_NO_WINOGRAD | IRSDE_FLAG_NAIVE_CONV | IRSDE_FLAG_BF16 | IRSDE_FLAG_BF16_ACT | IRSDE_FLAG_FP16 | IRSDE_FLAG_F16_ACT |
+                                   IRSDE_FLAG_SPLIT_BF16X2 | IRSDE_FLAG_SPLIT_F16X2 | IRSDE_FLAG_NO_SPLIT3;
+inline bool split3_wants_weights(int flags) { return !(flags & kSplit3NotExactF32) && split3_mode() > 0; }
+
 inline int wino_min_c(int tile) {
     return tuning_env_int(tile == 4 ? "IRSDE_WINO4_MINC" : "IRSDE_WINO2_MINC", tile == 4 ? 64 : 256);
 }
@@ -92,6 +104,8 @@ struct ConvW {
     float wino_uf64p_scale = 1.f;
     unsigned short* wino_up = nullptr;  // IRSDE_FLAG_SPLIT_BF16X2 / _F16X2: the F(4x4,3x3) weights as hi / lo pairs, [36][Cout][Cin / 32][2][32]
     float wino_up_scale = 1.f;          // fp16 pairs: the power of two U was multiplied by (max |U| * scale <= 512)
+    unsigned short* wino_u4t = nullptr;    // exact fp32, Cin > 512: wino_u4 as three bf16 pieces, [36] x split3_layout.h of [Cout][Cin] (gemm_split3i_kernel's B operand)
+    unsigned short* wino_polyt = nullptr;  // exact fp32: wino_poly as three bf16 pieces, [25 | 100] x split3_layout.h of [Cout][4 Cin | Cin]
     float* wino_poly = nullptr;  // polyphase F(4x4,2x2) weights (exact fp32 mode): 4x4 stride-2 layers [25][Cout][4 Cin], nearest-x2 + 3x3 layers [100][Cout][Cin]
 };
 struct ResW {
@@ -254,6 +268,29 @@ inline WinoSplitPlan make_wino_pairs(const ConvParams& d, const unsigned short* 
     g.pA = T * Ctot; g.pB = (long long)d.Cout * Ctot; g.pO = T * d.Cout;
     g.M = (int)T; g.N = d.Cout; g.K = Ctot; g.lda = Ctot; g.ldc = d.Cout;
     return sp;
+}
+// exact fp32 on three bf16 pieces (gemm_split3i_kernel): Vs holds 36 components of split3_comp_elems(T, Ctot) unsigned shorts, Ut the weights' triples
+inline WinoSplitPlan make_wino_triples(const ConvParams& d, const unsigned short* Ut, unsigned short* Vs, float* Mb) {
+    const WinoPlan w = make_wino(d, nullptr, nullptr, Mb, 4);
+    WinoSplitPlan sp;
+    sp.in = w.in; sp.out = w.out; sp.nplanes = 3;
+    const int Ctot = d.C0 + d.C1;
+    const long long T = w.in.T;
+    sp.in.Vs = Vs; sp.in.nplanes = 3; sp.in.v_triples = 1;
+    SplitGemmArgs& g = sp.gemm;
+    g.a = Vs; g.b = Ut; g.out = Mb;
+    g.pA = (long long)split3_comp_elems((size_t)T, (size_t)Ctot); g.pB = (long long)split3_comp_elems((size_t)d.Cout, (size_t)Ctot); g.pO = T * d.Cout;
+    g.M = (int)T; g.N = d.Cout; g.K = Ctot; g.lda = Ctot; g.ldc = d.Cout;
+    return sp;
+}
+// the polyphase triple on three-piece operands: wp from make_wino_poly (V unused), Vs / Ut as above with K = wp.K
+inline SplitGemmArgs make_wino_poly_triples(WinoPolyPlan& wp, int Cout, const unsigned short* Ut, unsigned short* Vs, float* Mb) {
+    wp.in.Vs = Vs; wp.in.V = nullptr;
+    SplitGemmArgs g;
+    g.a = Vs; g.b = Ut; g.out = Mb;
+    g.pA = (long long)split3_comp_elems((size_t)wp.T, (size_t)wp.K); g.pB = (long long)split3_comp_elems((size_t)Cout, (size_t)wp.K); g.pO = wp.T * Cout;
+    g.M = (int)wp.T; g.N = Cout; g.K = wp.K; g.lda = wp.K; g.ldc = Cout;
+    return g;
 }
 // split mode: three-launch Winograd layers with at least this many input channels run the pair GEMM (below it the fused
 // f32 kernel is faster: profiles/r03_split_gemm_bench.txt); IRSDE_SPLIT_MINC moves the crossover (tuning only)

@@ -77,7 +77,7 @@ struct VariantScope {
 // The selector codes irsde_debug_conv / irsde_bench_conv know (see their branches): any other code is refused, never run as the production dispatch.
 bool code_in(const std::initializer_list<int>& codes, int c) { return std::find(codes.begin(), codes.end(), c) != codes.end(); }
 bool debug_conv_code_known(int c) {
-    return code_in({0, 1, 2, 3, 4, 5, 12, 13, 22, 23, 24, 25, 33, 34, 35, 36, 37, 42, 43, 44, 45, 46, 47, 55, 56, 62, 63, 204, 260, 261, 262, 263}, c) ||
+    return code_in({0, 1, 2, 3, 4, 5, 12, 13, 22, 23, 24, 25, 26, 27, 48, 33, 34, 35, 36, 37, 42, 43, 44, 45, 46, 47, 55, 56, 62, 63, 204, 260, 261, 262, 263}, c) ||
            code_in({100, 103, 105, 106, 107, 150, 160, 161, 162, 163, 165, 166, 167, 170, 171, 172, 173}, c);   // 100 + a launch_conv tuning variant
 }
 bool bench_conv_variant_known(int v) {
@@ -85,6 +85,7 @@ bool bench_conv_variant_known(int v) {
            code_in({80, 81, 82, 412, 413, 421, 422, 423, 430, 431, 432, 434, 435, 460, 461, 462, 465, 467, 468, 469, 480, 481, 482}, v) ||
            code_in({2001, 2002, 2004, 4650, 4651, 4652, 4653}, v) ||
            (v >= 83 && v <= 82 + 255) ||   // the 32-cout fused kernel with tuning-aid flags v - 82
+           (v >= 490 && v <= 494) ||       // the three-piece GEMM and its ablation twins (PROBES build; launch_gemm_split_triples refuses the ones it lacks)
            (v >= 472 && v <= 476);         // the pair GEMM's ablation twins (launch_gemm_split_pairs refuses the ones it lacks)
 }
 
@@ -419,7 +420,40 @@ int irsde_debug_conv(const float* in0, int C0, const float* in1, int C1, int B, 
             p.splits = splits;
             p.partial = mem.alloc<float>((size_t)splits * B * p.Ho * p.Wo * Cout);
         }
-        if (naive == 24 || naive == 25) {   // polyphase Winograd F(4x4,2x2): 24 a 4x4 stride-2 pad-1 layer, 25 a 3x3 pad-1 layer behind the nearest x2 upsample
+        if (naive == 26 || naive == 27) {   // selectors 24 / 25 with the component GEMMs on three bf16 pieces (gemm_split3i_kernel)
+            if (!(naive == 26 ? wino_poly_down_shape(p) : wino_poly_up_shape(p)) || !wino_poly_eligible(p) || splits > 1)
+                throw HipError("debug_conv: selectors 26 / 27 run what 24 / 25 run (single source, channels a multiple of 32, bias only)");
+            const int up = naive == 27;
+            std::vector<float> U((size_t)100 * Cout * Cin);
+            wino_poly_transform_weights(pk.data(), Cout, Cin, U.data(), up);
+            float* dU = mem.upload(U);
+            WinoPolyPlan wp = make_wino_poly(p, dU, nullptr, nullptr);
+            if (!gemm_split_triples_fits(wp.T, Cout, wp.K, Cout)) throw HipError("debug_conv: shape not eligible for the three-piece GEMM");
+            unsigned short* dUt = mem.alloc<unsigned short>((size_t)wp.ncomp * split3_comp_elems((size_t)Cout, (size_t)wp.K));
+            unsigned short* dVt = mem.alloc<unsigned short>((size_t)wp.ncomp * split3_comp_elems((size_t)wp.T, (size_t)wp.K));
+            float* dM = mem.alloc<float>((size_t)wp.ncomp * wp.T * Cout);
+            launch_split_triples(dU, dUt, wp.ncomp, (size_t)Cout, wp.K, s);
+            wp = make_wino_poly(p, dU, nullptr, dM);
+            const SplitGemmArgs sg = make_wino_poly_triples(wp, Cout, dUt, dVt, dM);
+            launch_wino_poly_input(wp.in, s);
+            launch_gemm_split_triples(sg, wp.ncomp, s);
+            launch_wino_poly_output(wp.out, s);
+        } else if (naive == 48) {   // three-launch Winograd F(4x4,3x3) on the exact-fp32 engine's three-piece GEMM
+            if (!wino_shape_ok(p, 4) || Cin % 32) throw HipError("debug_conv: shape not eligible for the three-piece GEMM");
+            std::vector<float> U((size_t)36 * Cout * Cin);
+            wino_transform_weights(pk.data(), Cout, Cin, U.data(), 4);
+            const long long T = (long long)B * (p.Ho / 4) * (p.Wo / 4);
+            if (!gemm_split_triples_fits(T, Cout, Cin, Cout)) throw HipError("debug_conv: shape not eligible for the three-piece GEMM");
+            float* dU = mem.upload(U);
+            unsigned short* dUt = mem.alloc<unsigned short>((size_t)36 * split3_comp_elems((size_t)Cout, (size_t)Cin));
+            unsigned short* dVt = mem.alloc<unsigned short>((size_t)36 * split3_comp_elems((size_t)T, (size_t)Cin));
+            float* dM = mem.alloc<float>((size_t)36 * T * Cout);
+            launch_split_triples(dU, dUt, 36, (size_t)Cout, Cin, s);
+            const WinoSplitPlan sp = make_wino_triples(p, dUt, dVt, dM);
+            launch_wino_input(sp.in, s);
+            launch_gemm_split_triples(sp.gemm, 36, s);
+            launch_wino_output(sp.out, s);
+        } else if (naive == 24 || naive == 25) {   // polyphase Winograd F(4x4,2x2): 24 a 4x4 stride-2 pad-1 layer, 25 a 3x3 pad-1 layer behind the nearest x2 upsample
             if (!(naive == 24 ? wino_poly_down_shape(p) : wino_poly_up_shape(p)) || !wino_poly_eligible(p) || splits > 1)
                 throw HipError(naive == 24 ? "debug_conv: selector 24 runs a 4x4 stride-2 pad-1 convolution (single source, channels a multiple of 32, bias only)"
                                            : "debug_conv: selector 25 runs a 3x3 stride-1 pad-1 convolution with in_shift = 1 (single source, channels a multiple of 32, bias only)");
@@ -557,11 +591,26 @@ int irsde_debug_conv(const float* in0, int C0, const float* in1, int C1, int B, 
 int irsde_debug_split_gemm(const float* A, const float* Bm, float* C, int M, int N, int K, int ncomp, int nplanes, void* stream) {
     return guard([&] {
         // nplanes 2 / 3: the 128 x 128 plane-major prototype kernel; 42 / 44: the engine's pair-interleaved two-plane kernel
-        if (nplanes != 2 && nplanes != 3 && nplanes != 42 && nplanes != 44) throw HipError("debug_split_gemm: nplanes must be 2, 3, 42 or 44");
+        // 43: the exact-fp32 engine's three-piece kernel (row-pair-interleaved triples, six products)
+        if (nplanes != 2 && nplanes != 3 && nplanes != 42 && nplanes != 43 && nplanes != 44) throw HipError("debug_split_gemm: nplanes must be 2, 3, 42, 43 or 44");
         hipStream_t s = reinterpret_cast<hipStream_t>(stream);
         conv_global_init();
         const size_t na = (size_t)ncomp * M * K, nb = (size_t)ncomp * N * K;
         Scratch mem(s);
+        if (nplanes == 43) {
+            if (!gemm_split_triples_fits(M, N, K, N)) throw HipError("debug_split_gemm: shape not eligible for the three-piece GEMM");
+            const size_t ea = split3_comp_elems((size_t)M, (size_t)K), eb = split3_comp_elems((size_t)N, (size_t)K);
+            unsigned short *ta = mem.alloc<unsigned short>(ea * ncomp), *tb = mem.alloc<unsigned short>(eb * ncomp);
+            launch_split_triples(A, ta, ncomp, (size_t)M, K, s);
+            launch_split_triples(Bm, tb, ncomp, (size_t)N, K, s);
+            SplitGemmArgs gt;
+            gt.a = ta; gt.b = tb; gt.out = C;
+            gt.pA = (long long)ea; gt.pB = (long long)eb; gt.pO = (long long)M * N;
+            gt.M = M; gt.N = N; gt.K = K; gt.lda = K; gt.ldc = N;
+            launch_gemm_split_triples(gt, ncomp, s);
+            IRSDE_HIP_CHECK(hipStreamSynchronize(s));
+            return;
+        }
         if (nplanes == 42 || nplanes == 44) {   // the pair-interleaved two-plane kernel (LDS-DMA, 256 x 256 tiles): 42 bf16 pieces, 44 fp16 pieces
             const bool f16 = nplanes == 44;
             const float sa = f16 ? 1.0f / 16.0f : 1.f, sb = f16 ? 64.0f : 1.f;   // (any powers of two: the hook exercises the scaling)
@@ -593,6 +642,11 @@ int irsde_debug_split_gemm(const float* A, const float* Bm, float* C, int M, int
 
 int irsde_debug_force_chain_groups(int g) {
     set_force_chain_groups(g == 1 || g == 2 || g == 4 ? g : 0);
+    return IRSDE_OK;
+}
+
+int irsde_debug_force_split3(int mode) {
+    set_force_split3(mode >= 0 && mode <= 2 ? mode : -1);
     return IRSDE_OK;
 }
 
@@ -759,6 +813,26 @@ int irsde_bench_conv(int variant, int B, int H, int W, int Cin, int Cout, int K,
             launch_split_pairs(dw, dwp, (size_t)Cout, K * K * Cin, s, variant != 481, 64.0f);
             p.w_pair = dwp; p.pair_scale = 1.0f / 64.0f; p.f16 = variant != 481 ? 1 : 0;
             variant = variant == 482 ? 61 : 0;
+        }
+        if (variant >= 490 && variant <= 494) {   // the three-piece component GEMMs alone (gemm_split3i_kernel): 490 full, 491 no loads, 493 no MFMAs, 494 no output stores
+            if (K != 3 || stride != 1 || !wino_shape_ok(p, 4)) throw HipError("bench_conv: Winograd variants need an eligible 3x3 stride-1 layer");
+            const long long T = (long long)B * (p.Ho / 4) * (p.Wo / 4);
+            if (!gemm_split_triples_fits(T, Cout, Cin, Cout)) throw HipError("bench_conv: shape not eligible for the three-piece GEMM");
+            const size_t ea = split3_comp_elems((size_t)T, (size_t)Cin), eb = split3_comp_elems((size_t)Cout, (size_t)Cin);
+            float *vf = mem.alloc<float>((size_t)36 * T * Cin), *uf = mem.alloc<float>((size_t)36 * Cout * Cin), *mo = mem.alloc<float>((size_t)36 * T * Cout);
+            unsigned short *vt = mem.alloc<unsigned short>(36 * ea), *ut = mem.alloc<unsigned short>(36 * eb);
+            launch_fill_random(vf, (size_t)36 * T * Cin, 7, 1.0f, s);
+            launch_fill_random(uf, (size_t)36 * Cout * Cin, 8, 0.05f, s);
+            launch_split_triples(vf, vt, 36, (size_t)T, Cin, s);
+            launch_split_triples(uf, ut, 36, (size_t)Cout, Cin, s);
+            SplitGemmArgs gt;
+            gt.a = vt; gt.b = ut; gt.out = mo;
+            gt.pA = (long long)ea; gt.pB = (long long)eb; gt.pO = T * Cout;
+            gt.M = (int)T; gt.N = Cout; gt.K = Cin; gt.lda = Cin; gt.ldc = Cout;
+            const int abl = variant - 490;
+            for (int i = 0; i < 2; ++i) launch_gemm_split_triples(gt, 36, s, abl);
+            *ms_out = time_launches(s, iters, [&] { launch_gemm_split_triples(gt, 36, s, abl); });
+            return;
         }
         if (variant >= 472 && variant <= 476) {   // the pair-interleaved two-plane component GEMMs alone (v3 kernel): 472 full, 473 no loads, 475 no MFMAs, 476 no output stores
             if (K != 3 || stride != 1 || !wino_shape_ok(p, 4)) throw HipError("bench_conv: Winograd variants need an eligible 3x3 stride-1 layer");

@@ -123,12 +123,12 @@ struct Builder {
         p.silu = silu;
         if (res) { p.res = res->p; p.res_stride = res->C; }
         if (!naive) {  // prefer F(4x4,3x3), then F(2x2,3x3), then the direct implicit GEMM
-            if (w.wino_poly && push_wino_poly(p, w.wino_poly)) return out;   // the resampling layers: polyphase F(4x4,2x2)
+            if (w.wino_poly && push_wino_poly(p, w.wino_poly, w.wino_polyt)) return out;   // the resampling layers: polyphase F(4x4,2x2)
             if (w.wino_up && wino_shape_ok(p, 4) && push_wino(p, w.wino_u4, 4, w.wino_up, w.wino_up_scale)) return out;
             if (w.wino_uf64p && push_wino_fused(p, reinterpret_cast<const float*>(w.wino_uf64p), true, w.wino_uf64p_scale)) return out;
             if (w.wino_uf64 && push_wino_fused(p, w.wino_uf64, true)) return out;
             if (w.wino_uf && push_wino_fused(p, w.wino_uf, false)) return out;
-            if (w.wino_u4 && wino_shape_ok(p, 4) && push_wino(p, w.wino_u4, 4)) return out;
+            if (w.wino_u4 && wino_shape_ok(p, 4) && push_wino(p, w.wino_u4, 4, nullptr, 1.f, w.wino_u4t)) return out;
             if (w.wino_u2 && wino_shape_ok(p, 2) && push_wino(p, w.wino_u2, 2)) return out;
         }
         push_conv(p);
@@ -209,7 +209,24 @@ struct Builder {
     // (0.13 ms at the f32 MFMA roof) — below that the two extra launches and the V / M round trip through HBM cost what the saved products gain (B = 4 at 256^2:
     // Downsample 0.137 against 0.139 ms; B = 2: Upsample 512 -> 256 0.189 against 0.183 ms).  An Upsample needs >= 512 input channels (ConvW::wino_poly exists
     // only then): below, the fused F(4x4,3x3) kernel, which keeps V and M out of HBM, is as fast.
-    bool push_wino_poly(const ConvParams& d, const float* U) {
+    // Do ncomp component GEMMs [T][K] x [Cout][K]^T run on three bf16 pieces (gemm_split3i_kernel)?  Ut: the weights' triples (exact-fp32 engines only).
+    // Rule (IRSDE_SPLIT3 = 1; measured per layer as input transform + GEMM, profiles/split3.md):
+    //   * at least 256 rows: the kernel's row tile is 256, a GEMM with fewer rows multiplies padding (T = 128, the B = 2 plan's deepest level: 0.107 -> 0.154 ms);
+    //   * at least 512 output channels: V is written at 6 bytes per element instead of 4 and every V element feeds Cout products, so a narrow layer pays more
+    //     in its input transform than its GEMM gains (polyphase up 512 -> 256 at T = 4096: transform 0.19 -> 0.48 ms, GEMM 0.79 -> 0.57 ms; polyphase down
+    //     64 -> 128 at T = 16384: 0.388 -> 0.406 ms together);
+    //   * at least 9e9 executed f32-equivalent FLOP, the smallest GEMM measured to win (512 -> 1024 at T = 256: 0.106 -> 0.100 ms).
+    static constexpr long long kSplit3MinRows = 256;
+    static constexpr int kSplit3MinCout = 512;
+    static constexpr double kSplit3MinFlop = 9e9;
+    bool split3_adopts(const unsigned short* Ut, long long T, int K, int Cout, int ncomp) const {
+        const int mode = split3_mode();
+        if (!Ut || mode <= 0 || naive || (e->cfg.flags & kSplit3NotExactF32) || !gemm_split_triples_fits(T, Cout, K, Cout)) return false;
+        return mode >= 2 || (T >= kSplit3MinRows && Cout >= kSplit3MinCout && ncomp * 2.0 * (double)T * K * Cout >= kSplit3MinFlop);
+    }
+    float* alloc_triples(int ncomp, long long rows, int K) { return pl->alloc(((size_t)ncomp * split3_comp_elems((size_t)rows, (size_t)K) + 1) / 2, true); }
+
+    bool push_wino_poly(const ConvParams& d, const float* U, const unsigned short* Ut = nullptr) {
         const int mode = wino_poly_mode();
         if (mode <= 0 || !wino_poly_eligible(d)) return false;
         ConvParams dd = d;
@@ -220,9 +237,12 @@ struct Builder {
         const double exec_flops = wp.ncomp * 2.0 * (double)T * wp.K * d.Cout;
         if (mode == 1 && (gemm_blocks < 2ll * device_cu_count() || exec_flops < 2e10)) return false;
         if ((unsigned long long)T * std::max(wp.K, d.Cout) * 4ull >= 0x7fffffffull) return false;   // a component's V / M slice stays below 2 GiB (32-bit buffer offsets in the GEMM)
-        float* V = pl->alloc((size_t)wp.ncomp * T * wp.K, true);
+        const bool tri = split3_adopts(Ut, T, wp.K, d.Cout, wp.ncomp);   // V at 6 bytes per element
+        float* V = tri ? alloc_triples(wp.ncomp, T, wp.K) : pl->alloc((size_t)wp.ncomp * T * wp.K, true);
         float* Mb = pl->alloc((size_t)wp.ncomp * T * d.Cout, true);
         wp = make_wino_poly(dd, U, V, Mb);
+        SplitGemmArgs sg;
+        if (tri) sg = make_wino_poly_triples(wp, d.Cout, Ut, reinterpret_cast<unsigned short*>(V), Mb);
         const char* what = wp.in.up ? "up" : "down";
         {
             Op op;
@@ -239,11 +259,13 @@ struct Builder {
             op.exec_flops = exec_flops;
             op.bytes = 4.0 * (double)d.B * d.Hin * d.Win * d.C0 + 4.0 * (double)d.B * d.Ho * d.Wo * d.Cout + 4.0 * (double)d.KH * d.KW * d.Cout * d.C0;
             char buf[256];
-            snprintf(buf, sizeof buf, "conv(winograd F4x2 poly %s gemm x%d) T=%lld Cout=%d Cin=%d K=%d flops=%.4g exec=%.4g", what, wp.ncomp, T, d.Cout, d.C0, wp.K,
-                     op.flops, op.exec_flops);
+            snprintf(buf, sizeof buf, "conv(winograd F4x2 poly %s gemm x%d) T=%lld Cout=%d Cin=%d K=%d flops=%.4g exec=%.4g%s", what, wp.ncomp, T, d.Cout, d.C0, wp.K,
+                     op.flops, op.exec_flops, tri ? " bf16x3" : "");
             op.desc = buf;
             const ConvParams g = wp.gemm;
-            op.fn = [g](hipStream_t s) { launch_conv(g, s); };
+            const int ncomp = wp.ncomp;
+            if (tri) op.fn = [sg, ncomp](hipStream_t s) { launch_gemm_split_triples(sg, ncomp, s); };
+            else op.fn = [g](hipStream_t s) { launch_conv(g, s); };
             push_op(std::move(op));
         }
         {
@@ -261,7 +283,8 @@ struct Builder {
 
     // Winograd F(2x2,3x3): input transform -> 16 batched GEMMs on the MFMA kernel -> output transform + epilogue
     // (Up: IRSDE_FLAG_SPLIT_BF16X2 — the component GEMMs on bf16 hi / lo pairs, gemm_split.hip)
-    bool push_wino(const ConvParams& d, const float* U, int tile, const unsigned short* Up = nullptr, float up_scale = 1.f) {
+    // (Ut: the exact-fp32 engine's three-piece weights — the component GEMMs on gemm_split3i_kernel where split3_adopts says so)
+    bool push_wino(const ConvParams& d, const float* U, int tile, const unsigned short* Up = nullptr, float up_scale = 1.f, const unsigned short* Ut = nullptr) {
         const int Ctot = d.C0 + d.C1;
         const int ncomp = (tile + 2) * (tile + 2);
         const long long T = (long long)d.B * (d.Ho / tile) * (d.Wo / tile);
@@ -272,12 +295,16 @@ struct Builder {
         // pair GEMM: 256 x 256 tiles (fewer than 256 output channels leave half of every tile empty: the fused f32 kernel is faster
         // there — 256 -> 128 @ 256^2: 1.88 vs 1.56 ms), 32-bit offsets per component
         if (Up && (T < 256 || d.Cout < 256 || (unsigned long long)T * Ctot * 4ull >= 0xffffffffull)) return false;
-        float* V = pl->alloc((size_t)ncomp * T * Ctot, true);   // (pairs: 2 planes x 2 bytes = the same size)
+        const bool tri = !Up && tile == 4 && split3_adopts(Ut, T, Ctot, d.Cout, ncomp);
+        float* V = tri ? alloc_triples(ncomp, T, Ctot) : pl->alloc((size_t)ncomp * T * Ctot, true);   // (pairs: 2 planes x 2 bytes = the same size; triples: 6 bytes)
         float* Mb = pl->alloc((size_t)ncomp * T * d.Cout, true);
         WinoPlan wp = make_wino(dd, U, V, Mb, tile);
         WinoSplitPlan sp;
         if (Up) {
             sp = make_wino_pairs(dd, Up, reinterpret_cast<unsigned short*>(V), Mb, (e->cfg.flags & IRSDE_FLAG_SPLIT_F16X2) != 0, up_scale);
+            wp.in = sp.in;
+        } else if (tri) {
+            sp = make_wino_triples(dd, Ut, reinterpret_cast<unsigned short*>(V), Mb);
             wp.in = sp.in;
         }
         const double direct = conv_flops(d);
@@ -297,10 +324,13 @@ struct Builder {
             const double in_bytes = 4.0 * (double)d.B * d.Hin * d.Win * Ctot;
             op.bytes = in_bytes + 4.0 * (double)d.B * d.Ho * d.Wo * d.Cout + 4.0 * 9.0 * (double)d.Cout * Ctot;
             char buf[256];
-            snprintf(buf, sizeof buf, "conv(%s F%d gemm x%d) T=%lld Cout=%d Cin=%d flops=%.4g exec=%.4g", Up ? (sp.f16 ? "split f16x2 winograd" : "split bf16x2 winograd") : "winograd", tile, ncomp, T,
-                     d.Cout, Ctot, op.flops, op.exec_flops);
+            snprintf(buf, sizeof buf, "conv(%s F%d gemm x%d) T=%lld Cout=%d Cin=%d flops=%.4g exec=%.4g%s", Up ? (sp.f16 ? "split f16x2 winograd" : "split bf16x2 winograd") : "winograd", tile, ncomp, T,
+                     d.Cout, Ctot, op.flops, op.exec_flops, tri ? " bf16x3" : "");
             op.desc = buf;
-            if (Up) {
+            if (tri) {
+                const SplitGemmArgs sg = sp.gemm;
+                op.fn = [sg](hipStream_t s) { launch_gemm_split_triples(sg, 36, s); };
+            } else if (Up) {
                 const SplitGemmArgs sg = sp.gemm;
                 const bool f16 = sp.f16;
                 op.fn = [sg, f16](hipStream_t s) { launch_gemm_split_pairs(sg, 36, s, 0, f16); };
@@ -1007,6 +1037,12 @@ int forced_chain_groups() { return g_force_chain_groups.load(std::memory_order_r
 static std::atomic<int> g_force_scam_stream{0};   // irsde_debug_force_scam_stream: 0 = the rule (Builder::scam_stream_bw), else the block width of every SCAM core
 void set_force_scam_stream(int block_w) { g_force_scam_stream.store(block_w, std::memory_order_relaxed); }
 int forced_scam_stream() { return g_force_scam_stream.load(std::memory_order_relaxed); }
+static std::atomic<int> g_force_split3{-1};   // irsde_debug_force_split3: -1 = the IRSDE_SPLIT3 knob
+void set_force_split3(int mode) { g_force_split3.store(mode, std::memory_order_relaxed); }
+int split3_mode() {
+    const int f = g_force_split3.load(std::memory_order_relaxed);
+    return f >= 0 ? f : tuning_env_int("IRSDE_SPLIT3", 1);
+}
 static std::atomic<int> g_force_wino_poly{-1};   // irsde_debug_force_wino_poly: -1 = the IRSDE_WINO_POLY knob
 void set_force_wino_poly(int mode) { g_force_wino_poly.store(mode, std::memory_order_relaxed); }
 int wino_poly_mode() {

@@ -104,6 +104,17 @@ const HostTensor& need(irsde_engine* e, const std::string& n) {
     return it->second;
 }
 
+// three bf16 pieces of a device tensor U [ncomp][rows][K] (split3_layout.h), made on the device once; null where the GEMM could not address them
+static unsigned short* upload_triples(irsde_engine* e, const float* U, int ncomp, int rows, int K) {
+    if (!gemm_split_triples_fits(rows, rows, K, rows)) return nullptr;
+    unsigned short* ut = nullptr;
+    IRSDE_HIP_CHECK(hipMalloc(&ut, (size_t)ncomp * split3_comp_elems((size_t)rows, (size_t)K) * 2));
+    e->dev_allocs.push_back(reinterpret_cast<float*>(ut));
+    launch_split_triples(U, ut, ncomp, (size_t)rows, K, e->stream);
+    IRSDE_HIP_CHECK(hipStreamSynchronize(e->stream));
+    return ut;
+}
+
 // OIHW -> [O][KH][KW][I]
 // resample: 0 = plain layer, 1 = the layer reads its input through the nearest x2 upsample (a 4x4 layer is a stride-2 Downsample)
 ConvW pack_conv(irsde_engine* e, const std::string& wname, const std::string& bname, int resample = 0) {
@@ -128,6 +139,7 @@ ConvW pack_conv(irsde_engine* e, const std::string& wname, const std::string& bn
         std::vector<float> U((size_t)(poly_up ? 100 : 25 * 4) * O * I);
         wino_poly_transform_weights(p.data(), O, I, U.data(), poly_up ? 1 : 0);
         c.wino_poly = e->upload(U);
+        if (split3_wants_weights(e->cfg.flags)) c.wino_polyt = upload_triples(e, c.wino_poly, poly_up ? 100 : 25, O, poly_up ? I : 4 * I);
     }
     if (KH == 3 && KW == 3 && I % 32 == 0 && !(e->cfg.flags & (IRSDE_FLAG_NO_WINOGRAD | IRSDE_FLAG_BF16))) {
         for (int tile : {2, 4}) {
@@ -136,6 +148,7 @@ ConvW pack_conv(irsde_engine* e, const std::string& wname, const std::string& bn
             std::vector<float> U((size_t)(tile + 2) * (tile + 2) * O * I);
             wino_transform_weights(p.data(), O, I, U.data(), tile);
             (tile == 4 ? c.wino_u4 : c.wino_u2) = e->upload(U);
+            if (tile == 4 && (I >= kSplit3WinoMinCin || split3_mode() >= 2) && split3_wants_weights(e->cfg.flags)) c.wino_u4t = upload_triples(e, c.wino_u4, 36, O, I);
             if (tile == 4 && (e->cfg.flags & (IRSDE_FLAG_SPLIT_BF16X2 | IRSDE_FLAG_SPLIT_F16X2)) && I >= split_min_cin()) {
                 unsigned short* up = nullptr;   // hi / lo pairs of U, made on the device once
                 IRSDE_HIP_CHECK(hipMalloc(&up, U.size() * 4));

@@ -8,8 +8,11 @@
 //     NPL = 2:  a b ~= a0 b0 + (a0 b1 + a1 b0)                                3 MFMAs, dropped terms <= 3 * 2^-18 |a b|
 // i.e. NPL = 3 carries the operands' full 24 bits (the dropped part is below f32's own 2^-24 rounding of each
 // accumulation) at 6/16 of the f32-MFMA cycles; NPL = 2 is a 16-bit-significand mode at 3/16.  Accumulation is f32 in both.
-// This is NOT the bit-exact fmaf chain of the native kernels (different rounding points), so it is an opt-in engine mode
-// (IRSDE_FLAG_SPLIT_BF16 / IRSDE_FLAG_SPLIT_BF16X2) with its own measured error table (profiles/r03_split_gemm_*.txt).
+// This is NOT the bit-exact fmaf chain of the native kernels (different rounding points).  NPL = 2 is an opt-in engine mode
+// (IRSDE_FLAG_SPLIT_BF16X2 / _F16X2) with its own measured error table (profiles/r03_split_gemm_*.txt).  NPL = 3 is fp32-equivalent and, on
+// gemm_split3i_kernel below, the exact-fp32 engine's default for its deep component GEMMs (profiles/split3.md; IRSDE_FLAG_NO_SPLIT3 restores the
+// f32 MFMA kernels bit for bit).  The r03 verdict "no faster than native" belongs to the 128 x 128 plane-major prototype (gemm_split_kernel<3>,
+// vector-memory-bound: 0.71 against 0.57 ms for 1024^3 x 36), which stays as the kernel-level cross-check of irsde_debug_split_gemm.
 //
 // Where: the component GEMMs of the three-launch Winograd layers, M_z[t][n] = sum_c V_z[t][c] U_z[n][c] (reference call site:
 // Block.proj, module_util.py:108-122).  wino.hip writes V already split (NPL planes of bf16: 2 NPL bytes per element instead
@@ -374,7 +377,174 @@ __global__ __launch_bounds__(512, 2) void gemm_split2i_kernel(const SplitGemmArg
     }
     flush(0);
 }
+// ---------------------------------------------------------------------------------------------------------------
+// Three pieces on that structure: the exact-fp32 engine's deep component GEMMs (Winograd F(4x4,3x3) with Cin > 512, polyphase F(4x4,2x2)).
+// Operands: three bf16 planes, row-pair-interleaved (split3_layout.h: [row / 2][k / 32][row % 2][plane][32 k], 384-byte blocks = whole lines).
+// Per 16-k sub-step and output tile the six products are accumulated SMALLEST FIRST, in this fixed order:
+//     a0 b2, a1 b1, a2 b0   (<= 2^-18 |a b|),   a0 b1, a1 b0   (<= 2^-9 |a b|),   a0 b0
+// i.e. the four smallest cross terms have gone into the accumulator before the two that carry 2^-9 |a b| and more; every product is exact,
+// the accumulator rounds once per MFMA (f32), the dropped products a1 b2 + a2 b1 + a2 b2 are <= 3 * 2^-27 |a b|.
+// Block tile 256 x 128, 8 waves of 64 x 64 (2 x 2 MFMA tiles), K-step 32, two LDS stages of (256 + 128) x 192 B = 72 KB: 384 MFMAs per CU and K-step, as
+// many as the pair kernel's, for 72 KB of fill instead of 64.  One block per CU (144 KB of LDS), 2 waves per SIMD.
+// Staging: a stage is 24 groups of 16 rows (16 of A, 8 of B), a group 3 LDS-DMA wave-loads (16 rows x 12 pieces of 16 B = 192 lane slots); wave w stages the
+// A groups 2w, 2w + 1 and the B group w: 9 wave-loads per wave and K-step.  The LDS image of a group is lane-linear: slot = row * 12 + position, and a row's
+// piece j = plane * 4 + (k / 8) sits at position (j + ((row >> 2) & 3)) mod 12 — the rotation goes on the per-lane SOURCE address and on the fragment reads
+// (cdna_hip_programming.md rule 21).  With it the 16 rows of a ds_read_b128 lane group ({0-3, 12-15, 20-27} / {4-11, 16-19, 28-31} of a 32-row tile: every
+// residue mod 16 once) land on 16 different 16-byte bank slots: 192-byte rows alone put them on four (12 r mod 16).
+// Synchronisation as in the pair kernel: the loads of K-step t+1 are issued behind the first MFMA groups of step t, into the stage every wave finished
+// reading before the barrier that ended step t-1; __syncthreads() (vmcnt(0) + lgkmcnt(0) + s_barrier) ends a step, so every fragment read of step t+1
+// comes after the barrier behind which all of its stage's DMA writes have landed.
+// ---------------------------------------------------------------------------------------------------------------
+template <int ABL = 0>
+__global__ __launch_bounds__(512, 1) void gemm_split3i_kernel(const SplitGemmArgs g) {
+    constexpr int TM = 2, TN = 2, WN = 2, BM = 256, BN = 128;
+    constexpr int ROWB = 192, GROUP = 16 * ROWB;                       // bytes per LDS row (12 pieces) and per 16-row group
+    constexpr int A_STAGE = BM * ROWB, STAGE = (BM + BN) * ROWB;       // bytes
+    // smallest products first (see above): plane of A, plane of B
+    constexpr int PA[6] = {0, 1, 2, 0, 1, 0};
+    constexpr int PB[6] = {2, 1, 0, 1, 0, 0};
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave / WN, wn = wave % WN;
+    const int l31 = lane & 31, h = lane >> 5;
+    // XCD-contiguous (component, row tile) units with all their column tiles side by side, as in gemm_split2i_kernel
+    const int mtiles = (g.M + BM - 1) / BM;
+    const int units = mtiles * g.n_inner;          // (n_inner carries the component count here)
+    const int xcd = blockIdx.x & 7, jx = blockIdx.x >> 3;
+    const int ulo = (int)((long long)xcd * units / 8), uhi = (int)((long long)(xcd + 1) * units / 8);
+    const int unit = ulo + jx / g.nblk_n;
+    if (unit >= uhi) return;
+    const int nblk = jx % g.nblk_n;
+    const int plane0 = unit / mtiles, mblk = unit - plane0 * mtiles;
+    const int m0 = mblk * BM, n0 = nblk * BN;
+    const int nk = g.K / SG_BK;
+    const unsigned pairb = (unsigned)nk * 384u;   // bytes per operand row pair: K / 32 blocks of 2 rows x 3 planes x 64 B
+
+    // staging: lane slot s = wl * 64 + lane of a group = (row s / 12, position s % 12); the lane fetches the row's piece (position - rotation) mod 12.
+    // Rows past M / N are clamped: they feed accumulator rows / columns that are never stored.
+    unsigned a_voff[6], b_voff[3];
+#pragma unroll
+    for (int q = 0; q < 9; ++q) {
+        const int gi = q / 3, wl = q - gi * 3;     // gi 0, 1: the wave's A groups, 2: its B group
+        const int sl = wl * 64 + lane;
+        const int r = sl / 12, pos = sl - r * 12;
+        int j = pos - ((r >> 2) & 3);
+        j = j < 0 ? j + 12 : j;
+        if (gi < 2) {
+            int m = m0 + (2 * wave + gi) * 16 + r;
+            m = m < g.M ? m : g.M - 1;
+            a_voff[q] = (unsigned)(m >> 1) * pairb + (unsigned)(m & 1) * 192u + (unsigned)j * 16u;
+        } else {
+            int n = n0 + wave * 16 + r;
+            n = n < g.N ? n : g.N - 1;
+            b_voff[wl] = (unsigned)(n >> 1) * pairb + (unsigned)(n & 1) * 192u + (unsigned)j * 16u;
+        }
+    }
+    const char* acomp = reinterpret_cast<const char*>(g.a) + (long long)plane0 * g.pA * 2;   // pA / pB: unsigned shorts per component
+    const char* bcomp = reinterpret_cast<const char*>(g.b) + (long long)plane0 * g.pB * 2;
+    int kb = 0;
+    auto issue_loads_part = [&](int buf, int part) {   // the 9 loads of a stage in three groups: A group 2w | A group 2w+1 | B group w
+        const char* gsrc = (part < 2 ? acomp : bcomp) + (size_t)kb * 384;
+        char* l = lds + buf * STAGE + (part < 2 ? (2 * wave + part) * GROUP : A_STAGE + wave * GROUP);
+#pragma unroll
+        for (int wl = 0; wl < 3; ++wl) IRSDE_GLDS16(gsrc + (part < 2 ? a_voff[part * 3 + wl] : b_voff[wl]), l + wl * 1024);
+    };
+
+    floatx16 acc[TM][TN];
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+#pragma unroll
+    for (int part = 0; part < 3; ++part) issue_loads_part(0, part);
+    __syncthreads();
+
+    // fragment offsets: row l31 of a 32-row tile (two 16-row groups back to back = 192 bytes per row), piece plane * 4 + sb * 2 + h, rotated by (row >> 2) & 3
+    int fr_off[3][2];
+#pragma unroll
+    for (int p = 0; p < 3; ++p)
+#pragma unroll
+        for (int sb = 0; sb < 2; ++sb) fr_off[p][sb] = l31 * ROWB + ((p * 4 + sb * 2 + h + ((l31 >> 2) & 3)) % 12) * 16;
+    for (int st = 0; st < nk; ++st) {
+        const int buf = st & 1;
+        const bool more = st + 1 < nk;
+        if (more) ++kb;   // (stage buf^1 was last read in step st-1: every wave is past that step's barrier when the loads below are issued)
+        const char* a = lds + buf * STAGE + wm * TM * 32 * ROWB;
+        const char* b = lds + buf * STAGE + A_STAGE + wn * TN * 32 * ROWB;
+        bf16x8 fa[2][3][TM], fb[2][3][TN];
+#pragma unroll
+        for (int sb = 0; sb < 2; ++sb)
+#pragma unroll
+            for (int p = 0; p < 3; ++p) {
+#pragma unroll
+                for (int i = 0; i < TM; ++i) fa[sb][p][i] = *reinterpret_cast<const bf16x8*>(a + i * 32 * ROWB + fr_off[p][sb]);
+#pragma unroll
+                for (int j = 0; j < TN; ++j) fb[sb][p][j] = *reinterpret_cast<const bf16x8*>(b + j * 32 * ROWB + fr_off[p][sb]);
+            }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int sb = 0; sb < 2; ++sb)
+#pragma unroll
+            for (int pr = 0; pr < 6; ++pr) {
+#pragma unroll
+                for (int i = 0; i < TM; ++i)
+#pragma unroll
+                    for (int j = 0; j < TN; ++j) {
+                        if (ABL != 3) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[sb][PA[pr]][i], fb[sb][PB[pr]][j], acc[i][j], 0, 0, 0);
+                        else acc[i][j][0] += (float)fa[sb][PA[pr]][i][0] * (float)fb[sb][PB[pr]][j][0];
+                    }
+                if (sb == 0 && pr < 3 && ABL != 1 && more) issue_loads_part(buf ^ 1, pr);   // 3 + 3 + 3 loads behind the first three MFMA groups
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        __syncthreads();
+    }
+
+    // registers -> buffer stores: rows past M dropped by the descriptor, columns past N masked
+    const int rowb_ = m0 + wm * TM * 32, colb = n0 + wn * TN * 32;
+    float* ob = g.out + (long long)plane0 * g.pO + (long long)rowb_ * g.ldc;
+    const int rows = g.M - rowb_;
+    const unsigned nrec = rows <= 0 ? 0u : (unsigned)(rows < TM * 32 ? rows : TM * 32) * (unsigned)g.ldc * 4u;
+    const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(ob, 0, nrec, 0x00020000);
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+            const int colu = colb + j * 32;
+            if (colu + l31 < g.N && (ABL != 4 || acc[i][j][0] == 1.2345e30f)) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const float v = acc[i][j][r];
+                    // (the whole offset in the vector operand: that is the part the descriptor's range check is sure to cover)
+                    const unsigned voff = (unsigned)((i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h) * g.ldc + colu + l31) * 4u;
+                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), ro, (int)voff, 0, 0);
+                }
+            }
+        }
+}
 #undef IRSDE_GLDS16
+
+// f32 [ncomp][rows][K] -> the three-piece row-pair-interleaved layout (split3_layout.h)
+__global__ __launch_bounds__(256) void split_triples_kernel(const float* __restrict__ in, unsigned short* __restrict__ out, const size_t n, const size_t rows,
+                                                            const int K) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const size_t rk = rows * (size_t)K;
+    const size_t z = i / rk, rem = i - z * rk;
+    const size_t row = rem / K;
+    const int k = (int)(rem - row * K);
+    float r = in[i];
+    unsigned short* o = out + z * split3_comp_elems(rows, K);
+#pragma unroll
+    for (int p = 0; p < 3; ++p) {
+        const __bf16 hb = (__bf16)r;
+        o[split3_index(row, k, p, K / 32)] = __builtin_bit_cast(unsigned short, hb);
+        r -= (float)hb;
+    }
+}
 
 // f32 -> pair-interleaved hi / lo pieces: element (row, k) of a [rows][K] matrix -> out[(row * K / 32 + k / 32) * 64 + plane * 32 + k % 32].
 // F16: the pieces are IEEE binary16 of in * scale (scale = a power of two that brings the tensor into fp16's range).
@@ -433,6 +603,12 @@ void gemm_split_global_init() {
     IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split2i_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split2i_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split2i_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split3i_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+#ifdef IRSDE_PROBES
+    IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split3i_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split3i_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split3i_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+#endif
     IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
 }
@@ -474,6 +650,45 @@ void launch_gemm_split_pairs(const SplitGemmArgs& a, int ncomp, hipStream_t s, i
         case 4: hipLaunchKernelGGL(gemm_split2i_kernel<4>, grid, dim3(512), lds, s, g); break;
         default: throw HipError("gemm_split_pairs: bad ablation variant");
     }
+    IRSDE_HIP_CHECK(hipGetLastError());
+}
+
+bool gemm_split_triples_fits(long long M, long long N, long long K, long long ldc) {
+    if (M < 1 || N < 1 || K < 32 || K % SG_BK) return false;
+    return (unsigned long long)split3_comp_elems((size_t)M, (size_t)K) * 2ull < 0xffffffffull && (unsigned long long)split3_comp_elems((size_t)N, (size_t)K) * 2ull < 0xffffffffull &&
+           (unsigned long long)M * ldc * 4ull < 0xffffffffull;
+}
+
+// three-piece row-pair-interleaved operands (split3_layout.h; g.pA / g.pB = unsigned shorts per component)
+void launch_gemm_split_triples(const SplitGemmArgs& a, int ncomp, hipStream_t s, int abl) {
+    if (a.K % SG_BK) throw HipError("gemm_split_triples: K must be a multiple of 32");
+    if (!gemm_split_triples_fits(a.M, a.N, a.K, a.ldc)) throw HipError("gemm_split_triples: a component exceeds the 32-bit offset range");
+    if (ncomp < 1 || a.ldc < a.N) throw HipError("gemm_split_triples: bad component count or output stride");
+    SplitGemmArgs g = a;
+    g.nblk_n = (a.N + 127) / 128;
+    g.n_inner = ncomp;   // one (component, row tile, column tile) per block; n_inner carries the component count
+    const long long units = (long long)((a.M + 255) / 256) * ncomp;
+    long long per_xcd = 0;
+    for (int x = 0; x < 8; ++x) per_xcd = std::max(per_xcd, (x + 1) * units / 8 - x * units / 8);
+    if (8 * per_xcd * g.nblk_n >= 0x7fffffffll) throw HipError("gemm_split_triples: grid too large");
+    const dim3 grid((unsigned)(8 * per_xcd * g.nblk_n));
+    const size_t lds = (size_t)2 * (256 + 128) * 192;
+    switch (abl) {
+        case 0: hipLaunchKernelGGL(gemm_split3i_kernel<0>, grid, dim3(512), lds, s, g); break;
+#ifdef IRSDE_PROBES
+        case 1: hipLaunchKernelGGL(gemm_split3i_kernel<1>, grid, dim3(512), lds, s, g); break;
+        case 3: hipLaunchKernelGGL(gemm_split3i_kernel<3>, grid, dim3(512), lds, s, g); break;
+        case 4: hipLaunchKernelGGL(gemm_split3i_kernel<4>, grid, dim3(512), lds, s, g); break;
+#endif
+        default: throw HipError("gemm_split_triples: the ablation twins are part of the PROBES build");
+    }
+    IRSDE_HIP_CHECK(hipGetLastError());
+}
+
+void launch_split_triples(const float* in, unsigned short* out, int ncomp, size_t rows, int K, hipStream_t s) {
+    if (K % 32 || ncomp < 1 || rows < 1) throw HipError("split_triples: K must be a multiple of 32");
+    const size_t n = (size_t)ncomp * rows * (size_t)K;
+    hipLaunchKernelGGL(split_triples_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, in, out, n, rows, K);
     IRSDE_HIP_CHECK(hipGetLastError());
 }
 

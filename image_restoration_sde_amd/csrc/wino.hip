@@ -135,8 +135,10 @@ __global__ __launch_bounds__(256) void wino_input_kernel(const WinoParams p) {
 // Split-operand mode (gemm_split.hip): the same F(4x4,3x3) input transform, 4 channels per thread, but every V element is
 // written as NPL bf16 pieces (round to nearest even, residual exact in f32) into NPL planes: 2 NPL bytes per element instead
 // of 4, and the component GEMMs become bf16 GEMMs with f32-equivalent (NPL = 3) or 16-bit (NPL = 2) operands.
-template <int NPL, bool PAIRS = false, bool F16 = false>
+// TRI: the three planes in the row-pair-interleaved layout of split3_layout.h (gemm_split3i_kernel's operands)
+template <int NPL, bool PAIRS = false, bool F16 = false, bool TRI = false>
 __global__ __launch_bounds__(256) void wino_input_split_kernel(const WinoParams p) {
+    static_assert(!TRI || (NPL == 3 && !PAIRS && !F16), "three bf16 pieces");
     constexpr int A = 6;
     const int C4 = (p.C0 + p.C1) / 4;
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -185,9 +187,10 @@ __global__ __launch_bounds__(256) void wino_input_split_kernel(const WinoParams 
     }
     const size_t Ctot = (size_t)(p.C0 + p.C1);
     // PAIRS: [component][tile][c / 32][plane][c % 32] (both pieces of a 32-channel block in one 128-byte line)
-    unsigned short* vp = PAIRS ? p.Vs + ((size_t)t * (Ctot / 32) + c / 32) * 64 + (c & 31) : p.Vs + (size_t)t * Ctot + c;
-    const size_t kstride = PAIRS ? (size_t)p.T * Ctot * 2 : (size_t)p.T * Ctot;
-    const size_t plstride = PAIRS ? 32 : (size_t)p.v_plane;
+    unsigned short* vp = TRI ? p.Vs + split3_index((size_t)t, (size_t)c, 0, Ctot / 32)
+                       : PAIRS ? p.Vs + ((size_t)t * (Ctot / 32) + c / 32) * 64 + (c & 31) : p.Vs + (size_t)t * Ctot + c;
+    const size_t kstride = TRI ? split3_comp_elems((size_t)p.T, Ctot) : PAIRS ? (size_t)p.T * Ctot * 2 : (size_t)p.T * Ctot;
+    const size_t plstride = TRI || PAIRS ? 32 : (size_t)p.v_plane;
 #pragma unroll
     for (int r = 0; r < A; ++r) {
         float4 o[A];
@@ -300,7 +303,8 @@ __device__ __forceinline__ void at5_apply(const float4* m, float4* y) {
 }
 
 // one thread = (tile, phase, 4 channels): the phase's 5x5 patch (down: every second pixel from (8 ty - 1 + p, 8 tx - 1 + q); up: from (4 ty - 1 + py, 4 tx - 1 + px))
-template <bool UP>
+// TRI: V as three bf16 pieces in the layout of split3_layout.h (p.Vs) instead of f32 (p.V)
+template <bool UP, bool TRI = false>
 __global__ __launch_bounds__(256) void wino_poly_input_kernel(const WinoPolyParams p) {
     const int C4 = p.C / 4;
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -350,7 +354,29 @@ __global__ __launch_bounds__(256) void wino_poly_input_kernel(const WinoPolyPara
         float4 o[5];
         bt5_apply(w[r], o);
 #pragma unroll
-        for (int s = 0; s < 5; ++s) *reinterpret_cast<float4*>(vp + (size_t)(r * 5 + s) * kstride) = o[s];
+        for (int s = 0; s < 5; ++s) {
+            if constexpr (TRI) {
+                const size_t z = (UP ? (size_t)ph * 25 : 0) + (size_t)(r * 5 + s);
+                unsigned short* q = p.Vs + z * split3_comp_elems((size_t)p.T, K) + split3_index((size_t)t, UP ? (size_t)c : (size_t)ph * p.C + c, 0, K / 32);
+                float rem[4] = {o[s].x, o[s].y, o[s].z, o[s].w};
+#pragma unroll
+                for (int pl = 0; pl < 3; ++pl) {
+                    unsigned short b[4];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const __bf16 hb = (__bf16)rem[e];
+                        b[e] = __builtin_bit_cast(unsigned short, hb);
+                        rem[e] -= (float)hb;
+                    }
+                    uint2 pk;
+                    pk.x = (unsigned)b[0] | ((unsigned)b[1] << 16);
+                    pk.y = (unsigned)b[2] | ((unsigned)b[3] << 16);
+                    *reinterpret_cast<uint2*>(q + pl * 32) = pk;
+                }
+            } else {
+                *reinterpret_cast<float4*>(vp + (size_t)(r * 5 + s) * kstride) = o[s];
+            }
+        }
     }
 }
 
@@ -422,7 +448,11 @@ void launch_wino_poly_input(const WinoPolyParams& p, hipStream_t s) {
     wino_poly_check(p, false);
     const long long total = (long long)p.T * p.C;   // T * 4 phases * C / 4
     const dim3 grid((unsigned)((total + 255) / 256));
-    if (p.up) hipLaunchKernelGGL((wino_poly_input_kernel<true>), grid, dim3(256), 0, s, p);
+    if (p.Vs) {
+        if (p.C % 32) throw HipError("wino_poly_input (triples): channels must be a multiple of 32");
+        if (p.up) hipLaunchKernelGGL((wino_poly_input_kernel<true, true>), grid, dim3(256), 0, s, p);
+        else hipLaunchKernelGGL((wino_poly_input_kernel<false, true>), grid, dim3(256), 0, s, p);
+    } else if (p.up) hipLaunchKernelGGL((wino_poly_input_kernel<true>), grid, dim3(256), 0, s, p);
     else hipLaunchKernelGGL((wino_poly_input_kernel<false>), grid, dim3(256), 0, s, p);
     IRSDE_HIP_CHECK(hipGetLastError());
 }
@@ -487,7 +517,10 @@ void launch_wino_input(const WinoParams& p, hipStream_t s) {
         if (p.tile != 4 || (p.nplanes != 2 && p.nplanes != 3) || (p.C0 % 4) || (p.C1 % 4)) throw HipError("wino_input (split): F(4x4,3x3), 2 or 3 planes");
         const long long tot = (long long)p.T * ((p.C0 + p.C1) / 4);
         const dim3 gr((unsigned)((tot + 255) / 256));
-        if (p.v_pairs) {
+        if (p.v_triples) {
+            if (p.nplanes != 3 || p.v_pairs || p.v_f16 || (p.C0 + p.C1) % 32) throw HipError("wino_input (triples): three bf16 planes, channels a multiple of 32");
+            hipLaunchKernelGGL((wino_input_split_kernel<3, false, false, true>), gr, dim3(256), 0, s, p);
+        } else if (p.v_pairs) {
             if (p.nplanes != 2 || (p.C0 + p.C1) % 32) throw HipError("wino_input (pairs): two planes, channels a multiple of 32");
             if (p.v_f16) hipLaunchKernelGGL((wino_input_split_kernel<2, true, true>), gr, dim3(256), 0, s, p);
             else hipLaunchKernelGGL((wino_input_split_kernel<2, true, false>), gr, dim3(256), 0, s, p);

@@ -48,6 +48,11 @@
  *        Additive, same version: IRSDE_FLAG_SCAM_STREAM (the stereo networks on rows of any width: SCAMs beyond the strip kernels' width run a streaming
  *        online-softmax core, csrc/scam_stream.hip; narrower ones and engines without the flag are unchanged); debug header: irsde_debug_scam_stream,
  *        irsde_debug_scam_full_stream, irsde_debug_force_scam_stream.
+ *        Additive, same version: IRSDE_FLAG_NO_SPLIT3 (the exact-fp32 ConditionalUNet runs the component GEMMs of its Winograd F(4x4,3x3) layers with more
+ *        than 512 input channels and of its polyphase layers on the bf16 MFMA by default, where the plan's rule adopts it: every operand as three bf16
+ *        pieces = all 24 significand bits, six exact products, fp32 accumulation — fp32-equivalent results, not the bit-for-bit fmaf chain; the flag
+ *        restores that).  Debug header: irsde_debug_force_split3, irsde_debug_conv selectors 26 / 27 / 48, irsde_debug_split_gemm nplanes 43,
+ *        irsde_bench_conv 490 - 494.
  */
 #ifndef IRSDE_HIP_H
 #define IRSDE_HIP_H
@@ -191,6 +196,10 @@ enum {
                                         Every narrower SCAM keeps its strip kernel, so on inputs inside the old limits the results are bit-identical to an engine
                                         without the flag.  Limits under the flag: any width; at most 65535 image rows per SCAM launch (B * H' <= 65535, H' the
                                         level's height, / 4 for the NAFNet); the channel limits above */
+    IRSDE_FLAG_NO_SPLIT3 = 4194304,   /* measurement only: keep the deep component GEMMs of the exact-fp32 ConditionalUNet (Winograd F(4x4,3x3) layers with Cin > 512,
+                                        polyphase F(4x4,2x2) layers) on the f32 MFMA kernels: the bit-for-bit arithmetic of the engine before the three-piece
+                                        path.  Default: three bf16 pieces per operand and six products on the bf16 MFMA where the plan's rule adopts them
+                                        (csrc/gemm_split.hip gemm_split3i_kernel, profiles/split3.md); no effect in the other operand modes, which never use it */
     IRSDE_FLAG_NO_WINOGRAD_F43 = 8   /* Winograd F(2x2,3x3) only (>= 256 channels); default also uses F(4x4,3x3) from 128
                                         channels up where H, W are multiples of 4 */
 };

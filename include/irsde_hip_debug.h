@@ -23,6 +23,8 @@ extern "C" {
  *   24 / 25 polyphase Winograd F(4x4,2x2) (csrc/wino.hip: wino_poly_input_kernel, the component GEMMs, wino_poly_output_kernel): 24 a 4x4 stride-2 pad-1
  *           layer (25 components, K = 4 C0), 25 a 3x3 stride-1 pad-1 layer with in_shift = 1 (4 output phases x 25 components); single source, C0 a multiple
  *           of 32, Cout of 4, bias only — anything else (film, silu, res, in1, splits > 1, another geometry) is refused
+ *   48 three-launch Winograd F(4x4,3x3) on the exact-fp32 engine's three-piece GEMM (gemm_split3i_kernel: row-pair-interleaved bf16 triples, six products);
+ *      26 / 27 selectors 24 / 25 on that GEMM (V written as triples by the polyphase input transform)
  *   46 / 47 the direct implicit GEMM on the PAIR kernels (conv_igemm.hip: fp32 storage, activations split into 16-bit hi + lo pieces while
  *           staged, three cross products on the 16-bit MFMA): fp16 / bf16 pieces
  *   44 / 45 three-launch Winograd F(4x4,3x3) with the engine's pair GEMM (pair-interleaved operands, LDS-DMA): fp16 / bf16 hi + lo pieces
@@ -49,7 +51,7 @@ int irsde_debug_conv(const float* in0, int C0, const float* in1, int C1, int B, 
 
 /* Kernel-level test hook of csrc/gemm_split.hip: C_z[M][N] = A_z[M][K] . B_z[N][K]^T for z < ncomp (device f32 tensors, z-major),
  * operands split into `nplanes` (2 or 3) bf16 pieces on the device (plane-major prototype kernel; nplanes = 42 / 44: the engine's
- * pair-interleaved two-piece kernel with bf16 / fp16 pieces), products on v_mfma_f32_32x32x16_bf16, f32 accumulate.  K a multiple of 32.  Synchronises `stream`. */
+ * pair-interleaved two-piece kernel with bf16 / fp16 pieces; nplanes = 43: the exact-fp32 engine's three-piece kernel gemm_split3i_kernel, six products), products on v_mfma_f32_32x32x16_bf16, f32 accumulate.  K a multiple of 32.  Synchronises `stream`. */
 int irsde_debug_split_gemm(const float* A, const float* B, float* C, int M, int N, int K, int ncomp, int nplanes, void* stream);
 
 /* Kernel tuning hook: average ms of one KxK convolution (pad K/2, or 4x4 s2 p1) on random NHWC data.  variant (any other code is refused):
@@ -67,6 +69,8 @@ int irsde_debug_split_gemm(const float* A, const float* B, float* C, int M, int 
  *     transform arithmetic / also without gathers / without gathers only, 465 the kernel once with its per-wave cycle stamps printed to stdout,
  *     4650 / 4651 / 4652 that stamp run without patch traffic / output stores / residual loads, 4653 the stamps of the coalesced-epilogue twin (PROBES build)
  *   472 the engine's pair-interleaved two-plane GEMM alone, 473 / 475 / 476 without its global loads / MFMAs / output stores (474: no such twin, the launch refuses it)
+ *   490 the three-piece GEMM (gemm_split3i_kernel) alone on the layer's 36 F(4x4,3x3) component shapes, 491 / 493 / 494 without its global loads / MFMAs /
+ *     output stores (PROBES build; 492: no such twin, the launch refuses it)
  *   480 / 481 / 482 a direct layer on the PAIR kernels (fp16 / bf16 pieces / fp16 without the 256 x 256 tile)
  * epi: 0 none, 1 FiLM+SiLU, 2 SiLU+residual. */
 int irsde_bench_conv(int variant, int B, int H, int W, int Cin, int Cout, int K, int stride, int up, int epi, int iters,
@@ -88,6 +92,10 @@ int irsde_debug_force_chain_groups(int g);
  * weights are transformed at irsde_finalize_weights) — 0 never, 1 by the plan's rule, 2 wherever eligible (exact fp32, single source, bias only);
  * any other value returns to the default (the rule; the IRSDE_WINO_POLY tuning knob). */
 int irsde_debug_force_wino_poly(int mode);
+/* Test / measurement hook (process-wide): the three-piece bf16 component GEMMs of the exact-fp32 engine in engines CREATED from now on (the weights' triples
+ * are made at irsde_finalize_weights) — 0 never, 1 by the plan's rule, 2 wherever eligible (exact fp32, K a multiple of 32, 32-bit component offsets);
+ * any other value returns to the default (the rule; the IRSDE_SPLIT3 tuning knob).  IRSDE_FLAG_NO_SPLIT3 wins over every mode. */
+int irsde_debug_force_split3(int mode);
 
 /* Kernel-level test hook: ONE SCAM of the stereo-sr NAFBlock (csrc/scam.hip + the projection GEMM on the implicit-GEMM kernel, the engine's
  * fp32 path).  x / out: device NHWC [2 B_pairs][H][W][C] (views stacked [L_0..L_{B-1}, R_0..R_{B-1}] as inside the reference network);
