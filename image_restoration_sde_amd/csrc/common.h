@@ -144,6 +144,7 @@ struct WinoPolyParams {
     int B = 0, TH = 0, TW = 0, T = 0;
     float* V = nullptr;
     unsigned short* Vs = nullptr;   // != nullptr: V as three bf16 planes in the layout of split3_layout.h instead (component z, row t, K index as above)
+    int thread_writer = 0;          // up + Vs: 1 = the per-thread writer (the whole-line writer's bit-identity twin: irsde_debug_conv 28, IRSDE_WINO_POLY_LINES=0)
     const float* M = nullptr;
     int Cout = 0, Ho = 0, Wo = 0;
     float* out = nullptr;       // [B][Ho][Wo][out_stride]
@@ -179,7 +180,10 @@ void launch_gemm_split(const SplitGemmArgs& a, int nplanes, int ncomp, hipStream
 // three bf16 planes in the row-pair-interleaved layout of split3_layout.h (gemm_split3i_kernel: six products, LDS-DMA, 256 x 128 tiles): the default path of
 // the exact-fp32 engine's deep component GEMMs.  pA / pB = unsigned shorts per component (split3_comp_elems), plA / plB / lda unused.
 // abl: the measurement twins of the PROBES build (1 no global loads in the K loop, 3 no MFMAs, 4 no output stores)
-void launch_gemm_split_triples(const SplitGemmArgs& a, int ncomp, hipStream_t s, int abl = 0);
+// walk: 1 = the persistent launch (at most one block per CU, each walking its share of the items), 0 = one item per block (its bit-identity twin),
+// -1 = the tuning knob IRSDE_SPLIT3_WALK (default 1)
+void launch_gemm_split_triples(const SplitGemmArgs& a, int ncomp, hipStream_t s, int abl = 0, int walk = -1);
+void set_force_split3_blocks(int n);   // irsde_debug_force_split3_blocks: caps the persistent launch's grid (>= 8); -1 = one block per CU
 bool gemm_split_triples_fits(long long M, long long N, long long K, long long ldc);   // K % 32 == 0 and every component slice inside the 32-bit offset range
 void launch_split_triples(const float* in, unsigned short* out, int ncomp, size_t rows, int K, hipStream_t s);   // f32 [ncomp][rows][K] -> that layout
 void launch_split_planes(const float* in, unsigned short* out, size_t n, size_t plane, int nplanes, hipStream_t s, bool f16 = false,

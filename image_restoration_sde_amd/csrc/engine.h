@@ -58,9 +58,13 @@ inline bool wino_poly_wants_weights(int mode, bool up, int Cin) { return mode >=
 // of Builder::split3_adopts, 2 wherever eligible (irsde_debug_force_split3 overrides the knob for engines created afterwards); IRSDE_FLAG_NO_SPLIT3 = never
 int split3_mode();
 void set_force_split3(int mode);   // irsde_debug_force_split3
-// the rule's side that is known at weight-load time (profiles/split3.md): F(4x4,3x3) layers beyond the fused kernels' reach (Cin > 512; mode 2: every layer),
-// every polyphase layer
-constexpr int kSplit3WinoMinCin = 513;
+// the rule's side that is known at weight-load time (profiles/split3.md, profiles/split3_walk.md): F(4x4,3x3) layers beyond the fused kernels' reach (Cin > 512),
+// those with Cin = 512 and at least 512 output channels (mode 2: every layer), every polyphase layer
+constexpr int kSplit3WinoMinCin = 512;
+inline int split3_wino_min_cin() { return tuning_env_int("IRSDE_SPLIT3_MINCIN", kSplit3WinoMinCin); }   // (513: the Cin = 512 layers stay where they were)
+inline bool split3_wino_wants_weights(int mode, int Cin, int Cout) { return mode >= 2 || Cin > 512 || (Cin >= split3_wino_min_cin() && Cout >= 512); }
+// a layer the fused F(4x4,3x3) kernels would take leaves them for the three-launch path on triples from this many tiles on (IRSDE_SPLIT3_FUSED_MINT)
+inline long long split3_fused_min_tiles() { return tuning_env_int("IRSDE_SPLIT3_FUSED_MINT", 4096); }
 // every mode whose arithmetic is not the exact-fp32 engine's: the three-piece operands are never built there
 constexpr int kSplit3NotExactF32 = IRSDE_FLAG_NO_WINOGRAD | IRSDE_FLAG_NAIVE_CONV | IRSDE_FLAG_BF16 | IRSDE_FLAG_BF16_ACT | IRSDE_FLAG_FP16 | IRSDE_FLAG_F16_ACT |
                                    IRSDE_FLAG_SPLIT_BF16X2 | IRSDE_FLAG_SPLIT_F16X2 | IRSDE_FLAG_NO_SPLIT3;
@@ -104,7 +108,7 @@ struct ConvW {
     float wino_uf64p_scale = 1.f;
     unsigned short* wino_up = nullptr;  // IRSDE_FLAG_SPLIT_BF16X2 / _F16X2: the F(4x4,3x3) weights as hi / lo pairs, [36][Cout][Cin / 32][2][32]
     float wino_up_scale = 1.f;          // fp16 pairs: the power of two U was multiplied by (max |U| * scale <= 512)
-    unsigned short* wino_u4t = nullptr;    // exact fp32, Cin > 512: wino_u4 as three bf16 pieces, [36] x split3_layout.h of [Cout][Cin] (gemm_split3i_kernel's B operand)
+    unsigned short* wino_u4t = nullptr;    // exact fp32, Cin > 512 (or = 512 with Cout >= 512): wino_u4 as three bf16 pieces, [36] x split3_layout.h of [Cout][Cin] (gemm_split3i_kernel's B operand)
     unsigned short* wino_polyt = nullptr;  // exact fp32: wino_poly as three bf16 pieces, [25 | 100] x split3_layout.h of [Cout][4 Cin | Cin]
     float* wino_poly = nullptr;  // polyphase F(4x4,2x2) weights (exact fp32 mode): 4x4 stride-2 layers [25][Cout][4 Cin], nearest-x2 + 3x3 layers [100][Cout][Cin]
 };

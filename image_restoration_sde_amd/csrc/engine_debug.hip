@@ -77,7 +77,7 @@ struct VariantScope {
 // The selector codes irsde_debug_conv / irsde_bench_conv know (see their branches): any other code is refused, never run as the production dispatch.
 bool code_in(const std::initializer_list<int>& codes, int c) { return std::find(codes.begin(), codes.end(), c) != codes.end(); }
 bool debug_conv_code_known(int c) {
-    return code_in({0, 1, 2, 3, 4, 5, 12, 13, 22, 23, 24, 25, 26, 27, 48, 33, 34, 35, 36, 37, 42, 43, 44, 45, 46, 47, 55, 56, 62, 63, 204, 260, 261, 262, 263}, c) ||
+    return code_in({0, 1, 2, 3, 4, 5, 12, 13, 22, 23, 24, 25, 26, 27, 28, 48, 33, 34, 35, 36, 37, 42, 43, 44, 45, 46, 47, 55, 56, 62, 63, 204, 260, 261, 262, 263}, c) ||
            code_in({100, 103, 105, 106, 107, 150, 160, 161, 162, 163, 165, 166, 167, 170, 171, 172, 173}, c);   // 100 + a launch_conv tuning variant
 }
 bool bench_conv_variant_known(int v) {
@@ -85,7 +85,7 @@ bool bench_conv_variant_known(int v) {
            code_in({80, 81, 82, 412, 413, 421, 422, 423, 430, 431, 432, 434, 435, 460, 461, 462, 465, 467, 468, 469, 480, 481, 482}, v) ||
            code_in({2001, 2002, 2004, 4650, 4651, 4652, 4653}, v) ||
            (v >= 83 && v <= 82 + 255) ||   // the 32-cout fused kernel with tuning-aid flags v - 82
-           (v >= 490 && v <= 494) ||       // the three-piece GEMM and its ablation twins (PROBES build; launch_gemm_split_triples refuses the ones it lacks)
+           (v >= 490 && v <= 499) ||       // the three-piece GEMM and its ablation twins (PROBES build; launch_gemm_split_triples refuses the ones it lacks); 495 - 499: on the one-item-per-block launch
            (v >= 472 && v <= 476);         // the pair GEMM's ablation twins (launch_gemm_split_pairs refuses the ones it lacks)
 }
 
@@ -420,10 +420,10 @@ int irsde_debug_conv(const float* in0, int C0, const float* in1, int C1, int B, 
             p.splits = splits;
             p.partial = mem.alloc<float>((size_t)splits * B * p.Ho * p.Wo * Cout);
         }
-        if (naive == 26 || naive == 27) {   // selectors 24 / 25 with the component GEMMs on three bf16 pieces (gemm_split3i_kernel)
+        if (naive == 26 || naive == 27 || naive == 28) {   // selectors 24 / 25 with the component GEMMs on three bf16 pieces (gemm_split3i_kernel); 28: 27 with the per-thread V writer
             if (!(naive == 26 ? wino_poly_down_shape(p) : wino_poly_up_shape(p)) || !wino_poly_eligible(p) || splits > 1)
-                throw HipError("debug_conv: selectors 26 / 27 run what 24 / 25 run (single source, channels a multiple of 32, bias only)");
-            const int up = naive == 27;
+                throw HipError("debug_conv: selectors 26 / 27 / 28 run what 24 / 25 run (single source, channels a multiple of 32, bias only)");
+            const int up = naive != 26;
             std::vector<float> U((size_t)100 * Cout * Cin);
             wino_poly_transform_weights(pk.data(), Cout, Cin, U.data(), up);
             float* dU = mem.upload(U);
@@ -435,6 +435,7 @@ int irsde_debug_conv(const float* in0, int C0, const float* in1, int C1, int B, 
             launch_split_triples(dU, dUt, wp.ncomp, (size_t)Cout, wp.K, s);
             wp = make_wino_poly(p, dU, nullptr, dM);
             const SplitGemmArgs sg = make_wino_poly_triples(wp, Cout, dUt, dVt, dM);
+            wp.in.thread_writer = naive == 28;
             launch_wino_poly_input(wp.in, s);
             launch_gemm_split_triples(sg, wp.ncomp, s);
             launch_wino_poly_output(wp.out, s);
@@ -591,13 +592,14 @@ int irsde_debug_conv(const float* in0, int C0, const float* in1, int C1, int B, 
 int irsde_debug_split_gemm(const float* A, const float* Bm, float* C, int M, int N, int K, int ncomp, int nplanes, void* stream) {
     return guard([&] {
         // nplanes 2 / 3: the 128 x 128 plane-major prototype kernel; 42 / 44: the engine's pair-interleaved two-plane kernel
-        // 43: the exact-fp32 engine's three-piece kernel (row-pair-interleaved triples, six products)
-        if (nplanes != 2 && nplanes != 3 && nplanes != 42 && nplanes != 43 && nplanes != 44) throw HipError("debug_split_gemm: nplanes must be 2, 3, 42, 43 or 44");
+        // 43: the exact-fp32 engine's three-piece kernel (row-pair-interleaved triples, six products) on its production launch (the persistent item walk);
+        // 45: the same kernel on the one-item-per-block launch, the walk's bit-identity twin
+        if (nplanes != 2 && nplanes != 3 && (nplanes < 42 || nplanes > 45)) throw HipError("debug_split_gemm: nplanes must be 2, 3, 42, 43, 44 or 45");
         hipStream_t s = reinterpret_cast<hipStream_t>(stream);
         conv_global_init();
         const size_t na = (size_t)ncomp * M * K, nb = (size_t)ncomp * N * K;
         Scratch mem(s);
-        if (nplanes == 43) {
+        if (nplanes == 43 || nplanes == 45) {
             if (!gemm_split_triples_fits(M, N, K, N)) throw HipError("debug_split_gemm: shape not eligible for the three-piece GEMM");
             const size_t ea = split3_comp_elems((size_t)M, (size_t)K), eb = split3_comp_elems((size_t)N, (size_t)K);
             unsigned short *ta = mem.alloc<unsigned short>(ea * ncomp), *tb = mem.alloc<unsigned short>(eb * ncomp);
@@ -607,7 +609,7 @@ int irsde_debug_split_gemm(const float* A, const float* Bm, float* C, int M, int
             gt.a = ta; gt.b = tb; gt.out = C;
             gt.pA = (long long)ea; gt.pB = (long long)eb; gt.pO = (long long)M * N;
             gt.M = M; gt.N = N; gt.K = K; gt.lda = K; gt.ldc = N;
-            launch_gemm_split_triples(gt, ncomp, s);
+            launch_gemm_split_triples(gt, ncomp, s, 0, nplanes == 45 ? 0 : -1);
             IRSDE_HIP_CHECK(hipStreamSynchronize(s));
             return;
         }
@@ -647,6 +649,12 @@ int irsde_debug_force_chain_groups(int g) {
 
 int irsde_debug_force_split3(int mode) {
     set_force_split3(mode >= 0 && mode <= 2 ? mode : -1);
+    return IRSDE_OK;
+}
+
+int irsde_debug_force_split3_blocks(int n) {
+    if (n >= 0 && n < 8) return guard([&] { throw HipError("debug_force_split3_blocks: n must be at least 8 (one block per XCD), or negative for the default"); });
+    set_force_split3_blocks(n);
     return IRSDE_OK;
 }
 
@@ -814,7 +822,7 @@ int irsde_bench_conv(int variant, int B, int H, int W, int Cin, int Cout, int K,
             p.w_pair = dwp; p.pair_scale = 1.0f / 64.0f; p.f16 = variant != 481 ? 1 : 0;
             variant = variant == 482 ? 61 : 0;
         }
-        if (variant >= 490 && variant <= 494) {   // the three-piece component GEMMs alone (gemm_split3i_kernel): 490 full, 491 no loads, 493 no MFMAs, 494 no output stores
+        if (variant >= 490 && variant <= 499) {   // the three-piece component GEMMs alone (gemm_split3i_kernel): 490 full, 491 no loads, 493 no MFMAs, 494 no output stores; 495 - 499: the same on the one-item-per-block twin
             if (K != 3 || stride != 1 || !wino_shape_ok(p, 4)) throw HipError("bench_conv: Winograd variants need an eligible 3x3 stride-1 layer");
             const long long T = (long long)B * (p.Ho / 4) * (p.Wo / 4);
             if (!gemm_split_triples_fits(T, Cout, Cin, Cout)) throw HipError("bench_conv: shape not eligible for the three-piece GEMM");
@@ -829,9 +837,9 @@ int irsde_bench_conv(int variant, int B, int H, int W, int Cin, int Cout, int K,
             gt.a = vt; gt.b = ut; gt.out = mo;
             gt.pA = (long long)ea; gt.pB = (long long)eb; gt.pO = T * Cout;
             gt.M = (int)T; gt.N = Cout; gt.K = Cin; gt.lda = Cin; gt.ldc = Cout;
-            const int abl = variant - 490;
-            for (int i = 0; i < 2; ++i) launch_gemm_split_triples(gt, 36, s, abl);
-            *ms_out = time_launches(s, iters, [&] { launch_gemm_split_triples(gt, 36, s, abl); });
+            const int walk = variant >= 495 ? 0 : -1, abl = variant - (variant >= 495 ? 495 : 490);
+            for (int i = 0; i < 2; ++i) launch_gemm_split_triples(gt, 36, s, abl, walk);
+            *ms_out = time_launches(s, iters, [&] { launch_gemm_split_triples(gt, 36, s, abl, walk); });
             return;
         }
         if (variant >= 472 && variant <= 476) {   // the pair-interleaved two-plane component GEMMs alone (v3 kernel): 472 full, 473 no loads, 475 no MFMAs, 476 no output stores

@@ -125,6 +125,7 @@ struct Builder {
         if (!naive) {  // prefer F(4x4,3x3), then F(2x2,3x3), then the direct implicit GEMM
             if (w.wino_poly && push_wino_poly(p, w.wino_poly, w.wino_polyt)) return out;   // the resampling layers: polyphase F(4x4,2x2)
             if (w.wino_up && wino_shape_ok(p, 4) && push_wino(p, w.wino_u4, 4, w.wino_up, w.wino_up_scale)) return out;
+            if (split3_over_fused(w, p) && push_wino(p, w.wino_u4, 4, nullptr, 1.f, w.wino_u4t)) return out;
             if (w.wino_uf64p && push_wino_fused(p, reinterpret_cast<const float*>(w.wino_uf64p), true, w.wino_uf64p_scale)) return out;
             if (w.wino_uf64 && push_wino_fused(p, w.wino_uf64, true)) return out;
             if (w.wino_uf && push_wino_fused(p, w.wino_uf, false)) return out;
@@ -212,17 +213,30 @@ struct Builder {
     // Do ncomp component GEMMs [T][K] x [Cout][K]^T run on three bf16 pieces (gemm_split3i_kernel)?  Ut: the weights' triples (exact-fp32 engines only).
     // Rule (IRSDE_SPLIT3 = 1; measured per layer as input transform + GEMM, profiles/split3.md):
     //   * at least 256 rows: the kernel's row tile is 256, a GEMM with fewer rows multiplies padding (T = 128, the B = 2 plan's deepest level: 0.107 -> 0.154 ms);
-    //   * at least 512 output channels: V is written at 6 bytes per element instead of 4 and every V element feeds Cout products, so a narrow layer pays more
-    //     in its input transform than its GEMM gains (polyphase up 512 -> 256 at T = 4096: transform 0.19 -> 0.48 ms, GEMM 0.79 -> 0.57 ms; polyphase down
-    //     64 -> 128 at T = 16384: 0.388 -> 0.406 ms together);
+    //   * at least 512 output channels (polyphase layers: 256): V is written at 6 bytes per element instead of 4 and every V element feeds Cout products, so a
+    //     narrow layer pays more in its input transform than its GEMM gains (polyphase down 64 -> 128 at T = 16384: 0.385 -> 0.407 ms together).  With the
+    //     whole-line writer of the Upsample transform and the persistent GEMM launch the 256-channel polyphase layers win (profiles/split3_walk.md: up
+    //     512 -> 256 at T = 4096 0.995 -> 0.926 ms, at T = 1024 0.281 -> 0.262 ms; down 128 -> 256 at T = 4096 0.303 -> 0.280 ms);
     //   * at least 9e9 executed f32-equivalent FLOP, the smallest GEMM measured to win (512 -> 1024 at T = 256: 0.106 -> 0.100 ms).
     static constexpr long long kSplit3MinRows = 256;
-    static constexpr int kSplit3MinCout = 512;
+    static constexpr int kSplit3MinCout = 512, kSplit3MinCoutPoly = 256;
     static constexpr double kSplit3MinFlop = 9e9;
-    bool split3_adopts(const unsigned short* Ut, long long T, int K, int Cout, int ncomp) const {
+    bool split3_rule(long long T, int K, int Cout, int ncomp, int min_cout = kSplit3MinCout) const {
+        return T >= kSplit3MinRows && Cout >= min_cout && ncomp * 2.0 * (double)T * K * Cout >= kSplit3MinFlop;
+    }
+    bool split3_adopts(const unsigned short* Ut, long long T, int K, int Cout, int ncomp, int min_cout = kSplit3MinCout) const {
         const int mode = split3_mode();
         if (!Ut || mode <= 0 || naive || (e->cfg.flags & kSplit3NotExactF32) || !gemm_split_triples_fits(T, Cout, K, Cout)) return false;
-        return mode >= 2 || (T >= kSplit3MinRows && Cout >= kSplit3MinCout && ncomp * 2.0 * (double)T * K * Cout >= kSplit3MinFlop);
+        return mode >= 2 || split3_rule(T, K, Cout, ncomp, min_cout);
+    }
+    // Does an F(4x4,3x3) layer that the fused kernels would take (Cin <= 512) leave them for input transform + three-piece GEMMs + output transform?  By the rule
+    // above in every mode (mode 2 forces the three-piece GEMM onto the three-launch layers, it does not move layers between paths), and from
+    // split3_fused_min_tiles() tiles on: the fused kernel keeps V and M out of HBM, which the two transforms pay for
+    // (per layer, profiles/split3_walk.md).
+    bool split3_over_fused(const ConvW& w, const ConvParams& p) const {
+        if (!w.wino_u4t || p.C0 + p.C1 > 512 || !wino_shape_ok(p, 4)) return false;
+        const long long T = (long long)p.B * (p.Ho / 4) * (p.Wo / 4);
+        return T >= split3_fused_min_tiles() && split3_rule(T, p.C0 + p.C1, p.Cout, 36) && split3_adopts(w.wino_u4t, T, p.C0 + p.C1, p.Cout, 36);
     }
     float* alloc_triples(int ncomp, long long rows, int K) { return pl->alloc(((size_t)ncomp * split3_comp_elems((size_t)rows, (size_t)K) + 1) / 2, true); }
 
@@ -237,7 +251,8 @@ struct Builder {
         const double exec_flops = wp.ncomp * 2.0 * (double)T * wp.K * d.Cout;
         if (mode == 1 && (gemm_blocks < 2ll * device_cu_count() || exec_flops < 2e10)) return false;
         if ((unsigned long long)T * std::max(wp.K, d.Cout) * 4ull >= 0x7fffffffull) return false;   // a component's V / M slice stays below 2 GiB (32-bit buffer offsets in the GEMM)
-        const bool tri = split3_adopts(Ut, T, wp.K, d.Cout, wp.ncomp);   // V at 6 bytes per element
+        static const int poly_min_cout = tuning_env_int("IRSDE_SPLIT3_POLY_MINCOUT", kSplit3MinCoutPoly);
+        const bool tri = split3_adopts(Ut, T, wp.K, d.Cout, wp.ncomp, poly_min_cout);   // V at 6 bytes per element
         float* V = tri ? alloc_triples(wp.ncomp, T, wp.K) : pl->alloc((size_t)wp.ncomp * T * wp.K, true);
         float* Mb = pl->alloc((size_t)wp.ncomp * T * d.Cout, true);
         wp = make_wino_poly(dd, U, V, Mb);

@@ -148,7 +148,7 @@ ConvW pack_conv(irsde_engine* e, const std::string& wname, const std::string& bn
             std::vector<float> U((size_t)(tile + 2) * (tile + 2) * O * I);
             wino_transform_weights(p.data(), O, I, U.data(), tile);
             (tile == 4 ? c.wino_u4 : c.wino_u2) = e->upload(U);
-            if (tile == 4 && (I >= kSplit3WinoMinCin || split3_mode() >= 2) && split3_wants_weights(e->cfg.flags)) c.wino_u4t = upload_triples(e, c.wino_u4, 36, O, I);
+            if (tile == 4 && split3_wino_wants_weights(split3_mode(), I, O) && split3_wants_weights(e->cfg.flags)) c.wino_u4t = upload_triples(e, c.wino_u4, 36, O, I);
             if (tile == 4 && (e->cfg.flags & (IRSDE_FLAG_SPLIT_BF16X2 | IRSDE_FLAG_SPLIT_F16X2)) && I >= split_min_cin()) {
                 unsigned short* up = nullptr;   // hi / lo pairs of U, made on the device once
                 IRSDE_HIP_CHECK(hipMalloc(&up, U.size() * 4));

@@ -26,6 +26,7 @@
 //   writes finished accumulators straight from registers (buffer stores, rows past M dropped by the descriptor).
 #include "common.h"
 #include <algorithm>
+#include <atomic>
 #include <type_traits>
 
 namespace irsde {
@@ -378,7 +379,7 @@ __global__ __launch_bounds__(512, 2) void gemm_split2i_kernel(const SplitGemmArg
     flush(0);
 }
 // ---------------------------------------------------------------------------------------------------------------
-// Three pieces on that structure: the exact-fp32 engine's deep component GEMMs (Winograd F(4x4,3x3) with Cin > 512, polyphase F(4x4,2x2)).
+// Three pieces on that structure: the exact-fp32 engine's deep component GEMMs (Winograd F(4x4,3x3) with Cin >= 512, polyphase F(4x4,2x2)).
 // Operands: three bf16 planes, row-pair-interleaved (split3_layout.h: [row / 2][k / 32][row % 2][plane][32 k], 384-byte blocks = whole lines).
 // Per 16-k sub-step and output tile the six products are accumulated SMALLEST FIRST, in this fixed order:
 //     a0 b2, a1 b1, a2 b0   (<= 2^-18 |a b|),   a0 b1, a1 b0   (<= 2^-9 |a b|),   a0 b0
@@ -395,7 +396,15 @@ __global__ __launch_bounds__(512, 2) void gemm_split2i_kernel(const SplitGemmArg
 // reading before the barrier that ended step t-1; __syncthreads() (vmcnt(0) + lgkmcnt(0) + s_barrier) ends a step, so every fragment read of step t+1
 // comes after the barrier behind which all of its stage's DMA writes have landed.
 // ---------------------------------------------------------------------------------------------------------------
-template <int ABL = 0>
+// WALK (the production launch): at most one block per CU, and a block walks several items (component, row tile, column tile) as ONE pipelined loop.  The
+// items of an XCD (its units in order, column tiles innermost) are dealt round-robin to the XCD's blocks: block j of nb takes items j, j + nb, j + 2 nb ...,
+// so at any time the blocks of an XCD work on neighbouring items (the column tiles of a unit side by side, as the one-item launch's dispatch order has them)
+// and an A row tile is still read through one L2.  The map is a pure function of the shape and the grid: no atomics, graph replay = eager launches.
+// At an item boundary both LDS stages are free behind the barrier that ended the last K-step: the next item's first-stage LDS-DMA loads (no VGPRs) are
+// issued BEFORE the finished accumulators are stored, so their HBM / L2 latency runs under the 64 stores per wave, and the barrier that opens the next
+// item waits for both (vmcnt counts the stores too).  Per output element nothing changes (same six products, same order, same K order): WALK = false, the
+// one-item-per-block launch, is the bit-identity twin (irsde_debug_split_gemm 45, IRSDE_SPLIT3_WALK=0).
+template <int ABL = 0, bool WALK = true>
 __global__ __launch_bounds__(512, 1) void gemm_split3i_kernel(const SplitGemmArgs g) {
     constexpr int TM = 2, TN = 2, WN = 2, BM = 256, BN = 128;
     constexpr int ROWB = 192, GROUP = 16 * ROWB;                       // bytes per LDS row (12 pieces) and per 16-row group
@@ -413,36 +422,43 @@ __global__ __launch_bounds__(512, 1) void gemm_split3i_kernel(const SplitGemmArg
     const int units = mtiles * g.n_inner;          // (n_inner carries the component count here)
     const int xcd = blockIdx.x & 7, jx = blockIdx.x >> 3;
     const int ulo = (int)((long long)xcd * units / 8), uhi = (int)((long long)(xcd + 1) * units / 8);
-    const int unit = ulo + jx / g.nblk_n;
-    if (unit >= uhi) return;
-    const int nblk = jx % g.nblk_n;
-    const int plane0 = unit / mtiles, mblk = unit - plane0 * mtiles;
-    const int m0 = mblk * BM, n0 = nblk * BN;
+    const int nitems = (uhi - ulo) * g.nblk_n;     // this XCD's items: (unit, column tile), column tiles innermost
+    const int it_step = WALK ? ((int)gridDim.x - xcd + 7) >> 3 : nitems;   // blocks of this launch on this XCD (WALK = false: one item per block)
+    int it = jx;
+    if (it >= nitems) return;
     const int nk = g.K / SG_BK;
     const unsigned pairb = (unsigned)nk * 384u;   // bytes per operand row pair: K / 32 blocks of 2 rows x 3 planes x 64 B
 
     // staging: lane slot s = wl * 64 + lane of a group = (row s / 12, position s % 12); the lane fetches the row's piece (position - rotation) mod 12.
     // Rows past M / N are clamped: they feed accumulator rows / columns that are never stored.
+    int plane0, m0, n0;
     unsigned a_voff[6], b_voff[3];
+    const char *acomp, *bcomp;
+    auto set_item = [&](int i) {
+        const int unit = ulo + i / g.nblk_n, nblk = i % g.nblk_n;
+        plane0 = unit / mtiles;
+        m0 = (unit - plane0 * mtiles) * BM;
+        n0 = nblk * BN;
 #pragma unroll
-    for (int q = 0; q < 9; ++q) {
-        const int gi = q / 3, wl = q - gi * 3;     // gi 0, 1: the wave's A groups, 2: its B group
-        const int sl = wl * 64 + lane;
-        const int r = sl / 12, pos = sl - r * 12;
-        int j = pos - ((r >> 2) & 3);
-        j = j < 0 ? j + 12 : j;
-        if (gi < 2) {
-            int m = m0 + (2 * wave + gi) * 16 + r;
-            m = m < g.M ? m : g.M - 1;
-            a_voff[q] = (unsigned)(m >> 1) * pairb + (unsigned)(m & 1) * 192u + (unsigned)j * 16u;
-        } else {
-            int n = n0 + wave * 16 + r;
-            n = n < g.N ? n : g.N - 1;
-            b_voff[wl] = (unsigned)(n >> 1) * pairb + (unsigned)(n & 1) * 192u + (unsigned)j * 16u;
+        for (int q = 0; q < 9; ++q) {
+            const int gi = q / 3, wl = q - gi * 3;     // gi 0, 1: the wave's A groups, 2: its B group
+            const int sl = wl * 64 + lane;
+            const int r = sl / 12, pos = sl - r * 12;
+            int j = pos - ((r >> 2) & 3);
+            j = j < 0 ? j + 12 : j;
+            if (gi < 2) {
+                int m = m0 + (2 * wave + gi) * 16 + r;
+                m = m < g.M ? m : g.M - 1;
+                a_voff[q] = (unsigned)(m >> 1) * pairb + (unsigned)(m & 1) * 192u + (unsigned)j * 16u;
+            } else {
+                int n = n0 + wave * 16 + r;
+                n = n < g.N ? n : g.N - 1;
+                b_voff[wl] = (unsigned)(n >> 1) * pairb + (unsigned)(n & 1) * 192u + (unsigned)j * 16u;
+            }
         }
-    }
-    const char* acomp = reinterpret_cast<const char*>(g.a) + (long long)plane0 * g.pA * 2;   // pA / pB: unsigned shorts per component
-    const char* bcomp = reinterpret_cast<const char*>(g.b) + (long long)plane0 * g.pB * 2;
+        acomp = reinterpret_cast<const char*>(g.a) + (long long)plane0 * g.pA * 2;   // pA / pB: unsigned shorts per component
+        bcomp = reinterpret_cast<const char*>(g.b) + (long long)plane0 * g.pB * 2;
+    };
     int kb = 0;
     auto issue_loads_part = [&](int buf, int part) {   // the 9 loads of a stage in three groups: A group 2w | A group 2w+1 | B group w
         const char* gsrc = (part < 2 ? acomp : bcomp) + (size_t)kb * 384;
@@ -459,9 +475,9 @@ __global__ __launch_bounds__(512, 1) void gemm_split3i_kernel(const SplitGemmArg
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
+    set_item(it);
 #pragma unroll
     for (int part = 0; part < 3; ++part) issue_loads_part(0, part);
-    __syncthreads();
 
     // fragment offsets: row l31 of a 32-row tile (two 16-row groups back to back = 192 bytes per row), piece plane * 4 + sb * 2 + h, rotated by (row >> 2) & 3
     int fr_off[3][2];
@@ -469,61 +485,80 @@ __global__ __launch_bounds__(512, 1) void gemm_split3i_kernel(const SplitGemmArg
     for (int p = 0; p < 3; ++p)
 #pragma unroll
         for (int sb = 0; sb < 2; ++sb) fr_off[p][sb] = l31 * ROWB + ((p * 4 + sb * 2 + h + ((l31 >> 2) & 3)) % 12) * 16;
-    for (int st = 0; st < nk; ++st) {
-        const int buf = st & 1;
-        const bool more = st + 1 < nk;
-        if (more) ++kb;   // (stage buf^1 was last read in step st-1: every wave is past that step's barrier when the loads below are issued)
-        const char* a = lds + buf * STAGE + wm * TM * 32 * ROWB;
-        const char* b = lds + buf * STAGE + A_STAGE + wn * TN * 32 * ROWB;
-        bf16x8 fa[2][3][TM], fb[2][3][TN];
+    for (;;) {
+        __syncthreads();   // the item's first stage has landed (and, behind an earlier item, that item's stores have left)
+        for (int st = 0; st < nk; ++st) {
+            const int buf = st & 1;
+            const bool more = st + 1 < nk;
+            if (more) ++kb;   // (stage buf^1 was last read in step st-1: every wave is past that step's barrier when the loads below are issued)
+            const char* a = lds + buf * STAGE + wm * TM * 32 * ROWB;
+            const char* b = lds + buf * STAGE + A_STAGE + wn * TN * 32 * ROWB;
+            bf16x8 fa[2][3][TM], fb[2][3][TN];
 #pragma unroll
-        for (int sb = 0; sb < 2; ++sb)
+            for (int sb = 0; sb < 2; ++sb)
 #pragma unroll
-            for (int p = 0; p < 3; ++p) {
+                for (int p = 0; p < 3; ++p) {
 #pragma unroll
-                for (int i = 0; i < TM; ++i) fa[sb][p][i] = *reinterpret_cast<const bf16x8*>(a + i * 32 * ROWB + fr_off[p][sb]);
+                    for (int i = 0; i < TM; ++i) fa[sb][p][i] = *reinterpret_cast<const bf16x8*>(a + i * 32 * ROWB + fr_off[p][sb]);
 #pragma unroll
-                for (int j = 0; j < TN; ++j) fb[sb][p][j] = *reinterpret_cast<const bf16x8*>(b + j * 32 * ROWB + fr_off[p][sb]);
-            }
-        __builtin_amdgcn_sched_barrier(0);
+                    for (int j = 0; j < TN; ++j) fb[sb][p][j] = *reinterpret_cast<const bf16x8*>(b + j * 32 * ROWB + fr_off[p][sb]);
+                }
+            __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int sb = 0; sb < 2; ++sb)
+            for (int sb = 0; sb < 2; ++sb)
 #pragma unroll
-            for (int pr = 0; pr < 6; ++pr) {
+                for (int pr = 0; pr < 6; ++pr) {
 #pragma unroll
-                for (int i = 0; i < TM; ++i)
+                    for (int i = 0; i < TM; ++i)
 #pragma unroll
-                    for (int j = 0; j < TN; ++j) {
-                        if (ABL != 3) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[sb][PA[pr]][i], fb[sb][PB[pr]][j], acc[i][j], 0, 0, 0);
-                        else acc[i][j][0] += (float)fa[sb][PA[pr]][i][0] * (float)fb[sb][PB[pr]][j][0];
-                    }
-                if (sb == 0 && pr < 3 && ABL != 1 && more) issue_loads_part(buf ^ 1, pr);   // 3 + 3 + 3 loads behind the first three MFMA groups
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        __syncthreads();
-    }
+                        for (int j = 0; j < TN; ++j) {
+                            if (ABL != 3) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[sb][PA[pr]][i], fb[sb][PB[pr]][j], acc[i][j], 0, 0, 0);
+                            else acc[i][j][0] += (float)fa[sb][PA[pr]][i][0] * (float)fb[sb][PB[pr]][j][0];
+                        }
+                    if (sb == 0 && pr < 3 && ABL != 1 && more) issue_loads_part(buf ^ 1, pr);   // 3 + 3 + 3 loads behind the first three MFMA groups
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            __syncthreads();
+        }
 
-    // registers -> buffer stores: rows past M dropped by the descriptor, columns past N masked
-    const int rowb_ = m0 + wm * TM * 32, colb = n0 + wn * TN * 32;
-    float* ob = g.out + (long long)plane0 * g.pO + (long long)rowb_ * g.ldc;
-    const int rows = g.M - rowb_;
-    const unsigned nrec = rows <= 0 ? 0u : (unsigned)(rows < TM * 32 ? rows : TM * 32) * (unsigned)g.ldc * 4u;
-    const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(ob, 0, nrec, 0x00020000);
+        // registers -> buffer stores: rows past M dropped by the descriptor, columns past N masked
+        const int rowb_ = m0 + wm * TM * 32, colb = n0 + wn * TN * 32;
+        float* ob = g.out + (long long)plane0 * g.pO + (long long)rowb_ * g.ldc;
+        const int rows = g.M - rowb_;
+        const unsigned nrec = rows <= 0 ? 0u : (unsigned)(rows < TM * 32 ? rows : TM * 32) * (unsigned)g.ldc * 4u;
+        const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(ob, 0, nrec, 0x00020000);
+        it += it_step;
+        const bool next = WALK && it < nitems;
+        if (next) {   // both stages are free behind the last step's barrier: the next item's first stage goes out ahead of this item's stores
+            set_item(it);
+            kb = 0;
 #pragma unroll
-    for (int i = 0; i < TM; ++i)
+            for (int part = 0; part < 3; ++part) issue_loads_part(0, part);
+            __builtin_amdgcn_sched_barrier(0);
+        }
 #pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            const int colu = colb + j * 32;
-            if (colu + l31 < g.N && (ABL != 4 || acc[i][j][0] == 1.2345e30f)) {
+        for (int i = 0; i < TM; ++i)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const float v = acc[i][j][r];
-                    // (the whole offset in the vector operand: that is the part the descriptor's range check is sure to cover)
-                    const unsigned voff = (unsigned)((i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h) * g.ldc + colu + l31) * 4u;
-                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), ro, (int)voff, 0, 0);
+            for (int j = 0; j < TN; ++j) {
+                const int colu = colb + j * 32;
+                if (colu + l31 < g.N && (ABL != 4 || acc[i][j][0] == 1.2345e30f)) {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const float v = acc[i][j][r];
+                        // (the whole offset in the vector operand: that is the part the descriptor's range check is sure to cover)
+                        const unsigned voff = (unsigned)((i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h) * g.ldc + colu + l31) * 4u;
+                        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), ro, (int)voff, 0, 0);
+                    }
                 }
             }
-        }
+        if (!next) break;
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int j = 0; j < TN; ++j)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    }
 }
 #undef IRSDE_GLDS16
 
@@ -603,11 +638,15 @@ void gemm_split_global_init() {
     IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split2i_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split2i_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split2i_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split3i_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split3i_kernel<0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split3i_kernel<0, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
 #ifdef IRSDE_PROBES
-    IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split3i_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split3i_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split3i_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split3i_kernel<1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split3i_kernel<3, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split3i_kernel<4, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split3i_kernel<1, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split3i_kernel<3, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split3i_kernel<4, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
 #endif
     IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -659,26 +698,43 @@ bool gemm_split_triples_fits(long long M, long long N, long long K, long long ld
            (unsigned long long)M * ldc * 4ull < 0xffffffffull;
 }
 
+static std::atomic<int> g_force_split3_blocks{-1};   // irsde_debug_force_split3_blocks: -1 = one block per CU
+void set_force_split3_blocks(int n) { g_force_split3_blocks.store(n >= 8 ? n : -1, std::memory_order_relaxed); }
+
 // three-piece row-pair-interleaved operands (split3_layout.h; g.pA / g.pB = unsigned shorts per component)
-void launch_gemm_split_triples(const SplitGemmArgs& a, int ncomp, hipStream_t s, int abl) {
+// walk: 1 = at most one block per CU (or the forced cap), each walking its share of the items; 0 = one item per block (the twin); -1 = IRSDE_SPLIT3_WALK (1)
+void launch_gemm_split_triples(const SplitGemmArgs& a, int ncomp, hipStream_t s, int abl, int walk) {
     if (a.K % SG_BK) throw HipError("gemm_split_triples: K must be a multiple of 32");
     if (!gemm_split_triples_fits(a.M, a.N, a.K, a.ldc)) throw HipError("gemm_split_triples: a component exceeds the 32-bit offset range");
     if (ncomp < 1 || a.ldc < a.N) throw HipError("gemm_split_triples: bad component count or output stride");
+    if (walk < 0) {
+        static const int knob = tuning_env_int("IRSDE_SPLIT3_WALK", 1);
+        walk = knob != 0;
+    }
     SplitGemmArgs g = a;
     g.nblk_n = (a.N + 127) / 128;
-    g.n_inner = ncomp;   // one (component, row tile, column tile) per block; n_inner carries the component count
+    g.n_inner = ncomp;   // an item = (component, row tile, column tile); n_inner carries the component count
     const long long units = (long long)((a.M + 255) / 256) * ncomp;
     long long per_xcd = 0;
     for (int x = 0; x < 8; ++x) per_xcd = std::max(per_xcd, (x + 1) * units / 8 - x * units / 8);
-    if (8 * per_xcd * g.nblk_n >= 0x7fffffffll) throw HipError("gemm_split_triples: grid too large");
-    const dim3 grid((unsigned)(8 * per_xcd * g.nblk_n));
+    long long blocks = 8 * per_xcd * g.nblk_n;   // one per item of the fullest XCD, times eight
+    if (blocks >= 0x7fffffffll) throw HipError("gemm_split_triples: grid too large");
+    if (walk) {   // (a cap below 8 would leave an XCD's items without a block: set_force_split3_blocks refuses it, and no gfx950 part has fewer CUs)
+        const int forced = g_force_split3_blocks.load(std::memory_order_relaxed);
+        blocks = std::min<long long>(blocks, std::max(8, forced > 0 ? forced : device_cu_count()));
+    }
+    const dim3 grid((unsigned)blocks);
     const size_t lds = (size_t)2 * (256 + 128) * 192;
-    switch (abl) {
-        case 0: hipLaunchKernelGGL(gemm_split3i_kernel<0>, grid, dim3(512), lds, s, g); break;
+    switch (abl * 2 + (walk ? 1 : 0)) {
+        case 1: hipLaunchKernelGGL((gemm_split3i_kernel<0, true>), grid, dim3(512), lds, s, g); break;
+        case 0: hipLaunchKernelGGL((gemm_split3i_kernel<0, false>), grid, dim3(512), lds, s, g); break;
 #ifdef IRSDE_PROBES
-        case 1: hipLaunchKernelGGL(gemm_split3i_kernel<1>, grid, dim3(512), lds, s, g); break;
-        case 3: hipLaunchKernelGGL(gemm_split3i_kernel<3>, grid, dim3(512), lds, s, g); break;
-        case 4: hipLaunchKernelGGL(gemm_split3i_kernel<4>, grid, dim3(512), lds, s, g); break;
+        case 3: hipLaunchKernelGGL((gemm_split3i_kernel<1, true>), grid, dim3(512), lds, s, g); break;
+        case 7: hipLaunchKernelGGL((gemm_split3i_kernel<3, true>), grid, dim3(512), lds, s, g); break;
+        case 9: hipLaunchKernelGGL((gemm_split3i_kernel<4, true>), grid, dim3(512), lds, s, g); break;
+        case 2: hipLaunchKernelGGL((gemm_split3i_kernel<1, false>), grid, dim3(512), lds, s, g); break;
+        case 6: hipLaunchKernelGGL((gemm_split3i_kernel<3, false>), grid, dim3(512), lds, s, g); break;
+        case 8: hipLaunchKernelGGL((gemm_split3i_kernel<4, false>), grid, dim3(512), lds, s, g); break;
 #endif
         default: throw HipError("gemm_split_triples: the ablation twins are part of the PROBES build");
     }

@@ -304,16 +304,37 @@ __device__ __forceinline__ void at5_apply(const float4* m, float4* y) {
 
 // one thread = (tile, phase, 4 channels): the phase's 5x5 patch (down: every second pixel from (8 ty - 1 + p, 8 tx - 1 + q); up: from (4 ty - 1 + py, 4 tx - 1 + px))
 // TRI: V as three bf16 pieces in the layout of split3_layout.h (p.Vs) instead of f32 (p.V)
-template <bool UP, bool TRI = false>
+// LINES (UP and TRI): the whole-line writer.  Sixteen threads form a group = (tile pair, phase, 32-k block): 2 tiles x 8 channel quads, i.e. what one
+// 384-byte row-pair block of every component holds, and a work-group is 16 groups (consecutive 32-k blocks first).  Same loads, same bt5_apply order and the
+// same round-to-nearest-even splitting per thread, but the pieces of five components at a time (one r) go through LDS, and the work-group then stores them
+// 16 bytes per lane at consecutive addresses: whole 384-byte blocks, neighbouring 32-k blocks of a component back to back, instead of 8 bytes per thread and
+// plane into 64-byte runs with the two rows of a block coming from different waves.  The pad row of an odd T stays unwritten.
+constexpr int kPolyLinesGroups = 16;
+template <bool UP, bool TRI = false, bool LINES = false>
 __global__ __launch_bounds__(256) void wino_poly_input_kernel(const WinoPolyParams p) {
+    static_assert(!LINES || (UP && TRI), "the whole-line writer exists for the Upsample triples");
+    __shared__ uint4 stage[LINES ? kPolyLinesGroups * 5 * 24 : 1];
     const int C4 = p.C / 4;
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long long total = (long long)p.T * 4 * C4;
-    if (idx >= total) return;
-    const int c = (int)(idx % C4) * 4;
-    const long long i1 = idx / C4;
-    const int ph = (int)(i1 & 3);
-    const int t = (int)(i1 >> 2);
+    int c, ph, t;
+    bool active = true;
+    if constexpr (LINES) {
+        const int nkb = p.C / 32, sub = threadIdx.x & 15;
+        const long long grp = (long long)blockIdx.x * kPolyLinesGroups + (threadIdx.x >> 4);
+        const long long u = grp / (4 * nkb);
+        c = (int)(grp % nkb) * 32 + (sub & 7) * 4;
+        ph = (int)((grp / nkb) & 3);
+        const long long tt = 2 * u + (sub >> 3);
+        active = tt < p.T;
+        t = (int)(active ? tt : p.T - 1);   // (an idle thread loads a valid tile and stores nothing: it still has to reach the barriers)
+    } else {
+        const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+        const long long total = (long long)p.T * 4 * C4;
+        if (idx >= total) return;
+        c = (int)(idx % C4) * 4;
+        const long long i1 = idx / C4;
+        ph = (int)(i1 & 3);
+        t = (int)(i1 >> 2);
+    }
     const int tx = t % p.TW;
     const int t1 = t / p.TW;
     const int ty = t1 % p.TH;
@@ -357,7 +378,9 @@ __global__ __launch_bounds__(256) void wino_poly_input_kernel(const WinoPolyPara
         for (int s = 0; s < 5; ++s) {
             if constexpr (TRI) {
                 const size_t z = (UP ? (size_t)ph * 25 : 0) + (size_t)(r * 5 + s);
-                unsigned short* q = p.Vs + z * split3_comp_elems((size_t)p.T, K) + split3_index((size_t)t, UP ? (size_t)c : (size_t)ph * p.C + c, 0, K / 32);
+                // LINES: the group's 384-byte block of component s of this r in LDS, laid out as in memory: [tile parity][plane][32 k]
+                unsigned short* q = LINES ? reinterpret_cast<unsigned short*>(stage) + ((threadIdx.x >> 4) * 5 + s) * 192 + ((threadIdx.x >> 3) & 1) * 96 + (threadIdx.x & 7) * 4
+                                          : p.Vs + z * split3_comp_elems((size_t)p.T, K) + split3_index((size_t)t, UP ? (size_t)c : (size_t)ph * p.C + c, 0, K / 32);
                 float rem[4] = {o[s].x, o[s].y, o[s].z, o[s].w};
 #pragma unroll
                 for (int pl = 0; pl < 3; ++pl) {
@@ -376,6 +399,23 @@ __global__ __launch_bounds__(256) void wino_poly_input_kernel(const WinoPolyPara
             } else {
                 *reinterpret_cast<float4*>(vp + (size_t)(r * 5 + s) * kstride) = o[s];
             }
+        }
+        if constexpr (LINES) {
+            __syncthreads();
+            const int nkb = p.C / 32;
+            const long long ngroups = (long long)((p.T + 1) / 2) * 4 * nkb;
+            // 16-byte chunk i of this r: component s = i / 384, group (i % 384) / 24, chunk i % 24 of its block (12 per tile row)
+            for (int i = threadIdx.x; i < 5 * kPolyLinesGroups * 24; i += 256) {
+                const int s = i / (kPolyLinesGroups * 24), gl = (i / 24) % kPolyLinesGroups, ch = i % 24;
+                const long long grp = (long long)blockIdx.x * kPolyLinesGroups + gl;
+                if (grp >= ngroups) continue;
+                const long long u = grp / (4 * nkb);
+                if (ch >= 12 && 2 * u + 1 >= p.T) continue;   // the pad row of an odd T
+                const size_t z = (size_t)((grp / nkb) & 3) * 25 + (size_t)(r * 5 + s);
+                unsigned short* dst = p.Vs + z * split3_comp_elems((size_t)p.T, K) + ((size_t)u * nkb + (size_t)(grp % nkb)) * 192 + ch * 8;
+                *reinterpret_cast<uint4*>(dst) = stage[(gl * 5 + s) * 24 + ch];
+            }
+            __syncthreads();
         }
     }
 }
@@ -450,7 +490,11 @@ void launch_wino_poly_input(const WinoPolyParams& p, hipStream_t s) {
     const dim3 grid((unsigned)((total + 255) / 256));
     if (p.Vs) {
         if (p.C % 32) throw HipError("wino_poly_input (triples): channels must be a multiple of 32");
-        if (p.up) hipLaunchKernelGGL((wino_poly_input_kernel<true, true>), grid, dim3(256), 0, s, p);
+        static const int lines = tuning_env_int("IRSDE_WINO_POLY_LINES", 1);
+        if (p.up && lines && !p.thread_writer) {   // the whole-line writer: 16 groups of (tile pair, phase, 32-k block) per work-group
+            const long long groups = (long long)((p.T + 1) / 2) * 4 * (p.C / 32);
+            hipLaunchKernelGGL((wino_poly_input_kernel<true, true, true>), dim3((unsigned)((groups + kPolyLinesGroups - 1) / kPolyLinesGroups)), dim3(256), 0, s, p);
+        } else if (p.up) hipLaunchKernelGGL((wino_poly_input_kernel<true, true>), grid, dim3(256), 0, s, p);
         else hipLaunchKernelGGL((wino_poly_input_kernel<false, true>), grid, dim3(256), 0, s, p);
     } else if (p.up) hipLaunchKernelGGL((wino_poly_input_kernel<true>), grid, dim3(256), 0, s, p);
     else hipLaunchKernelGGL((wino_poly_input_kernel<false>), grid, dim3(256), 0, s, p);

@@ -53,6 +53,8 @@
  *        pieces = all 24 significand bits, six exact products, fp32 accumulation — fp32-equivalent results, not the bit-for-bit fmaf chain; the flag
  *        restores that).  Debug header: irsde_debug_force_split3, irsde_debug_conv selectors 26 / 27 / 48, irsde_debug_split_gemm nplanes 43,
  *        irsde_bench_conv 490 - 494.
+ *        Debug header only, same version: irsde_debug_force_split3_blocks, irsde_debug_split_gemm nplanes 45, irsde_debug_conv selector 28, irsde_bench_conv 495 - 499 (the three-piece
+ *        GEMM launches at most one block per compute unit and a block walks several tiles; same results bit for bit; tuning knob IRSDE_SPLIT3_WALK).
  */
 #ifndef IRSDE_HIP_H
 #define IRSDE_HIP_H

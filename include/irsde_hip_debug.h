@@ -24,7 +24,8 @@ extern "C" {
  *           layer (25 components, K = 4 C0), 25 a 3x3 stride-1 pad-1 layer with in_shift = 1 (4 output phases x 25 components); single source, C0 a multiple
  *           of 32, Cout of 4, bias only — anything else (film, silu, res, in1, splits > 1, another geometry) is refused
  *   48 three-launch Winograd F(4x4,3x3) on the exact-fp32 engine's three-piece GEMM (gemm_split3i_kernel: row-pair-interleaved bf16 triples, six products);
- *      26 / 27 selectors 24 / 25 on that GEMM (V written as triples by the polyphase input transform)
+ *      26 / 27 selectors 24 / 25 on that GEMM (V written as triples by the polyphase input transform); 28: selector 27 with the transform's per-thread V
+ *      writer instead of its whole-line writer (the bit-identity twin)
  *   46 / 47 the direct implicit GEMM on the PAIR kernels (conv_igemm.hip: fp32 storage, activations split into 16-bit hi + lo pieces while
  *           staged, three cross products on the 16-bit MFMA): fp16 / bf16 pieces
  *   44 / 45 three-launch Winograd F(4x4,3x3) with the engine's pair GEMM (pair-interleaved operands, LDS-DMA): fp16 / bf16 hi + lo pieces
@@ -51,7 +52,9 @@ int irsde_debug_conv(const float* in0, int C0, const float* in1, int C1, int B, 
 
 /* Kernel-level test hook of csrc/gemm_split.hip: C_z[M][N] = A_z[M][K] . B_z[N][K]^T for z < ncomp (device f32 tensors, z-major),
  * operands split into `nplanes` (2 or 3) bf16 pieces on the device (plane-major prototype kernel; nplanes = 42 / 44: the engine's
- * pair-interleaved two-piece kernel with bf16 / fp16 pieces; nplanes = 43: the exact-fp32 engine's three-piece kernel gemm_split3i_kernel, six products), products on v_mfma_f32_32x32x16_bf16, f32 accumulate.  K a multiple of 32.  Synchronises `stream`. */
+ * pair-interleaved two-piece kernel with bf16 / fp16 pieces; nplanes = 43: the exact-fp32 engine's three-piece kernel gemm_split3i_kernel, six products, on
+ * its production launch — at most one block per compute unit, each walking several (component, row tile, column tile) items; nplanes = 45: the same kernel
+ * with one item per block, the walk's bit-identity twin), products on v_mfma_f32_32x32x16_bf16, f32 accumulate.  K a multiple of 32.  Synchronises `stream`. */
 int irsde_debug_split_gemm(const float* A, const float* B, float* C, int M, int N, int K, int ncomp, int nplanes, void* stream);
 
 /* Kernel tuning hook: average ms of one KxK convolution (pad K/2, or 4x4 s2 p1) on random NHWC data.  variant (any other code is refused):
@@ -70,7 +73,7 @@ int irsde_debug_split_gemm(const float* A, const float* B, float* C, int M, int 
  *     4650 / 4651 / 4652 that stamp run without patch traffic / output stores / residual loads, 4653 the stamps of the coalesced-epilogue twin (PROBES build)
  *   472 the engine's pair-interleaved two-plane GEMM alone, 473 / 475 / 476 without its global loads / MFMAs / output stores (474: no such twin, the launch refuses it)
  *   490 the three-piece GEMM (gemm_split3i_kernel) alone on the layer's 36 F(4x4,3x3) component shapes, 491 / 493 / 494 without its global loads / MFMAs /
- *     output stores (PROBES build; 492: no such twin, the launch refuses it)
+ *     output stores (PROBES build; 492: no such twin, the launch refuses it); 495 - 499: the same five on the one-item-per-block launch (the walk's twin)
  *   480 / 481 / 482 a direct layer on the PAIR kernels (fp16 / bf16 pieces / fp16 without the 256 x 256 tile)
  * epi: 0 none, 1 FiLM+SiLU, 2 SiLU+residual. */
 int irsde_bench_conv(int variant, int B, int H, int W, int Cin, int Cout, int K, int stride, int up, int epi, int iters,
@@ -96,6 +99,10 @@ int irsde_debug_force_wino_poly(int mode);
  * are made at irsde_finalize_weights) — 0 never, 1 by the plan's rule, 2 wherever eligible (exact fp32, K a multiple of 32, 32-bit component offsets);
  * any other value returns to the default (the rule; the IRSDE_SPLIT3 tuning knob).  IRSDE_FLAG_NO_SPLIT3 wins over every mode. */
 int irsde_debug_force_split3(int mode);
+/* Test / measurement hook (process-wide, read at every launch): caps the grid of the three-piece GEMM's persistent launch at n blocks, n >= 8 (one per XCD),
+ * so that a small problem makes every block walk several items; a negative n returns to the default (one block per compute unit).  0 .. 7: IRSDE_ERR_INVALID,
+ * nothing changes.  Results do not depend on it (tests/test_gpu_split3_walk.py). */
+int irsde_debug_force_split3_blocks(int n);
 
 /* Kernel-level test hook: ONE SCAM of the stereo-sr NAFBlock (csrc/scam.hip + the projection GEMM on the implicit-GEMM kernel, the engine's
  * fp32 path).  x / out: device NHWC [2 B_pairs][H][W][C] (views stacked [L_0..L_{B-1}, R_0..R_{B-1}] as inside the reference network);
