@@ -181,8 +181,9 @@ void launch_gemm_split(const SplitGemmArgs& a, int nplanes, int ncomp, hipStream
 // the exact-fp32 engine's deep component GEMMs.  pA / pB = unsigned shorts per component (split3_comp_elems), plA / plB / lda unused.
 // abl: the measurement twins of the PROBES build (1 no global loads in the K loop, 3 no MFMAs, 4 no output stores)
 // walk: 1 = the persistent launch (at most one block per CU, each walking its share of the items), 0 = one item per block (its bit-identity twin),
-// -1 = the tuning knob IRSDE_SPLIT3_WALK (default 1)
-void launch_gemm_split_triples(const SplitGemmArgs& a, int ncomp, hipStream_t s, int abl = 0, int walk = -1);
+// -1 = the tuning knob IRSDE_SPLIT3_WALK (default 1).  drain: 1 = the walk with vmcnt(0) in front of every barrier of the K loop (the ring's twin), 0 = the ring,
+// -1 = the tuning knob IRSDE_SPLIT3_DRAIN (default 0)
+void launch_gemm_split_triples(const SplitGemmArgs& a, int ncomp, hipStream_t s, int abl = 0, int walk = -1, int drain = -1);
 void set_force_split3_blocks(int n);   // irsde_debug_force_split3_blocks: caps the persistent launch's grid (>= 8); -1 = one block per CU
 bool gemm_split_triples_fits(long long M, long long N, long long K, long long ldc);   // K % 32 == 0 and every component slice inside the 32-bit offset range
 void launch_split_triples(const float* in, unsigned short* out, int ncomp, size_t rows, int K, hipStream_t s);   // f32 [ncomp][rows][K] -> that layout

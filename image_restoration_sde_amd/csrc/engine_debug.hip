@@ -85,7 +85,7 @@ bool bench_conv_variant_known(int v) {
            code_in({80, 81, 82, 412, 413, 421, 422, 423, 430, 431, 432, 434, 435, 460, 461, 462, 465, 467, 468, 469, 480, 481, 482}, v) ||
            code_in({2001, 2002, 2004, 4650, 4651, 4652, 4653}, v) ||
            (v >= 83 && v <= 82 + 255) ||   // the 32-cout fused kernel with tuning-aid flags v - 82
-           (v >= 490 && v <= 499) ||       // the three-piece GEMM and its ablation twins (PROBES build; launch_gemm_split_triples refuses the ones it lacks); 495 - 499: on the one-item-per-block launch
+           (v >= 490 && v <= 504) ||       // the three-piece GEMM and its ablation twins (PROBES build; launch_gemm_split_triples refuses the ones it lacks); 495 - 499: on the one-item-per-block launch; 500 - 504: the drain twin
            (v >= 472 && v <= 476);         // the pair GEMM's ablation twins (launch_gemm_split_pairs refuses the ones it lacks)
 }
 
@@ -593,13 +593,13 @@ int irsde_debug_split_gemm(const float* A, const float* Bm, float* C, int M, int
     return guard([&] {
         // nplanes 2 / 3: the 128 x 128 plane-major prototype kernel; 42 / 44: the engine's pair-interleaved two-plane kernel
         // 43: the exact-fp32 engine's three-piece kernel (row-pair-interleaved triples, six products) on its production launch (the persistent item walk);
-        // 45: the same kernel on the one-item-per-block launch, the walk's bit-identity twin
-        if (nplanes != 2 && nplanes != 3 && (nplanes < 42 || nplanes > 45)) throw HipError("debug_split_gemm: nplanes must be 2, 3, 42, 43, 44 or 45");
+        // 45: the same kernel on the one-item-per-block launch, the walk's bit-identity twin; 47: the walk with vmcnt(0) in front of every barrier, the ring's twin
+        if (nplanes != 2 && nplanes != 3 && (nplanes < 42 || nplanes > 45) && nplanes != 47) throw HipError("debug_split_gemm: nplanes must be 2, 3, 42, 43, 44, 45 or 47");
         hipStream_t s = reinterpret_cast<hipStream_t>(stream);
         conv_global_init();
         const size_t na = (size_t)ncomp * M * K, nb = (size_t)ncomp * N * K;
         Scratch mem(s);
-        if (nplanes == 43 || nplanes == 45) {
+        if (nplanes == 43 || nplanes == 45 || nplanes == 47) {
             if (!gemm_split_triples_fits(M, N, K, N)) throw HipError("debug_split_gemm: shape not eligible for the three-piece GEMM");
             const size_t ea = split3_comp_elems((size_t)M, (size_t)K), eb = split3_comp_elems((size_t)N, (size_t)K);
             unsigned short *ta = mem.alloc<unsigned short>(ea * ncomp), *tb = mem.alloc<unsigned short>(eb * ncomp);
@@ -609,7 +609,7 @@ int irsde_debug_split_gemm(const float* A, const float* Bm, float* C, int M, int
             gt.a = ta; gt.b = tb; gt.out = C;
             gt.pA = (long long)ea; gt.pB = (long long)eb; gt.pO = (long long)M * N;
             gt.M = M; gt.N = N; gt.K = K; gt.lda = K; gt.ldc = N;
-            launch_gemm_split_triples(gt, ncomp, s, 0, nplanes == 45 ? 0 : -1);
+            launch_gemm_split_triples(gt, ncomp, s, 0, nplanes == 45 ? 0 : nplanes == 47 ? 1 : -1, nplanes == 47 ? 1 : nplanes == 43 ? -1 : 0);
             IRSDE_HIP_CHECK(hipStreamSynchronize(s));
             return;
         }
@@ -822,7 +822,7 @@ int irsde_bench_conv(int variant, int B, int H, int W, int Cin, int Cout, int K,
             p.w_pair = dwp; p.pair_scale = 1.0f / 64.0f; p.f16 = variant != 481 ? 1 : 0;
             variant = variant == 482 ? 61 : 0;
         }
-        if (variant >= 490 && variant <= 499) {   // the three-piece component GEMMs alone (gemm_split3i_kernel): 490 full, 491 no loads, 493 no MFMAs, 494 no output stores; 495 - 499: the same on the one-item-per-block twin
+        if (variant >= 490 && variant <= 504) {   // the three-piece component GEMMs alone (gemm_split3i_kernel): 490 full, 491 no loads, 493 no MFMAs, 494 no output stores; 495 - 499: the same on the one-item-per-block twin; 500 - 504: on the drain twin
             if (K != 3 || stride != 1 || !wino_shape_ok(p, 4)) throw HipError("bench_conv: Winograd variants need an eligible 3x3 stride-1 layer");
             const long long T = (long long)B * (p.Ho / 4) * (p.Wo / 4);
             if (!gemm_split_triples_fits(T, Cout, Cin, Cout)) throw HipError("bench_conv: shape not eligible for the three-piece GEMM");
@@ -837,9 +837,10 @@ int irsde_bench_conv(int variant, int B, int H, int W, int Cin, int Cout, int K,
             gt.a = vt; gt.b = ut; gt.out = mo;
             gt.pA = (long long)ea; gt.pB = (long long)eb; gt.pO = T * Cout;
             gt.M = (int)T; gt.N = Cout; gt.K = Cin; gt.lda = Cin; gt.ldc = Cout;
-            const int walk = variant >= 495 ? 0 : -1, abl = variant - (variant >= 495 ? 495 : 490);
-            for (int i = 0; i < 2; ++i) launch_gemm_split_triples(gt, 36, s, abl, walk);
-            *ms_out = time_launches(s, iters, [&] { launch_gemm_split_triples(gt, 36, s, abl, walk); });
+            const int twin = (variant - 490) / 5, abl = (variant - 490) % 5;   // twin 0: the production launch, 1: one item per block, 2: the drain twin
+            const int walk = twin == 1 ? 0 : twin == 2 ? 1 : -1, drain = twin == 2 ? 1 : twin == 1 ? 0 : -1;
+            for (int i = 0; i < 2; ++i) launch_gemm_split_triples(gt, 36, s, abl, walk, drain);
+            *ms_out = time_launches(s, iters, [&] { launch_gemm_split_triples(gt, 36, s, abl, walk, drain); });
             return;
         }
         if (variant >= 472 && variant <= 476) {   // the pair-interleaved two-plane component GEMMs alone (v3 kernel): 472 full, 473 no loads, 475 no MFMAs, 476 no output stores

@@ -388,23 +388,46 @@ __global__ __launch_bounds__(512, 2) void gemm_split2i_kernel(const SplitGemmArg
 // Block tile 256 x 128, 8 waves of 64 x 64 (2 x 2 MFMA tiles), K-step 32, two LDS stages of (256 + 128) x 192 B = 72 KB: 384 MFMAs per CU and K-step, as
 // many as the pair kernel's, for 72 KB of fill instead of 64.  One block per CU (144 KB of LDS), 2 waves per SIMD.
 // Staging: a stage is 24 groups of 16 rows (16 of A, 8 of B), a group 3 LDS-DMA wave-loads (16 rows x 12 pieces of 16 B = 192 lane slots); wave w stages the
-// A groups 2w, 2w + 1 and the B group w: 9 wave-loads per wave and K-step.  The LDS image of a group is lane-linear: slot = row * 12 + position, and a row's
+// A groups 4 (w / 2) + w % 2 and the one two further (the same 16 rows of the first and of the second 32 rows of a wave tile) and the B group w: 9 wave-loads per wave and K-step.  The LDS image of a group is lane-linear: slot = row * 12 + position, and a row's
 // piece j = plane * 4 + (k / 8) sits at position (j + ((row >> 2) & 3)) mod 12 — the rotation goes on the per-lane SOURCE address and on the fragment reads
 // (cdna_hip_programming.md rule 21).  With it the 16 rows of a ds_read_b128 lane group ({0-3, 12-15, 20-27} / {4-11, 16-19, 28-31} of a 32-row tile: every
 // residue mod 16 once) land on 16 different 16-byte bank slots: 192-byte rows alone put them on four (12 r mod 16).
-// Synchronisation as in the pair kernel: the loads of K-step t+1 are issued behind the first MFMA groups of step t, into the stage every wave finished
-// reading before the barrier that ended step t-1; __syncthreads() (vmcnt(0) + lgkmcnt(0) + s_barrier) ends a step, so every fragment read of step t+1
-// comes after the barrier behind which all of its stage's DMA writes have landed.
+// The ring (profiles/split3_ring.md).  The two 72 KB stages are six units of 24 KB: of K-step t (stage t & 1) the unit A0(t) = the first 32 rows of every wave's
+// 64 tile rows, A1(t) = the second 32, B(t) = the 128 column rows.  A wave stages one 16-row group (3 wave-loads) of each.  A K-step is two PHASES of 24 MFMAs per
+// wave, each ended by s_waitcnt vmcnt (counted), s_waitcnt lgkmcnt(0) and a raw s_barrier.  Fragments live in two register sets, one per 16-k sub-step:
+//     phase 0 of step t   multiplies tile row 0: sub-step 0 from set 0 (A0, B: read in the phase before), behind its first MFMA group reads sub-step 1 of A0(t), B(t)
+//                         into set 1;  issues A1(t+1);  ends with vmcnt(3): A1(t) and A0, B(t+1) have landed, A1(t+1) stays in flight  (vmcnt(0) in the last step)
+//     phase 1 of step t   multiplies tile row 1 against the same B fragments: reads sub-step 0 of A1(t) (the only reads no MFMA covers), then sub-step 1 behind the
+//                         first group, and behind the first group of sub-step 1 reads sub-step 0 of A0(t+1), B(t+1) into set 0 for the next phase;  issues A0(t+2),
+//                         B(t+2);  ends with no vmcnt wait at all: those six and A1(t+1) stay in flight
+// A unit is restaged one phase after the phase that last read it (A1(t+1) overwrites A1(t-1), read in phase 1 of t-1; A0 / B(t+2) overwrite A0 / B(t), last read in
+// phase 0 of t; every read has returned before its phase's barrier: lgkmcnt(0)) and is first read in a phase after the wait + barrier that retired it.  Every unit
+// has two phases of matrix work to land under, and nine / three wave-loads per wave are in flight across the barriers; with __syncthreads() (vmcnt(0)) a stage
+// had less than one K-step and nothing crossed a barrier.  Every wave issues the same number of loads per phase: the counts are constants for all waves.
+// A phase's loads go out one per MFMA group, and the two waves of a SIMD (w and w + 4), which leave every barrier in step, issue theirs in different sub-steps:
+// while one waits for the vector-memory pipe to take a load the other multiplies.  That stagger is what moved the K loop's slope (0.193 -> 0.18 ms per 512 of
+// K); the span alone moved the fixed cost.  While an LDS-DMA is pending the compiler turns every wait for a fragment into lgkmcnt(0), so a read is placed behind
+// the MFMA group in front of which the previous reads are waited for (sched_barrier pins that), never in front of it.
+// Operand layout, LDS image, rotation and global access (whole 384-byte row-pair blocks) are unchanged, which is why the ring is cut by tile ROW and not into
+// 16-k half-stages: those need the operands re-laid at 16-k granularity in every writer to keep whole-line traffic, and leave 4.5 wave-loads per wave and
+// half-stage.  Per output element: the same six products per 16-k sub-step in the same order over the same K order.
+// DRAIN = true (the twin: irsde_debug_split_gemm 47, IRSDE_SPLIT3_DRAIN=1) waits vmcnt(0) in front of every barrier: same issue order, same bits, no span.
 // ---------------------------------------------------------------------------------------------------------------
 // WALK (the production launch): at most one block per CU, and a block walks several items (component, row tile, column tile) as ONE pipelined loop.  The
 // items of an XCD (its units in order, column tiles innermost) are dealt round-robin to the XCD's blocks: block j of nb takes items j, j + nb, j + 2 nb ...,
 // so at any time the blocks of an XCD work on neighbouring items (the column tiles of a unit side by side, as the one-item launch's dispatch order has them)
 // and an A row tile is still read through one L2.  The map is a pure function of the shape and the grid: no atomics, graph replay = eager launches.
-// At an item boundary both LDS stages are free behind the barrier that ended the last K-step: the next item's first-stage LDS-DMA loads (no VGPRs) are
-// issued BEFORE the finished accumulators are stored, so their HBM / L2 latency runs under the 64 stores per wave, and the barrier that opens the next
-// item waits for both (vmcnt counts the stores too).  Per output element nothing changes (same six products, same order, same K order): WALK = false, the
-// one-item-per-block launch, is the bit-identity twin (irsde_debug_split_gemm 45, IRSDE_SPLIT3_WALK=0).
-template <int ABL = 0, bool WALK = true>
+// At an item boundary both LDS stages are free behind the barrier that ended the last K-step and nothing is in flight: the next item's first LDS-DMA loads
+// (step 0 and A0, B of step 1; no VGPRs) are issued BEFORE the finished accumulators are stored, so their HBM / L2 latency runs under the 64 stores per wave,
+// and the item opens with a full drain (vmcnt(0): the counter holds the stores too, which do not retire in order with loads) and a barrier.  Per output
+// element nothing changes: WALK = false, the one-item-per-block launch, is the bit-identity twin (irsde_debug_split_gemm 45, IRSDE_SPLIT3_WALK=0).
+#define IRSDE_WAIT_VM(N) asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory")
+#define IRSDE_PHASE_BARRIER()                              \
+    do {                                                   \
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); \
+        __builtin_amdgcn_s_barrier();                      \
+    } while (0)
+template <int ABL = 0, bool WALK = true, bool DRAIN = false>
 __global__ __launch_bounds__(512, 1) void gemm_split3i_kernel(const SplitGemmArgs g) {
     constexpr int TM = 2, TN = 2, WN = 2, BM = 256, BN = 128;
     constexpr int ROWB = 192, GROUP = 16 * ROWB;                       // bytes per LDS row (12 pieces) and per 16-row group
@@ -429,8 +452,10 @@ __global__ __launch_bounds__(512, 1) void gemm_split3i_kernel(const SplitGemmArg
     const int nk = g.K / SG_BK;
     const unsigned pairb = (unsigned)nk * 384u;   // bytes per operand row pair: K / 32 blocks of 2 rows x 3 planes x 64 B
 
-    // staging: lane slot s = wl * 64 + lane of a group = (row s / 12, position s % 12); the lane fetches the row's piece (position - rotation) mod 12.
+    // staging: the wave's 16-row groups: of A0 group 4 (w / 2) + w % 2 (rows 64 (w / 2) + 16 (w % 2) ...), of A1 the group two further (32 rows on), of B group w.
+    // Lane slot s = wl * 64 + lane of a group = (row s / 12, position s % 12); the lane fetches the row's piece (position - rotation) mod 12.
     // Rows past M / N are clamped: they feed accumulator rows / columns that are never stored.
+    const int ga0 = 4 * (wave >> 1) + (wave & 1);
     int plane0, m0, n0;
     unsigned a_voff[6], b_voff[3];
     const char *acomp, *bcomp;
@@ -441,13 +466,13 @@ __global__ __launch_bounds__(512, 1) void gemm_split3i_kernel(const SplitGemmArg
         n0 = nblk * BN;
 #pragma unroll
         for (int q = 0; q < 9; ++q) {
-            const int gi = q / 3, wl = q - gi * 3;     // gi 0, 1: the wave's A groups, 2: its B group
+            const int gi = q / 3, wl = q - gi * 3;     // gi 0: the wave's A0 group, 1: its A1 group, 2: its B group
             const int sl = wl * 64 + lane;
             const int r = sl / 12, pos = sl - r * 12;
             int j = pos - ((r >> 2) & 3);
             j = j < 0 ? j + 12 : j;
             if (gi < 2) {
-                int m = m0 + (2 * wave + gi) * 16 + r;
+                int m = m0 + (ga0 + 2 * gi) * 16 + r;
                 m = m < g.M ? m : g.M - 1;
                 a_voff[q] = (unsigned)(m >> 1) * pairb + (unsigned)(m & 1) * 192u + (unsigned)j * 16u;
             } else {
@@ -459,12 +484,25 @@ __global__ __launch_bounds__(512, 1) void gemm_split3i_kernel(const SplitGemmArg
         acomp = reinterpret_cast<const char*>(g.a) + (long long)plane0 * g.pA * 2;   // pA / pB: unsigned shorts per component
         bcomp = reinterpret_cast<const char*>(g.b) + (long long)plane0 * g.pB * 2;
     };
-    int kb = 0;
-    auto issue_loads_part = [&](int buf, int part) {   // the 9 loads of a stage in three groups: A group 2w | A group 2w+1 | B group w
-        const char* gsrc = (part < 2 ? acomp : bcomp) + (size_t)kb * 384;
-        char* l = lds + buf * STAGE + (part < 2 ? (2 * wave + part) * GROUP : A_STAGE + wave * GROUP);
+    auto issue_unit = [&](int kb, int kind) {   // the wave's 3 loads of a unit of K-step kb (stage kb & 1): kind 0 = A0, 1 = A1, 2 = B
+        const char* gsrc = (kind < 2 ? acomp : bcomp) + (size_t)kb * 384;
+        char* l = lds + (kb & 1) * STAGE + (kind < 2 ? (ga0 + 2 * kind) * GROUP : A_STAGE + wave * GROUP);
 #pragma unroll
-        for (int wl = 0; wl < 3; ++wl) IRSDE_GLDS16(gsrc + (part < 2 ? a_voff[part * 3 + wl] : b_voff[wl]), l + wl * 1024);
+        for (int wl = 0; wl < 3; ++wl) IRSDE_GLDS16(gsrc + (kind < 2 ? a_voff[kind * 3 + wl] : b_voff[wl]), l + wl * 1024);
+    };
+    auto issue_one = [&](int kb, int kind, int wl) {   // one of those loads
+        const char* gsrc = (kind < 2 ? acomp : bcomp) + (size_t)kb * 384;
+        char* l = lds + (kb & 1) * STAGE + (kind < 2 ? (ga0 + 2 * kind) * GROUP : A_STAGE + wave * GROUP);
+        IRSDE_GLDS16(gsrc + (kind < 2 ? a_voff[kind * 3 + wl] : b_voff[wl]), l + wl * 1024);
+    };
+    auto issue_first = [&]() {   // an item's opening loads, in the ring's order: A0, B, A1 of step 0, then A0, B of step 1
+        issue_unit(0, 0);
+        issue_unit(0, 2);
+        issue_unit(0, 1);
+        if (nk > 1) {
+            issue_unit(1, 0);
+            issue_unit(1, 2);
+        }
     };
 
     floatx16 acc[TM][TN];
@@ -476,8 +514,7 @@ __global__ __launch_bounds__(512, 1) void gemm_split3i_kernel(const SplitGemmArg
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
     set_item(it);
-#pragma unroll
-    for (int part = 0; part < 3; ++part) issue_loads_part(0, part);
+    issue_first();
 
     // fragment offsets: row l31 of a 32-row tile (two 16-row groups back to back = 192 bytes per row), piece plane * 4 + sb * 2 + h, rotated by (row >> 2) & 3
     int fr_off[3][2];
@@ -485,40 +522,75 @@ __global__ __launch_bounds__(512, 1) void gemm_split3i_kernel(const SplitGemmArg
     for (int p = 0; p < 3; ++p)
 #pragma unroll
         for (int sb = 0; sb < 2; ++sb) fr_off[p][sb] = l31 * ROWB + ((p * 4 + sb * 2 + h + ((l31 >> 2) & 3)) % 12) * 16;
+    // fragment sets: [sb] = the 16-k sub-step; fb holds the B fragments of a K-step through both phases
+    bf16x8 fa[2][3], fb[2][3][TN];
+    auto read_a = [&](int sb, const char* a) {
+#pragma unroll
+        for (int p = 0; p < 3; ++p) fa[sb][p] = *reinterpret_cast<const bf16x8*>(a + fr_off[p][sb]);
+    };
+    auto read_b = [&](int sb, const char* b) {
+#pragma unroll
+        for (int p = 0; p < 3; ++p)
+#pragma unroll
+            for (int j = 0; j < TN; ++j) fb[sb][p][j] = *reinterpret_cast<const bf16x8*>(b + j * 32 * ROWB + fr_off[p][sb]);
+    };
+    const bool late = wave >= 4;
+    const int a_base = wm * TM * 32 * ROWB, b_base = A_STAGE + wn * TN * 32 * ROWB;
     for (;;) {
-        __syncthreads();   // the item's first stage has landed (and, behind an earlier item, that item's stores have left)
+        IRSDE_WAIT_VM(0);   // the item's opening loads have landed (and, behind an earlier item, that item's stores have left)
+        IRSDE_PHASE_BARRIER();
+        read_a(0, lds + a_base);   // sub-step 0 of step 0: the only fragment reads of an item that no MFMA covers
+        read_b(0, lds + b_base);
+        __builtin_amdgcn_sched_barrier(0);
         for (int st = 0; st < nk; ++st) {
-            const int buf = st & 1;
-            const bool more = st + 1 < nk;
-            if (more) ++kb;   // (stage buf^1 was last read in step st-1: every wave is past that step's barrier when the loads below are issued)
-            const char* a = lds + buf * STAGE + wm * TM * 32 * ROWB;
-            const char* b = lds + buf * STAGE + A_STAGE + wn * TN * 32 * ROWB;
-            bf16x8 fa[2][3][TM], fb[2][3][TN];
+            const bool more1 = st + 1 < nk, more2 = st + 2 < nk;
+            const char* a = lds + (st & 1) * STAGE + a_base;
+            const char* b = lds + (st & 1) * STAGE + b_base;
+            const char* an = lds + ((st + 1) & 1) * STAGE + a_base;
+            const char* bn = lds + ((st + 1) & 1) * STAGE + b_base;
 #pragma unroll
-            for (int sb = 0; sb < 2; ++sb)
-#pragma unroll
-                for (int p = 0; p < 3; ++p) {
-#pragma unroll
-                    for (int i = 0; i < TM; ++i) fa[sb][p][i] = *reinterpret_cast<const bf16x8*>(a + i * 32 * ROWB + fr_off[p][sb]);
-#pragma unroll
-                    for (int j = 0; j < TN; ++j) fb[sb][p][j] = *reinterpret_cast<const bf16x8*>(b + j * 32 * ROWB + fr_off[p][sb]);
-                }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int sb = 0; sb < 2; ++sb)
-#pragma unroll
-                for (int pr = 0; pr < 6; ++pr) {
-#pragma unroll
-                    for (int i = 0; i < TM; ++i)
-#pragma unroll
-                        for (int j = 0; j < TN; ++j) {
-                            if (ABL != 3) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[sb][PA[pr]][i], fb[sb][PB[pr]][j], acc[i][j], 0, 0, 0);
-                            else acc[i][j][0] += (float)fa[sb][PA[pr]][i][0] * (float)fb[sb][PB[pr]][j][0];
-                        }
-                    if (sb == 0 && pr < 3 && ABL != 1 && more) issue_loads_part(buf ^ 1, pr);   // 3 + 3 + 3 loads behind the first three MFMA groups
+            for (int i = 0; i < TM; ++i) {   // phase i: tile row i
+                if (i == 1) {
+                    read_a(0, a + 32 * ROWB);
                     __builtin_amdgcn_sched_barrier(0);
                 }
-            __syncthreads();
+#pragma unroll
+                for (int sb = 0; sb < 2; ++sb)
+#pragma unroll
+                    for (int pr = 0; pr < 6; ++pr) {
+#pragma unroll
+                        for (int j = 0; j < TN; ++j) {
+                            if (ABL != 3) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[sb][PA[pr]], fb[sb][PB[pr]][j], acc[i][j], 0, 0, 0);
+                            else acc[i][j][0] += (float)fa[sb][PA[pr]][0] * (float)fb[sb][PB[pr]][j][0];
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
+                        // fragment reads a whole sub-step ahead of their first use, behind the first MFMA group of the sub-step that covers them (the
+                        // compiler waits lgkmcnt(0) at the first use of any fragment while an LDS-DMA is pending: reads issued before that group would be waited for)
+                        if (sb == 0 && pr == 0) {
+                            if (i == 0) {
+                                read_a(1, a);
+                                read_b(1, b);
+                            } else {
+                                read_a(1, a + 32 * ROWB);
+                            }
+                        }
+                        if (i == 1 && sb == 1 && pr == 0 && more1) {   // sub-step 0 of the next step: A0, B(st + 1) were retired at the end of phase 0
+                            read_a(0, an);
+                            read_b(0, bn);
+                        }
+                        // the phase's loads one per MFMA group; the two waves of a SIMD (w and w + 4 leave a barrier in step) issue theirs in different sub-steps,
+                        // so that one of them multiplies while the other waits for the vector-memory pipe to take its load
+                        if (ABL != 1 && (sb == 1) == late) {
+                            if (i == 0 && pr >= 1 && pr <= 3 && more1) issue_one(st + 1, 1, pr - 1);
+                            if (i == 1 && more2) issue_one(st + 2, pr < 3 ? 0 : 2, pr % 3);
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                // phase 0 retires A1(st) and A0, B(st + 1) and leaves A1(st + 1) in flight; phase 1 retires nothing and leaves that and A0, B(st + 2) in flight
+                if (DRAIN || (i == 0 && !more1)) IRSDE_WAIT_VM(0);
+                else if (i == 0) IRSDE_WAIT_VM(3);
+                IRSDE_PHASE_BARRIER();
+            }
         }
 
         // registers -> buffer stores: rows past M dropped by the descriptor, columns past N masked
@@ -529,11 +601,9 @@ __global__ __launch_bounds__(512, 1) void gemm_split3i_kernel(const SplitGemmArg
         const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(ob, 0, nrec, 0x00020000);
         it += it_step;
         const bool next = WALK && it < nitems;
-        if (next) {   // both stages are free behind the last step's barrier: the next item's first stage goes out ahead of this item's stores
+        if (next) {   // both stages are free behind the last step's barrier: the next item's opening loads go out ahead of this item's stores
             set_item(it);
-            kb = 0;
-#pragma unroll
-            for (int part = 0; part < 3; ++part) issue_loads_part(0, part);
+            issue_first();
             __builtin_amdgcn_sched_barrier(0);
         }
 #pragma unroll
@@ -560,6 +630,8 @@ __global__ __launch_bounds__(512, 1) void gemm_split3i_kernel(const SplitGemmArg
                 for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
     }
 }
+#undef IRSDE_PHASE_BARRIER
+#undef IRSDE_WAIT_VM
 #undef IRSDE_GLDS16
 
 // f32 [ncomp][rows][K] -> the three-piece row-pair-interleaved layout (split3_layout.h)
@@ -640,6 +712,7 @@ void gemm_split_global_init() {
     IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split2i_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split3i_kernel<0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split3i_kernel<0, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split3i_kernel<0, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
 #ifdef IRSDE_PROBES
     IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split3i_kernel<1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split3i_kernel<3, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -647,6 +720,9 @@ void gemm_split_global_init() {
     IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split3i_kernel<1, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split3i_kernel<3, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split3i_kernel<4, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split3i_kernel<1, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split3i_kernel<3, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split3i_kernel<4, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
 #endif
     IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -703,7 +779,8 @@ void set_force_split3_blocks(int n) { g_force_split3_blocks.store(n >= 8 ? n : -
 
 // three-piece row-pair-interleaved operands (split3_layout.h; g.pA / g.pB = unsigned shorts per component)
 // walk: 1 = at most one block per CU (or the forced cap), each walking its share of the items; 0 = one item per block (the twin); -1 = IRSDE_SPLIT3_WALK (1)
-void launch_gemm_split_triples(const SplitGemmArgs& a, int ncomp, hipStream_t s, int abl, int walk) {
+// drain: 1 = the walk's drain twin (vmcnt(0) in front of every barrier of the K loop); 0 = the ring; -1 = IRSDE_SPLIT3_DRAIN (0)
+void launch_gemm_split_triples(const SplitGemmArgs& a, int ncomp, hipStream_t s, int abl, int walk, int drain) {
     if (a.K % SG_BK) throw HipError("gemm_split_triples: K must be a multiple of 32");
     if (!gemm_split_triples_fits(a.M, a.N, a.K, a.ldc)) throw HipError("gemm_split_triples: a component exceeds the 32-bit offset range");
     if (ncomp < 1 || a.ldc < a.N) throw HipError("gemm_split_triples: bad component count or output stride");
@@ -711,6 +788,11 @@ void launch_gemm_split_triples(const SplitGemmArgs& a, int ncomp, hipStream_t s,
         static const int knob = tuning_env_int("IRSDE_SPLIT3_WALK", 1);
         walk = knob != 0;
     }
+    if (drain < 0) {
+        static const int knob = tuning_env_int("IRSDE_SPLIT3_DRAIN", 0);
+        drain = knob != 0;
+    }
+    if (drain && !walk) throw HipError("gemm_split_triples: the drain twin exists on the walk only");
     SplitGemmArgs g = a;
     g.nblk_n = (a.N + 127) / 128;
     g.n_inner = ncomp;   // an item = (component, row tile, column tile); n_inner carries the component count
@@ -725,9 +807,10 @@ void launch_gemm_split_triples(const SplitGemmArgs& a, int ncomp, hipStream_t s,
     }
     const dim3 grid((unsigned)blocks);
     const size_t lds = (size_t)2 * (256 + 128) * 192;
-    switch (abl * 2 + (walk ? 1 : 0)) {
+    switch (abl * 2 + (walk ? 1 : 0) + (drain ? 100 : 0)) {
         case 1: hipLaunchKernelGGL((gemm_split3i_kernel<0, true>), grid, dim3(512), lds, s, g); break;
         case 0: hipLaunchKernelGGL((gemm_split3i_kernel<0, false>), grid, dim3(512), lds, s, g); break;
+        case 101: hipLaunchKernelGGL((gemm_split3i_kernel<0, true, true>), grid, dim3(512), lds, s, g); break;
 #ifdef IRSDE_PROBES
         case 3: hipLaunchKernelGGL((gemm_split3i_kernel<1, true>), grid, dim3(512), lds, s, g); break;
         case 7: hipLaunchKernelGGL((gemm_split3i_kernel<3, true>), grid, dim3(512), lds, s, g); break;
@@ -735,6 +818,9 @@ void launch_gemm_split_triples(const SplitGemmArgs& a, int ncomp, hipStream_t s,
         case 2: hipLaunchKernelGGL((gemm_split3i_kernel<1, false>), grid, dim3(512), lds, s, g); break;
         case 6: hipLaunchKernelGGL((gemm_split3i_kernel<3, false>), grid, dim3(512), lds, s, g); break;
         case 8: hipLaunchKernelGGL((gemm_split3i_kernel<4, false>), grid, dim3(512), lds, s, g); break;
+        case 103: hipLaunchKernelGGL((gemm_split3i_kernel<1, true, true>), grid, dim3(512), lds, s, g); break;
+        case 107: hipLaunchKernelGGL((gemm_split3i_kernel<3, true, true>), grid, dim3(512), lds, s, g); break;
+        case 109: hipLaunchKernelGGL((gemm_split3i_kernel<4, true, true>), grid, dim3(512), lds, s, g); break;
 #endif
         default: throw HipError("gemm_split_triples: the ablation twins are part of the PROBES build");
     }

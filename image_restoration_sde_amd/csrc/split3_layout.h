@@ -6,6 +6,8 @@
 // so the 16 rows x 192 bytes a stage's LDS-DMA group fetches are 8 blocks of whole lines (a single row's 192 bytes would start on a half line every
 // second row).  A component holds split3_rows(rows) rows (rows rounded up to even; the pad row of an odd matrix is never read: the kernel clamps
 // its row index to rows - 1) = split3_comp_elems(rows, K) unsigned shorts, 6 bytes per f32 element.
+// The kernel's load ring (profiles/split3_ring.md) cuts a K-step's stage by tile ROWS (24 KB units of 16-row groups), never inside a block: every LDS-DMA
+// wave-load still fetches whole 384-byte blocks, so the ring needed no 16-k re-layout of the blocks and every writer stores what it stored before.
 #pragma once
 #include <cstddef>
 

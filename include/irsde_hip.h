@@ -55,6 +55,8 @@
  *        irsde_bench_conv 490 - 494.
  *        Debug header only, same version: irsde_debug_force_split3_blocks, irsde_debug_split_gemm nplanes 45, irsde_debug_conv selector 28, irsde_bench_conv 495 - 499 (the three-piece
  *        GEMM launches at most one block per compute unit and a block walks several tiles; same results bit for bit; tuning knob IRSDE_SPLIT3_WALK).
+ *        Debug header only, same version: irsde_debug_split_gemm nplanes 47, irsde_bench_conv 500 - 504 (the three-piece GEMM keeps nine LDS-DMA wave-loads per
+ *        wave in flight across every barrier of its K loop; same results bit for bit; the twin that drains them is the tuning knob IRSDE_SPLIT3_DRAIN).
  */
 #ifndef IRSDE_HIP_H
 #define IRSDE_HIP_H

@@ -54,7 +54,8 @@ int irsde_debug_conv(const float* in0, int C0, const float* in1, int C1, int B, 
  * operands split into `nplanes` (2 or 3) bf16 pieces on the device (plane-major prototype kernel; nplanes = 42 / 44: the engine's
  * pair-interleaved two-piece kernel with bf16 / fp16 pieces; nplanes = 43: the exact-fp32 engine's three-piece kernel gemm_split3i_kernel, six products, on
  * its production launch — at most one block per compute unit, each walking several (component, row tile, column tile) items; nplanes = 45: the same kernel
- * with one item per block, the walk's bit-identity twin), products on v_mfma_f32_32x32x16_bf16, f32 accumulate.  K a multiple of 32.  Synchronises `stream`. */
+ * with one item per block, the walk's bit-identity twin; nplanes = 47: the production launch with s_waitcnt vmcnt(0) in front of every barrier of the K loop,
+ * the bit-identity twin of the kernel's load ring), products on v_mfma_f32_32x32x16_bf16, f32 accumulate.  K a multiple of 32.  Synchronises `stream`. */
 int irsde_debug_split_gemm(const float* A, const float* B, float* C, int M, int N, int K, int ncomp, int nplanes, void* stream);
 
 /* Kernel tuning hook: average ms of one KxK convolution (pad K/2, or 4x4 s2 p1) on random NHWC data.  variant (any other code is refused):
@@ -74,6 +75,7 @@ int irsde_debug_split_gemm(const float* A, const float* B, float* C, int M, int 
  *   472 the engine's pair-interleaved two-plane GEMM alone, 473 / 475 / 476 without its global loads / MFMAs / output stores (474: no such twin, the launch refuses it)
  *   490 the three-piece GEMM (gemm_split3i_kernel) alone on the layer's 36 F(4x4,3x3) component shapes, 491 / 493 / 494 without its global loads / MFMAs /
  *     output stores (PROBES build; 492: no such twin, the launch refuses it); 495 - 499: the same five on the one-item-per-block launch (the walk's twin)
+ *     500 - 504: the same five on the drain twin (vmcnt(0) in front of every barrier of the K loop: what the load ring's span across barriers buys)
  *   480 / 481 / 482 a direct layer on the PAIR kernels (fp16 / bf16 pieces / fp16 without the 256 x 256 tile)
  * epi: 0 none, 1 FiLM+SiLU, 2 SiLU+residual. */
 int irsde_bench_conv(int variant, int B, int H, int W, int Cin, int Cout, int K, int stride, int up, int epi, int iters,
