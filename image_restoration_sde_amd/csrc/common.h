@@ -109,11 +109,9 @@ struct WinoParams {
     int B = 0, TH = 0, TW = 0, T = 0;
     int tile = 2;               // output tile edge m of F(m x m, 3x3): 2 or 4; components = (m+2)^2
     float* V = nullptr;         // [(m+2)^2][T][C0+C1]
-    // split-operand mode (gemm_split.hip): V is written as `nplanes` bf16 planes instead, element (p, k, t, c) at
-    // Vs + p * v_plane + (k * T + t) * (C0 + C1) + c
+    // split-operand mode (gemm_split.hip): V is written as `nplanes` 16-bit pieces instead, in the layout v_pairs / v_triples names
     unsigned short* Vs = nullptr;
     int nplanes = 0;
-    long long v_plane = 0;
     int v_f16 = 0;              // pairs only: 1 = IEEE fp16 pieces of V * v_scale (v_scale a power of two), 0 = bf16 pieces of V
     float v_scale = 1.f;
     int v_pairs = 0;            // 1: two planes, pair-interleaved: element (k, t, c, p) at Vs + ((k * T + t) * (Ctot / 32) + c / 32) * 64 + p * 32 + c % 32
@@ -156,34 +154,37 @@ void launch_wino_poly_output(const WinoPolyParams& p, hipStream_t s);
 // host: U of the layouts above from the packed weights [Cout][KH][KW][Cin] (up = 0: 4x4, 25 * Cout * 4 Cin floats; up = 1: 3x3, 100 * Cout * Cin floats)
 void wino_poly_transform_weights(const float* w_packed, int Cout, int Cin, float* U, int up);
 // fp32-equivalent GEMMs on the bf16 MFMA pipe (gemm_split.hip): C_z[m][n] = sum_k A_z[m][k] B_z[n][k] with both operands given
-// as 2 or 3 bf16 planes (hi / mid / lo pieces of the f32 value), f32 accumulate, z = 0 .. ncomp-1.
+// as 2 or 3 16-bit planes (hi / mid / lo pieces of the f32 value), f32 accumulate, z = 0 .. ncomp-1.
 struct SplitGemmArgs {
-    const unsigned short* a = nullptr;  // element (plane p, z, m, k) at a + p * plA + z * pA + m * lda + k
-    const unsigned short* b = nullptr;  // element (plane q, z, n, k) at b + q * plB + z * pB + n * K + k
+    const unsigned short* a = nullptr;  // component z at a + z * pA, b + z * pB, in the launcher's interleaved layout
+    const unsigned short* b = nullptr;
     float* out = nullptr;               // element (z, m, n) at out + z * pO + m * ldc + n
-    long long plA = 0, plB = 0, pA = 0, pB = 0, pO = 0;
+    long long plA = 0, plB = 0, pA = 0, pB = 0, pO = 0;   // (plA / plB / lda: read by no kernel; kept so that the kernels' argument block stays as it was)
     int M = 0, N = 0, K = 0, lda = 0, ldc = 0;
     float out_scale = 1.f;              // fp16 pairs: the power of two that undoes the operand scales (applied to the accumulators)
-    int n_inner = 1;                    // components walked by one block (gemm_split_inner)
+    int n_inner = 1;                    // set by the launcher: the component count
     int nblk_n = 0;                     // set by the launcher
 };
 void gemm_split_global_init();
-int gemm_split_inner(int M, int N, int ncomp);
 // two planes in the pair-interleaved layout [row][k / 32][plane][32 k] (v3 kernel: LDS-DMA, 256 x 256 tiles); pA / pB = elements
-// per component and plane (M * K resp. N * K), plA / plB unused
+// per component and plane (M * K resp. N * K)
 // f16: IEEE binary16 pieces (hi + lo = 22+ significand bits: fp32-equivalent products) instead of bf16 (16 bits); a.out_scale undoes
 // the power-of-two scales the operand writers applied to stay inside fp16's range
 void launch_gemm_split_pairs(const SplitGemmArgs& a, int ncomp, hipStream_t s, int abl = 0, bool f16 = false);
 void launch_split_pairs(const float* in, unsigned short* out, size_t rows, int K, hipStream_t s, bool f16 = false,
                         float scale = 1.0f);  // f32 [rows][K] -> pair-interleaved hi / lo (f16: of in * scale)
-void launch_gemm_split(const SplitGemmArgs& a, int nplanes, int ncomp, hipStream_t s);
 // three bf16 planes in the row-pair-interleaved layout of split3_layout.h (gemm_split3i_kernel: six products, LDS-DMA, 256 x 128 tiles): the default path of
-// the exact-fp32 engine's deep component GEMMs.  pA / pB = unsigned shorts per component (split3_comp_elems), plA / plB / lda unused.
-// abl: the measurement twins of the PROBES build (1 no global loads in the K loop, 3 no MFMAs, 4 no output stores)
-// walk: 1 = the persistent launch (at most one block per CU, each walking its share of the items), 0 = one item per block (its bit-identity twin),
-// -1 = the tuning knob IRSDE_SPLIT3_WALK (default 1).  drain: 1 = the walk with vmcnt(0) in front of every barrier of the K loop (the ring's twin), 0 = the ring,
-// -1 = the tuning knob IRSDE_SPLIT3_DRAIN (default 0)
-void launch_gemm_split_triples(const SplitGemmArgs& a, int ncomp, hipStream_t s, int abl = 0, int walk = -1, int drain = -1);
+// the exact-fp32 engine's deep component GEMMs.  pA / pB = unsigned shorts per component (split3_comp_elems).
+// Split3Launch picks the instance: the defaults are what every plan runs.
+struct Split3Launch {
+    enum Abl { FULL = 0, NO_LOADS = 1, NO_MFMA = 3, NO_STORES = 4 };   // the measurement twins of the PROBES build: no global loads in the K loop / MFMAs / output stores
+    enum Tri { RULE, ON, OFF };                                         // RULE: the tuning knob, else the default
+    Abl abl = FULL;
+    Tri walk = RULE;    // ON: the persistent launch (at most one block per CU, each walking its share of the items), OFF: one item per block (its bit-identity twin);
+                        // RULE: IRSDE_SPLIT3_WALK (default on)
+    Tri drain = RULE;   // ON: the walk with vmcnt(0) in front of every barrier of the K loop (the ring's twin), OFF: the ring; RULE: IRSDE_SPLIT3_DRAIN (default off)
+};
+void launch_gemm_split_triples(const SplitGemmArgs& a, int ncomp, hipStream_t s, const Split3Launch& o = {});
 void set_force_split3_blocks(int n);   // irsde_debug_force_split3_blocks: caps the persistent launch's grid (>= 8); -1 = one block per CU
 bool gemm_split_triples_fits(long long M, long long N, long long K, long long ldc);   // K % 32 == 0 and every component slice inside the 32-bit offset range
 void launch_split_triples(const float* in, unsigned short* out, int ncomp, size_t rows, int K, hipStream_t s);   // f32 [ncomp][rows][K] -> that layout
@@ -236,14 +237,25 @@ void naf_chain_set_sabotage(int on);   // PROBES build: one group per image neve
 void attention_global_init();
 
 double conv_flops(const ConvParams& p);  // 2*M*Cout*K (algorithmic)
-void launch_conv(const ConvParams& p, hipStream_t s);
+// Tuning overrides of ONE launch_conv call (the kernel-level hooks of engine_debug.hip; never part of a kernel's arguments).  The default is the production dispatch.
+struct ConvTune {
+    enum Tile { TILE_AUTO, TILE_128, TILE_256x128, TILE_256, TILE_128_ONE_PER_CU };
+    enum Halo { HALO_AUTO, HALO_OFF, HALO_FORCE_512, HALO_FORCE_256 };
+    enum ZLoop { ZLOOP_AUTO, ZLOOP_OFF, ZLOOP_ALL, ZLOOP_PAIRS, ZLOOP_FORCE_1X1 };
+    bool rules_off = false;        // off: the IRSDE_SMALL_BN(_F32) narrowing, the vector-pipe 3-channel kernel, the automatic 256 x 256 tile of the f32 kernels
+    Tile tile = TILE_AUTO;         // f32, Cout >= 128: 256x128 / 256 / one 128 x 128 block per CU (120 KB of LDS); 16-bit operands and PAIR: 256 / 128
+    bool no_buffer_desc = false;   // f32: generic pointer staging instead of buffer descriptors
+    bool no_direct_epi = false;    // f32: LDS-transposed instead of direct epilogue
+    Halo halo = HALO_AUTO;         // 16-bit operands, eligible 3x3 layers: generic tiles / the 512-pixel x 128-channel / the 256-pixel halo kernel
+    ZLoop zloop = ZLOOP_AUTO;      // tile-loop kernel: both forms off / its batch-loop form with all / 2 components per block / forced (2 row tiles) for 1x1 layers
+};
+void launch_conv(const ConvParams& p, hipStream_t s, const ConvTune& t = {});
 void conv_global_init();
 // bf16 mode: 3x3 s1 p1 layers with an LDS-resident halo tile (conv_halo.hip)
 void conv_halo_global_init();
 bool conv_halo_eligible(const ConvParams& p);
 bool conv_halo2_wanted(const ConvParams& p, int force);   // true: launch_conv_halo runs the layer on the 512-pixel x 128-channel kernel (irsde_plan_describe names it)
 void launch_conv_halo(const ConvParams& p, hipStream_t s, int force_halo2 = 0);   // force_halo2: 1 = the 512-pixel x 128-channel kernel, -1 = the 256-pixel one, 0 = by shape
-void conv_set_variant(int v);  // tuning experiments (irsde_bench_conv)
 void launch_fill_random(float* p, size_t n, unsigned seed, float scale, hipStream_t s);  // sets the dynamic-LDS attribute of every tile configuration (call before graph capture)
 // SiLU for the epilogues of the f32 MFMA kernels: v_exp_f32 + v_rcp_f32 (1 ulp each) — 5 vector instructions instead of the
 // ~25 of expf() + IEEE division.  On gfx950 the vector instructions of an f32-MFMA kernel are paid in matrix-pipe time

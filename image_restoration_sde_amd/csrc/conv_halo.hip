@@ -679,7 +679,7 @@ bool conv_halo_eligible(const ConvParams& p) {
 }
 
 // r05: the 512-pixel x 128-channel kernel where it fills the chip (one block per CU: >= 256 blocks) without padding the feature map by more than a
-// quarter; force: 1 = always (if the layer fits its descriptors), -1 = never (conv_set_variant 64 / 65: irsde_debug_conv 162 / 262 / 166 and 163 / 263 / 167, irsde_bench_conv 64 .. 67)
+// quarter; force: 1 = always (if the layer fits its descriptors), -1 = never (ConvTune::halo: irsde_debug_conv 162 / 262 / 166 and 163 / 263 / 167, irsde_bench_conv 64 .. 67)
 bool conv_halo2_wanted(const ConvParams& p, int force) {
     if (force < 0 || p.Cout < 128 || !halo2_fits(p)) return false;
     if (force > 0) return true;

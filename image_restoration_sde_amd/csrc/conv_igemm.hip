@@ -1203,8 +1203,6 @@ __global__ void conv_naive_kernel(const ConvParams p, const int M) {
     p.out[(size_t)m * p.out_stride + n] = v;
 }
 
-int g_variant = 0;  // tuning experiments only (irsde_bench_conv); 6 = generic pointer staging instead of buffer descriptors
-
 // PAIR kernels (split-operand arithmetic on fp32 storage): bf16 or fp16 pieces by p.f16
 template <int BM, int BN, int WAVES_M, int WAVES_N, int MINW, bool INSCALE>
 void launch_cfg_pair(const ConvParams& p, int M, int nk_total, hipStream_t s) {
@@ -1231,11 +1229,11 @@ void init_cfg_pair() {
 }
 
 template <int BM, int BN, int WAVES_M, int WAVES_N, int MINW, bool BF16, bool INSCALE = false, bool ABF = false, bool F16 = false, bool AF16 = false>
-void launch_cfg(const ConvParams& p, int M, int nk_total, hipStream_t s, int lds_override = 0) {
+void launch_cfg(const ConvParams& p, int M, int nk_total, hipStream_t s, const ConvTune& t, int lds_override = 0) {
     using C = Cfg<BM, BN, WAVES_M, WAVES_N, BF16, ABF || AF16>;
     if constexpr (BF16 && !ABF && !F16) {
-        if (p.f16 && p.in_f16) return launch_cfg<BM, BN, WAVES_M, WAVES_N, MINW, true, INSCALE, false, true, true>(p, M, nk_total, s, lds_override);
-        if (p.f16) return launch_cfg<BM, BN, WAVES_M, WAVES_N, MINW, true, INSCALE, false, true>(p, M, nk_total, s, lds_override);
+        if (p.f16 && p.in_f16) return launch_cfg<BM, BN, WAVES_M, WAVES_N, MINW, true, INSCALE, false, true, true>(p, M, nk_total, s, t, lds_override);
+        if (p.f16) return launch_cfg<BM, BN, WAVES_M, WAVES_N, MINW, true, INSCALE, false, true>(p, M, nk_total, s, t, lds_override);
     }
     auto kern = conv_igemm_kernel<BM, BN, WAVES_M, WAVES_N, MINW, BF16, INSCALE, ABF, F16, false, false, AF16>;
     if constexpr (!BF16) {  // f32: the buffer-descriptor staging when every operand tensor is below 2 GiB
@@ -1243,7 +1241,7 @@ void launch_cfg(const ConvParams& p, int M, int nk_total, hipStream_t s, int lds
         const long long e0 = ((npix - 1) * p.pix0 + p.C0) * 4, e1 = p.C1 ? ((npix - 1) * p.pix1 + p.C1) * 4 : 0;
         const long long ew = (long long)p.Cout * p.KH * p.KW * (p.C0 + p.C1) * 4;
         static const int nobuf = tuning_env_int("IRSDE_NO_BUFA", 0);
-        if (!nobuf && e0 < (1ll << 31) && e1 < (1ll << 31) && ew < (1ll << 31) && g_variant != 6)
+        if (!nobuf && e0 < (1ll << 31) && e1 < (1ll << 31) && ew < (1ll << 31) && !t.no_buffer_desc)
             kern = conv_igemm_kernel<BM, BN, WAVES_M, WAVES_N, MINW, BF16, INSCALE, ABF, F16, true>;
     }
     const int nblk_m = (M + BM - 1) / BM;
@@ -1251,7 +1249,7 @@ void launch_cfg(const ConvParams& p, int M, int nk_total, hipStream_t s, int lds
     dim3 grid(nblk_m * nblk_n, p.splits, p.nz);
     ConvParams pk = p;
     static const int no_direct = tuning_env_int("IRSDE_NO_DIRECT_EPI", 0);
-    if (no_direct || g_variant == 7) pk.no_direct_epi = 1;
+    if (no_direct || t.no_direct_epi) pk.no_direct_epi = 1;
     hipLaunchKernelGGL(kern, grid, dim3(C::NT), lds_override ? lds_override : C::LDS_BYTES, s, pk, nblk_n, M, nk_total);
     IRSDE_HIP_CHECK(hipGetLastError());
 }
@@ -1277,15 +1275,15 @@ void init_cfg() {
 
 
 // 1x1 convolutions with a short K on the tile-loop kernel: row tiles per block, or 0 = generic kernel.
-int zloop_1x1_rows(const ConvParams& p) {
+int zloop_1x1_rows(const ConvParams& p, const ConvTune& t) {
     if (p.nz != 1 || p.w_bf || p.KH != 1 || p.KW != 1 || p.stride != 1 || p.pad_y || p.pad_x || p.in_shift || p.film || p.silu ||
         p.res || p.splits != 1 || p.gate || p.shuffle || p.ch_scale || p.in_scale || p.ln_g || p.in_bf16 || p.out_bf16)
         return 0;
     static const int env = tuning_env_int("IRSDE_ZLOOP_1X1", -1);  // tuning: 0 = off, n = rows tiles
-    if (g_variant == 70 || env == 0) return 0;
+    if (t.zloop == ConvTune::ZLOOP_OFF || env == 0) return 0;
     const int M = p.B * p.Ho * p.Wo, K = p.C0 + p.C1;
     const int mtiles = (M + 127) / 128, ntiles = (p.Cout + 127) / 128, nk = K / 32;
-    if (g_variant == 73) return 2;  // test hook: force the path on small shapes
+    if (t.zloop == ConvTune::ZLOOP_FORCE_1X1) return 2;  // test hook: force the path on small shapes
     if (env > 0) return env;
     if (nk > 12 || mtiles < 1024) return 0;  // long K amortises the per-tile overhead already; small M: not enough blocks
     int mb = 1;
@@ -1311,14 +1309,14 @@ bool zloop_small_m(const ConvParams& p) {
 }
 
 // components per block for gemm_zloop_kernel, or 0 = use one block per (component, tile)
-int zloop_batch(const ConvParams& p) {
+int zloop_batch(const ConvParams& p, const ConvTune& t) {
     if (p.nz <= 1 || p.w_bf || p.KH != 1 || p.KW != 1 || p.C1 || p.bias || p.film || p.silu || p.res || p.splits != 1 ||
         p.gate || p.shuffle || p.ch_scale || p.in_scale || p.stride != 1 || p.out_stride != p.Cout || p.pix0 != p.C0 ||
         p.B != 1 || p.Ho != 1)
         return 0;
     static const int env_force = tuning_env_int("IRSDE_ZLOOP", -1);  // tuning: 0 = off, n = fixed batch
-    // test hooks: variant 71 = all components in one block, 72 = batches of 2 (F2: 16, F4: 36 components), 70 = off
-    const int force = g_variant == 70 ? 0 : g_variant == 71 ? p.nz : g_variant == 72 ? 2 : env_force;
+    // test hooks: all components in one block, batches of 2 (F2: 16, F4: 36 components), off
+    const int force = t.zloop == ConvTune::ZLOOP_OFF ? 0 : t.zloop == ConvTune::ZLOOP_ALL ? p.nz : t.zloop == ConvTune::ZLOOP_PAIRS ? 2 : env_force;
     if (force == 0) return 0;
     const int nk = p.C0 / 32;
     const long long tiles = (long long)((p.Wo + 127) / 128) * ((p.Cout + 127) / 128);
@@ -1339,8 +1337,6 @@ int zloop_batch(const ConvParams& p) {
 }
 
 }  // namespace
-
-void conv_set_variant(int v) { g_variant = v; }
 
 // CU count of the CURRENT device, cached per device ordinal (a process may hold parts with different CU counts)
 int device_cu_count() {
@@ -1412,10 +1408,10 @@ bool conv_use_tile256(int M, int Cout, int splits, int nk_total) {
 }
 
 // r06 (measurement knob, default off): the under-filled-grid rule of the 16-bit-operand kernels for the f32 direct kernels — column-tile width 128 / 64 / 32
-static int f32_narrow(const ConvParams& p, int M) {
+static int f32_narrow(const ConvParams& p, int M, const ConvTune& t) {
     int bn = p.Cout >= 128 ? 128 : p.Cout > 32 ? 64 : 32;
     static const int k = tuning_env_int("IRSDE_SMALL_BN_F32", 0);
-    if (k && g_variant == 0) {
+    if (k && !t.rules_off) {
         const long long slots = (long long)k * device_cu_count();
         auto blocks = [&](int n) { return (long long)((M + 127) / 128) * ((p.Cout + n - 1) / n) * p.splits * p.nz; };
         while (bn > 32 && blocks(bn) < slots) bn >>= 1;
@@ -1423,7 +1419,7 @@ static int f32_narrow(const ConvParams& p, int M) {
     return bn;
 }
 
-void launch_conv(const ConvParams& p, hipStream_t s) {
+void launch_conv(const ConvParams& p, hipStream_t s, const ConvTune& t) {
     const int M = p.B * p.Ho * p.Wo;
     const int Ctot = p.C0 + p.C1;
     if (p.C0 % 32 || p.C1 % 32 || Ctot == 0)
@@ -1444,7 +1440,7 @@ void launch_conv(const ConvParams& p, hipStream_t s) {
         static const int inscale256 = tuning_env_int("IRSDE_PAIR_INSCALE256", 0);
         // (measured and dropped: a 128 x 128 tile at two blocks per CU, so that one block's write-back overlaps the other's K loop — 10-20 %
         //  SLOWER on every layer class, profiles/r03_pair_conv_sweep.txt: the doubled L2 -> CU operand traffic costs more than the overlap buys)
-        if (t256 && (!p.in_scale || inscale256) && p.Cout % 256 == 0 && (long long)((M + 255) / 256) * (p.Cout / 256) * p.splits >= 256 && g_variant != 61) {
+        if (t256 && (!p.in_scale || inscale256) && p.Cout % 256 == 0 && (long long)((M + 255) / 256) * (p.Cout / 256) * p.splits >= 256 && t.tile != ConvTune::TILE_128) {
             if (p.in_scale) launch_cfg_pair<256, 256, 2, 4, 2, true>(p, M, nk, s);
             else launch_cfg_pair<256, 256, 2, 4, 2, false>(p, M, nk, s);
         } else if (p.Cout >= 128 && M >= 256) {
@@ -1461,14 +1457,14 @@ void launch_conv(const ConvParams& p, hipStream_t s) {
         }
         return;
     }
-    if (!p.w_bf && g_variant == 0 && p.Cout <= 3 && p.C0 == 64 && p.KH == 3 && p.KW == 3 && p.stride == 1 && p.pad_y == 1 && p.pad_x == 1 &&
+    if (!p.w_bf && !t.rules_off && p.Cout <= 3 && p.C0 == 64 && p.KH == 3 && p.KW == 3 && p.stride == 1 && p.pad_y == 1 && p.pad_x == 1 &&
         !p.in_shift && !p.C1 && !p.film && !p.silu && !p.res && p.splits == 1 && p.nz == 1 && !p.gate && !p.shuffle &&
         !p.ch_scale && !p.in_scale && !p.ln_g && M >= 65536) {  // final_conv: vector-pipe kernel (big feature maps only)
         hipLaunchKernelGGL(conv3x3_narrow_kernel, dim3((M + 16 * kNarrowPPG - 1) / (16 * kNarrowPPG)), dim3(256), 0, s, p, M);
         IRSDE_HIP_CHECK(hipGetLastError());
         return;
     }
-    if (const int zb = zloop_batch(p)) {  // short-K Winograd component GEMMs: component loop inside the block
+    if (const int zb = zloop_batch(p, t)) {  // short-K Winograd component GEMMs: component loop inside the block
         using C = Cfg<128, 128, 2, 2, false>;
         ZLoopArgs g{};
         g.a0 = p.in0; g.a1 = nullptr; g.C0 = p.C0; g.C1 = 0; g.lda0 = p.C0; g.lda1 = 0;
@@ -1496,7 +1492,7 @@ void launch_conv(const ConvParams& p, hipStream_t s) {
         IRSDE_HIP_CHECK(hipGetLastError());
         return;
     }
-    if (const int mb = zloop_1x1_rows(p)) {  // short-K 1x1 convolutions: (row tiles x all column tiles) loop inside the block
+    if (const int mb = zloop_1x1_rows(p, t)) {  // short-K 1x1 convolutions: (row tiles x all column tiles) loop inside the block
         using C = Cfg<128, 128, 2, 2, false>;
         const int M = p.B * p.Ho * p.Wo;
         ZLoopArgs g{};
@@ -1531,32 +1527,32 @@ void launch_conv(const ConvParams& p, hipStream_t s) {
         if (p.w_bf) {
             int bn = p.Cout >= 128 ? 128 : p.Cout > 32 ? 64 : 32;
             static const int small_bn = tuning_env_int("IRSDE_SMALL_BN", 2);   // block slots per CU the grid should fill (0 = rule off)
-            if (small_bn && g_variant == 0) {   // (see the rule at the plain 16-bit-operand branch below)
+            if (small_bn && !t.rules_off) {   // (see the rule at the plain 16-bit-operand branch below)
                 const long long slots = (long long)small_bn * device_cu_count();
                 auto blocks = [&](int n) { return (long long)((M + 127) / 128) * ((p.Cout + n - 1) / n) * p.splits * p.nz; };
                 while (bn > 32 && blocks(bn) < slots) bn >>= 1;
             }
-            if (bn == 128) launch_cfg<128, 128, 2, 2, 2, true, true>(p, M, nk_total, s);
-            else if (bn == 64) launch_cfg<128, 64, 2, 2, 2, true, true>(p, M, nk_total, s);
-            else launch_cfg<128, 32, 4, 1, 2, true, true>(p, M, nk_total, s);
+            if (bn == 128) launch_cfg<128, 128, 2, 2, 2, true, true>(p, M, nk_total, s, t);
+            else if (bn == 64) launch_cfg<128, 64, 2, 2, 2, true, true>(p, M, nk_total, s, t);
+            else launch_cfg<128, 32, 4, 1, 2, true, true>(p, M, nk_total, s, t);
         } else {
-            if (p.Cout >= 128) launch_cfg<128, 128, 2, 2, 2, false, true>(p, M, nk_total, s);
-            else if (p.Cout > 32) launch_cfg<128, 64, 2, 2, 2, false, true>(p, M, nk_total, s);
-            else launch_cfg<128, 32, 4, 1, 2, false, true>(p, M, nk_total, s);
+            if (p.Cout >= 128) launch_cfg<128, 128, 2, 2, 2, false, true>(p, M, nk_total, s, t);
+            else if (p.Cout > 32) launch_cfg<128, 64, 2, 2, 2, false, true>(p, M, nk_total, s, t);
+            else launch_cfg<128, 32, 4, 1, 2, false, true>(p, M, nk_total, s, t);
         }
-    } else if (p.w_bf && g_variant != 60 && g_variant != 61 && conv_halo_eligible(p)) {
-        launch_conv_halo(p, s, g_variant == 64 ? 1 : g_variant == 65 ? -1 : 0);  // 3x3 s1 p1: LDS-resident halo tile (conv_halo.hip)
+    } else if (p.w_bf && t.halo != ConvTune::HALO_OFF && conv_halo_eligible(p)) {
+        launch_conv_halo(p, s, t.halo == ConvTune::HALO_FORCE_512 ? 1 : t.halo == ConvTune::HALO_FORCE_256 ? -1 : 0);  // 3x3 s1 p1: LDS-resident halo tile (conv_halo.hip)
         return;
     } else if (p.w_bf && p.in_bf16) {  // bf16 operands AND bf16 activation storage
         if (p.Cout >= 128) {
-            if (g_variant != 61 && (g_variant == 60 || conv_use_tile256(M, p.Cout, p.splits, nk_total)))
-                launch_cfg<256, 256, 2, 4, 2, true, false, true>(p, M, nk_total, s);
+            if (t.tile != ConvTune::TILE_128 && (t.tile == ConvTune::TILE_256 || conv_use_tile256(M, p.Cout, p.splits, nk_total)))
+                launch_cfg<256, 256, 2, 4, 2, true, false, true>(p, M, nk_total, s, t);
             else
-                launch_cfg<128, 128, 2, 2, 2, true, false, true>(p, M, nk_total, s);
+                launch_cfg<128, 128, 2, 2, 2, true, false, true>(p, M, nk_total, s, t);
         } else if (p.Cout > 32) {
-            launch_cfg<128, 64, 2, 2, 2, true, false, true>(p, M, nk_total, s);
+            launch_cfg<128, 64, 2, 2, 2, true, false, true>(p, M, nk_total, s, t);
         } else {
-            launch_cfg<128, 32, 4, 1, 2, true, false, true>(p, M, nk_total, s);
+            launch_cfg<128, 32, 4, 1, 2, true, false, true>(p, M, nk_total, s, t);
         }
     } else if (p.w_bf) {  // bf16 operands, fp32 accumulation
         // r06: an under-filled grid of 16-bit-operand tiles is latency-bound — one block per CU keeps ~24 KB of loads in flight against 2 us of cross-XCD
@@ -1564,36 +1560,36 @@ void launch_conv(const ConvParams& p, hipStream_t s) {
         // (the A rows are re-read from L2).  IRSDE_SMALL_BN = block slots per CU to fill (0 switches the rule off).
         int bn = p.Cout >= 128 ? 128 : p.Cout > 32 ? 64 : 32;
         static const int small_bn = tuning_env_int("IRSDE_SMALL_BN", 2);   // block slots per CU the grid should fill (0 = rule off)
-        if (small_bn && g_variant == 0) {
+        if (small_bn && !t.rules_off) {
             const long long slots = (long long)small_bn * device_cu_count();
             auto blocks = [&](int n) { return (long long)((M + 127) / 128) * ((p.Cout + n - 1) / n) * p.splits * p.nz; };
             while (bn > 32 && blocks(bn) < slots) bn >>= 1;
         }
         if (bn == 128) {
-            if (g_variant != 61 && (g_variant == 60 || conv_use_tile256(M, p.Cout, p.splits, nk_total)))
-                launch_cfg<256, 256, 2, 4, 2, true>(p, M, nk_total, s);
+            if (t.tile != ConvTune::TILE_128 && (t.tile == ConvTune::TILE_256 || conv_use_tile256(M, p.Cout, p.splits, nk_total)))
+                launch_cfg<256, 256, 2, 4, 2, true>(p, M, nk_total, s, t);
             else
-                launch_cfg<128, 128, 2, 2, 2, true>(p, M, nk_total, s);
+                launch_cfg<128, 128, 2, 2, 2, true>(p, M, nk_total, s, t);
         } else if (bn == 64) {
-            launch_cfg<128, 64, 2, 2, 2, true>(p, M, nk_total, s);
+            launch_cfg<128, 64, 2, 2, 2, true>(p, M, nk_total, s, t);
         } else {
-            launch_cfg<128, 32, 4, 1, 2, true>(p, M, nk_total, s);
+            launch_cfg<128, 32, 4, 1, 2, true>(p, M, nk_total, s, t);
         }
-    } else if (p.Cout >= 128 && f32_narrow(p, M) == 128) {
-        if (g_variant == 3)
-            launch_cfg<256, 128, 4, 2, 2, false>(p, M, nk_total, s);
-        else if (g_variant == 50)
-            launch_cfg<256, 256, 2, 4, 2, false>(p, M, nk_total, s);
-        else if (g_variant == 5)
-            launch_cfg<128, 128, 2, 2, 2, false>(p, M, nk_total, s, 120 * 1024);  // diagnostic: force 1 block/CU
-        else if (g_variant == 0 && conv_use_tile256(M, p.Cout, p.splits, nk_total))
-            launch_cfg<256, 256, 2, 4, 2, false>(p, M, nk_total, s);
+    } else if (p.Cout >= 128 && f32_narrow(p, M, t) == 128) {
+        if (t.tile == ConvTune::TILE_256x128)
+            launch_cfg<256, 128, 4, 2, 2, false>(p, M, nk_total, s, t);
+        else if (t.tile == ConvTune::TILE_256)
+            launch_cfg<256, 256, 2, 4, 2, false>(p, M, nk_total, s, t);
+        else if (t.tile == ConvTune::TILE_128_ONE_PER_CU)
+            launch_cfg<128, 128, 2, 2, 2, false>(p, M, nk_total, s, t, 120 * 1024);  // diagnostic: force 1 block/CU
+        else if (!t.rules_off && conv_use_tile256(M, p.Cout, p.splits, nk_total))
+            launch_cfg<256, 256, 2, 4, 2, false>(p, M, nk_total, s, t);
         else
-            launch_cfg<128, 128, 2, 2, 2, false>(p, M, nk_total, s);
-    } else if (p.Cout > 32 && f32_narrow(p, M) >= 64) {
-        launch_cfg<128, 64, 2, 2, 2, false>(p, M, nk_total, s);
+            launch_cfg<128, 128, 2, 2, 2, false>(p, M, nk_total, s, t);
+    } else if (p.Cout > 32 && f32_narrow(p, M, t) >= 64) {
+        launch_cfg<128, 64, 2, 2, 2, false>(p, M, nk_total, s, t);
     } else {
-        launch_cfg<128, 32, 4, 1, 2, false>(p, M, nk_total, s);
+        launch_cfg<128, 32, 4, 1, 2, false>(p, M, nk_total, s, t);
     }
     if (p.splits > 1) {
         const size_t total = (size_t)M * p.Cout;

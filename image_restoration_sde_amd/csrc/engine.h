@@ -231,29 +231,14 @@ inline WinoPolyPlan make_wino_poly(const ConvParams& d, const float* U, float* V
     g.nz = w.ncomp; g.z_in = (long long)q.T * w.K; g.z_w = (long long)d.Cout * w.K; g.z_out = (long long)q.T * d.Cout;
     return w;
 }
-// Split-operand variant (gemm_split.hip): V as `nplanes` bf16 planes (Vs: nplanes * 36 * T * Ctot elements), Us the weights'
-// planes (nplanes * 36 * Cout * Ctot), the component GEMMs on the bf16 MFMA pipe, M and the output transform unchanged (f32)
+// Split-operand variants (gemm_split.hip): V and the weights as `nplanes` 16-bit pieces in the GEMM kernel's interleaved layout, the component GEMMs on the
+// 16-bit MFMA pipe, M and the output transform unchanged (f32)
 struct WinoSplitPlan {
     WinoParams in, out;
     SplitGemmArgs gemm;
     int nplanes = 0;
     bool f16 = false;
 };
-inline WinoSplitPlan make_wino_split(const ConvParams& d, const unsigned short* Us, unsigned short* Vs, float* Mb, int nplanes) {
-    const WinoPlan w = make_wino(d, nullptr, nullptr, Mb, 4);
-    WinoSplitPlan sp;
-    sp.in = w.in; sp.out = w.out; sp.nplanes = nplanes;
-    const int Ctot = d.C0 + d.C1;
-    const long long T = w.in.T;
-    sp.in.Vs = Vs; sp.in.nplanes = nplanes; sp.in.v_plane = 36ll * T * Ctot;
-    SplitGemmArgs& g = sp.gemm;
-    g.a = Vs; g.b = Us; g.out = Mb;
-    g.plA = 36ll * T * Ctot; g.plB = 36ll * d.Cout * Ctot;
-    g.pA = T * Ctot; g.pB = (long long)d.Cout * Ctot; g.pO = T * d.Cout;
-    g.M = (int)T; g.N = d.Cout; g.K = Ctot; g.lda = Ctot; g.ldc = d.Cout;
-    g.n_inner = gemm_split_inner(g.M, g.N, 36);
-    return sp;
-}
 // IRSDE_FLAG_SPLIT_BF16X2: pair-interleaved operands for launch_gemm_split_pairs (Vs: 36 * T * Ctot * 2 elements)
 constexpr float kSplitF16VScale = 1.0f / 16.0f;   // fp16 pairs: V is written as V / 16 (finite up to |V| = 1e6)
 inline WinoSplitPlan make_wino_pairs(const ConvParams& d, const unsigned short* Up, unsigned short* Vs, float* Mb, bool f16 = false,

@@ -67,26 +67,206 @@ double time_launches(hipStream_t s, int iters, Run&& run) {
     return ms / iters;
 }
 
-// irsde_debug_conv / irsde_bench_conv only: selects a kernel variant for the launches of ONE call and always returns to
-// the production dispatch (also when a launch throws).
-struct VariantScope {
-    explicit VariantScope(int v) { conv_set_variant(v); }
-    ~VariantScope() { conv_set_variant(0); }
+// ---------------------------------------------------------------------------------------------------------------
+// The selector codes of irsde_debug_conv / irsde_bench_conv (include/irsde_hip_debug.h documents them).  A code is looked up ONCE, in the tables below; a code
+// without a row is refused, never run as the production dispatch.  The numbers live here and nowhere else.
+// ---------------------------------------------------------------------------------------------------------------
+
+// launch_conv's tuning codes (irsde_bench_conv's small variants; irsde_debug_conv 100 + code) -> the overrides of that one call.  Every code but 0 also
+// switches the grid-filling rules off.  50 belongs to the f32 kernels, 60 / 61 to the 16-bit-operand and PAIR kernels (with the halo kernel out of the way).
+ConvTune conv_tune_from_code(int code) {
+    ConvTune t;
+    t.rules_off = code != 0;
+    switch (code) {
+        case 3: t.tile = ConvTune::TILE_256x128; break;
+        case 50: t.tile = ConvTune::TILE_256; break;
+        case 5: t.tile = ConvTune::TILE_128_ONE_PER_CU; break;
+        case 6: t.no_buffer_desc = true; break;
+        case 7: t.no_direct_epi = true; break;
+        case 60: t.tile = ConvTune::TILE_256; t.halo = ConvTune::HALO_OFF; break;
+        case 61: t.tile = ConvTune::TILE_128; t.halo = ConvTune::HALO_OFF; break;
+        case 64: t.halo = ConvTune::HALO_FORCE_512; break;
+        case 65: t.halo = ConvTune::HALO_FORCE_256; break;
+        case 70: t.zloop = ConvTune::ZLOOP_OFF; break;
+        case 71: t.zloop = ConvTune::ZLOOP_ALL; break;
+        case 72: t.zloop = ConvTune::ZLOOP_PAIRS; break;
+        case 73: t.zloop = ConvTune::ZLOOP_FORCE_1X1; break;
+        default: break;
+    }
+    return t;
+}
+
+// The three-piece GEMM's launch twins: 0 the production launch (the tuning knobs apply), 1 one item per block, 2 the walk's drain twin — irsde_debug_split_gemm
+// 43 / 45 / 47 in that order, irsde_bench_conv 490 + 5 twin + abl (abl: Split3Launch::Abl by number; one the kernel lacks is refused by the launcher)
+Split3Launch split3_launch_twin(int twin, int abl = 0) {
+    Split3Launch o;
+    o.abl = static_cast<Split3Launch::Abl>(abl);
+    o.walk = twin == 0 ? Split3Launch::RULE : twin == 1 ? Split3Launch::OFF : Split3Launch::ON;
+    o.drain = twin == 0 ? Split3Launch::RULE : twin == 1 ? Split3Launch::OFF : Split3Launch::ON;
+    return o;
+}
+
+enum class Operand { F32, BF16, F16 };
+
+enum class ConvPath {
+    Direct,        // launch_conv: operand mode, bf16 activation storage, tuning code
+    Valu,          // the VALU cross-check kernel
+    WinoF2,        // three-launch Winograd F(2x2,3x3) on the f32 GEMM: tuning code
+    WinoF4,        // the same, F(4x4,3x3)
+    Poly,          // polyphase F(4x4,2x2) on the f32 GEMM: up
+    PolyTriples,   // polyphase on the three-piece GEMM: up, thread writer
+    F4Triples,     // three-launch F(4x4,3x3) on the three-piece GEMM
+    F4Pairs,       // three-launch F(4x4,3x3) on the pair GEMM: fp16 / bf16 pieces
+    DirectPair,    // launch_conv on the PAIR kernels: fp16 / bf16 pieces
+    Fused32,       // wino_fused.hip, 32 couts per block
+    Fused64,       // 64 couts per block: launch variant
+    Fused64Pair,   // its fp16-pair twin: launch variant
+    Fused64T,      // wino_fused_t.hip, two tile groups: launch variant
+};
+struct DebugConvRow {
+    int code;
+    ConvPath path;
+    Operand op;
+    bool act_bf16;        // bf16 activation storage (IRSDE_FLAG_BF16_ACT): inputs / residual are rounded, the result widened back
+    int tune;             // conv_tune_from_code
+    int variant;          // the variant int of launch_wino_fused64 / launch_wino_fused64t
+    bool up;              // polyphase: the 3x3 layer behind the nearest x2 upsample (else the 4x4 stride-2 layer)
+    bool thread_writer;   // polyphase on triples: the per-thread V writer
+};
+constexpr DebugConvRow direct(int code, Operand op, bool act_bf16, int tune) { return {code, ConvPath::Direct, op, act_bf16, tune, 0, false, false}; }
+constexpr DebugConvRow on_path(int code, ConvPath path, Operand op = Operand::F32) { return {code, path, op, false, 0, 0, false, false}; }
+constexpr DebugConvRow wino(int code, ConvPath path, int tune) { return {code, path, Operand::F32, false, tune, 0, false, false}; }
+constexpr DebugConvRow poly(int code, ConvPath path, bool up, bool thread_writer = false) { return {code, path, Operand::F32, false, 0, 0, up, thread_writer}; }
+constexpr DebugConvRow fused(int code, ConvPath path, int variant) { return {code, path, Operand::F32, false, 0, variant, false, false}; }
+constexpr DebugConvRow kDebugConv[] = {
+    direct(0, Operand::F32, false, 0),
+    on_path(1, ConvPath::Valu),
+    wino(2, ConvPath::WinoF2, 0), wino(12, ConvPath::WinoF2, 71), wino(22, ConvPath::WinoF2, 72),
+    wino(3, ConvPath::WinoF4, 0), wino(13, ConvPath::WinoF4, 71), wino(23, ConvPath::WinoF4, 72),
+    poly(24, ConvPath::Poly, false), poly(25, ConvPath::Poly, true),
+    poly(26, ConvPath::PolyTriples, false), poly(27, ConvPath::PolyTriples, true), poly(28, ConvPath::PolyTriples, true, true),
+    on_path(48, ConvPath::F4Triples),
+    on_path(44, ConvPath::F4Pairs, Operand::F16), on_path(45, ConvPath::F4Pairs, Operand::BF16),
+    on_path(46, ConvPath::DirectPair, Operand::F16), on_path(47, ConvPath::DirectPair, Operand::BF16),
+    on_path(33, ConvPath::Fused32),
+    fused(34, ConvPath::Fused64, 0), fused(36, ConvPath::Fused64, 64), fused(55, ConvPath::Fused64, 20),               // 64: + cout block by XCD where legal; 20: the production variant by number
+    fused(35, ConvPath::Fused64Pair, 4), fused(37, ConvPath::Fused64Pair, 4 + 64), fused(56, ConvPath::Fused64Pair, 24),
+    fused(62, ConvPath::Fused64T, 0), fused(63, ConvPath::Fused64T, 64),
+    // 16-bit operands: production dispatch, the generic 256 / 128 tile, the 512- / 256-pixel halo kernel
+    direct(4, Operand::BF16, false, 0), direct(160, Operand::BF16, false, 60), direct(161, Operand::BF16, false, 61), direct(162, Operand::BF16, false, 64),
+    direct(163, Operand::BF16, false, 65),
+    direct(5, Operand::F16, false, 0), direct(165, Operand::F16, false, 61), direct(166, Operand::F16, false, 64), direct(167, Operand::F16, false, 65),
+    direct(204, Operand::BF16, true, 0), direct(260, Operand::BF16, true, 60), direct(261, Operand::BF16, true, 61), direct(262, Operand::BF16, true, 64),
+    direct(263, Operand::BF16, true, 65),
+    // 100 + a tuning code of the f32 kernels
+    direct(100, Operand::F32, false, 0), direct(103, Operand::F32, false, 3), direct(105, Operand::F32, false, 5), direct(106, Operand::F32, false, 6),
+    direct(107, Operand::F32, false, 7), direct(150, Operand::F32, false, 50), direct(170, Operand::F32, false, 70), direct(171, Operand::F32, false, 71),
+    direct(172, Operand::F32, false, 72), direct(173, Operand::F32, false, 73),
 };
 
-// The selector codes irsde_debug_conv / irsde_bench_conv know (see their branches): any other code is refused, never run as the production dispatch.
-bool code_in(const std::initializer_list<int>& codes, int c) { return std::find(codes.begin(), codes.end(), c) != codes.end(); }
-bool debug_conv_code_known(int c) {
-    return code_in({0, 1, 2, 3, 4, 5, 12, 13, 22, 23, 24, 25, 26, 27, 28, 48, 33, 34, 35, 36, 37, 42, 43, 44, 45, 46, 47, 55, 56, 62, 63, 204, 260, 261, 262, 263}, c) ||
-           code_in({100, 103, 105, 106, 107, 150, 160, 161, 162, 163, 165, 166, 167, 170, 171, 172, 173}, c);   // 100 + a launch_conv tuning variant
+enum class BenchKind {
+    Conv,             // launch_conv: operand mode, PAIR kernels, bf16 activation storage, tuning code
+    Fused32,          // wino_fused.hip: tuning-aid flags
+    Fused32Stamps,    // once, with its phase timeline printed
+    Wino3,            // the three-launch F(4x4,3x3) path on the f32 GEMM
+    Wino3Gemm,        // its component GEMMs alone
+    Fused64,          // launch_wino_fused64: launch variant (fp16 operands: the pair twin's weights)
+    Fused64Stamps,    // once, with its per-wave cycle budget printed: stamp variant
+    Fused64T,         // launch_wino_fused64t: launch variant
+    Fused64TStamps,   // once, with its per-wave cycle stamps printed: stamp variant
+    PairGemm,         // the pair GEMM alone: ablation twin
+    TripleGemm,       // the three-piece GEMM alone: 5 launch twin + ablation twin
+};
+struct BenchRow {
+    int lo, hi;   // the codes lo .. hi
+    BenchKind kind;
+    int arg;      // of code lo; code lo + i carries arg + i (bench_conv_lookup): tuning code, flags, launch / stamp / ablation variant as the kind names it
+    Operand op;
+    bool pair;       // Conv: the PAIR kernels on hi + lo pieces of kind `op`
+    bool act_bf16;   // Conv: bf16 activation storage
+};
+constexpr BenchRow bench(int lo, int hi, BenchKind kind, int arg, Operand op = Operand::F32, bool pair = false, bool act_bf16 = false) {
+    return {lo, hi, kind, arg, op, pair, act_bf16};
 }
-bool bench_conv_variant_known(int v) {
-    return code_in({0, 3, 5, 6, 7, 50, 60, 61, 62, 63, 64, 65, 66, 67, 70, 71, 72, 73}, v) ||   // launch_conv and its tuning variants
-           code_in({80, 81, 82, 412, 413, 421, 422, 423, 430, 431, 432, 434, 435, 460, 461, 462, 465, 467, 468, 469, 480, 481, 482}, v) ||
-           code_in({2001, 2002, 2004, 4650, 4651, 4652, 4653}, v) ||
-           (v >= 83 && v <= 82 + 255) ||   // the 32-cout fused kernel with tuning-aid flags v - 82
-           (v >= 490 && v <= 504) ||       // the three-piece GEMM and its ablation twins (PROBES build; launch_gemm_split_triples refuses the ones it lacks); 495 - 499: on the one-item-per-block launch; 500 - 504: the drain twin
-           (v >= 472 && v <= 476);         // the pair GEMM's ablation twins (launch_gemm_split_pairs refuses the ones it lacks)
+constexpr BenchRow kBenchConv[] = {
+    bench(0, 0, BenchKind::Conv, 0), bench(3, 3, BenchKind::Conv, 3), bench(5, 7, BenchKind::Conv, 5), bench(50, 50, BenchKind::Conv, 50),
+    bench(70, 73, BenchKind::Conv, 70),
+    bench(60, 61, BenchKind::Conv, 60, Operand::BF16),                 // 256 / 128 tile
+    bench(62, 62, BenchKind::Conv, 0, Operand::BF16),                  // automatic, incl. the halo kernel
+    bench(63, 63, BenchKind::Conv, 0, Operand::BF16, false, true),
+    bench(64, 65, BenchKind::Conv, 64, Operand::BF16),                 // 62 / 63 with the 512- / 256-pixel halo kernel forced
+    bench(66, 67, BenchKind::Conv, 64, Operand::BF16, false, true),
+    bench(480, 480, BenchKind::Conv, 0, Operand::F16, true), bench(481, 481, BenchKind::Conv, 0, Operand::BF16, true),
+    bench(482, 482, BenchKind::Conv, 61, Operand::F16, true),          // 480 without the 256 x 256 tile
+    bench(80, 80, BenchKind::Fused32, 0),
+    bench(83, 82 + 255, BenchKind::Fused32, 1),                        // flags 1 .. 255: 1 no patch traffic, 2 no weight traffic, 4 / 8 producer / MFMA waves at s_setprio 2
+    bench(82, 82, BenchKind::Fused32Stamps, 0),
+    bench(81, 81, BenchKind::Wino3, 0), bench(421, 421, BenchKind::Wino3Gemm, 0),
+    bench(430, 432, BenchKind::Fused64, 20),                           // r04 persistent kernel: production, weight fragments / patch loads read zeros
+    bench(434, 434, BenchKind::Fused64, 24, Operand::F16),             // its fp16-pair twin
+    bench(435, 435, BenchKind::Fused64Stamps, 25), bench(2004, 2004, BenchKind::Fused64Stamps, 25),
+    bench(2001, 2002, BenchKind::Fused64Stamps, 28),                   // the stamp twins without weight / patch traffic
+    bench(460, 462, BenchKind::Fused64T, 0),                           // r06 two-tile-group kernel: production, weight fragments / patch gathers read zeros
+    bench(467, 469, BenchKind::Fused64T, 6),                           // measurement twins: no transform arithmetic / + no gathers / no gathers only
+    bench(465, 465, BenchKind::Fused64TStamps, 5),
+    bench(4650, 4653, BenchKind::Fused64TStamps, 12),                  // no patch traffic / output stores dropped / residual loads dropped / the coalesced-epilogue twin
+    bench(472, 476, BenchKind::PairGemm, 0),                           // full, no loads, (none), no MFMAs, no output stores: launch_gemm_split_pairs refuses the one it lacks
+    bench(490, 504, BenchKind::TripleGemm, 0),                         // split3_launch_twin(arg / 5, arg % 5)
+};
+
+template <class Row, size_t N, class Lo, class Hi>
+constexpr bool codes_disjoint(const Row (&rows)[N], Lo lo, Hi hi) {
+    for (size_t i = 0; i < N; ++i)
+        for (size_t j = 0; j < N; ++j)
+            if (i != j && lo(rows[i]) <= hi(rows[j]) && lo(rows[j]) <= hi(rows[i])) return false;
+    return true;
+}
+constexpr int row_code(const DebugConvRow& r) { return r.code; }
+constexpr int row_lo(const BenchRow& r) { return r.lo; }
+constexpr int row_hi(const BenchRow& r) { return r.hi; }
+static_assert(codes_disjoint(kDebugConv, row_code, row_code), "irsde_debug_conv: a selector code has two rows");
+static_assert(codes_disjoint(kBenchConv, row_lo, row_hi), "irsde_bench_conv: a variant has two rows");
+
+const DebugConvRow& debug_conv_lookup(int code) {
+    for (const DebugConvRow& r : kDebugConv)
+        if (r.code == code) return r;
+    throw HipError("debug_conv: unknown selector code " + std::to_string(code));
+}
+struct BenchSel {
+    const BenchRow& row;
+    int arg;
+};
+BenchSel bench_conv_lookup(int code) {
+    for (const BenchRow& r : kBenchConv)
+        if (code >= r.lo && code <= r.hi) return {r, r.arg + (code - r.lo)};
+    throw HipError("bench_conv: unknown variant " + std::to_string(code));
+}
+
+// The arguments of ncomp GEMMs C_z [M][N] = A_z [M][K] . B_z [N][K]^T over split operands (pA / pB: unsigned shorts resp. elements per component, as the launcher counts them)
+SplitGemmArgs split_gemm_args(const unsigned short* a, const unsigned short* b, float* C, int M, int N, int K, size_t pA, size_t pB) {
+    SplitGemmArgs g;
+    g.a = a; g.b = b; g.out = C;
+    g.pA = (long long)pA; g.pB = (long long)pB; g.pO = (long long)M * N;
+    g.M = M; g.N = N; g.K = K; g.lda = K; g.ldc = N;
+    return g;
+}
+// f32 operands [ncomp][M][K] and [ncomp][N][K] on the device -> their three-piece / pair copies in `mem` and the GEMM arguments over them
+SplitGemmArgs split_triples(Scratch& mem, const float* A, const float* Bm, float* C, int M, int N, int K, int ncomp, hipStream_t s) {
+    const size_t ea = split3_comp_elems((size_t)M, (size_t)K), eb = split3_comp_elems((size_t)N, (size_t)K);
+    unsigned short *ta = mem.alloc<unsigned short>(ea * ncomp), *tb = mem.alloc<unsigned short>(eb * ncomp);
+    launch_split_triples(A, ta, ncomp, (size_t)M, K, s);
+    launch_split_triples(Bm, tb, ncomp, (size_t)N, K, s);
+    return split_gemm_args(ta, tb, C, M, N, K, ea, eb);
+}
+// (fp16 pieces: of A * sa and B * sb, powers of two, undone by out_scale)
+SplitGemmArgs split_pairs(Scratch& mem, const float* A, const float* Bm, float* C, int M, int N, int K, int ncomp, hipStream_t s, bool f16 = false, float sa = 1.f,
+                          float sb = 1.f) {
+    unsigned short *pa = mem.alloc<unsigned short>((size_t)2 * ncomp * M * K), *pb = mem.alloc<unsigned short>((size_t)2 * ncomp * N * K);
+    launch_split_pairs(A, pa, (size_t)ncomp * M, K, s, f16, sa);
+    launch_split_pairs(Bm, pb, (size_t)ncomp * N, K, s, f16, sb);
+    SplitGemmArgs g = split_gemm_args(pa, pb, C, M, N, K, (size_t)M * K, (size_t)N * K);
+    g.out_scale = 1.0f / (sa * sb);
+    return g;
 }
 
 // What irsde_debug_scam and irsde_debug_scam_full share; the projections run on the B x Hs x Ws map of each view.  In order: the argument check, the hook's own
@@ -390,7 +570,7 @@ int irsde_debug_conv(const float* in0, int C0, const float* in1, int C1, int B, 
                      int splits, void* stream) {
     return guard([&] {
         if (!in0 || !w_oihw || !out) throw HipError("null argument");
-        if (!debug_conv_code_known(naive)) throw HipError("debug_conv: unknown selector code " + std::to_string(naive));
+        const DebugConvRow& r = debug_conv_lookup(naive);
         hipStream_t s = reinterpret_cast<hipStream_t>(stream);
         conv_global_init();
         const int Cin = C0 + C1;
@@ -415,157 +595,154 @@ int irsde_debug_conv(const float* in0, int C0, const float* in1, int C1, int B, 
         float* dz = mem.alloc<float>(256);
         IRSDE_HIP_CHECK(hipMemset(dz, 0, 1024));
         p.zeros = dz;
-        const int wino_tile = (naive == 2 || naive == 12 || naive == 22) ? 2 : (naive == 3 || naive == 13 || naive == 23) ? 4 : 0;
-        if (splits > 1 && naive != 1 && !wino_tile) {
+        if (splits > 1 && r.path != ConvPath::Valu && r.path != ConvPath::WinoF2 && r.path != ConvPath::WinoF4) {
             p.splits = splits;
             p.partial = mem.alloc<float>((size_t)splits * B * p.Ho * p.Wo * Cout);
         }
-        if (naive == 26 || naive == 27 || naive == 28) {   // selectors 24 / 25 with the component GEMMs on three bf16 pieces (gemm_split3i_kernel); 28: 27 with the per-thread V writer
-            if (!(naive == 26 ? wino_poly_down_shape(p) : wino_poly_up_shape(p)) || !wino_poly_eligible(p) || splits > 1)
-                throw HipError("debug_conv: selectors 26 / 27 / 28 run what 24 / 25 run (single source, channels a multiple of 32, bias only)");
-            const int up = naive != 26;
+        // the three-launch and fused Winograd paths: the host weight transform U [(tile + 2)^2][Cout][Cin], the tile count, the component products M
+        auto wino_weights = [&](int tile) {
+            std::vector<float> U((size_t)(tile + 2) * (tile + 2) * Cout * Cin);
+            wino_transform_weights(pk.data(), Cout, Cin, U.data(), tile);
+            return U;
+        };
+        auto wino_tiles = [&](int tile) { return (long long)B * (p.Ho / tile) * (p.Wo / tile); };
+        auto alloc_M = [&](int ncomp, long long T) { return mem.alloc<float>((size_t)ncomp * T * Cout); };
+        // the polyphase paths: shape check, U (25 x Cout x 4 Cin resp. 100 x Cout x Cin) on the device, the plan without its V / M buffers
+        auto poly_plan = [&](const char* refusal, float*& dU) {
+            if (!(r.up ? wino_poly_up_shape(p) : wino_poly_down_shape(p)) || !wino_poly_eligible(p) || splits > 1) throw HipError(refusal);
             std::vector<float> U((size_t)100 * Cout * Cin);
-            wino_poly_transform_weights(pk.data(), Cout, Cin, U.data(), up);
-            float* dU = mem.upload(U);
-            WinoPolyPlan wp = make_wino_poly(p, dU, nullptr, nullptr);
+            wino_poly_transform_weights(pk.data(), Cout, Cin, U.data(), r.up);
+            dU = mem.upload(U);
+            return make_wino_poly(p, dU, nullptr, nullptr);
+        };
+        switch (r.path) {
+        case ConvPath::PolyTriples: {
+            float* dU = nullptr;
+            WinoPolyPlan wp = poly_plan("debug_conv: selectors 26 / 27 / 28 run what 24 / 25 run (single source, channels a multiple of 32, bias only)", dU);
             if (!gemm_split_triples_fits(wp.T, Cout, wp.K, Cout)) throw HipError("debug_conv: shape not eligible for the three-piece GEMM");
             unsigned short* dUt = mem.alloc<unsigned short>((size_t)wp.ncomp * split3_comp_elems((size_t)Cout, (size_t)wp.K));
             unsigned short* dVt = mem.alloc<unsigned short>((size_t)wp.ncomp * split3_comp_elems((size_t)wp.T, (size_t)wp.K));
-            float* dM = mem.alloc<float>((size_t)wp.ncomp * wp.T * Cout);
+            float* dM = alloc_M(wp.ncomp, wp.T);
             launch_split_triples(dU, dUt, wp.ncomp, (size_t)Cout, wp.K, s);
             wp = make_wino_poly(p, dU, nullptr, dM);
             const SplitGemmArgs sg = make_wino_poly_triples(wp, Cout, dUt, dVt, dM);
-            wp.in.thread_writer = naive == 28;
+            wp.in.thread_writer = r.thread_writer;
             launch_wino_poly_input(wp.in, s);
             launch_gemm_split_triples(sg, wp.ncomp, s);
             launch_wino_poly_output(wp.out, s);
-        } else if (naive == 48) {   // three-launch Winograd F(4x4,3x3) on the exact-fp32 engine's three-piece GEMM
+            break;
+        }
+        case ConvPath::Poly: {
+            float* dU = nullptr;
+            WinoPolyPlan wp = poly_plan(r.up ? "debug_conv: selector 25 runs a 3x3 stride-1 pad-1 convolution with in_shift = 1 (single source, channels a multiple of 32, bias only)"
+                                             : "debug_conv: selector 24 runs a 4x4 stride-2 pad-1 convolution (single source, channels a multiple of 32, bias only)", dU);
+            float* dV = mem.alloc<float>((size_t)wp.ncomp * wp.T * wp.K);
+            wp = make_wino_poly(p, dU, dV, alloc_M(wp.ncomp, wp.T));
+            launch_wino_poly_input(wp.in, s);
+            launch_conv(wp.gemm, s);
+            launch_wino_poly_output(wp.out, s);
+            break;
+        }
+        case ConvPath::F4Triples: {
             if (!wino_shape_ok(p, 4) || Cin % 32) throw HipError("debug_conv: shape not eligible for the three-piece GEMM");
-            std::vector<float> U((size_t)36 * Cout * Cin);
-            wino_transform_weights(pk.data(), Cout, Cin, U.data(), 4);
-            const long long T = (long long)B * (p.Ho / 4) * (p.Wo / 4);
+            const std::vector<float> U = wino_weights(4);
+            const long long T = wino_tiles(4);
             if (!gemm_split_triples_fits(T, Cout, Cin, Cout)) throw HipError("debug_conv: shape not eligible for the three-piece GEMM");
             float* dU = mem.upload(U);
             unsigned short* dUt = mem.alloc<unsigned short>((size_t)36 * split3_comp_elems((size_t)Cout, (size_t)Cin));
             unsigned short* dVt = mem.alloc<unsigned short>((size_t)36 * split3_comp_elems((size_t)T, (size_t)Cin));
-            float* dM = mem.alloc<float>((size_t)36 * T * Cout);
             launch_split_triples(dU, dUt, 36, (size_t)Cout, Cin, s);
-            const WinoSplitPlan sp = make_wino_triples(p, dUt, dVt, dM);
+            const WinoSplitPlan sp = make_wino_triples(p, dUt, dVt, alloc_M(36, T));
             launch_wino_input(sp.in, s);
             launch_gemm_split_triples(sp.gemm, 36, s);
             launch_wino_output(sp.out, s);
-        } else if (naive == 24 || naive == 25) {   // polyphase Winograd F(4x4,2x2): 24 a 4x4 stride-2 pad-1 layer, 25 a 3x3 pad-1 layer behind the nearest x2 upsample
-            if (!(naive == 24 ? wino_poly_down_shape(p) : wino_poly_up_shape(p)) || !wino_poly_eligible(p) || splits > 1)
-                throw HipError(naive == 24 ? "debug_conv: selector 24 runs a 4x4 stride-2 pad-1 convolution (single source, channels a multiple of 32, bias only)"
-                                           : "debug_conv: selector 25 runs a 3x3 stride-1 pad-1 convolution with in_shift = 1 (single source, channels a multiple of 32, bias only)");
-            const int up = naive == 25;
-            std::vector<float> U((size_t)100 * Cout * Cin);   // 25 x Cout x 4 Cin resp. 100 x Cout x Cin
-            wino_poly_transform_weights(pk.data(), Cout, Cin, U.data(), up);
-            float* dU = mem.upload(U);
-            WinoPolyPlan wp = make_wino_poly(p, dU, nullptr, nullptr);
-            float* dV = mem.alloc<float>((size_t)wp.ncomp * wp.T * wp.K);
-            float* dM = mem.alloc<float>((size_t)wp.ncomp * wp.T * Cout);
-            wp = make_wino_poly(p, dU, dV, dM);
-            launch_wino_poly_input(wp.in, s);
-            launch_conv(wp.gemm, s);
-            launch_wino_poly_output(wp.out, s);
-        } else if (naive == 44 || naive == 45) {  // three-launch Winograd F(4x4,3x3) with the engine's pair GEMM: 44 fp16 pairs, 45 bf16 pairs
-            const bool f16 = naive == 44;
+            break;
+        }
+        case ConvPath::F4Pairs: {
+            const bool f16 = r.op == Operand::F16;
             if (!wino_shape_ok(p, 4) || Cin % 32) throw HipError("debug_conv: shape not eligible for the pair GEMM");
-            std::vector<float> U((size_t)36 * Cout * Cin);
-            wino_transform_weights(pk.data(), Cout, Cin, U.data(), 4);
+            std::vector<float> U = wino_weights(4);
             const float us = f16 ? pow2_scale_into_512(U.data(), U.size()) : 1.f;
-            const long long T = (long long)B * (p.Ho / 4) * (p.Wo / 4);
+            const long long T = wino_tiles(4);
             float* dU = mem.upload(U);
             unsigned short* dUp = mem.alloc<unsigned short>(2 * U.size());
             unsigned short* dVp = mem.alloc<unsigned short>((size_t)36 * T * Cin * 2);
-            float* dM = mem.alloc<float>((size_t)36 * T * Cout);
             launch_split_pairs(dU, dUp, (size_t)36 * Cout, Cin, s, f16, us);
-            const WinoSplitPlan sp = make_wino_pairs(p, dUp, dVp, dM, f16, us);
+            const WinoSplitPlan sp = make_wino_pairs(p, dUp, dVp, alloc_M(36, T), f16, us);
             launch_wino_input(sp.in, s);
             launch_gemm_split_pairs(sp.gemm, 36, s, 0, f16);
             launch_wino_output(sp.out, s);
-        } else if (naive == 42 || naive == 43) {  // three-launch Winograd F(4x4,3x3) with split-operand component GEMMs: 2 / 3 bf16 planes
-            const int npl = naive - 40;
-            if (!wino_shape_ok(p, 4)) throw HipError("debug_conv: shape not eligible for Winograd");
-            std::vector<float> U((size_t)36 * Cout * Cin);
-            wino_transform_weights(pk.data(), Cout, Cin, U.data(), 4);
-            const long long T = (long long)B * (p.Ho / 4) * (p.Wo / 4);
-            float* dU = mem.upload(U);
-            unsigned short* dUs = mem.alloc<unsigned short>(U.size() * npl);
-            unsigned short* dVs = mem.alloc<unsigned short>((size_t)36 * T * Cin * npl);
-            float* dM = mem.alloc<float>((size_t)36 * T * Cout);
-            launch_split_planes(dU, dUs, U.size(), U.size(), npl, s);
-            const WinoSplitPlan sp = make_wino_split(p, dUs, dVs, dM, npl);
-            launch_wino_input(sp.in, s);
-            launch_gemm_split(sp.gemm, npl, 36, s);
-            launch_wino_output(sp.out, s);
-        } else if (naive == 35 || naive == 37 || naive == 56) {  // the 64-cout fused Winograd kernel on fp16 hi + lo operand pairs (IRSDE_FLAG_SPLIT_F16X2's big-feature-map path)
+            break;
+        }
+        case ConvPath::Fused64Pair: {   // the 64-cout fused kernel on fp16 hi + lo operand pairs (IRSDE_FLAG_SPLIT_F16X2's big-feature-map path)
             if (!wino_fused64_eligible(p)) throw HipError("debug_conv: shape not eligible for the fused Winograd kernel");
-            std::vector<float> U((size_t)36 * Cout * Cin), Uf((size_t)36 * Cout * Cin);
-            wino_transform_weights(pk.data(), Cout, Cin, U.data(), 4);
+            std::vector<float> U = wino_weights(4), Uf(U.size());
             wino_fused64_pack_weights(U.data(), Cout, Cin, Uf.data());
             const float usc = pow2_scale_into_512(U.data(), U.size());
             float* dUf = mem.upload(Uf);
             unsigned short* dUp = mem.alloc<unsigned short>(2 * Uf.size());
             launch_wino_fused64_split_weights(dUf, dUp, Uf.size(), usc, s);
             p.pair_scale = 1.0f / (kWinoFused64PairVScale * usc);
-            launch_wino_fused64(p, reinterpret_cast<const float*>(dUp), s, naive == 56 ? 24 : naive == 37 ? 4 + 64 : 4);   // 37: + cout block by XCD where legal
-        } else if (naive == 33 || naive == 34 || naive == 36 || naive == 55 || naive == 62 || naive == 63) {  // fused Winograd F(4x4,3x3) kernels (wino_fused.hip): 33 = 32 couts per block, 34 = 64
-            if (naive == 33 ? !wino_fused_eligible(p) : !wino_fused64_eligible(p)) throw HipError("debug_conv: shape not eligible for the fused Winograd kernel");
-            std::vector<float> U((size_t)36 * Cout * Cin), Uf((size_t)36 * Cout * Cin);
-            wino_transform_weights(pk.data(), Cout, Cin, U.data(), 4);
-            if (naive == 33) wino_fused_pack_weights(U.data(), Cout, Cin, Uf.data());
+            launch_wino_fused64(p, reinterpret_cast<const float*>(dUp), s, r.variant);
+            break;
+        }
+        case ConvPath::Fused32:
+        case ConvPath::Fused64:
+        case ConvPath::Fused64T: {
+            const bool f32k = r.path == ConvPath::Fused32;
+            if (f32k ? !wino_fused_eligible(p) : !wino_fused64_eligible(p)) throw HipError("debug_conv: shape not eligible for the fused Winograd kernel");
+            const std::vector<float> U = wino_weights(4);
+            std::vector<float> Uf(U.size());
+            if (f32k) wino_fused_pack_weights(U.data(), Cout, Cin, Uf.data());
             else wino_fused64_pack_weights(U.data(), Cout, Cin, Uf.data());
             float* dUf = mem.upload(Uf);
-            if (naive == 62 || naive == 63) {   // r06: the two-tile-group kernel (wino_fused_t.hip; 63: + cout block by XCD where legal)
+            if (r.path == ConvPath::Fused64T) {
                 if (!wino_fused64t_eligible(p)) throw HipError("debug_conv: shape not eligible for the two-tile-group fused Winograd kernel");
-                launch_wino_fused64t(p, dUf, s, naive == 63 ? 64 : 0);
-            } else
-            if (naive == 33) launch_wino_fused(p, dUf, s);
-            else launch_wino_fused64(p, dUf, s, naive == 55 ? 20 : naive == 36 ? 64 : 0);   // 36: + cout block by XCD where legal; 55: the production variant by number
-        } else if (wino_tile) {  // naive / 10: 0 = production dispatch, 1 / 2 = force the batch-loop GEMM kernel (all / 2 components per block)
-            const int tile = wino_tile, ncomp = (tile + 2) * (tile + 2);
+                launch_wino_fused64t(p, dUf, s, r.variant);
+            } else if (f32k) {
+                launch_wino_fused(p, dUf, s);
+            } else {
+                launch_wino_fused64(p, dUf, s, r.variant);
+            }
+            break;
+        }
+        case ConvPath::WinoF2:
+        case ConvPath::WinoF4: {
+            const int tile = r.path == ConvPath::WinoF2 ? 2 : 4, ncomp = (tile + 2) * (tile + 2);
             if (!wino_shape_ok(p, tile)) throw HipError("debug_conv: shape not eligible for Winograd");
-            std::vector<float> U((size_t)ncomp * Cout * Cin);
-            wino_transform_weights(pk.data(), Cout, Cin, U.data(), tile);
-            const long long T = (long long)B * (p.Ho / tile) * (p.Wo / tile);
+            const std::vector<float> U = wino_weights(tile);
+            const long long T = wino_tiles(tile);
             float* dU = mem.upload(U);
             float* dV = mem.alloc<float>((size_t)ncomp * T * Cin);
-            float* dM = mem.alloc<float>((size_t)ncomp * T * Cout);
-            const WinoPlan wp = make_wino(p, dU, dV, dM, tile);
+            const WinoPlan wp = make_wino(p, dU, dV, alloc_M(ncomp, T), tile);
             launch_wino_input(wp.in, s);
-            {
-                VariantScope vs(naive >= 20 ? 72 : naive >= 10 ? 71 : 0);
-                launch_conv(wp.gemm, s);
-            }
+            launch_conv(wp.gemm, s, conv_tune_from_code(r.tune));
             launch_wino_output(wp.out, s);
-        } else if (naive == 46 || naive == 47) {   // direct implicit GEMM on the PAIR kernels: 46 fp16 hi + lo pieces, 47 bf16
-            const bool f16 = naive == 46;
+            break;
+        }
+        case ConvPath::DirectPair: {
+            const bool f16 = r.op == Operand::F16;
             const float sc = f16 ? pow2_scale_into_512(pk.data(), pk.size()) : 1.f;
             unsigned short* dwp = mem.alloc<unsigned short>(2 * pk.size());
             launch_split_pairs(dw, dwp, (size_t)Cout, KH * KW * (C0 + C1), s, f16, sc);
             p.w_pair = dwp; p.pair_scale = 1.0f / sc; p.f16 = f16 ? 1 : 0;
             launch_conv(p, s);
-        } else if (naive == 1) {
+            break;
+        }
+        case ConvPath::Valu:
             launch_conv_naive(p, s);
-        } else {   // the direct kernels: 0 production dispatch, 4 / 5 bf16 / fp16 operands, 204 / 26x bf16 activation storage, 100 + v launch_conv tuning variant v
+            break;
+        case ConvPath::Direct: {
             unsigned short* ao = nullptr;
-            const bool act = naive == 204 || (naive >= 260 && naive <= 263);  // + bf16 activation storage (IRSDE_FLAG_BF16_ACT)
-            if (naive == 4 || (naive >= 160 && naive <= 163) || act) {  // bf16-MFMA mode (variants 60 / 61: force the 256 / 128 tile; 64 / 65: the 512- / 256-pixel halo kernel)
-                unsigned short* dbf = mem.alloc<unsigned short>(pk.size());
-                launch_f32_to_bf16(dw, dbf, pk.size(), s);
-                p.w_bf = dbf;
-            }
-            const bool f16 = naive == 5 || (naive >= 165 && naive <= 167);  // fp16-MFMA mode: production dispatch / generic 128-row tile / 512- / 256-pixel halo kernel
-            if (f16) {
-                unsigned short* dbf = mem.alloc<unsigned short>(pk.size());
-                launch_f32_to_f16(dw, dbf, pk.size(), s);
-                p.w_bf = dbf;
-                p.f16 = 1;
+            if (r.op != Operand::F32) {   // bf16- / fp16-MFMA mode
+                unsigned short* d16 = mem.alloc<unsigned short>(pk.size());
+                if (r.op == Operand::F16) launch_f32_to_f16(dw, d16, pk.size(), s);
+                else launch_f32_to_bf16(dw, d16, pk.size(), s);
+                p.w_bf = d16;
+                p.f16 = r.op == Operand::F16 ? 1 : 0;
             }
             const size_t npix_in = (size_t)B * Hin * Win, nout = (size_t)B * p.Ho * p.Wo * Cout;
-            if (act) {  // the caller's fp32 tensors are rounded into bf16 copies; the bf16 result is widened back
+            if (r.act_bf16) {  // the caller's fp32 tensors are rounded into bf16 copies; the bf16 result is widened back
                 auto to_bf = [&](const float* src, size_t n) {
                     unsigned short* d = mem.alloc<unsigned short>(n + 32);
                     launch_f32_to_bf16(src, d, n, s);
@@ -578,12 +755,10 @@ int irsde_debug_conv(const float* in0, int C0, const float* in1, int C1, int B, 
                 p.out = reinterpret_cast<float*>(ao);
                 p.in_bf16 = p.out_bf16 = 1;
             }
-            {
-                const int halo_v = (naive == 162 || naive == 262 || naive == 166) ? 64 : (naive == 163 || naive == 263 || naive == 167) ? 65 : 0;   // 64 / 65: force the 512- / 256-pixel halo kernel
-                VariantScope vs(halo_v ? halo_v : f16 ? (naive == 165 ? 61 : 0) : act ? (naive == 204 ? 0 : naive - 200) : (naive >= 100 ? naive - 100 : 0));  // tile variants
-                launch_conv(p, s);
-            }
-            if (act) launch_bf16_to_f32(ao, out, nout, s);
+            launch_conv(p, s, conv_tune_from_code(r.tune));
+            if (r.act_bf16) launch_bf16_to_f32(ao, out, nout, s);
+            break;
+        }
         }
         IRSDE_HIP_CHECK(hipStreamSynchronize(s));
     });
@@ -591,53 +766,21 @@ int irsde_debug_conv(const float* in0, int C0, const float* in1, int C1, int B, 
 
 int irsde_debug_split_gemm(const float* A, const float* Bm, float* C, int M, int N, int K, int ncomp, int nplanes, void* stream) {
     return guard([&] {
-        // nplanes 2 / 3: the 128 x 128 plane-major prototype kernel; 42 / 44: the engine's pair-interleaved two-plane kernel
+        // 42 / 44: the engine's pair-interleaved two-plane kernel on bf16 / fp16 pieces
         // 43: the exact-fp32 engine's three-piece kernel (row-pair-interleaved triples, six products) on its production launch (the persistent item walk);
         // 45: the same kernel on the one-item-per-block launch, the walk's bit-identity twin; 47: the walk with vmcnt(0) in front of every barrier, the ring's twin
-        if (nplanes != 2 && nplanes != 3 && (nplanes < 42 || nplanes > 45) && nplanes != 47) throw HipError("debug_split_gemm: nplanes must be 2, 3, 42, 43, 44, 45 or 47");
+        const int twin3 = nplanes == 43 ? 0 : nplanes == 45 ? 1 : nplanes == 47 ? 2 : -1;   // split3_launch_twin
+        if (twin3 < 0 && nplanes != 42 && nplanes != 44) throw HipError("debug_split_gemm: nplanes must be 42, 43, 44, 45 or 47");
         hipStream_t s = reinterpret_cast<hipStream_t>(stream);
         conv_global_init();
-        const size_t na = (size_t)ncomp * M * K, nb = (size_t)ncomp * N * K;
         Scratch mem(s);
-        if (nplanes == 43 || nplanes == 45 || nplanes == 47) {
+        if (twin3 >= 0) {
             if (!gemm_split_triples_fits(M, N, K, N)) throw HipError("debug_split_gemm: shape not eligible for the three-piece GEMM");
-            const size_t ea = split3_comp_elems((size_t)M, (size_t)K), eb = split3_comp_elems((size_t)N, (size_t)K);
-            unsigned short *ta = mem.alloc<unsigned short>(ea * ncomp), *tb = mem.alloc<unsigned short>(eb * ncomp);
-            launch_split_triples(A, ta, ncomp, (size_t)M, K, s);
-            launch_split_triples(Bm, tb, ncomp, (size_t)N, K, s);
-            SplitGemmArgs gt;
-            gt.a = ta; gt.b = tb; gt.out = C;
-            gt.pA = (long long)ea; gt.pB = (long long)eb; gt.pO = (long long)M * N;
-            gt.M = M; gt.N = N; gt.K = K; gt.lda = K; gt.ldc = N;
-            launch_gemm_split_triples(gt, ncomp, s, 0, nplanes == 45 ? 0 : nplanes == 47 ? 1 : -1, nplanes == 47 ? 1 : nplanes == 43 ? -1 : 0);
-            IRSDE_HIP_CHECK(hipStreamSynchronize(s));
-            return;
-        }
-        if (nplanes == 42 || nplanes == 44) {   // the pair-interleaved two-plane kernel (LDS-DMA, 256 x 256 tiles): 42 bf16 pieces, 44 fp16 pieces
+            launch_gemm_split_triples(split_triples(mem, A, Bm, C, M, N, K, ncomp, s), ncomp, s, split3_launch_twin(twin3));
+        } else {   // (fp16: any powers of two, the hook exercises the scaling)
             const bool f16 = nplanes == 44;
-            const float sa = f16 ? 1.0f / 16.0f : 1.f, sb = f16 ? 64.0f : 1.f;   // (any powers of two: the hook exercises the scaling)
-            unsigned short *pa = mem.alloc<unsigned short>(2 * na), *pb = mem.alloc<unsigned short>(2 * nb);
-            launch_split_pairs(A, pa, (size_t)ncomp * M, K, s, f16, sa);
-            launch_split_pairs(Bm, pb, (size_t)ncomp * N, K, s, f16, sb);
-            SplitGemmArgs gp;
-            gp.a = pa; gp.b = pb; gp.out = C;
-            gp.pA = (long long)M * K; gp.pB = (long long)N * K; gp.pO = (long long)M * N;
-            gp.M = M; gp.N = N; gp.K = K; gp.lda = K; gp.ldc = N;
-            gp.out_scale = 1.0f / (sa * sb);
-            launch_gemm_split_pairs(gp, ncomp, s, 0, f16);
-            IRSDE_HIP_CHECK(hipStreamSynchronize(s));
-            return;
+            launch_gemm_split_pairs(split_pairs(mem, A, Bm, C, M, N, K, ncomp, s, f16, f16 ? 1.0f / 16.0f : 1.f, f16 ? 64.0f : 1.f), ncomp, s, 0, f16);
         }
-        unsigned short *da = mem.alloc<unsigned short>(na * nplanes), *db = mem.alloc<unsigned short>(nb * nplanes);
-        launch_split_planes(A, da, na, na, nplanes, s);
-        launch_split_planes(Bm, db, nb, nb, nplanes, s);
-        SplitGemmArgs g;
-        g.a = da; g.b = db; g.out = C;
-        g.plA = (long long)na; g.plB = (long long)nb;
-        g.pA = (long long)M * K; g.pB = (long long)N * K; g.pO = (long long)M * N;
-        g.M = M; g.N = N; g.K = K; g.lda = K; g.ldc = N;
-        g.n_inner = gemm_split_inner(M, N, ncomp);
-        launch_gemm_split(g, nplanes, ncomp, s);
         IRSDE_HIP_CHECK(hipStreamSynchronize(s));
     });
 }
@@ -776,7 +919,10 @@ int irsde_bench_conv(int variant, int B, int H, int W, int Cin, int Cout, int K,
                      double* ms_out) {
     return guard([&] {
         if (!ms_out || iters < 1) throw HipError("bad argument");
-        if (!bench_conv_variant_known(variant)) throw HipError("bench_conv: unknown variant " + std::to_string(variant));
+        const BenchSel sel = bench_conv_lookup(variant);
+        const BenchRow& r = sel.row;
+        const BenchKind kind = r.kind;
+        const int arg = sel.arg;
         conv_global_init();
         OwnedStream stream(hipStreamNonBlocking);
         hipStream_t s = stream.s;
@@ -797,105 +943,47 @@ int irsde_bench_conv(int variant, int B, int H, int W, int Cin, int Cout, int K,
         launch_fill_random(dres, nout, 3, 1.0f, s);
         launch_fill_random(dfilm, (size_t)2 * Cout, 4, 0.3f, s);
         p.in0 = din; p.w = dw; p.out = dout; p.out_stride = Cout;
-        const int halo_force = (variant == 64 || variant == 66) ? 64 : (variant == 65 || variant == 67) ? 65 : 0;   // r05: 64 / 65 = variant 62 with the 512- / 256-pixel halo kernel forced, 66 / 67 = the same on variant 63
-        if (halo_force) variant = variant <= 65 ? 62 : 63;
-        if (variant >= 60 && variant <= 63) {  // bf16-MFMA mode: 60 = 256x256 tile, 61 = 128x128, 62 = automatic, 63 = automatic + bf16 activations
+        if (kind == BenchKind::Conv && r.op == Operand::BF16 && !r.pair) {  // bf16-MFMA mode
             unsigned short* dbf = mem.alloc<unsigned short>(nw);
             launch_f32_to_bf16(dw, dbf, nw, s);
             p.w_bf = dbf;
         }
         if (epi == 1) { p.film = dfilm; p.silu = 1; }
         if (epi == 2) { p.silu = 1; p.res = dres; p.res_stride = Cout; }
-        if (variant == 63) {  // bf16 activation storage (the output / residual buffers are simply twice the size needed)
+        if (r.act_bf16) {  // bf16 activation storage (the output / residual buffers are simply twice the size needed)
             unsigned short* dabf = mem.alloc<unsigned short>(nin);
             launch_f32_to_bf16(din, dabf, nin, s);
             launch_f32_to_bf16(dout, reinterpret_cast<unsigned short*>(dres), nout / 2, s);
             p.in0 = reinterpret_cast<const float*>(dabf);
             p.in_bf16 = 1; p.out_bf16 = 1;
         }
-        // 80: fused Winograd F(4x4,3x3) kernel; 81: the three-launch Winograd F(4x4,3x3) path (random U: timing only)
+        if (r.pair) {   // direct convolution on the PAIR kernels
+            const bool f16 = r.op == Operand::F16;
+            unsigned short* dwp = mem.alloc<unsigned short>(2 * nw);
+            launch_split_pairs(dw, dwp, (size_t)Cout, K * K * Cin, s, f16, 64.0f);
+            p.w_pair = dwp; p.pair_scale = 1.0f / 64.0f; p.f16 = f16 ? 1 : 0;
+        }
+        if (kind == BenchKind::TripleGemm || kind == BenchKind::PairGemm) {   // the 36 component GEMMs of the layer alone, on random operands
+            if (K != 3 || stride != 1 || !wino_shape_ok(p, 4)) throw HipError("bench_conv: Winograd variants need an eligible 3x3 stride-1 layer");
+            const long long T = (long long)B * (p.Ho / 4) * (p.Wo / 4);
+            const bool triples = kind == BenchKind::TripleGemm;
+            if (triples && !gemm_split_triples_fits(T, Cout, Cin, Cout)) throw HipError("bench_conv: shape not eligible for the three-piece GEMM");
+            float *vf = mem.alloc<float>((size_t)36 * T * Cin), *uf = mem.alloc<float>((size_t)36 * Cout * Cin), *mo = mem.alloc<float>((size_t)36 * T * Cout);
+            launch_fill_random(vf, (size_t)36 * T * Cin, 7, 1.0f, s);
+            launch_fill_random(uf, (size_t)36 * Cout * Cin, 8, 0.05f, s);
+            const SplitGemmArgs g = triples ? split_triples(mem, vf, uf, mo, (int)T, Cout, Cin, 36, s) : split_pairs(mem, vf, uf, mo, (int)T, Cout, Cin, 36, s);
+            const Split3Launch twin = split3_launch_twin(arg / 5, arg % 5);
+            auto gemms = [&] {
+                if (triples) launch_gemm_split_triples(g, 36, s, twin);
+                else launch_gemm_split_pairs(g, 36, s, arg);
+            };
+            for (int i = 0; i < 2; ++i) gemms();
+            *ms_out = time_launches(s, iters, gemms);
+            return;
+        }
         float* dU = nullptr;
         WinoPlan wp{};
-        if (variant == 480 || variant == 481 || variant == 482) {   // direct convolution on the PAIR kernels: 480 fp16 pieces, 481 bf16 pieces, 482 = 480 without the 256 x 256 tile
-            unsigned short* dwp = mem.alloc<unsigned short>(2 * nw);
-            launch_split_pairs(dw, dwp, (size_t)Cout, K * K * Cin, s, variant != 481, 64.0f);
-            p.w_pair = dwp; p.pair_scale = 1.0f / 64.0f; p.f16 = variant != 481 ? 1 : 0;
-            variant = variant == 482 ? 61 : 0;
-        }
-        if (variant >= 490 && variant <= 504) {   // the three-piece component GEMMs alone (gemm_split3i_kernel): 490 full, 491 no loads, 493 no MFMAs, 494 no output stores; 495 - 499: the same on the one-item-per-block twin; 500 - 504: on the drain twin
-            if (K != 3 || stride != 1 || !wino_shape_ok(p, 4)) throw HipError("bench_conv: Winograd variants need an eligible 3x3 stride-1 layer");
-            const long long T = (long long)B * (p.Ho / 4) * (p.Wo / 4);
-            if (!gemm_split_triples_fits(T, Cout, Cin, Cout)) throw HipError("bench_conv: shape not eligible for the three-piece GEMM");
-            const size_t ea = split3_comp_elems((size_t)T, (size_t)Cin), eb = split3_comp_elems((size_t)Cout, (size_t)Cin);
-            float *vf = mem.alloc<float>((size_t)36 * T * Cin), *uf = mem.alloc<float>((size_t)36 * Cout * Cin), *mo = mem.alloc<float>((size_t)36 * T * Cout);
-            unsigned short *vt = mem.alloc<unsigned short>(36 * ea), *ut = mem.alloc<unsigned short>(36 * eb);
-            launch_fill_random(vf, (size_t)36 * T * Cin, 7, 1.0f, s);
-            launch_fill_random(uf, (size_t)36 * Cout * Cin, 8, 0.05f, s);
-            launch_split_triples(vf, vt, 36, (size_t)T, Cin, s);
-            launch_split_triples(uf, ut, 36, (size_t)Cout, Cin, s);
-            SplitGemmArgs gt;
-            gt.a = vt; gt.b = ut; gt.out = mo;
-            gt.pA = (long long)ea; gt.pB = (long long)eb; gt.pO = T * Cout;
-            gt.M = (int)T; gt.N = Cout; gt.K = Cin; gt.lda = Cin; gt.ldc = Cout;
-            const int twin = (variant - 490) / 5, abl = (variant - 490) % 5;   // twin 0: the production launch, 1: one item per block, 2: the drain twin
-            const int walk = twin == 1 ? 0 : twin == 2 ? 1 : -1, drain = twin == 2 ? 1 : twin == 1 ? 0 : -1;
-            for (int i = 0; i < 2; ++i) launch_gemm_split_triples(gt, 36, s, abl, walk, drain);
-            *ms_out = time_launches(s, iters, [&] { launch_gemm_split_triples(gt, 36, s, abl, walk, drain); });
-            return;
-        }
-        if (variant >= 472 && variant <= 476) {   // the pair-interleaved two-plane component GEMMs alone (v3 kernel): 472 full, 473 no loads, 475 no MFMAs, 476 no output stores
-            if (K != 3 || stride != 1 || !wino_shape_ok(p, 4)) throw HipError("bench_conv: Winograd variants need an eligible 3x3 stride-1 layer");
-            const long long T = (long long)B * (p.Ho / 4) * (p.Wo / 4);
-            float *vf = mem.alloc<float>((size_t)36 * T * Cin), *uf = mem.alloc<float>((size_t)36 * Cout * Cin), *mo = mem.alloc<float>((size_t)36 * T * Cout);
-            unsigned short *vp = mem.alloc<unsigned short>((size_t)36 * T * Cin * 2), *up = mem.alloc<unsigned short>((size_t)36 * Cout * Cin * 2);
-            launch_fill_random(vf, (size_t)36 * T * Cin, 7, 1.0f, s);
-            launch_fill_random(uf, (size_t)36 * Cout * Cin, 8, 0.05f, s);
-            launch_split_pairs(vf, vp, (size_t)36 * T, Cin, s);
-            launch_split_pairs(uf, up, (size_t)36 * Cout, Cin, s);
-            SplitGemmArgs gp;
-            gp.a = vp; gp.b = up; gp.out = mo;
-            gp.pA = T * Cin; gp.pB = (long long)Cout * Cin; gp.pO = T * Cout;
-            gp.M = (int)T; gp.N = Cout; gp.K = Cin; gp.lda = Cin; gp.ldc = Cout;
-            const int abl = variant - 472;
-            for (int i = 0; i < 2; ++i) launch_gemm_split_pairs(gp, 36, s, abl);
-            *ms_out = time_launches(s, iters, [&] { launch_gemm_split_pairs(gp, 36, s, abl); });
-            return;
-        }
-        const bool split_v = variant == 412 || variant == 413 || variant == 422 || variant == 423;  // split-operand GEMMs: 41x whole three-launch layer, 42x the GEMM alone; x = planes
-        WinoSplitPlan sp{};
-        if (variant == 80 || variant == 81 || variant == 421 || split_v || (variant >= 83 && variant <= 82 + 255) || (variant >= 430 && variant <= 469) || variant >= 2000) {
-            if (K != 3 || stride != 1) throw HipError("bench_conv: Winograd variants need a 3x3 stride-1 layer");
-            dU = mem.alloc<float>((size_t)36 * nw / 9);
-            launch_fill_random(dU, (size_t)36 * nw / 9, 5, 1.0f / sqrtf((float)(9 * Cin)), s);
-            if (variant != 81 && variant != 421 && !split_v && !wino_fused_eligible(p)) throw HipError("bench_conv: shape not eligible for the fused Winograd kernel");
-            if (variant >= 400 && !wino_fused64_eligible(p)) throw HipError("bench_conv: shape not eligible for the 64-cout fused Winograd kernel");
-            if (variant == 434) {  // the fp16-pair kernel: the random weights as hi / lo halves
-                float* dUp = mem.alloc<float>((size_t)36 * nw / 9);
-                launch_wino_fused64_split_weights(dU, reinterpret_cast<unsigned short*>(dUp), (size_t)36 * nw / 9, 256.0f, s);
-                dU = dUp;
-                p.pair_scale = 1.0f / (kWinoFused64PairVScale * 256.0f);
-            }
-            if (variant == 81 || variant == 421) {
-                if (!wino_shape_ok(p, 4)) throw HipError("bench_conv: shape not eligible for Winograd F(4x4,3x3)");
-                const long long T = (long long)B * (p.Ho / 4) * (p.Wo / 4);
-                float* dV = mem.alloc<float>((size_t)36 * T * Cin);
-                float* dM = mem.alloc<float>((size_t)36 * T * Cout);
-                wp = make_wino(p, dU, dV, dM, 4);
-                if (variant == 421) launch_wino_input(wp.in, s);
-            }
-            if (split_v) {
-                if (!wino_shape_ok(p, 4)) throw HipError("bench_conv: shape not eligible for Winograd F(4x4,3x3)");
-                const int npl = variant % 10;
-                const long long T = (long long)B * (p.Ho / 4) * (p.Wo / 4);
-                const size_t nu = (size_t)36 * Cout * Cin;
-                unsigned short *dUs = mem.alloc<unsigned short>(nu * npl), *dVs = mem.alloc<unsigned short>((size_t)36 * T * Cin * npl);
-                float* dM = mem.alloc<float>((size_t)36 * T * Cout);
-                launch_split_planes(dU, dUs, nu, nu, npl, s);
-                sp = make_wino_split(p, dUs, dVs, dM, npl);
-                launch_wino_input(sp.in, s);
-            }
-        }
-        if (variant == 82) {  // fused Winograd kernel once, with per-wave phase stamps: prints the averaged timeline
+        if (kind == BenchKind::Fused32Stamps) {  // fused Winograd kernel once, with per-wave phase stamps: prints the averaged timeline
             dU = mem.alloc<float>((size_t)36 * nw / 9);
             launch_fill_random(dU, (size_t)36 * nw / 9, 5, 1.0f / sqrtf((float)(9 * Cin)), s);
             const int nb = wino_fused_num_blocks(p);
@@ -926,14 +1014,38 @@ int irsde_bench_conv(int variant, int B, int H, int W, int Cin, int Cout, int K,
             *ms_out = 0.0;
             return;
         }
-        if (variant == 465 || (variant >= 4650 && variant <= 4653)) {   // r06: the two-tile-group kernel once with per-wave cycle stamps (4650 / 4651 / 4652: no patch traffic / output stores dropped / residual loads dropped)
+        if (kind != BenchKind::Conv) {   // the Winograd kinds: random U (timing only)
+            const bool three_launch = kind == BenchKind::Wino3 || kind == BenchKind::Wino3Gemm;
+            if (K != 3 || stride != 1) throw HipError("bench_conv: Winograd variants need a 3x3 stride-1 layer");
+            dU = mem.alloc<float>((size_t)36 * nw / 9);
+            launch_fill_random(dU, (size_t)36 * nw / 9, 5, 1.0f / sqrtf((float)(9 * Cin)), s);
+            if (!three_launch && !wino_fused_eligible(p)) throw HipError("bench_conv: shape not eligible for the fused Winograd kernel");
+            // (the GEMMs-alone variant is held to the 64-cout kernel's shapes too: it is timed next to those kernels)
+            if (kind != BenchKind::Fused32 && kind != BenchKind::Wino3 && !wino_fused64_eligible(p))
+                throw HipError("bench_conv: shape not eligible for the 64-cout fused Winograd kernel");
+            if (kind == BenchKind::Fused64 && r.op == Operand::F16) {  // the fp16-pair kernel: the random weights as hi / lo halves
+                float* dUp = mem.alloc<float>((size_t)36 * nw / 9);
+                launch_wino_fused64_split_weights(dU, reinterpret_cast<unsigned short*>(dUp), (size_t)36 * nw / 9, 256.0f, s);
+                dU = dUp;
+                p.pair_scale = 1.0f / (kWinoFused64PairVScale * 256.0f);
+            }
+            if (three_launch) {
+                if (!wino_shape_ok(p, 4)) throw HipError("bench_conv: shape not eligible for Winograd F(4x4,3x3)");
+                const long long T = (long long)B * (p.Ho / 4) * (p.Wo / 4);
+                float* dV = mem.alloc<float>((size_t)36 * T * Cin);
+                float* dM = mem.alloc<float>((size_t)36 * T * Cout);
+                wp = make_wino(p, dU, dV, dM, 4);
+                if (kind == BenchKind::Wino3Gemm) launch_wino_input(wp.in, s);
+            }
+        }
+        if (kind == BenchKind::Fused64TStamps) {   // r06: the two-tile-group kernel once with per-wave cycle stamps
             if (!wino_fused64t_eligible(p)) throw HipError("bench_conv: shape not eligible for the two-tile-group fused Winograd kernel");
             const int nbp = 256;
             unsigned long long* dd = mem.alloc<unsigned long long>((size_t)nbp * 64);
             launch_wino_fused64t(p, dU, s, 0);  // warm
             IRSDE_HIP_CHECK(hipMemsetAsync(dd, 0, (size_t)nbp * 64 * 8, s));
             wino_fused64t_set_debug(dd);
-            launch_wino_fused64t(p, dU, s, variant == 465 ? 5 : 12 + (variant - 4650));
+            launch_wino_fused64t(p, dU, s, arg);
             IRSDE_HIP_CHECK(hipStreamSynchronize(s));
             wino_fused64t_set_debug(nullptr);
             std::vector<unsigned long long> hd((size_t)nbp * 64);
@@ -959,15 +1071,13 @@ int irsde_bench_conv(int variant, int B, int H, int W, int Cin, int Cout, int K,
             *ms_out = 0.0;
             return;
         }
-        if (variant == 435 || (variant >= 2001 && variant <= 2004)) {  // the persistent fused Winograd kernel once with per-wave cycle stamps: prints the averaged budget
-            // 2001 / 2002: the stamp twins without weight / patch traffic (2004 = 435)
-            const int stamp_variant = variant == 2001 ? 28 : variant == 2002 ? 29 : 25;
+        if (kind == BenchKind::Fused64Stamps) {  // the persistent fused Winograd kernel once with per-wave cycle stamps: prints the averaged budget
             const int nbp = 256;
             unsigned long long* dd = mem.alloc<unsigned long long>((size_t)nbp * 64);
             launch_wino_fused64(p, dU, s, 20);  // warm
             IRSDE_HIP_CHECK(hipMemsetAsync(dd, 0, (size_t)nbp * 64 * 8, s));
             wino_fused64_set_debug(dd);
-            launch_wino_fused64(p, dU, s, stamp_variant);
+            launch_wino_fused64(p, dU, s, arg);
             IRSDE_HIP_CHECK(hipStreamSynchronize(s));
             wino_fused64_set_debug(nullptr);
             std::vector<unsigned long long> hd((size_t)nbp * 64);
@@ -994,34 +1104,21 @@ int irsde_bench_conv(int variant, int B, int H, int W, int Cin, int Cout, int K,
             *ms_out = 0.0;
             return;
         }
+        const ConvTune tune = kind == BenchKind::Conv ? conv_tune_from_code(arg) : ConvTune{};
         auto run = [&] {
-            if (variant == 80) {
-                launch_wino_fused(p, dU, s);
-            } else if (variant >= 467 && variant <= 469) {  // measurement twins of the two-tile-group kernel: no transform arithmetic / + no gathers / no gathers only
-                launch_wino_fused64t(p, dU, s, variant - 461);
-            } else if (variant >= 460 && variant <= 462) {  // r06 two-tile-group kernel: 460 production, 461 / 462 weight fragments / patch gathers read zeros
-                launch_wino_fused64t(p, dU, s, variant - 460);
-            } else if (variant >= 430 && variant <= 434) {  // r04 persistent kernel: 430 production, 431 / 432 weight fragments / patch loads read zeros, 434 fp16 pairs
-                launch_wino_fused64(p, dU, s, variant - 410);
-            } else if (variant >= 83 && variant <= 82 + 255) {  // tuning aids: dflags = variant - 82 (1 no patch traffic, 2 no weight traffic, 4 / 8 producer / MFMA waves at s_setprio 2)
-                launch_wino_fused(p, dU, s, nullptr, variant - 82);
-            } else if (variant == 81) {
+            switch (kind) {
+            case BenchKind::Fused32: launch_wino_fused(p, dU, s, nullptr, arg); break;
+            case BenchKind::Fused64T: launch_wino_fused64t(p, dU, s, arg); break;
+            case BenchKind::Fused64: launch_wino_fused64(p, dU, s, arg); break;
+            case BenchKind::Wino3:
                 launch_wino_input(wp.in, s);
                 launch_conv(wp.gemm, s);
                 launch_wino_output(wp.out, s);
-            } else if (variant == 421) {   // the f32 component GEMMs alone
-                launch_conv(wp.gemm, s);
-            } else if (variant == 412 || variant == 413) {
-                launch_wino_input(sp.in, s);
-                launch_gemm_split(sp.gemm, sp.nplanes, 36, s);
-                launch_wino_output(sp.out, s);
-            } else if (variant == 422 || variant == 423) {   // the split-operand component GEMMs alone
-                launch_gemm_split(sp.gemm, sp.nplanes, 36, s);
-            } else {
-                launch_conv(p, s);
+                break;
+            case BenchKind::Wino3Gemm: launch_conv(wp.gemm, s); break;   // the f32 component GEMMs alone
+            default: launch_conv(p, s, tune); break;
             }
         };
-        VariantScope vs(halo_force ? halo_force : variant >= 80 || variant == 63 || variant == 62 ? 0 : variant);
         for (int i = 0; i < 2; ++i) run();
         *ms_out = time_launches(s, iters, run);
     });

@@ -1,4 +1,4 @@
-// fp32-equivalent GEMM on the bf16 matrix pipe (r03 prototype; SURVEY.md 7 lists the route, VERDICT r02 #3 asks for it).
+// fp32-equivalent GEMMs on the 16-bit matrix pipe (SURVEY.md 7 lists the route).
 //
 // gfx950 has no tf32 / xf32 MFMA: an exact-f32 product costs v_mfma_f32_32x32x2_f32 = 1/16 of the bf16 rate.  Split every
 // f32 operand into NPL bf16 pieces (round-to-nearest-even, the residual is exact in f32):
@@ -8,22 +8,14 @@
 //     NPL = 2:  a b ~= a0 b0 + (a0 b1 + a1 b0)                                3 MFMAs, dropped terms <= 3 * 2^-18 |a b|
 // i.e. NPL = 3 carries the operands' full 24 bits (the dropped part is below f32's own 2^-24 rounding of each
 // accumulation) at 6/16 of the f32-MFMA cycles; NPL = 2 is a 16-bit-significand mode at 3/16.  Accumulation is f32 in both.
-// This is NOT the bit-exact fmaf chain of the native kernels (different rounding points).  NPL = 2 is an opt-in engine mode
-// (IRSDE_FLAG_SPLIT_BF16X2 / _F16X2) with its own measured error table (profiles/r03_split_gemm_*.txt).  NPL = 3 is fp32-equivalent and, on
-// gemm_split3i_kernel below, the exact-fp32 engine's default for its deep component GEMMs (profiles/split3.md; IRSDE_FLAG_NO_SPLIT3 restores the
-// f32 MFMA kernels bit for bit).  The r03 verdict "no faster than native" belongs to the 128 x 128 plane-major prototype (gemm_split_kernel<3>,
-// vector-memory-bound: 0.71 against 0.57 ms for 1024^3 x 36), which stays as the kernel-level cross-check of irsde_debug_split_gemm.
+// This is NOT the bit-exact fmaf chain of the native kernels (different rounding points).  NPL = 2 (gemm_split2i_kernel) is an opt-in engine mode
+// (IRSDE_FLAG_SPLIT_BF16X2 / _F16X2) with its own measured error table (profiles/r03_split_gemm_*.txt).  NPL = 3 (gemm_split3i_kernel) is fp32-equivalent
+// and the exact-fp32 engine's default for its deep component GEMMs (profiles/split3.md; IRSDE_FLAG_NO_SPLIT3 restores the f32 MFMA kernels bit for bit).
 //
 // Where: the component GEMMs of the three-launch Winograd layers, M_z[t][n] = sum_c V_z[t][c] U_z[n][c] (reference call site:
-// Block.proj, module_util.py:108-122).  wino.hip writes V already split (NPL planes of bf16: 2 NPL bytes per element instead
-// of 4), U is split once at weight load, so the GEMM kernel below is a pure bf16 GEMM over NPL + NPL operand planes:
-//   block 128 x 128 outputs, 4 waves of 64 x 64 (2 x 2 tiles of v_mfma_f32_32x32x16_bf16), K-step 32;
-//   per K-step and plane one 128 x 32 bf16 slice of A and of B in LDS (80-byte rows: conflict-free ds_read_b128, the layout of
-//   the bf16 kernels in conv_igemm.hip), double-buffered, global -> register -> LDS staging one K-step ahead;
-//   per 16-k sub-step a wave reads NPL A + NPL B fragments per tile row / column and issues NPROD MFMAs per output tile:
-//   one LDS fragment read per MFMA (x3) instead of two for the plain bf16 kernel, which is LDS-read-bound.
-//   Like gemm_zloop_kernel a block walks n_inner components of its (row tile, column tile) as one pipelined K loop and
-//   writes finished accumulators straight from registers (buffer stores, rows past M dropped by the descriptor).
+// Block.proj, module_util.py:108-122).  wino.hip writes V already split (2 NPL bytes per element instead of 4) in the kernel's interleaved
+// layout, U is split once at weight load, so the kernels below are pure 16-bit GEMMs over NPL + NPL operand pieces; the plane-major
+// split_planes_kernel makes the pair copies of the fused kernels' weights (engine.h).
 #include "common.h"
 #include <algorithm>
 #include <atomic>
@@ -39,160 +31,6 @@ typedef unsigned uintx4 __attribute__((ext_vector_type(4)));
 namespace {
 
 constexpr int SG_BK = 32;            // k per K-step and plane
-constexpr int SG_ROWB = 80;          // LDS bytes per row: 32 bf16 + 16 B pad
-constexpr int SG_PLANE = 128 * SG_ROWB;
-
-template <int NPL>
-__global__ __launch_bounds__(256, 1) void gemm_split_kernel(const SplitGemmArgs g) {
-    constexpr int NPROD = NPL == 3 ? 6 : 3;
-    // smallest terms first; consecutive MFMAs of one product hit the four different accumulators of the wave
-    constexpr int PA[6] = {0, 1, 2, 0, 1, 0};
-    constexpr int PB[6] = {2, 1, 0, 1, 0, 0};
-    constexpr int P0 = 6 - NPROD;  // NPL = 2 uses the last three pairs: (0,1), (1,0), (0,0)
-    constexpr int A_BYTES = NPL * SG_PLANE;
-    extern __shared__ __attribute__((aligned(16))) char lds[];
-    char* As = lds;
-    char* Bs = lds + 2 * A_BYTES;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1;
-    const int l31 = lane & 31, h = lane >> 5;
-    int wgid;
-    {
-        const int orig = blockIdx.x, nwg = gridDim.x;
-        const int xcd = orig & 7, q = nwg >> 3, r = nwg & 7;
-        wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
-    }
-    const int mblk = wgid / g.nblk_n, nblk = wgid - mblk * g.nblk_n;
-    const int m0 = mblk * 128, n0 = nblk * 128;
-    const int plane0 = blockIdx.y * g.n_inner;  // first component of this block
-    const int nk = g.K / SG_BK;
-    const int steps = g.n_inner * nk;
-
-    const int piece = tid & 3, row0 = tid >> 2;  // 16-byte piece of a 64-byte row slice; rows row0 and row0 + 64
-    const char* arow[2];
-    const char* brow[2];
-    int st_i = 0;
-    auto set_tile_ptrs = [&]() {
-        const long long z = plane0 + st_i;
-#pragma unroll
-        for (int ps = 0; ps < 2; ++ps) {
-            int m = m0 + row0 + ps * 64;
-            m = m < g.M ? m : g.M - 1;   // clamped rows feed accumulator rows that are never stored
-            arow[ps] = reinterpret_cast<const char*>(g.a + z * g.pA + (long long)m * g.lda) + piece * 16;
-            int n = n0 + row0 + ps * 64;
-            n = n < g.N ? n : g.N - 1;
-            brow[ps] = reinterpret_cast<const char*>(g.b + z * g.pB + (long long)n * g.K) + piece * 16;
-        }
-    };
-    set_tile_ptrs();
-    uintx4 rs[4 * NPL];
-    int kk = 0;
-    const long long plA2 = g.plA * 2, plB2 = g.plB * 2;
-    auto load_all = [&]() {
-#pragma unroll
-        for (int ps = 0; ps < 2; ++ps)
-#pragma unroll
-            for (int p = 0; p < NPL; ++p) {
-                rs[ps * NPL + p] = *reinterpret_cast<const uintx4*>(arow[ps] + p * plA2 + kk * 2);
-                rs[2 * NPL + ps * NPL + p] = *reinterpret_cast<const uintx4*>(brow[ps] + p * plB2 + kk * 2);
-            }
-    };
-    auto store_all = [&](int buf) {
-#pragma unroll
-        for (int ps = 0; ps < 2; ++ps)
-#pragma unroll
-            for (int p = 0; p < NPL; ++p) {
-                *reinterpret_cast<uintx4*>(As + buf * A_BYTES + p * SG_PLANE + (row0 + ps * 64) * SG_ROWB + piece * 16) = rs[ps * NPL + p];
-                *reinterpret_cast<uintx4*>(Bs + buf * A_BYTES + p * SG_PLANE + (row0 + ps * 64) * SG_ROWB + piece * 16) = rs[2 * NPL + ps * NPL + p];
-            }
-    };
-
-    floatx16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    load_all();
-    store_all(0);
-    __syncthreads();
-
-    const int wm_s = __builtin_amdgcn_readfirstlane(wm), wn_s = __builtin_amdgcn_readfirstlane(wn);
-    unsigned o_voff[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) o_voff[r] = (unsigned)(((r & 3) + 8 * (r >> 2) + 4 * h) * g.ldc + l31) * 4u;
-    auto flush = [&](int fi) {
-        const int rowb = m0 + wm_s * 64, colb = n0 + wn_s * 64;
-        float* ob = g.out + (long long)(plane0 + fi) * g.pO + (long long)rowb * g.ldc;
-        const int rows = g.M - rowb;
-        const unsigned nrec = rows <= 0 ? 0u : (unsigned)(rows < 64 ? rows : 64) * (unsigned)g.ldc * 4u;
-        const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(ob, 0, nrec, 0x00020000);
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const int colu = colb + j * 32;
-                if (colu + l31 < g.N) {
-                    const int soff = (i * 32 * g.ldc + colu) * 4;
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const float v = acc[i][j][r];  // (bit_cast straight on the vector element stored element 0 sixteen times: hipcc 7.2)
-                        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), ro, (int)o_voff[r], soff, 0);
-                    }
-                }
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-            }
-    };
-    int kdone = 0, cu_i = 0, fl_i = 0;
-    bool pending = false;
-    for (int st = 0; st < steps; ++st) {
-        const int buf = st & 1;
-        if (st + 1 < steps) {  // advance the staging position (the last step re-stages its own operands into the dead buffer)
-            kk += SG_BK;
-            if (kk == g.K) {
-                kk = 0;
-                ++st_i;
-                set_tile_ptrs();
-            }
-        }
-        if (pending) {
-            flush(fl_i);
-            pending = false;
-        }
-        load_all();
-        const char* a = As + buf * A_BYTES + (wm * 64 + l31) * SG_ROWB + h * 16;
-        const char* b = Bs + buf * A_BYTES + (wn * 64 + l31) * SG_ROWB + h * 16;
-#pragma unroll
-        for (int sb = 0; sb < 2; ++sb) {
-            bf16x8 fa[NPL][2], fb[NPL][2];
-#pragma unroll
-            for (int p = 0; p < NPL; ++p)
-#pragma unroll
-                for (int i = 0; i < 2; ++i) {
-                    fa[p][i] = *reinterpret_cast<const bf16x8*>(a + p * SG_PLANE + i * 32 * SG_ROWB + sb * 32);
-                    fb[p][i] = *reinterpret_cast<const bf16x8*>(b + p * SG_PLANE + i * 32 * SG_ROWB + sb * 32);
-                }
-#pragma unroll
-            for (int pr = P0; pr < 6; ++pr)
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[PA[pr]][i], fb[PB[pr]][j], acc[i][j], 0, 0, 0);
-        }
-        store_all(buf ^ 1);
-        if (++kdone == nk) {
-            kdone = 0;
-            fl_i = cu_i++;
-            pending = true;
-        }
-        __syncthreads();
-    }
-    flush(fl_i);
-}
 
 // ---------------------------------------------------------------------------------------------------------------
 // The engine's kernel: two planes, pair-interleaved operands, LDS-DMA, 256 x 256 tiles.  Its predecessor (v2, removed: plane-major
@@ -724,16 +562,6 @@ void gemm_split_global_init() {
     IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split3i_kernel<3, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split3i_kernel<4, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
 #endif
-    IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-}
-
-// components per block: the largest divisor of `ncomp` that still leaves >= 512 blocks (2 per CU)
-int gemm_split_inner(int M, int N, int ncomp) {
-    const long long tiles = (long long)((M + 127) / 128) * ((N + 127) / 128);
-    for (int d = ncomp; d >= 1; --d)
-        if (ncomp % d == 0 && tiles * (ncomp / d) >= 512) return d;
-    return 1;
 }
 
 // pair-interleaved operands (g.a / g.b in the [row][k/32][plane][32] layout, g.pA / g.pB = elements per component and plane)
@@ -778,20 +606,21 @@ static std::atomic<int> g_force_split3_blocks{-1};   // irsde_debug_force_split3
 void set_force_split3_blocks(int n) { g_force_split3_blocks.store(n >= 8 ? n : -1, std::memory_order_relaxed); }
 
 // three-piece row-pair-interleaved operands (split3_layout.h; g.pA / g.pB = unsigned shorts per component)
-// walk: 1 = at most one block per CU (or the forced cap), each walking its share of the items; 0 = one item per block (the twin); -1 = IRSDE_SPLIT3_WALK (1)
-// drain: 1 = the walk's drain twin (vmcnt(0) in front of every barrier of the K loop); 0 = the ring; -1 = IRSDE_SPLIT3_DRAIN (0)
-void launch_gemm_split_triples(const SplitGemmArgs& a, int ncomp, hipStream_t s, int abl, int walk, int drain) {
+// o.walk: at most one block per CU (or the forced cap), each walking its share of the items / one item per block (the twin)
+// o.drain: the walk's drain twin (vmcnt(0) in front of every barrier of the K loop) / the ring
+template <int ABL>
+static void launch_split3_abl(bool walk, bool drain, dim3 grid, size_t lds, hipStream_t s, const SplitGemmArgs& g) {
+    if (drain) hipLaunchKernelGGL((gemm_split3i_kernel<ABL, true, true>), grid, dim3(512), lds, s, g);
+    else if (walk) hipLaunchKernelGGL((gemm_split3i_kernel<ABL, true>), grid, dim3(512), lds, s, g);
+    else hipLaunchKernelGGL((gemm_split3i_kernel<ABL, false>), grid, dim3(512), lds, s, g);
+}
+void launch_gemm_split_triples(const SplitGemmArgs& a, int ncomp, hipStream_t s, const Split3Launch& o) {
     if (a.K % SG_BK) throw HipError("gemm_split_triples: K must be a multiple of 32");
     if (!gemm_split_triples_fits(a.M, a.N, a.K, a.ldc)) throw HipError("gemm_split_triples: a component exceeds the 32-bit offset range");
     if (ncomp < 1 || a.ldc < a.N) throw HipError("gemm_split_triples: bad component count or output stride");
-    if (walk < 0) {
-        static const int knob = tuning_env_int("IRSDE_SPLIT3_WALK", 1);
-        walk = knob != 0;
-    }
-    if (drain < 0) {
-        static const int knob = tuning_env_int("IRSDE_SPLIT3_DRAIN", 0);
-        drain = knob != 0;
-    }
+    static const bool walk_knob = tuning_env_int("IRSDE_SPLIT3_WALK", 1) != 0, drain_knob = tuning_env_int("IRSDE_SPLIT3_DRAIN", 0) != 0;
+    const bool walk = o.walk == Split3Launch::RULE ? walk_knob : o.walk == Split3Launch::ON;
+    const bool drain = o.drain == Split3Launch::RULE ? drain_knob : o.drain == Split3Launch::ON;
     if (drain && !walk) throw HipError("gemm_split_triples: the drain twin exists on the walk only");
     SplitGemmArgs g = a;
     g.nblk_n = (a.N + 127) / 128;
@@ -807,20 +636,12 @@ void launch_gemm_split_triples(const SplitGemmArgs& a, int ncomp, hipStream_t s,
     }
     const dim3 grid((unsigned)blocks);
     const size_t lds = (size_t)2 * (256 + 128) * 192;
-    switch (abl * 2 + (walk ? 1 : 0) + (drain ? 100 : 0)) {
-        case 1: hipLaunchKernelGGL((gemm_split3i_kernel<0, true>), grid, dim3(512), lds, s, g); break;
-        case 0: hipLaunchKernelGGL((gemm_split3i_kernel<0, false>), grid, dim3(512), lds, s, g); break;
-        case 101: hipLaunchKernelGGL((gemm_split3i_kernel<0, true, true>), grid, dim3(512), lds, s, g); break;
+    switch (o.abl) {
+        case Split3Launch::FULL: launch_split3_abl<0>(walk, drain, grid, lds, s, g); break;
 #ifdef IRSDE_PROBES
-        case 3: hipLaunchKernelGGL((gemm_split3i_kernel<1, true>), grid, dim3(512), lds, s, g); break;
-        case 7: hipLaunchKernelGGL((gemm_split3i_kernel<3, true>), grid, dim3(512), lds, s, g); break;
-        case 9: hipLaunchKernelGGL((gemm_split3i_kernel<4, true>), grid, dim3(512), lds, s, g); break;
-        case 2: hipLaunchKernelGGL((gemm_split3i_kernel<1, false>), grid, dim3(512), lds, s, g); break;
-        case 6: hipLaunchKernelGGL((gemm_split3i_kernel<3, false>), grid, dim3(512), lds, s, g); break;
-        case 8: hipLaunchKernelGGL((gemm_split3i_kernel<4, false>), grid, dim3(512), lds, s, g); break;
-        case 103: hipLaunchKernelGGL((gemm_split3i_kernel<1, true, true>), grid, dim3(512), lds, s, g); break;
-        case 107: hipLaunchKernelGGL((gemm_split3i_kernel<3, true, true>), grid, dim3(512), lds, s, g); break;
-        case 109: hipLaunchKernelGGL((gemm_split3i_kernel<4, true, true>), grid, dim3(512), lds, s, g); break;
+        case Split3Launch::NO_LOADS: launch_split3_abl<1>(walk, drain, grid, lds, s, g); break;
+        case Split3Launch::NO_MFMA: launch_split3_abl<3>(walk, drain, grid, lds, s, g); break;
+        case Split3Launch::NO_STORES: launch_split3_abl<4>(walk, drain, grid, lds, s, g); break;
 #endif
         default: throw HipError("gemm_split_triples: the ablation twins are part of the PROBES build");
     }
@@ -842,26 +663,12 @@ void launch_split_pairs(const float* in, unsigned short* out, size_t rows, int K
     IRSDE_HIP_CHECK(hipGetLastError());
 }
 
-void launch_gemm_split(const SplitGemmArgs& a, int nplanes, int ncomp, hipStream_t s) {
-    if (nplanes != 2 && nplanes != 3) throw HipError("gemm_split: 2 or 3 planes");
-    if (a.K % SG_BK || a.n_inner < 1 || ncomp % a.n_inner) throw HipError("gemm_split: K must be a multiple of 32, n_inner a divisor of the component count");
-    if ((size_t)a.M * a.ldc * 4 >= 0xffffffffull) throw HipError("gemm_split: output plane exceeds the 32-bit buffer range");
-    SplitGemmArgs g = a;
-    g.nblk_n = (a.N + 127) / 128;
-    const dim3 grid((unsigned)(((a.M + 127) / 128) * g.nblk_n), (unsigned)(ncomp / a.n_inner));
-    const size_t lds = (size_t)4 * nplanes * SG_PLANE;
-    if (nplanes == 3) hipLaunchKernelGGL(gemm_split_kernel<3>, grid, dim3(256), lds, s, g);
-    else hipLaunchKernelGGL(gemm_split_kernel<2>, grid, dim3(256), lds, s, g);
-    IRSDE_HIP_CHECK(hipGetLastError());
-}
-
 void launch_split_planes(const float* in, unsigned short* out, size_t n, size_t plane, int nplanes, hipStream_t s, bool f16, float scale) {
     const dim3 grid((unsigned)((n + 255) / 256));
     if (f16 && nplanes != 2) throw HipError("split_planes: fp16 pieces come in pairs");
     if (f16) hipLaunchKernelGGL((split_planes_kernel<2, true>), grid, dim3(256), 0, s, in, out, n, plane, scale);
-    else if (nplanes == 3) hipLaunchKernelGGL((split_planes_kernel<3, false>), grid, dim3(256), 0, s, in, out, n, plane, 1.0f);
     else if (nplanes == 2) hipLaunchKernelGGL((split_planes_kernel<2, false>), grid, dim3(256), 0, s, in, out, n, plane, 1.0f);
-    else throw HipError("split_planes: 2 or 3 planes");
+    else throw HipError("split_planes: 2 planes");
     IRSDE_HIP_CHECK(hipGetLastError());
 }
 

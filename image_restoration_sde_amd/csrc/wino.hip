@@ -133,12 +133,13 @@ __global__ __launch_bounds__(256) void wino_input_kernel(const WinoParams p) {
 }
 
 // Split-operand mode (gemm_split.hip): the same F(4x4,3x3) input transform, 4 channels per thread, but every V element is
-// written as NPL bf16 pieces (round to nearest even, residual exact in f32) into NPL planes: 2 NPL bytes per element instead
-// of 4, and the component GEMMs become bf16 GEMMs with f32-equivalent (NPL = 3) or 16-bit (NPL = 2) operands.
+// written as NPL 16-bit pieces (round to nearest even, residual exact in f32): 2 NPL bytes per element instead
+// of 4, and the component GEMMs become 16-bit GEMMs with f32-equivalent (NPL = 3, fp16 pairs) or 16-bit (bf16 pairs) operands.
+// PAIRS: two pieces pair-interleaved (gemm_split2i_kernel's operands)
 // TRI: the three planes in the row-pair-interleaved layout of split3_layout.h (gemm_split3i_kernel's operands)
 template <int NPL, bool PAIRS = false, bool F16 = false, bool TRI = false>
 __global__ __launch_bounds__(256) void wino_input_split_kernel(const WinoParams p) {
-    static_assert(!TRI || (NPL == 3 && !PAIRS && !F16), "three bf16 pieces");
+    static_assert(TRI != PAIRS && (!TRI || (NPL == 3 && !F16)) && (!PAIRS || NPL == 2), "three bf16 pieces, or a pair");
     constexpr int A = 6;
     const int C4 = (p.C0 + p.C1) / 4;
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -187,10 +188,9 @@ __global__ __launch_bounds__(256) void wino_input_split_kernel(const WinoParams 
     }
     const size_t Ctot = (size_t)(p.C0 + p.C1);
     // PAIRS: [component][tile][c / 32][plane][c % 32] (both pieces of a 32-channel block in one 128-byte line)
-    unsigned short* vp = TRI ? p.Vs + split3_index((size_t)t, (size_t)c, 0, Ctot / 32)
-                       : PAIRS ? p.Vs + ((size_t)t * (Ctot / 32) + c / 32) * 64 + (c & 31) : p.Vs + (size_t)t * Ctot + c;
-    const size_t kstride = TRI ? split3_comp_elems((size_t)p.T, Ctot) : PAIRS ? (size_t)p.T * Ctot * 2 : (size_t)p.T * Ctot;
-    const size_t plstride = TRI || PAIRS ? 32 : (size_t)p.v_plane;
+    unsigned short* vp = TRI ? p.Vs + split3_index((size_t)t, (size_t)c, 0, Ctot / 32) : p.Vs + ((size_t)t * (Ctot / 32) + c / 32) * 64 + (c & 31);
+    const size_t kstride = TRI ? split3_comp_elems((size_t)p.T, Ctot) : (size_t)p.T * Ctot * 2;
+    constexpr size_t plstride = 32;   // both layouts: the pieces of a 32-channel block sit side by side
 #pragma unroll
     for (int r = 0; r < A; ++r) {
         float4 o[A];
@@ -557,19 +557,18 @@ static int wino_vec() {
 }
 
 void launch_wino_input(const WinoParams& p, hipStream_t s) {
-    if (p.Vs) {  // split-operand mode: bf16 planes
-        if (p.tile != 4 || (p.nplanes != 2 && p.nplanes != 3) || (p.C0 % 4) || (p.C1 % 4)) throw HipError("wino_input (split): F(4x4,3x3), 2 or 3 planes");
+    if (p.Vs) {  // split-operand mode: 16-bit pieces
+        if (p.tile != 4 || (p.C0 % 4) || (p.C1 % 4)) throw HipError("wino_input (split): F(4x4,3x3) only");
         const long long tot = (long long)p.T * ((p.C0 + p.C1) / 4);
         const dim3 gr((unsigned)((tot + 255) / 256));
         if (p.v_triples) {
             if (p.nplanes != 3 || p.v_pairs || p.v_f16 || (p.C0 + p.C1) % 32) throw HipError("wino_input (triples): three bf16 planes, channels a multiple of 32");
             hipLaunchKernelGGL((wino_input_split_kernel<3, false, false, true>), gr, dim3(256), 0, s, p);
-        } else if (p.v_pairs) {
-            if (p.nplanes != 2 || (p.C0 + p.C1) % 32) throw HipError("wino_input (pairs): two planes, channels a multiple of 32");
+        } else {
+            if (!p.v_pairs || p.nplanes != 2 || (p.C0 + p.C1) % 32) throw HipError("wino_input (pairs): two planes, channels a multiple of 32");
             if (p.v_f16) hipLaunchKernelGGL((wino_input_split_kernel<2, true, true>), gr, dim3(256), 0, s, p);
             else hipLaunchKernelGGL((wino_input_split_kernel<2, true, false>), gr, dim3(256), 0, s, p);
-        } else if (p.nplanes == 3) hipLaunchKernelGGL((wino_input_split_kernel<3, false>), gr, dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((wino_input_split_kernel<2, false>), gr, dim3(256), 0, s, p);
+        }
         IRSDE_HIP_CHECK(hipGetLastError());
         return;
     }

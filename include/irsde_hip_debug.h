@@ -3,7 +3,7 @@
  * Not part of the drop-in boundary (include/irsde_hip.h): nothing here replaces a reference interface.  The parity
  * tests use irsde_debug_conv to exercise one convolution code path at a time; tools/ uses irsde_bench_conv for the
  * A/B measurements logged under profiles/.  Neither changes the launch plan of an engine: the `naive` / `variant`
- * selector is scoped to the one call (reset to the production dispatch before returning).
+ * selector is turned into overrides that are handed to the launches of that one call only (no process-wide state).
  */
 #ifndef IRSDE_HIP_DEBUG_H
 #define IRSDE_HIP_DEBUG_H
@@ -29,7 +29,6 @@ extern "C" {
  *   46 / 47 the direct implicit GEMM on the PAIR kernels (conv_igemm.hip: fp32 storage, activations split into 16-bit hi + lo pieces while
  *           staged, three cross products on the 16-bit MFMA): fp16 / bf16 pieces
  *   44 / 45 three-launch Winograd F(4x4,3x3) with the engine's pair GEMM (pair-interleaved operands, LDS-DMA): fp16 / bf16 hi + lo pieces
- *   42 / 43 three-launch Winograd F(4x4,3x3) with split-operand component GEMMs on the bf16 MFMA pipe (csrc/gemm_split.hip): 2 / 3 bf16 planes
  *   34 the 64-cout fused Winograd kernel (r03: Cout and C0 + C1 multiples of 64); 36: with its cout-block-by-XCD block mapping forced wherever legal;
  *      55: its production variant selected by number
  *   35 / 37 the same kernel's fp16-pair twin (IRSDE_FLAG_SPLIT_F16X2; all four hi / lo cross products on v_mfma_f32_16x16x32_f16) / with the mapping forced;
@@ -44,29 +43,30 @@ extern "C" {
  *   100 + v: tuning variant v of the fp32 kernel: 0 production dispatch, 3 / 50 the 256x128 / 256x256 tile, 5 one block per CU, 6 generic pointer staging
  *           instead of buffer descriptors, 7 LDS-transposed instead of direct epilogue, 70 the tile-loop kernel off, 71 / 72 its batch-loop form with all / 2
  *           components per block, 73 the tile-loop kernel forced for 1x1 layers
- * Any other code is refused.  splits > 1 forces split-K.  Synchronises `stream`. */
+ * Any other code is refused, 42 / 43 (the retired plane-major prototype GEMM) among them.  splits > 1 forces split-K.  Synchronises `stream`. */
 int irsde_debug_conv(const float* in0, int C0, const float* in1, int C1, int B, int Hin, int Win, int in_shift,
                      const float* w_oihw, int Cout, int KH, int KW, int stride, int pad, const float* bias,
                      const float* film, int film_bstride, int silu, const float* res, float* out, int naive,
                      int splits, void* stream);
 
 /* Kernel-level test hook of csrc/gemm_split.hip: C_z[M][N] = A_z[M][K] . B_z[N][K]^T for z < ncomp (device f32 tensors, z-major),
- * operands split into `nplanes` (2 or 3) bf16 pieces on the device (plane-major prototype kernel; nplanes = 42 / 44: the engine's
+ * operands split into 16-bit pieces on the device (nplanes = 42 / 44: the engine's
  * pair-interleaved two-piece kernel with bf16 / fp16 pieces; nplanes = 43: the exact-fp32 engine's three-piece kernel gemm_split3i_kernel, six products, on
  * its production launch — at most one block per compute unit, each walking several (component, row tile, column tile) items; nplanes = 45: the same kernel
  * with one item per block, the walk's bit-identity twin; nplanes = 47: the production launch with s_waitcnt vmcnt(0) in front of every barrier of the K loop,
- * the bit-identity twin of the kernel's load ring), products on v_mfma_f32_32x32x16_bf16, f32 accumulate.  K a multiple of 32.  Synchronises `stream`. */
+ * the bit-identity twin of the kernel's load ring), products on the 16-bit MFMA, f32 accumulate.  K a multiple of 32.  Any other nplanes is refused, 2 / 3 (the
+ * retired plane-major prototype kernel) among them.  Synchronises `stream`. */
 int irsde_debug_split_gemm(const float* A, const float* B, float* C, int M, int N, int K, int ncomp, int nplanes, void* stream);
 
-/* Kernel tuning hook: average ms of one KxK convolution (pad K/2, or 4x4 s2 p1) on random NHWC data.  variant (any other code is refused):
+/* Kernel tuning hook: average ms of one KxK convolution (pad K/2, or 4x4 s2 p1) on random NHWC data.  variant (any other code is refused, 412 / 413 / 422 / 423
+ * of the retired plane-major prototype GEMM among them):
  *   0 production dispatch, 3 / 50 fp32 256x128 / 256x256 tiles, 5 one block per CU, 6 generic pointer staging instead of buffer descriptors,
  *     7 LDS-transposed instead of direct epilogue, 70 the tile-loop kernel off, 71 / 72 its batch-loop form with all / 2 components per block, 73 forced for 1x1 layers
  *   60 / 61 / 62 bf16 mode (256 tile / 128 tile / automatic incl. the halo kernel), 63 = 62 with bf16 activation storage,
  *     64 / 65 = 62 and 66 / 67 = 63 with the 512- / 256-pixel halo kernel forced (r05)
  *   80 / 81 Winograd F(4x4,3x3) fused kernel / three-launch path (3x3 s1 only), 82 the fused kernel once with its phase timeline printed to stdout,
  *     82 + f (f in 1..255) the fused kernel with tuning-aid flags f (1 no patch traffic, 2 no weight traffic, 4 / 8 producer / MFMA waves at raised priority)
- *   412 / 413 the three-launch Winograd layer with split-operand GEMMs (2 / 3 bf16 planes on the 128 x 128 plane-major prototype kernel),
- *     421 / 422 / 423 the component GEMMs alone: native f32 / 2 planes / 3 planes
+ *   421 the three-launch path's native f32 component GEMMs alone
  *   430 the 64-cout fused Winograd kernel (r04 persistent form, production), 431 / 432 its weight fragments / patch loads read zeros, 434 its fp16-pair twin,
  *     435 (= 2004) the kernel once with its per-wave cycle budget printed to stdout, 2001 / 2002 that stamp run without weight / patch traffic
  *   460 the two-tile-group fused Winograd kernel (r06, production), 461 / 462 its weight fragments / patch gathers read zeros, 467 / 468 / 469 without

@@ -93,6 +93,23 @@ def test_load_weight_errors():
         L.irsde_destroy(h)
 
 
+def test_hooks_refuse_retired_and_unknown_selectors():
+    """The selectors of the retired plane-major prototype GEMM, and a code nobody assigned, are refused before a hook touches the device."""
+    L = _lib.lib()
+    buf = (ctypes.c_float * 64)()
+    ptr = ctypes.cast(buf, ctypes.c_void_p)
+    for code in (42, 43, 9999):
+        assert L.irsde_debug_conv(ptr, 32, None, 0, 1, 8, 8, 0, ptr, 32, 3, 3, 1, 1, None, None, 0, 0, None, ptr, code, 1, None) != 0
+        assert b"unknown selector code %d" % code in L.irsde_last_error()
+    for nplanes in (2, 3):
+        assert L.irsde_debug_split_gemm(ptr, ptr, ptr, 32, 32, 32, 1, nplanes, None) != 0
+        assert b"nplanes must be" in L.irsde_last_error()
+    ms = ctypes.c_double()
+    for variant in (412, 413, 422, 423):
+        assert L.irsde_bench_conv(variant, 1, 8, 8, 32, 32, 3, 1, 0, 0, 1, ctypes.byref(ms)) != 0
+        assert b"unknown variant %d" % variant in L.irsde_last_error()
+
+
 def test_plain_c_host(tmp_path):
     """include/irsde_hip.h is valid C99 and a plain C program (no HIP / torch headers) can drive the library."""
     import shutil

@@ -1,5 +1,5 @@
-"""GPU tests of the split-operand GEMM path (csrc/gemm_split.hip, r03): fp32 operands split into 3 (fp32-equivalent) or 2
-(16-bit significand) bf16 pieces, cross products on v_mfma_f32_32x32x16_bf16, fp32 accumulate.
+"""GPU tests of the split-operand GEMM path (csrc/gemm_split.hip, r03): fp32 operands split into 3 bf16 (fp32-equivalent), 2 fp16 (fp32-equivalent)
+or 2 bf16 (16-bit significand) pieces, cross products on the 16-bit MFMA, fp32 accumulate.
 
 The gate VERDICT r02 #3 set: per-layer error against the FLOAT64 oracle must not exceed the native f32 kernel's (3 pieces);
 the table this file prints (and writes to gpurun_out/split_error_table.txt when that directory exists) is the evidence.
@@ -42,10 +42,10 @@ def note(line):
 
 @pytest.mark.parametrize("shape", LAYERS)
 def test_split_gemm_error_vs_float64(shape):
-    """Winograd F(4x4,3x3) layer with the component GEMMs (a) on the native f32 MFMA, (b) split into 3 bf16 pieces, (c) 2 pieces
-    - all against the float64 oracle convolution.  Gates: 3 pieces <= 2 x the native kernel's error (measured 0.6 .. 1.5 x: the
-    same 24 operand bits, other rounding points), i.e. fp32-equivalent; 2 pieces <= 2e-4 (16-bit operands, Winograd-amplified;
-    measured 6e-5 .. 8e-5)."""
+    """Winograd F(4x4,3x3) layer with the component GEMMs (a) on the native f32 MFMA, (b) split into 3 bf16 pieces on the kernel the exact-fp32
+    engine ships (gemm_split3i_kernel, selector 48), (c) on the engine's pair GEMM - all against the float64 oracle convolution.  Gates: 3 pieces <= 2 x the
+    native kernel's error (measured 0.73 .. 1.48 x: the same 24 operand bits, other rounding points), i.e. fp32-equivalent; bf16 pairs <= 2e-4 (16-bit operands,
+    Winograd-amplified; measured 6e-5 .. 8e-5)."""
     B, C0, C1, H, W, Cout = shape
     rs = np.random.RandomState(C0 + H)
     x0 = rs.standard_normal((B, C0, H, W)).astype(np.float32)
@@ -55,7 +55,7 @@ def test_split_gemm_error_vs_float64(shape):
     res = rs.standard_normal((B, Cout, H, W)).astype(np.float32)
     ref = oracle_conv(x0, x1, w, bias, 1, 1, 0, None, 1, res)
     e = {}
-    for name, naive in (("direct f32", 0), ("winograd f32", 3), ("winograd split x3", 43), ("winograd split x2", 42), ("winograd pairs bf16", 45),
+    for name, naive in (("direct f32", 0), ("winograd f32", 3), ("winograd split x3", 48), ("winograd pairs bf16", 45),
                         ("winograd pairs f16", 44)):
         got = run_conv(x0, x1, w, bias, 1, 1, 0, None, 1, res, naive=naive)
         assert np.isfinite(got).all(), name
@@ -63,21 +63,20 @@ def test_split_gemm_error_vs_float64(shape):
     _ROWS.append((shape, e))
     print("split table %s: %s" % (shape, "  ".join("%s %.3g" % kv for kv in e.items())))
     assert e["winograd split x3"] <= 2.0 * e["winograd f32"] + 1e-7, e
-    assert e["winograd split x2"] <= 2e-4 and e["winograd pairs bf16"] <= 2e-4, e
-    # the engine's two modes: bf16 pairs = the 2-plane prototype's arithmetic; fp16 pairs = fp32-equivalent per layer
+    assert e["winograd pairs bf16"] <= 2e-4, e
+    # the engine's two modes: bf16 pairs = 16-bit operands; fp16 pairs = fp32-equivalent per layer
     assert e["winograd pairs f16"] <= 2.0 * e["winograd f32"] + 1e-7, e
 
 
 # ---------------------------------------------------------------------------------------------
-# kernel level: the three GEMM kernels against float64
+# kernel level: the pair GEMM kernels against float64 (the three-piece kernel: tests/test_gpu_split3.py)
 # ---------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("variant,tol", [(3, 2e-6), (2, 2e-5), (42, 2e-5), (44, 1e-6)])
+@pytest.mark.parametrize("variant,tol", [(42, 2e-5), (44, 1e-6)])
 @pytest.mark.parametrize("shape", [(256, 256, 32, 1), (100, 96, 64, 3), (1000, 520, 96, 4), (777, 256, 512, 5)])
 def test_split_gemm_kernels_vs_float64(variant, tol, shape):
-    """C_z = A_z . B_z^T with f32 operands split on the device: 3 / 2 = three / two bf16 pieces on the 128 x 128 plane-major
-    prototype kernel, 42 / 44 = two bf16 / fp16 pieces pair-interleaved on the LDS-DMA kernel the engine uses (44 with operand scales
-    2^-4 and 2^6 undone in the kernel).  Ragged M / N, several components.  Tolerances relative to max|C|: 24-bit operands 2e-6,
-    16-bit operands 2e-5, fp16 pairs (22+ bits) 1e-6."""
+    """C_z = A_z . B_z^T with f32 operands split on the device: 42 / 44 = two bf16 / fp16 pieces pair-interleaved on the LDS-DMA kernel
+    the engine uses (44 with operand scales 2^-4 and 2^6 undone in the kernel).  Ragged M / N, several components.  Tolerances relative to
+    max|C|: 16-bit operands 2e-5, fp16 pairs (22+ bits) 1e-6."""
     M, N, K, ncomp = shape
     rs = np.random.RandomState(M + K)
     A = rs.standard_normal((ncomp, M, K)).astype(np.float32)
@@ -321,11 +320,10 @@ def test_zz_split_error_table_written():
     if not _ROWS:
         pytest.skip("the parametrised error tests did not run")
     lines = ["# per-layer max-abs error / max|ref| vs the float64 oracle convolution (tests/test_gpu_split.py)",
-             "%-28s %12s %12s %14s %14s %16s %16s" % ("layer (B,C0,C1,H,W,Cout)", "direct f32", "wino f32", "wino 3 x bf16", "wino 2 x bf16",
-                                                     "pairs bf16 (eng)", "pairs f16 (eng)")]
+             "%-28s %12s %12s %18s %16s %16s" % ("layer (B,C0,C1,H,W,Cout)", "direct f32", "wino f32", "wino 3 x bf16 (48)", "pairs bf16 (eng)", "pairs f16 (eng)")]
     for shape, e in _ROWS:
-        lines.append("%-28s %12.3g %12.3g %14.3g %14.3g %16.3g %16.3g" % (str(shape), e["direct f32"], e["winograd f32"], e["winograd split x3"],
-                                                                    e["winograd split x2"], e["winograd pairs bf16"], e["winograd pairs f16"]))
+        lines.append("%-28s %12.3g %12.3g %18.3g %16.3g %16.3g" % (str(shape), e["direct f32"], e["winograd f32"], e["winograd split x3"],
+                                                               e["winograd pairs bf16"], e["winograd pairs f16"]))
     lines += ["", "# the other kernels and the network level, same session (GEMM kernels vs float64; fused Winograd kernel: f32 instance vs fp16-pair twin;",
               "# direct PAIR kernels vs their native f32 twins; engine modes vs the REAL reference's goldens):"] + _NOTES
     out = os.path.join(ROOT, "gpurun_out")
