@@ -249,6 +249,37 @@ struct ConvTune {
     Halo halo = HALO_AUTO;         // 16-bit operands, eligible 3x3 layers: generic tiles / the 512-pixel x 128-channel / the 256-pixel halo kernel
     ZLoop zloop = ZLOOP_AUTO;      // tile-loop kernel: both forms off / its batch-loop form with all / 2 components per block / forced (2 row tiles) for 1x1 layers
 };
+// The tuning knobs the kernel choice reads (IRSDE_<FIELD NAME>, DESIGN.md "Tuning knobs"); the defaults are the production values.  conv_knobs_from_env
+// reads the environment once per process.
+struct ConvKnobs {
+    int small_bn = 2, small_bn_f32 = 0;         // block slots per CU an under-filled grid narrows its column tiles for (0 = rule off): 16-bit operands / f32
+    int pair_tile256 = 1, pair_inscale256 = 0;  // PAIR: the 256 x 256 tile at all / for the SCA-scaled layers too (that instance spills)
+    int no_bufa = 0;                            // f32: generic pointer staging instead of buffer descriptors
+    int zloop = -1, zloop_1x1 = -1;             // tile-loop kernel: 0 = off, n = fixed batch resp. row tiles per block, -1 = by shape
+    int zloop_maxnk = 32, zloop_minblk = 1024, zloop_deep = 1, zloop_ragged64 = 2048;
+};
+const ConvKnobs& conv_knobs_from_env();
+// What launch_conv runs for one layer: conv_choose is a pure function of its arguments (no device, no environment), conv_validate holds launch_conv's refusals.
+struct ConvChoice {
+    enum Family { PAIR, NARROW3, ZLOOP_BATCH, ZLOOP_1X1, HALO, IGEMM };
+    enum Operand { OP_F32, OP_F32_BUF, OP_BF16, OP_F16 };   // f32 MFMA with generic pointers / buffer descriptors; the 16-bit MFMA (PAIR: the pieces' type)
+    enum Storage { ACT_F32, ACT_BF16, ACT_F16 };            // what the kernel's staging reads
+    Family family = IGEMM;
+    int BM = 0, BN = 0;
+    Operand op = OP_F32;
+    Storage act = ACT_F32;
+    bool inscale = false;
+    int zbatch = 0, zrows = 0;         // tile-loop forms: components resp. row tiles per block
+    unsigned gx = 0, gy = 1, gz = 1;   // HALO: conv_halo.hip chooses its own kernel and grid (gx == 0 here)
+    int threads = 0, lds = 0;
+    int row = -1;                      // index into the instance tables (implicit-GEMM / PAIR rows first, then the tile-loop rows); -1: the family has none, or no such instance
+    std::string name() const;          // stable short name: igemm128x64, pair256x256, zloop64x128, zloop1x1_128x128, narrow3, halo
+    long long blocks() const { return (long long)gx * gy * gz; }
+};
+int conv_base_bn(int Cout);   // column-tile width before any narrowing: 128 / 64 / 32
+void conv_validate(const ConvParams& p);
+ConvChoice conv_choose(const ConvParams& p, const ConvTune& t, const ConvKnobs& k, int cu_count);
+int conv_instance_count();    // rows of the instance tables
 void launch_conv(const ConvParams& p, hipStream_t s, const ConvTune& t = {});
 void conv_global_init();
 // bf16 mode: 3x3 s1 p1 layers with an LDS-resident halo tile (conv_halo.hip)

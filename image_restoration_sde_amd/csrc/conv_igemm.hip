@@ -113,7 +113,7 @@ __device__ __forceinline__ void static_for(F&& f) {
 // offsets that change only with the tap / concat source, the K-step's channel offset in an SGPR — so a K-step's loads cost
 // no vector instruction.  On gfx950 the f32 MFMA shares the SIMD's vector ALU: vector instructions between MFMAs are paid
 // in full (4+ cycles each) plus ~16 cycles per MFMA they follow (tools/probe/mfma_valu_samewave.hip), and the pointer
-// arithmetic of the generic path was ~100 of them per K-step.  Needs every operand tensor < 2 GiB (launch_cfg checks).
+// arithmetic of the generic path was ~100 of them per K-step.  Needs every operand tensor < 2 GiB (conv_choose checks).
 // PAIR (r03, IRSDE_FLAG_SPLIT_BF16X2 / _F16X2): fp32 activations and fp32-derived weights, but every operand is split into a 16-bit
 // hi + lo pair (hi = round(x), lo = round(x - hi): exact residual) and the three cross products hi.hi + hi.lo + lo.hi run on the
 // 16-bit MFMA — the arithmetic of gemm_split.hip for the direct (implicit-GEMM) layers.  Activations are split while they are
@@ -1203,83 +1203,71 @@ __global__ void conv_naive_kernel(const ConvParams p, const int M) {
     p.out[(size_t)m * p.out_stride + n] = v;
 }
 
-// PAIR kernels (split-operand arithmetic on fp32 storage): bf16 or fp16 pieces by p.f16
-template <int BM, int BN, int WAVES_M, int WAVES_N, int MINW, bool INSCALE>
-void launch_cfg_pair(const ConvParams& p, int M, int nk_total, hipStream_t s) {
-    using C = Cfg<BM, BN, WAVES_M, WAVES_N, true, false, 2>;
-    const int nblk_m = (M + BM - 1) / BM;
-    const int nblk_n = (p.Cout + BN - 1) / BN;
-    dim3 grid(nblk_m * nblk_n, p.splits, 1);
-    if (p.f16)
-        hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WAVES_M, WAVES_N, MINW, true, INSCALE, false, true, false, true>), grid, dim3(C::NT),
-                           C::LDS_BYTES, s, p, nblk_n, M, nk_total);
-    else
-        hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WAVES_M, WAVES_N, MINW, true, INSCALE, false, false, false, true>), grid, dim3(C::NT),
-                           C::LDS_BYTES, s, p, nblk_n, M, nk_total);
-    IRSDE_HIP_CHECK(hipGetLastError());
+// Host side: conv_validate (the refusals), conv_choose (which kernel, tile and grid: a pure function), the instance tables (every kernel launch_conv can
+// launch, once: conv_global_init and the launch both read them) and launch_conv itself.
+using CC = ConvChoice;
+using IgemmFn = void (*)(const ConvParams, const int, const int, const int);
+struct IgemmRow {
+    bool pair; int BM, BN; CC::Operand op; CC::Storage act; bool inscale;   // the key conv_choose produces
+    IgemmFn fn; int nt, lds;                                                // what the launch needs
+};
+// The kernel's positional template arguments, written out here and nowhere else.  Waves per tile: 128 x 128 and 128 x 64 2 x 2, 128 x 32 4 x 1, 256 x 128 4 x 2,
+// 256 x 256 2 x 4; two waves per SIMD at least.  PAIR: op names the type of the hi + lo pieces, two LDS planes per operand.
+template <int BM, int BN, bool PAIR, CC::Operand OP, CC::Storage ACT, bool INSCALE>
+IgemmRow igemm_row() {
+    constexpr int WM = BN == 32 || (BM == 256 && BN == 128) ? 4 : 2, WN = BN == 32 ? 1 : BM == 256 && BN == 256 ? 4 : 2;
+    constexpr bool BF16 = OP == CC::OP_BF16 || OP == CC::OP_F16, F16 = OP == CC::OP_F16, BUFA = OP == CC::OP_F32_BUF;
+    constexpr bool ABF = ACT == CC::ACT_BF16, AF16 = ACT == CC::ACT_F16;
+    using C = Cfg<BM, BN, WM, WN, BF16, ABF || AF16, PAIR ? 2 : 1>;
+    return {PAIR, BM, BN, OP, ACT, INSCALE, conv_igemm_kernel<BM, BN, WM, WN, 2, BF16, INSCALE, ABF, F16, BUFA, PAIR, AF16>, C::NT, C::LDS_BYTES};
 }
-template <int BM, int BN, int WAVES_M, int WAVES_N, int MINW, bool INSCALE>
-void init_cfg_pair() {
-    IRSDE_HIP_CHECK(hipFuncSetAttribute(
-        reinterpret_cast<const void*>(conv_igemm_kernel<BM, BN, WAVES_M, WAVES_N, MINW, true, INSCALE, false, true, false, true>),
-        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    IRSDE_HIP_CHECK(hipFuncSetAttribute(
-        reinterpret_cast<const void*>(conv_igemm_kernel<BM, BN, WAVES_M, WAVES_N, MINW, true, INSCALE, false, false, false, true>),
-        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+template <int BM_, int BN_> struct Tile { static constexpr int BM = BM_, BN = BN_; };
+template <bool PAIR, CC::Operand OP, CC::Storage ACT, bool INSCALE, typename... T>
+void add_rows(std::vector<IgemmRow>& v, T...) {
+    (v.push_back(igemm_row<T::BM, T::BN, PAIR, OP, ACT, INSCALE>()), ...);
 }
-
-template <int BM, int BN, int WAVES_M, int WAVES_N, int MINW, bool BF16, bool INSCALE = false, bool ABF = false, bool F16 = false, bool AF16 = false>
-void launch_cfg(const ConvParams& p, int M, int nk_total, hipStream_t s, const ConvTune& t, int lds_override = 0) {
-    using C = Cfg<BM, BN, WAVES_M, WAVES_N, BF16, ABF || AF16>;
-    if constexpr (BF16 && !ABF && !F16) {
-        if (p.f16 && p.in_f16) return launch_cfg<BM, BN, WAVES_M, WAVES_N, MINW, true, INSCALE, false, true, true>(p, M, nk_total, s, t, lds_override);
-        if (p.f16) return launch_cfg<BM, BN, WAVES_M, WAVES_N, MINW, true, INSCALE, false, true>(p, M, nk_total, s, t, lds_override);
-    }
-    auto kern = conv_igemm_kernel<BM, BN, WAVES_M, WAVES_N, MINW, BF16, INSCALE, ABF, F16, false, false, AF16>;
-    if constexpr (!BF16) {  // f32: the buffer-descriptor staging when every operand tensor is below 2 GiB
-        const long long npix = (long long)p.B * p.Hin * p.Win;
-        const long long e0 = ((npix - 1) * p.pix0 + p.C0) * 4, e1 = p.C1 ? ((npix - 1) * p.pix1 + p.C1) * 4 : 0;
-        const long long ew = (long long)p.Cout * p.KH * p.KW * (p.C0 + p.C1) * 4;
-        static const int nobuf = tuning_env_int("IRSDE_NO_BUFA", 0);
-        if (!nobuf && e0 < (1ll << 31) && e1 < (1ll << 31) && ew < (1ll << 31) && !t.no_buffer_desc)
-            kern = conv_igemm_kernel<BM, BN, WAVES_M, WAVES_N, MINW, BF16, INSCALE, ABF, F16, true>;
-    }
-    const int nblk_m = (M + BM - 1) / BM;
-    const int nblk_n = (p.Cout + BN - 1) / BN;
-    dim3 grid(nblk_m * nblk_n, p.splits, p.nz);
-    ConvParams pk = p;
-    static const int no_direct = tuning_env_int("IRSDE_NO_DIRECT_EPI", 0);
-    if (no_direct || t.no_direct_epi) pk.no_direct_epi = 1;
-    hipLaunchKernelGGL(kern, grid, dim3(C::NT), lds_override ? lds_override : C::LDS_BYTES, s, pk, nblk_n, M, nk_total);
-    IRSDE_HIP_CHECK(hipGetLastError());
+const std::vector<IgemmRow>& igemm_table() {
+    static const std::vector<IgemmRow> tab = [] {
+        const Tile<128, 128> t128; const Tile<128, 64> t64; const Tile<128, 32> t32; const Tile<256, 128> t256x128; const Tile<256, 256> t256;
+        std::vector<IgemmRow> v;
+        //       PAIR   operands        storage       INSCALE  (SCA fused into the staging: 128-row tiles only)
+        add_rows<false, CC::OP_F32,     CC::ACT_F32,  false>(v, t128, t64, t32, t256x128, t256);
+        add_rows<false, CC::OP_F32_BUF, CC::ACT_F32,  false>(v, t128, t64, t32, t256x128, t256);
+        add_rows<false, CC::OP_F32,     CC::ACT_F32,  true>(v, t128, t64, t32);
+        add_rows<false, CC::OP_F32_BUF, CC::ACT_F32,  true>(v, t128, t64, t32);
+        add_rows<false, CC::OP_BF16,    CC::ACT_F32,  false>(v, t128, t64, t32, t256);
+        add_rows<false, CC::OP_F16,     CC::ACT_F32,  false>(v, t128, t64, t32, t256);
+        add_rows<false, CC::OP_F16,     CC::ACT_F16,  false>(v, t128, t64, t32, t256);
+        add_rows<false, CC::OP_BF16,    CC::ACT_BF16, false>(v, t128, t64, t32, t256);
+        add_rows<false, CC::OP_BF16,    CC::ACT_F32,  true>(v, t128, t64, t32);
+        add_rows<false, CC::OP_F16,     CC::ACT_F32,  true>(v, t128, t64, t32);
+        add_rows<false, CC::OP_F16,     CC::ACT_F16,  true>(v, t128, t64, t32);
+        add_rows<true,  CC::OP_BF16,    CC::ACT_F32,  false>(v, t256, t256x128, t64);
+        add_rows<true,  CC::OP_F16,     CC::ACT_F32,  false>(v, t256, t256x128, t64);
+        add_rows<true,  CC::OP_BF16,    CC::ACT_F32,  true>(v, t256, t256x128, t64);
+        add_rows<true,  CC::OP_F16,     CC::ACT_F32,  true>(v, t256, t256x128, t64);
+        return v;
+    }();
+    return tab;
 }
 
-template <int BM, int BN, int WAVES_M, int WAVES_N, int MINW, bool BF16, bool INSCALE = false, bool ABF = false>
-void init_cfg() {
-    IRSDE_HIP_CHECK(hipFuncSetAttribute(
-        reinterpret_cast<const void*>(conv_igemm_kernel<BM, BN, WAVES_M, WAVES_N, MINW, BF16, INSCALE, ABF>),
-        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    if constexpr (BF16 && !ABF) {  // the fp16 twin of every bf16-operand kernel, and its fp16-storage twin
-        IRSDE_HIP_CHECK(hipFuncSetAttribute(
-            reinterpret_cast<const void*>(conv_igemm_kernel<BM, BN, WAVES_M, WAVES_N, MINW, true, INSCALE, false, true>),
-            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        IRSDE_HIP_CHECK(hipFuncSetAttribute(
-            reinterpret_cast<const void*>(conv_igemm_kernel<BM, BN, WAVES_M, WAVES_N, MINW, true, INSCALE, false, true, false, false, true>),
-            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    }
-    if constexpr (!BF16)  // the buffer-descriptor twin of every f32 kernel
-        IRSDE_HIP_CHECK(hipFuncSetAttribute(
-            reinterpret_cast<const void*>(conv_igemm_kernel<BM, BN, WAVES_M, WAVES_N, MINW, false, INSCALE, false, false, true>),
-            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+struct ZLoopRow { int BM, BN; void (*fn)(const ZLoopArgs); int nt, lds; };   // the tile-loop kernel: both of its forms run the same three instances
+template <int BM, int BN, int WM, int WN>
+ZLoopRow zloop_row() {
+    using C = Cfg<BM, BN, WM, WN, false>;
+    return {BM, BN, gemm_zloop_kernel<BM, BN, WM, WN, 2>, C::NT, C::MAIN_BYTES};
 }
-
+const std::vector<ZLoopRow>& zloop_table() {   // (64 x 128: 4 waves of 64 x 32, all four SIMDs busy)
+    static const std::vector<ZLoopRow> tab = {zloop_row<128, 128, 2, 2>(), zloop_row<128, 64, 2, 2>(), zloop_row<64, 128, 1, 4>()};
+    return tab;
+}
 
 // 1x1 convolutions with a short K on the tile-loop kernel: row tiles per block, or 0 = generic kernel.
-int zloop_1x1_rows(const ConvParams& p, const ConvTune& t) {
+int zloop_1x1_rows(const ConvParams& p, const ConvTune& t, const ConvKnobs& k) {
     if (p.nz != 1 || p.w_bf || p.KH != 1 || p.KW != 1 || p.stride != 1 || p.pad_y || p.pad_x || p.in_shift || p.film || p.silu ||
         p.res || p.splits != 1 || p.gate || p.shuffle || p.ch_scale || p.in_scale || p.ln_g || p.in_bf16 || p.out_bf16)
         return 0;
-    static const int env = tuning_env_int("IRSDE_ZLOOP_1X1", -1);  // tuning: 0 = off, n = rows tiles
+    const int env = k.zloop_1x1;  // tuning: 0 = off, n = rows tiles
     if (t.zloop == ConvTune::ZLOOP_OFF || env == 0) return 0;
     const int M = p.B * p.Ho * p.Wo, K = p.C0 + p.C1;
     const int mtiles = (M + 127) / 128, ntiles = (p.Cout + 127) / 128, nk = K / 32;
@@ -1292,48 +1280,89 @@ int zloop_1x1_rows(const ConvParams& p, const ConvTune& t) {
 }
 
 // few rows (single image, deep levels): 64 x 128 tiles — a 128-row tile would be half empty or the grid under-filled
-bool zloop_small_m(const ConvParams& p) {
+bool zloop_small_m(const ConvParams& p, const ConvKnobs& k, int cu_count) {
     const long long b128 = (long long)((p.Wo + 127) / 128) * ((p.Cout + 127) / 128) * p.nz;
     if (p.Wo <= 64 || b128 < 512) return true;
     // r05: a ragged last round of 128-row tiles (the small-batch shards: 512 tiles x 512 channels x 36 components = 576 blocks on 512 block slots — one full round
     // and 64 blocks alone) against 64-row tiles (1152 blocks: three rounds of half the work, ~7 % less efficient per tile); only where rounds are few
     // (measured, one box: B = 2 / 4 / 8 x 256^2 3.11 / 3.68 / 4.03 -> 3.16 / 3.77 / 4.07 img/s; the T = 512 layers 98 -> 111 TFLOP/s.)  IRSDE_ZLOOP_RAGGED64 = the block
     // count below which the rule applies (0 = off)
-    static const int cutoff = tuning_env_int("IRSDE_ZLOOP_RAGGED64", 2048);
+    const int cutoff = k.zloop_ragged64;
     if (cutoff <= 0 || b128 >= cutoff) return false;
     const long long b64 = (long long)((p.Wo + 63) / 64) * ((p.Cout + 127) / 128) * p.nz;
-    const long long slots = 2ll * device_cu_count();   // resident block slots: two 256-thread blocks per CU
+    const long long slots = 2ll * cu_count;   // resident block slots: two 256-thread blocks per CU
     const double e128 = (double)b128 / ((double)slots * (double)((b128 + slots - 1) / slots));
     const double e64 = 0.93 * (double)b64 / ((double)slots * (double)((b64 + slots - 1) / slots));
     return e64 > e128;
 }
 
 // components per block for gemm_zloop_kernel, or 0 = use one block per (component, tile)
-int zloop_batch(const ConvParams& p, const ConvTune& t) {
+int zloop_batch(const ConvParams& p, const ConvTune& t, const ConvKnobs& k, int cu_count) {
     if (p.nz <= 1 || p.w_bf || p.KH != 1 || p.KW != 1 || p.C1 || p.bias || p.film || p.silu || p.res || p.splits != 1 ||
         p.gate || p.shuffle || p.ch_scale || p.in_scale || p.stride != 1 || p.out_stride != p.Cout || p.pix0 != p.C0 ||
         p.B != 1 || p.Ho != 1)
         return 0;
-    static const int env_force = tuning_env_int("IRSDE_ZLOOP", -1);  // tuning: 0 = off, n = fixed batch
-    // test hooks: all components in one block, batches of 2 (F2: 16, F4: 36 components), off
-    const int force = t.zloop == ConvTune::ZLOOP_OFF ? 0 : t.zloop == ConvTune::ZLOOP_ALL ? p.nz : t.zloop == ConvTune::ZLOOP_PAIRS ? 2 : env_force;
+    // test hooks: all components in one block, batches of 2 (F2: 16, F4: 36 components), off; IRSDE_ZLOOP: 0 = off, n = fixed batch
+    const int force = t.zloop == ConvTune::ZLOOP_OFF ? 0 : t.zloop == ConvTune::ZLOOP_ALL ? p.nz : t.zloop == ConvTune::ZLOOP_PAIRS ? 2 : k.zloop;
     if (force == 0) return 0;
     const int nk = p.C0 / 32;
     const long long tiles = (long long)((p.Wo + 127) / 128) * ((p.Cout + 127) / 128);
     if (force > 0) return p.nz % force == 0 ? force : 0;
-    if (zloop_small_m(p)) return nk >= 4 ? 1 : 0;  // single-image deep levels: 64-row tiles, one component per block
-    static const int max_nk = tuning_env_int("IRSDE_ZLOOP_MAXNK", 32);
-    static const int min_blocks = tuning_env_int("IRSDE_ZLOOP_MINBLK", 1024);
-    if (nk > max_nk) return 0;  // long K: the per-block overhead is already amortised (measured: 12 / 32 / 48 -> 2.82 / 2.87 / 2.83 img/s)
-    static const int deep_rule = tuning_env_int("IRSDE_ZLOOP_DEEP", 1);
-    if (deep_rule && nk > 16 && (p.Wo + 127) / 128 < 32) return 0;  // few row tiles + long K (32x32 level): generic kernel is ahead
+    if (zloop_small_m(p, k, cu_count)) return nk >= 4 ? 1 : 0;  // single-image deep levels: 64-row tiles, one component per block
+    if (nk > k.zloop_maxnk) return 0;  // long K: the per-block overhead is already amortised (measured: 12 / 32 / 48 -> 2.82 / 2.87 / 2.83 img/s)
+    if (k.zloop_deep && nk > 16 && (p.Wo + 127) / 128 < 32) return 0;  // few row tiles + long K (32x32 level): generic kernel is ahead
     int best = 0;
     for (int zb = p.nz; zb >= 2; --zb) {  // largest batch that still fills the 2 x 256 block slots evenly
         if (p.nz % zb) continue;
         const long long blocks = tiles * (p.nz / zb);
-        if (blocks >= 512 && (blocks % 512 == 0 || blocks >= min_blocks)) { best = zb; break; }
+        if (blocks >= 512 && (blocks % 512 == 0 || blocks >= k.zloop_minblk)) { best = zb; break; }
     }
     return best;
+}
+
+// 256x256 tiles (8 waves, 128x64 per wave) halve the staging instructions per MFMA (+5..8 % on deep layers) but
+// need Cout % 256 == 0 and a tile count that fills the 256 CUs without a ragged last round.
+bool conv_use_tile256(int M, int Cout, int splits) {
+    if (splits != 1 || Cout % 256) return false;
+    const long long nb = (long long)((M + 255) / 256) * (Cout / 256);
+    return nb % 256 == 0 || nb >= 1024;
+}
+
+// r06: an under-filled grid of 16-bit-operand tiles is latency-bound — one block per CU keeps ~24 KB of loads in flight against 2 us of cross-XCD
+// latency (the small-batch NAFNet levels of configs[4]: every 1x1 layer took 17-19 us whatever its size) — narrower column tiles put 2-4 blocks on a CU
+// (the A rows are re-read from L2).  slots_per_cu: block slots per CU the grid should fill, IRSDE_SMALL_BN (2) for the 16-bit operands, IRSDE_SMALL_BN_F32
+// (a measurement knob, default off) for the f32 kernels; 0 = the base rule alone.
+int narrowed_bn(const ConvParams& p, int M, int slots_per_cu, int cu_count) {
+    int bn = conv_base_bn(p.Cout);
+    if (slots_per_cu) {
+        const long long slots = (long long)slots_per_cu * cu_count;
+        auto blocks = [&](int n) { return (long long)((M + 127) / 128) * ((p.Cout + n - 1) / n) * p.splits * p.nz; };
+        while (bn > 32 && blocks(bn) < slots) bn >>= 1;
+    }
+    return bn;
+}
+
+// The implicit-GEMM and PAIR forms: tile in c -> grid, and threads / LDS / row from the instance table (row stays -1 if the table has no such kernel)
+void finish_igemm(ConvChoice& c, const ConvParams& p, int M) {
+    c.gx = (unsigned)(((M + c.BM - 1) / c.BM) * ((p.Cout + c.BN - 1) / c.BN));
+    c.gy = (unsigned)p.splits;
+    c.gz = c.family == CC::PAIR ? 1u : (unsigned)p.nz;
+    const auto& tab = igemm_table();
+    for (size_t i = 0; i < tab.size(); ++i) {
+        const IgemmRow& r = tab[i];
+        if (r.pair == (c.family == CC::PAIR) && r.BM == c.BM && r.BN == c.BN && r.op == c.op && r.act == c.act && r.inscale == c.inscale) {
+            c.row = (int)i; c.threads = r.nt; c.lds = r.lds;
+            return;
+        }
+    }
+}
+
+void finish_zloop(ConvChoice& c, int bias_bytes) {
+    const auto& tab = zloop_table();
+    for (size_t i = 0; i < tab.size(); ++i)
+        if (tab[i].BM == c.BM && tab[i].BN == c.BN) {
+            c.row = (int)(igemm_table().size() + i); c.threads = tab[i].nt; c.lds = tab[i].lds + bias_bytes;
+        }
 }
 
 }  // namespace
@@ -1362,67 +1391,46 @@ void conv_global_init() {
     attention_global_init();
     naf_lnconv_global_init();
     gemm_split_global_init();
-    IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_zloop_kernel<128, 128, 2, 2, 2>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_zloop_kernel<128, 64, 2, 2, 2>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_zloop_kernel<64, 128, 1, 4, 2>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    init_cfg_pair<256, 256, 2, 4, 2, false>();
-    init_cfg_pair<256, 256, 2, 4, 2, true>();
-    init_cfg_pair<256, 128, 4, 2, 2, false>();
-    init_cfg_pair<256, 128, 4, 2, 2, true>();
-    init_cfg_pair<128, 64, 2, 2, 2, false>();
-    init_cfg_pair<128, 64, 2, 2, 2, true>();
-    init_cfg<128, 128, 2, 2, 2, false>();
-    init_cfg<128, 64, 2, 2, 2, false>();
-    init_cfg<128, 32, 4, 1, 2, false>();
-    init_cfg<256, 128, 4, 2, 2, false>();
-    init_cfg<256, 256, 2, 4, 2, false>();
-    init_cfg<128, 128, 2, 2, 2, true>();
-    init_cfg<128, 64, 2, 2, 2, true>();
-    init_cfg<128, 32, 4, 1, 2, true>();
-    init_cfg<256, 256, 2, 4, 2, true>();
-    init_cfg<128, 128, 2, 2, 2, true, false, true>();
-    init_cfg<128, 64, 2, 2, 2, true, false, true>();
-    init_cfg<128, 32, 4, 1, 2, true, false, true>();
-    init_cfg<256, 256, 2, 4, 2, true, false, true>();
-    init_cfg<128, 128, 2, 2, 2, false, true>();
-    init_cfg<128, 64, 2, 2, 2, false, true>();
-    init_cfg<128, 32, 4, 1, 2, false, true>();
-    init_cfg<128, 128, 2, 2, 2, true, true>();
-    init_cfg<128, 64, 2, 2, 2, true, true>();
-    init_cfg<128, 32, 4, 1, 2, true, true>();
+    for (const ZLoopRow& r : zloop_table())
+        IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(r.fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    for (const IgemmRow& r : igemm_table())
+        IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(r.fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
 }
 
 double conv_flops(const ConvParams& p) {
     return 2.0 * (double)p.B * p.Ho * p.Wo * (double)p.Cout * (double)(p.KH * p.KW) * (double)(p.C0 + p.C1);
 }
 
-// 256x256 tiles (8 waves, 128x64 per wave) halve the staging instructions per MFMA (+5..8 % on deep layers) but
-// need Cout % 256 == 0 and a tile count that fills the 256 CUs without a ragged last round.
-bool conv_use_tile256(int M, int Cout, int splits, int nk_total) {
-    if (splits != 1 || Cout % 256) return false;
-    const long long nb = (long long)((M + 255) / 256) * (Cout / 256);
-    return nb % 256 == 0 || nb >= 1024;
+const ConvKnobs& conv_knobs_from_env() {
+    static const ConvKnobs knobs = [] {
+        ConvKnobs k;
+        k.small_bn = tuning_env_int("IRSDE_SMALL_BN", k.small_bn);
+        k.small_bn_f32 = tuning_env_int("IRSDE_SMALL_BN_F32", k.small_bn_f32);
+        k.pair_tile256 = tuning_env_int("IRSDE_PAIR_TILE256", k.pair_tile256);
+        k.pair_inscale256 = tuning_env_int("IRSDE_PAIR_INSCALE256", k.pair_inscale256);
+        k.no_bufa = tuning_env_int("IRSDE_NO_BUFA", k.no_bufa);
+        k.zloop = tuning_env_int("IRSDE_ZLOOP", k.zloop);
+        k.zloop_1x1 = tuning_env_int("IRSDE_ZLOOP_1X1", k.zloop_1x1);
+        k.zloop_maxnk = tuning_env_int("IRSDE_ZLOOP_MAXNK", k.zloop_maxnk);
+        k.zloop_minblk = tuning_env_int("IRSDE_ZLOOP_MINBLK", k.zloop_minblk);
+        k.zloop_deep = tuning_env_int("IRSDE_ZLOOP_DEEP", k.zloop_deep);
+        k.zloop_ragged64 = tuning_env_int("IRSDE_ZLOOP_RAGGED64", k.zloop_ragged64);
+        return k;
+    }();
+    return knobs;
 }
 
-// r06 (measurement knob, default off): the under-filled-grid rule of the 16-bit-operand kernels for the f32 direct kernels — column-tile width 128 / 64 / 32
-static int f32_narrow(const ConvParams& p, int M, const ConvTune& t) {
-    int bn = p.Cout >= 128 ? 128 : p.Cout > 32 ? 64 : 32;
-    static const int k = tuning_env_int("IRSDE_SMALL_BN_F32", 0);
-    if (k && !t.rules_off) {
-        const long long slots = (long long)k * device_cu_count();
-        auto blocks = [&](int n) { return (long long)((M + 127) / 128) * ((p.Cout + n - 1) / n) * p.splits * p.nz; };
-        while (bn > 32 && blocks(bn) < slots) bn >>= 1;
-    }
-    return bn;
+int conv_base_bn(int Cout) { return Cout >= 128 ? 128 : Cout > 32 ? 64 : 32; }
+int conv_instance_count() { return (int)(igemm_table().size() + zloop_table().size()); }
+
+std::string ConvChoice::name() const {
+    const char* const fam[] = {"pair", "narrow3", "zloop", "zloop1x1_", "halo", "igemm"};
+    if (family == NARROW3 || family == HALO) return fam[family];
+    return fam[family] + std::to_string(BM) + "x" + std::to_string(BN);
 }
 
-void launch_conv(const ConvParams& p, hipStream_t s, const ConvTune& t) {
-    const int M = p.B * p.Ho * p.Wo;
-    const int Ctot = p.C0 + p.C1;
-    if (p.C0 % 32 || p.C1 % 32 || Ctot == 0)
+void conv_validate(const ConvParams& p) {
+    if (p.C0 % 32 || p.C1 % 32 || p.C0 + p.C1 == 0)
         throw HipError("launch_conv: channel counts must be multiples of 32 (got " + std::to_string(p.C0) + "+" +
                        std::to_string(p.C1) + ")");
     if (p.splits > 1 && !p.partial) throw HipError("launch_conv: split-K needs a partial buffer");
@@ -1433,165 +1441,139 @@ void launch_conv(const ConvParams& p, hipStream_t s, const ConvTune& t) {
         if (p.w_bf || p.in_bf16 || p.out_bf16 || p.in_f16 || p.out_f16 || p.nz != 1) throw HipError("launch_conv: split-operand pairs go with fp32 storage, one component");
         if (p.in_scale && p.C1) throw HipError("launch_conv: in_scale needs a single source");
         if (p.ln_g) throw HipError("launch_conv: the fused LayerNorm epilogue (BN == Cout) is not available on the PAIR tiles");
-        const int nk = p.KH * p.KW * (Ctot / 32);
-        static const int t256 = tuning_env_int("IRSDE_PAIR_TILE256", 1);
-        // 256 x 256: half the staging work per MFMA (160 KB of LDS: one block per CU) — where it still fills the 256 CUs
-        // (the INSCALE instance of that tile spills since the two-step A staging: SCA-scaled layers take 256 x 128 unless IRSDE_PAIR_INSCALE256=1)
-        static const int inscale256 = tuning_env_int("IRSDE_PAIR_INSCALE256", 0);
-        // (measured and dropped: a 128 x 128 tile at two blocks per CU, so that one block's write-back overlaps the other's K loop — 10-20 %
-        //  SLOWER on every layer class, profiles/r03_pair_conv_sweep.txt: the doubled L2 -> CU operand traffic costs more than the overlap buys)
-        if (t256 && (!p.in_scale || inscale256) && p.Cout % 256 == 0 && (long long)((M + 255) / 256) * (p.Cout / 256) * p.splits >= 256 && t.tile != ConvTune::TILE_128) {
-            if (p.in_scale) launch_cfg_pair<256, 256, 2, 4, 2, true>(p, M, nk, s);
-            else launch_cfg_pair<256, 256, 2, 4, 2, false>(p, M, nk, s);
-        } else if (p.Cout >= 128 && M >= 256) {
-            if (p.in_scale) launch_cfg_pair<256, 128, 4, 2, 2, true>(p, M, nk, s);
-            else launch_cfg_pair<256, 128, 4, 2, 2, false>(p, M, nk, s);
-        } else {
-            if (p.in_scale) launch_cfg_pair<128, 64, 2, 2, 2, true>(p, M, nk, s);
-            else launch_cfg_pair<128, 64, 2, 2, 2, false>(p, M, nk, s);
-        }
-        if (p.splits > 1) {
-            const size_t total = (size_t)M * p.Cout;
-            hipLaunchKernelGGL(conv_splitk_reduce, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, p, M);
-            IRSDE_HIP_CHECK(hipGetLastError());
-        }
         return;
     }
-    if (!p.w_bf && !t.rules_off && p.Cout <= 3 && p.C0 == 64 && p.KH == 3 && p.KW == 3 && p.stride == 1 && p.pad_y == 1 && p.pad_x == 1 &&
-        !p.in_shift && !p.C1 && !p.film && !p.silu && !p.res && p.splits == 1 && p.nz == 1 && !p.gate && !p.shuffle &&
-        !p.ch_scale && !p.in_scale && !p.ln_g && M >= 65536) {  // final_conv: vector-pipe kernel (big feature maps only)
-        hipLaunchKernelGGL(conv3x3_narrow_kernel, dim3((M + 16 * kNarrowPPG - 1) / (16 * kNarrowPPG)), dim3(256), 0, s, p, M);
-        IRSDE_HIP_CHECK(hipGetLastError());
-        return;
-    }
-    if (const int zb = zloop_batch(p, t)) {  // short-K Winograd component GEMMs: component loop inside the block
-        using C = Cfg<128, 128, 2, 2, false>;
-        ZLoopArgs g{};
-        g.a0 = p.in0; g.a1 = nullptr; g.C0 = p.C0; g.C1 = 0; g.lda0 = p.C0; g.lda1 = 0;
-        g.b = p.w; g.out = p.out; g.bias = nullptr;
-        g.M = p.Wo; g.N = p.Cout; g.K = p.C0; g.ldc = p.Cout;
-        g.n_inner = zb; g.n_outer = 1; g.pA = p.z_in; g.pB = p.z_w; g.pO = p.z_out; g.col_step = 0; g.row_step = 0;
-        g.nblk_n = (p.Cout + 127) / 128;
-        if (zloop_small_m(p)) {  // 64 x 128 tiles, 4 waves of 64 x 32 (all four SIMDs busy)
-            using C64 = Cfg<64, 128, 1, 4, false>;
-            dim3 grid64(((p.Wo + 63) / 64) * g.nblk_n, p.nz / zb);
-            hipLaunchKernelGGL((gemm_zloop_kernel<64, 128, 1, 4, 2>), grid64, dim3(C64::NT), C64::MAIN_BYTES, s, g);
-            IRSDE_HIP_CHECK(hipGetLastError());
-            return;
-        }
-        if (p.Cout <= 64) {  // 128 x 64 tiles: a 128-wide tile would be half padding (the 64-channel full-resolution layers)
-            using C64n = Cfg<128, 64, 2, 2, false>;
-            g.nblk_n = 1;
-            dim3 grid_n((p.Wo + 127) / 128, p.nz / zb);
-            hipLaunchKernelGGL((gemm_zloop_kernel<128, 64, 2, 2, 2>), grid_n, dim3(C64n::NT), C64n::MAIN_BYTES, s, g);
-            IRSDE_HIP_CHECK(hipGetLastError());
-            return;
-        }
-        dim3 grid(((p.Wo + 127) / 128) * g.nblk_n, p.nz / zb);
-        hipLaunchKernelGGL((gemm_zloop_kernel<128, 128, 2, 2, 2>), grid, dim3(C::NT), C::MAIN_BYTES, s, g);
-        IRSDE_HIP_CHECK(hipGetLastError());
-        return;
-    }
-    if (const int mb = zloop_1x1_rows(p, t)) {  // short-K 1x1 convolutions: (row tiles x all column tiles) loop inside the block
-        using C = Cfg<128, 128, 2, 2, false>;
-        const int M = p.B * p.Ho * p.Wo;
-        ZLoopArgs g{};
-        g.a0 = p.in0; g.a1 = p.C1 ? p.in1 : nullptr; g.C0 = p.C0; g.C1 = p.C1; g.lda0 = p.pix0; g.lda1 = p.pix1;
-        g.b = p.w; g.out = p.out; g.bias = p.bias;
-        g.M = M; g.N = p.Cout; g.K = p.C0 + p.C1; g.ldc = p.out_stride;
-        g.n_inner = (p.Cout + 127) / 128; g.n_outer = mb; g.pA = g.pB = g.pO = 0; g.col_step = 128; g.row_step = 128;
-        g.nblk_n = 1;
-        const int mtiles = (M + 127) / 128;
-        dim3 grid((mtiles + mb - 1) / mb, 1);
-        if (p.Cout <= 64) {  // one 64-wide column tile
-            using C64n = Cfg<128, 64, 2, 2, false>;
-            g.col_step = 64;
-            hipLaunchKernelGGL((gemm_zloop_kernel<128, 64, 2, 2, 2>), grid, dim3(C64n::NT),
-                               C64n::MAIN_BYTES + (p.bias ? 64 * 4 : 0), s, g);
-            IRSDE_HIP_CHECK(hipGetLastError());
-            return;
-        }
-        const int lds = C::MAIN_BYTES + (p.bias ? g.n_inner * 128 * 4 : 0);  // + the block's bias columns
-        hipLaunchKernelGGL((gemm_zloop_kernel<128, 128, 2, 2, 2>), grid, dim3(C::NT), lds, s, g);
-        IRSDE_HIP_CHECK(hipGetLastError());
-        return;
-    }
-    const int nk_total = p.KH * p.KW * (Ctot / 32);
     if ((p.in_bf16 || p.out_bf16) && !p.w_bf) throw HipError("launch_conv: bf16 activation storage needs the bf16-MFMA mode");
     if (p.f16 && (!p.w_bf || p.in_bf16 || p.out_bf16)) throw HipError("launch_conv: fp16 operands go with fp32 activation storage");
     if ((p.in_f16 || p.out_f16) && (!p.w_bf || !p.f16 || p.in_bf16 || p.out_bf16 || p.ln_g || p.nz != 1))
         throw HipError("launch_conv: fp16 activation storage needs the fp16-MFMA mode (one component, no fused LayerNorm)");
     if (p.in_bf16 && (p.in_scale || p.gate || p.shuffle)) throw HipError("launch_conv: NAFNet fusions are fp32- or fp16-storage only");
-    if (p.in_scale) {  // NAFNet SCA fused into the staging (128-row tiles only)
-        if (p.C1) throw HipError("launch_conv: in_scale needs a single source");
-        if (p.w_bf) {
-            int bn = p.Cout >= 128 ? 128 : p.Cout > 32 ? 64 : 32;
-            static const int small_bn = tuning_env_int("IRSDE_SMALL_BN", 2);   // block slots per CU the grid should fill (0 = rule off)
-            if (small_bn && !t.rules_off) {   // (see the rule at the plain 16-bit-operand branch below)
-                const long long slots = (long long)small_bn * device_cu_count();
-                auto blocks = [&](int n) { return (long long)((M + 127) / 128) * ((p.Cout + n - 1) / n) * p.splits * p.nz; };
-                while (bn > 32 && blocks(bn) < slots) bn >>= 1;
-            }
-            if (bn == 128) launch_cfg<128, 128, 2, 2, 2, true, true>(p, M, nk_total, s, t);
-            else if (bn == 64) launch_cfg<128, 64, 2, 2, 2, true, true>(p, M, nk_total, s, t);
-            else launch_cfg<128, 32, 4, 1, 2, true, true>(p, M, nk_total, s, t);
-        } else {
-            if (p.Cout >= 128) launch_cfg<128, 128, 2, 2, 2, false, true>(p, M, nk_total, s, t);
-            else if (p.Cout > 32) launch_cfg<128, 64, 2, 2, 2, false, true>(p, M, nk_total, s, t);
-            else launch_cfg<128, 32, 4, 1, 2, false, true>(p, M, nk_total, s, t);
-        }
-    } else if (p.w_bf && t.halo != ConvTune::HALO_OFF && conv_halo_eligible(p)) {
-        launch_conv_halo(p, s, t.halo == ConvTune::HALO_FORCE_512 ? 1 : t.halo == ConvTune::HALO_FORCE_256 ? -1 : 0);  // 3x3 s1 p1: LDS-resident halo tile (conv_halo.hip)
-        return;
-    } else if (p.w_bf && p.in_bf16) {  // bf16 operands AND bf16 activation storage
-        if (p.Cout >= 128) {
-            if (t.tile != ConvTune::TILE_128 && (t.tile == ConvTune::TILE_256 || conv_use_tile256(M, p.Cout, p.splits, nk_total)))
-                launch_cfg<256, 256, 2, 4, 2, true, false, true>(p, M, nk_total, s, t);
-            else
-                launch_cfg<128, 128, 2, 2, 2, true, false, true>(p, M, nk_total, s, t);
-        } else if (p.Cout > 32) {
-            launch_cfg<128, 64, 2, 2, 2, true, false, true>(p, M, nk_total, s, t);
-        } else {
-            launch_cfg<128, 32, 4, 1, 2, true, false, true>(p, M, nk_total, s, t);
-        }
-    } else if (p.w_bf) {  // bf16 operands, fp32 accumulation
-        // r06: an under-filled grid of 16-bit-operand tiles is latency-bound — one block per CU keeps ~24 KB of loads in flight against 2 us of cross-XCD
-        // latency (the small-batch NAFNet levels of configs[4]: every 1x1 layer took 17-19 us whatever its size) — narrower column tiles put 2-4 blocks on a CU
-        // (the A rows are re-read from L2).  IRSDE_SMALL_BN = block slots per CU to fill (0 switches the rule off).
-        int bn = p.Cout >= 128 ? 128 : p.Cout > 32 ? 64 : 32;
-        static const int small_bn = tuning_env_int("IRSDE_SMALL_BN", 2);   // block slots per CU the grid should fill (0 = rule off)
-        if (small_bn && !t.rules_off) {
-            const long long slots = (long long)small_bn * device_cu_count();
-            auto blocks = [&](int n) { return (long long)((M + 127) / 128) * ((p.Cout + n - 1) / n) * p.splits * p.nz; };
-            while (bn > 32 && blocks(bn) < slots) bn >>= 1;
-        }
-        if (bn == 128) {
-            if (t.tile != ConvTune::TILE_128 && (t.tile == ConvTune::TILE_256 || conv_use_tile256(M, p.Cout, p.splits, nk_total)))
-                launch_cfg<256, 256, 2, 4, 2, true>(p, M, nk_total, s, t);
-            else
-                launch_cfg<128, 128, 2, 2, 2, true>(p, M, nk_total, s, t);
-        } else if (bn == 64) {
-            launch_cfg<128, 64, 2, 2, 2, true>(p, M, nk_total, s, t);
-        } else {
-            launch_cfg<128, 32, 4, 1, 2, true>(p, M, nk_total, s, t);
-        }
-    } else if (p.Cout >= 128 && f32_narrow(p, M, t) == 128) {
-        if (t.tile == ConvTune::TILE_256x128)
-            launch_cfg<256, 128, 4, 2, 2, false>(p, M, nk_total, s, t);
-        else if (t.tile == ConvTune::TILE_256)
-            launch_cfg<256, 256, 2, 4, 2, false>(p, M, nk_total, s, t);
-        else if (t.tile == ConvTune::TILE_128_ONE_PER_CU)
-            launch_cfg<128, 128, 2, 2, 2, false>(p, M, nk_total, s, t, 120 * 1024);  // diagnostic: force 1 block/CU
-        else if (!t.rules_off && conv_use_tile256(M, p.Cout, p.splits, nk_total))
-            launch_cfg<256, 256, 2, 4, 2, false>(p, M, nk_total, s, t);
+    if (p.in_scale && p.C1) throw HipError("launch_conv: in_scale needs a single source");
+}
+
+// The branch order is part of the behaviour: PAIR, the 3-channel vector-pipe kernel, the tile-loop kernel's two forms, then the halo kernel and the implicit GEMM.
+ConvChoice conv_choose(const ConvParams& p, const ConvTune& t, const ConvKnobs& k, int cu_count) {
+    ConvChoice c;
+    const int M = p.B * p.Ho * p.Wo;
+    if (p.w_pair) {   // (rules_off does not reach the PAIR tiles)
+        c.family = CC::PAIR;
+        c.op = p.f16 ? CC::OP_F16 : CC::OP_BF16;
+        c.inscale = p.in_scale != nullptr;
+        // 256 x 256: half the staging work per MFMA (160 KB of LDS: one block per CU) — where it still fills the 256 CUs
+        // (the INSCALE instance of that tile spills since the two-step A staging: SCA-scaled layers take 256 x 128 unless IRSDE_PAIR_INSCALE256=1)
+        // (measured and dropped: a 128 x 128 tile at two blocks per CU, so that one block's write-back overlaps the other's K loop — 10-20 %
+        //  SLOWER on every layer class, profiles/r03_pair_conv_sweep.txt: the doubled L2 -> CU operand traffic costs more than the overlap buys)
+        if (k.pair_tile256 && (!p.in_scale || k.pair_inscale256) && p.Cout % 256 == 0 && (long long)((M + 255) / 256) * (p.Cout / 256) * p.splits >= 256 &&
+            t.tile != ConvTune::TILE_128)
+            c.BM = 256, c.BN = 256;
+        else if (p.Cout >= 128 && M >= 256)
+            c.BM = 256, c.BN = 128;
         else
-            launch_cfg<128, 128, 2, 2, 2, false>(p, M, nk_total, s, t);
-    } else if (p.Cout > 32 && f32_narrow(p, M, t) >= 64) {
-        launch_cfg<128, 64, 2, 2, 2, false>(p, M, nk_total, s, t);
-    } else {
-        launch_cfg<128, 32, 4, 1, 2, false>(p, M, nk_total, s, t);
+            c.BM = 128, c.BN = 64;
+        finish_igemm(c, p, M);
+        return c;
     }
-    if (p.splits > 1) {
+    if (!p.w_bf && !t.rules_off && p.Cout <= 3 && p.C0 == 64 && p.KH == 3 && p.KW == 3 && p.stride == 1 && p.pad_y == 1 && p.pad_x == 1 &&
+        !p.in_shift && !p.C1 && !p.film && !p.silu && !p.res && p.splits == 1 && p.nz == 1 && !p.gate && !p.shuffle &&
+        !p.ch_scale && !p.in_scale && !p.ln_g && M >= 65536) {  // final_conv: vector-pipe kernel (big feature maps only)
+        c.family = CC::NARROW3;
+        c.gx = (unsigned)((M + 16 * kNarrowPPG - 1) / (16 * kNarrowPPG));
+        c.threads = 256;
+        return c;
+    }
+    if (const int zb = zloop_batch(p, t, k, cu_count)) {  // short-K Winograd component GEMMs: component loop inside the block
+        c.family = CC::ZLOOP_BATCH;
+        c.zbatch = zb;
+        if (zloop_small_m(p, k, cu_count)) c.BM = 64, c.BN = 128;
+        else if (p.Cout <= 64) c.BM = 128, c.BN = 64;  // a 128-wide tile would be half padding (the 64-channel full-resolution layers)
+        else c.BM = 128, c.BN = 128;
+        c.gx = (unsigned)(((p.Wo + c.BM - 1) / c.BM) * ((p.Cout + 127) / 128));
+        c.gy = (unsigned)(p.nz / zb);
+        finish_zloop(c, 0);
+        return c;
+    }
+    if (const int mb = zloop_1x1_rows(p, t, k)) {  // short-K 1x1 convolutions: (row tiles x all column tiles) loop inside the block
+        c.family = CC::ZLOOP_1X1;
+        c.zrows = mb;
+        c.BM = 128, c.BN = p.Cout <= 64 ? 64 : 128;  // (one 64-wide column tile)
+        c.gx = (unsigned)(((M + 127) / 128 + mb - 1) / mb);
+        finish_zloop(c, p.bias ? (p.Cout + 127) / 128 * c.BN * 4 : 0);  // + the block's bias columns
+        return c;
+    }
+    if (p.w_bf && !p.in_scale && t.halo != ConvTune::HALO_OFF && conv_halo_eligible(p)) {  // 3x3 s1 p1: LDS-resident halo tile (conv_halo.hip)
+        c.family = CC::HALO;
+        c.op = p.f16 ? CC::OP_F16 : CC::OP_BF16;
+        c.act = p.in_bf16 ? CC::ACT_BF16 : CC::ACT_F32;
+        return c;
+    }
+    c.family = CC::IGEMM;
+    c.inscale = p.in_scale != nullptr;  // NAFNet SCA fused into the staging (128-row tiles only: no 256 tile)
+    c.BM = 128;
+    if (p.w_bf) {
+        c.op = p.f16 ? CC::OP_F16 : CC::OP_BF16;
+        c.act = p.in_bf16 && !p.in_scale ? CC::ACT_BF16 : p.f16 && p.in_f16 ? CC::ACT_F16 : CC::ACT_F32;
+        // bf16 tensors keep the base rule; the 16-bit paths take the automatic 256 tile with rules_off too, and a forced one without the Cout % 256 test
+        c.BN = narrowed_bn(p, M, c.act == CC::ACT_BF16 || t.rules_off ? 0 : k.small_bn, cu_count);
+        if (c.BN == 128 && !p.in_scale && t.tile != ConvTune::TILE_128 && (t.tile == ConvTune::TILE_256 || conv_use_tile256(M, p.Cout, p.splits)))
+            c.BM = c.BN = 256;
+    } else {
+        // the buffer-descriptor staging when every operand tensor is below 2 GiB
+        const long long npix = (long long)p.B * p.Hin * p.Win;
+        const long long e0 = ((npix - 1) * p.pix0 + p.C0) * 4, e1 = p.C1 ? ((npix - 1) * p.pix1 + p.C1) * 4 : 0;
+        const long long ew = (long long)p.Cout * p.KH * p.KW * (p.C0 + p.C1) * 4;
+        c.op = !k.no_bufa && e0 < (1ll << 31) && e1 < (1ll << 31) && ew < (1ll << 31) && !t.no_buffer_desc ? CC::OP_F32_BUF : CC::OP_F32;
+        c.BN = narrowed_bn(p, M, p.in_scale || t.rules_off ? 0 : k.small_bn_f32, cu_count);
+        if (c.BN == 128 && !p.in_scale) {
+            if (t.tile == ConvTune::TILE_256x128) c.BM = 256;
+            else if (t.tile == ConvTune::TILE_256 || (t.tile != ConvTune::TILE_128_ONE_PER_CU && !t.rules_off && conv_use_tile256(M, p.Cout, p.splits))) c.BM = c.BN = 256;
+        }
+    }
+    finish_igemm(c, p, M);
+    if (!p.w_bf && !p.in_scale && c.BM == 128 && c.BN == 128 && t.tile == ConvTune::TILE_128_ONE_PER_CU) c.lds = 120 * 1024;  // diagnostic: force 1 block/CU
+    return c;
+}
+
+void launch_conv(const ConvParams& p, hipStream_t s, const ConvTune& t) {
+    conv_validate(p);
+    const ConvChoice c = conv_choose(p, t, conv_knobs_from_env(), device_cu_count());
+    const int M = p.B * p.Ho * p.Wo;
+    const dim3 grid(c.gx, c.gy, c.gz);
+    const int nrows = (int)igemm_table().size();
+    if (c.family != CC::NARROW3 && c.family != CC::HALO && c.row < 0) throw HipError("launch_conv: no kernel instance " + c.name());
+    switch (c.family) {
+    case CC::HALO:
+        launch_conv_halo(p, s, t.halo == ConvTune::HALO_FORCE_512 ? 1 : t.halo == ConvTune::HALO_FORCE_256 ? -1 : 0);
+        return;
+    case CC::NARROW3:
+        hipLaunchKernelGGL(conv3x3_narrow_kernel, grid, dim3(c.threads), 0, s, p, M);
+        break;
+    case CC::ZLOOP_BATCH:
+    case CC::ZLOOP_1X1: {
+        const bool batch = c.family == CC::ZLOOP_BATCH;   // the component loop reads one dense source and writes dense rows (zloop_batch checks)
+        ZLoopArgs g{};
+        g.a0 = p.in0; g.a1 = !batch && p.C1 ? p.in1 : nullptr; g.C0 = p.C0; g.C1 = batch ? 0 : p.C1; g.lda0 = batch ? p.C0 : p.pix0; g.lda1 = batch ? 0 : p.pix1;
+        g.b = p.w; g.out = p.out; g.bias = batch ? nullptr : p.bias;
+        g.M = batch ? p.Wo : M; g.N = p.Cout; g.K = g.C0 + g.C1; g.ldc = batch ? p.Cout : p.out_stride;
+        g.n_inner = batch ? c.zbatch : (p.Cout + 127) / 128; g.n_outer = batch ? 1 : c.zrows;
+        if (batch) { g.pA = p.z_in; g.pB = p.z_w; g.pO = p.z_out; }
+        g.col_step = batch ? 0 : c.BN; g.row_step = batch ? 0 : 128;
+        g.nblk_n = batch ? (p.Cout + 127) / 128 : 1;
+        hipLaunchKernelGGL(zloop_table()[c.row - nrows].fn, grid, dim3(c.threads), c.lds, s, g);
+        break;
+    }
+    case CC::PAIR:
+        hipLaunchKernelGGL(igemm_table()[c.row].fn, grid, dim3(c.threads), c.lds, s, p, (p.Cout + c.BN - 1) / c.BN, M, p.KH * p.KW * ((p.C0 + p.C1) / 32));
+        break;
+    case CC::IGEMM: {
+        ConvParams pk = p;
+        static const int no_direct = tuning_env_int("IRSDE_NO_DIRECT_EPI", 0);
+        if (no_direct || t.no_direct_epi) pk.no_direct_epi = 1;
+        hipLaunchKernelGGL(igemm_table()[c.row].fn, grid, dim3(c.threads), c.lds, s, pk, (p.Cout + c.BN - 1) / c.BN, M, p.KH * p.KW * ((p.C0 + p.C1) / 32));
+        break;
+    }
+    }
+    IRSDE_HIP_CHECK(hipGetLastError());
+    if (p.splits > 1 && (c.family == CC::PAIR || c.family == CC::IGEMM)) {
         const size_t total = (size_t)M * p.Cout;
         hipLaunchKernelGGL(conv_splitk_reduce, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, p, M);
         IRSDE_HIP_CHECK(hipGetLastError());

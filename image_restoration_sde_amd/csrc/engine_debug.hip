@@ -764,6 +764,44 @@ int irsde_debug_conv(const float* in0, int C0, const float* in1, int C1, int B, 
     });
 }
 
+int irsde_debug_conv_choice(int B, int Hin, int Win, int C0, int C1, int Cout, int K, int stride, int pad, int in_shift, int operand, int storage, int pair,
+                            unsigned features, int splits, int nz, int tune, int cu_count, const int* knobs, char* out, int out_len) {
+    return guard([&] {
+        if (!out || out_len < 1 || K < 1 || stride < 1 || cu_count < 1 || operand < 0 || operand > 2 || storage < 0 || storage > 2 || (pair && operand == 0))
+            throw HipError("debug_conv_choice: bad argument");
+        static const float dummy[4] = {};   // stands for every tensor: the choice reads which pointers are set, never what they point at
+        float* const some = const_cast<float*>(dummy);
+        auto bit = [&](int i) { return (features >> i & 1u) ? some : nullptr; };
+        ConvParams p;
+        p.in0 = some; p.C0 = C0; p.pix0 = C0; p.in1 = C1 ? some : nullptr; p.C1 = C1; p.pix1 = C1;
+        p.Hin = Hin; p.Win = Win; p.in_shift = in_shift;
+        p.w = some; p.Cout = Cout; p.KH = K; p.KW = K; p.stride = stride; p.pad_y = pad; p.pad_x = pad;
+        p.B = B;
+        p.Ho = ((Hin << in_shift) + 2 * pad - K) / stride + 1;
+        p.Wo = ((Win << in_shift) + 2 * pad - K) / stride + 1;
+        p.out = some; p.out_stride = Cout; p.res_stride = Cout; p.zeros = some;
+        p.bias = bit(0); p.film = bit(1); p.silu = bit(2) != nullptr; p.res = bit(3); p.in_scale = bit(4); p.ch_scale = bit(5);
+        p.gate = bit(6) != nullptr; p.shuffle = bit(7) != nullptr; p.ln_g = bit(8);
+        if (pair) p.w_pair = reinterpret_cast<const unsigned short*>(some);
+        else if (operand) p.w_bf = reinterpret_cast<const unsigned short*>(some);
+        p.f16 = operand == 2;
+        p.in_bf16 = p.out_bf16 = storage == 1;
+        p.in_f16 = p.out_f16 = storage == 2;
+        p.nz = nz;
+        if (splits > 1) { p.splits = splits; p.partial = some; }
+        ConvKnobs k;
+        static_assert(sizeof(ConvKnobs) == 11 * sizeof(int), "the hook's knob array is ConvKnobs, field by field");
+        if (knobs) memcpy(&k, knobs, sizeof k);
+        conv_validate(p);
+        const ConvChoice c = conv_choose(p, conv_tune_from_code(tune), k, cu_count);
+        const bool tabled = c.family != ConvChoice::NARROW3 && c.family != ConvChoice::HALO;
+        if (tabled && c.row < 0) throw HipError("launch_conv: no kernel instance " + c.name());
+        snprintf(out, (size_t)out_len, "name=%s family=%d tile=%dx%d op=%d act=%d inscale=%d zbatch=%d zrows=%d grid=%ux%ux%u threads=%d lds=%d row=%d of %d",
+                 c.name().c_str(), (int)c.family, c.BM, c.BN, (int)c.op, (int)c.act, (int)c.inscale, c.zbatch, c.zrows, c.gx, c.gy, c.gz, c.threads, c.lds, c.row,
+                 conv_instance_count());
+    });
+}
+
 int irsde_debug_split_gemm(const float* A, const float* Bm, float* C, int M, int N, int K, int ncomp, int nplanes, void* stream) {
     return guard([&] {
         // 42 / 44: the engine's pair-interleaved two-plane kernel on bf16 / fp16 pieces

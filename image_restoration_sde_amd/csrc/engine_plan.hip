@@ -47,7 +47,7 @@ struct Builder {
     void push_conv(ConvParams p) {
         const int M = p.B * p.Ho * p.Wo;
         // split-K for under-filled grids (small batch / deep levels)
-        const int bn = p.Cout >= 128 ? 128 : (p.Cout > 32 ? 64 : 32);
+        const int bn = conv_base_bn(p.Cout);
         const int blocks = ((M + 127) / 128) * ((p.Cout + bn - 1) / bn);
         const int nk = p.KH * p.KW * ((p.C0 + p.C1) / 32);
         int splits = 1;
@@ -80,12 +80,19 @@ struct Builder {
                    (p.w_bf ? 2.0 : 4.0) * (double)p.Cout * p.KH * p.KW * (p.C0 + p.C1);
         op.exec_flops = op.flops;
         {
+            // which kernel the layer runs on and the grid it launches (launch_conv's own choice, conv_igemm.hip) — the plan tests pin the benchmarked plan's
+            // kernel mix with it.  The halo path chooses between its two kernels itself (conv_halo.hip): named here, blocks= stays the 128-row tile count
+            long long launched = blocks;
+            std::string kernel;
+            if (!naive) {
+                const ConvChoice c = conv_choose(p, ConvTune{}, conv_knobs_from_env(), device_cu_count());
+                if (c.family == ConvChoice::HALO) kernel = conv_halo2_wanted(p, 0) ? " kernel=halo512" : " kernel=halo256";
+                else launched = c.blocks(), kernel = " kernel=" + c.name();
+            }
             char buf[256];
-            snprintf(buf, sizeof buf, "conv%s M=%d Cout=%d Cin=%d k=%dx%d s=%d up=%d splits=%d blocks=%d flops=%.4g",
-                     p.w_pair ? (p.f16 ? "(split f16x2)" : "(split bf16x2)") : p.w_bf ? (p.f16 ? (p.in_f16 || p.out_f16 ? "(fp16 operands + storage)" : "(fp16)") : "(bf16)") : "", M, p.Cout, p.C0 + p.C1, p.KH, p.KW, p.stride, p.in_shift, splits, blocks, op.flops);
-            op.desc = buf;
-            // r06: which 3x3 kernel a 16-bit layer runs on (launch_conv's own choice, conv_igemm.hip) — the plan tests pin the benchmarked plan's kernel mix with it
-            if (!naive && p.w_bf && conv_halo_eligible(p)) op.desc += conv_halo2_wanted(p, 0) ? " kernel=halo512" : " kernel=halo256";
+            snprintf(buf, sizeof buf, "conv%s M=%d Cout=%d Cin=%d k=%dx%d s=%d up=%d splits=%d blocks=%lld flops=%.4g",
+                     p.w_pair ? (p.f16 ? "(split f16x2)" : "(split bf16x2)") : p.w_bf ? (p.f16 ? (p.in_f16 || p.out_f16 ? "(fp16 operands + storage)" : "(fp16)") : "(bf16)") : "", M, p.Cout, p.C0 + p.C1, p.KH, p.KW, p.stride, p.in_shift, splits, launched, op.flops);
+            op.desc = buf + kernel;
         }
         const bool nv = naive;
         op.fn = [p, nv](hipStream_t s) {

@@ -49,6 +49,20 @@ int irsde_debug_conv(const float* in0, int C0, const float* in1, int C1, int B, 
                      const float* film, int film_bstride, int silu, const float* res, float* out, int naive,
                      int splits, void* stream);
 
+/* Host-only test hook: which kernel launch_conv (csrc/conv_igemm.hip: conv_validate, conv_choose) would run for one layer.  Never touches a device.
+ * Geometry as for irsde_debug_conv (K x K taps; pixel strides = channel counts, out_stride = Cout).  operand: 0 f32, 1 bf16, 2 fp16 (pair != 0: the pieces'
+ * type, 1 or 2).  storage: 0 f32, 1 bf16, 2 fp16 tensors on both sides.  features: bit 0 bias, 1 film, 2 silu, 3 res, 4 in_scale, 5 ch_scale, 6 gate,
+ * 7 shuffle, 8 ln_g.  splits > 1: split-K with a partial buffer.  nz: components of a batched launch.  tune: a tuning code of irsde_bench_conv (0 production
+ * dispatch, 3 5 6 7 50 60 61 64 65 70 - 73).  cu_count: compute units of the device to choose for.  knobs: NULL = the default tuning knobs, else 11 ints in
+ * the order IRSDE_SMALL_BN, _SMALL_BN_F32, _PAIR_TILE256, _PAIR_INSCALE256, _NO_BUFA, _ZLOOP, _ZLOOP_1X1, _ZLOOP_MAXNK, _ZLOOP_MINBLK, _ZLOOP_DEEP,
+ * _ZLOOP_RAGGED64 (the environment is never read).  Writes one line into out:
+ *   name=<kernel> family=<n> tile=<BM>x<BN> op=<n> act=<n> inscale=<0|1> zbatch=<n> zrows=<n> grid=<x>x<y>x<z> threads=<n> lds=<bytes> row=<instance> of <rows>
+ * (family: 0 pair, 1 narrow3, 2 zloop batch, 3 zloop 1x1, 4 halo, 5 igemm; op: 0 f32, 1 f32 with buffer descriptors, 2 bf16, 3 fp16; act as storage; row -1:
+ * the family has no instance table; the halo path chooses its kernel and grid in csrc/conv_halo.hip: grid 0x1x1).  A layer launch_conv refuses, or a choice
+ * without a kernel instance, fails with launch_conv's message. */
+int irsde_debug_conv_choice(int B, int Hin, int Win, int C0, int C1, int Cout, int K, int stride, int pad, int in_shift, int operand, int storage, int pair,
+                            unsigned features, int splits, int nz, int tune, int cu_count, const int* knobs, char* out, int out_len);
+
 /* Kernel-level test hook of csrc/gemm_split.hip: C_z[M][N] = A_z[M][K] . B_z[N][K]^T for z < ncomp (device f32 tensors, z-major),
  * operands split into 16-bit pieces on the device (nplanes = 42 / 44: the engine's
  * pair-interleaved two-piece kernel with bf16 / fp16 pieces; nplanes = 43: the exact-fp32 engine's three-piece kernel gemm_split3i_kernel, six products, on
