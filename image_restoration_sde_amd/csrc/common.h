@@ -280,7 +280,8 @@ int conv_base_bn(int Cout);   // column-tile width before any narrowing: 128 / 6
 void conv_validate(const ConvParams& p);
 ConvChoice conv_choose(const ConvParams& p, const ConvTune& t, const ConvKnobs& k, int cu_count);
 int conv_instance_count();    // rows of the instance tables
-void launch_conv(const ConvParams& p, hipStream_t s, const ConvTune& t = {});
+// knobs: the tuning knobs of this one call (null: conv_knobs_from_env(), what every production caller runs on); chosen: receives the choice the launch made
+void launch_conv(const ConvParams& p, hipStream_t s, const ConvTune& t = {}, const ConvKnobs* knobs = nullptr, ConvChoice* chosen = nullptr);
 void conv_global_init();
 // bf16 mode: 3x3 s1 p1 layers with an LDS-resident halo tile (conv_halo.hip)
 void conv_halo_global_init();
@@ -300,6 +301,7 @@ __device__ __forceinline__ float silu_hw(const float v) {
 void launch_f32_to_bf16(const float* in, unsigned short* out, size_t n, hipStream_t s);  // round-to-nearest-even
 void launch_f32_to_f16(const float* in, unsigned short* out, size_t n, hipStream_t s);   // IEEE binary16, round-to-nearest-even
 void launch_bf16_to_f32(const unsigned short* in, float* out, size_t n, hipStream_t s);
+void launch_f16_to_f32(const unsigned short* in, float* out, size_t n, hipStream_t s);
 // naive direct convolution on VALU (one thread per output) — debug / cross-check path only
 void launch_conv_naive(const ConvParams& p, hipStream_t s);
 

@@ -1434,6 +1434,7 @@ void conv_validate(const ConvParams& p) {
         throw HipError("launch_conv: channel counts must be multiples of 32 (got " + std::to_string(p.C0) + "+" +
                        std::to_string(p.C1) + ")");
     if (p.splits > 1 && !p.partial) throw HipError("launch_conv: split-K needs a partial buffer");
+    if (p.splits > 1 && (p.gate || p.shuffle)) throw HipError("launch_conv: split-K has no gate or pixel-shuffle epilogue (conv_splitk_reduce writes plain rows)");
     if (p.ln_g && (p.splits != 1 || (p.Cout != 64 && p.Cout != 128) || p.nz != 1 || (p.out_stride & 3) || (p.res && (p.res_stride & 3))))
         throw HipError("launch_conv: fused LayerNorm needs Cout == 64 or 128 in one tile, no split-K");
     if (!p.zeros) throw HipError("launch_conv: ConvParams::zeros (zero page for out-of-image taps) is not set");
@@ -1513,7 +1514,8 @@ ConvChoice conv_choose(const ConvParams& p, const ConvTune& t, const ConvKnobs& 
         c.op = p.f16 ? CC::OP_F16 : CC::OP_BF16;
         c.act = p.in_bf16 && !p.in_scale ? CC::ACT_BF16 : p.f16 && p.in_f16 ? CC::ACT_F16 : CC::ACT_F32;
         // bf16 tensors keep the base rule; the 16-bit paths take the automatic 256 tile with rules_off too, and a forced one without the Cout % 256 test
-        c.BN = narrowed_bn(p, M, c.act == CC::ACT_BF16 || t.rules_off ? 0 : k.small_bn, cu_count);
+        // (a fused LayerNorm normalises over the tile's BN columns: its layer keeps the base tile, BN == Cout)
+        c.BN = narrowed_bn(p, M, c.act == CC::ACT_BF16 || t.rules_off || p.ln_g ? 0 : k.small_bn, cu_count);
         if (c.BN == 128 && !p.in_scale && t.tile != ConvTune::TILE_128 && (t.tile == ConvTune::TILE_256 || conv_use_tile256(M, p.Cout, p.splits)))
             c.BM = c.BN = 256;
     } else {
@@ -1522,7 +1524,7 @@ ConvChoice conv_choose(const ConvParams& p, const ConvTune& t, const ConvKnobs& 
         const long long e0 = ((npix - 1) * p.pix0 + p.C0) * 4, e1 = p.C1 ? ((npix - 1) * p.pix1 + p.C1) * 4 : 0;
         const long long ew = (long long)p.Cout * p.KH * p.KW * (p.C0 + p.C1) * 4;
         c.op = !k.no_bufa && e0 < (1ll << 31) && e1 < (1ll << 31) && ew < (1ll << 31) && !t.no_buffer_desc ? CC::OP_F32_BUF : CC::OP_F32;
-        c.BN = narrowed_bn(p, M, p.in_scale || t.rules_off ? 0 : k.small_bn_f32, cu_count);
+        c.BN = narrowed_bn(p, M, p.in_scale || t.rules_off || p.ln_g ? 0 : k.small_bn_f32, cu_count);
         if (c.BN == 128 && !p.in_scale) {
             if (t.tile == ConvTune::TILE_256x128) c.BM = 256;
             else if (t.tile == ConvTune::TILE_256 || (t.tile != ConvTune::TILE_128_ONE_PER_CU && !t.rules_off && conv_use_tile256(M, p.Cout, p.splits))) c.BM = c.BN = 256;
@@ -1533,13 +1535,16 @@ ConvChoice conv_choose(const ConvParams& p, const ConvTune& t, const ConvKnobs& 
     return c;
 }
 
-void launch_conv(const ConvParams& p, hipStream_t s, const ConvTune& t) {
+void launch_conv(const ConvParams& p, hipStream_t s, const ConvTune& t, const ConvKnobs* knobs, ConvChoice* chosen) {
     conv_validate(p);
-    const ConvChoice c = conv_choose(p, t, conv_knobs_from_env(), device_cu_count());
+    const ConvChoice c = conv_choose(p, t, knobs ? *knobs : conv_knobs_from_env(), device_cu_count());
+    if (chosen) *chosen = c;
     const int M = p.B * p.Ho * p.Wo;
     const dim3 grid(c.gx, c.gy, c.gz);
     const int nrows = (int)igemm_table().size();
     if (c.family != CC::NARROW3 && c.family != CC::HALO && c.row < 0) throw HipError("launch_conv: no kernel instance " + c.name());
+    if (p.ln_g && (c.family != CC::IGEMM || c.BN != p.Cout))   // the epilogue's mean and variance run over BN columns
+        throw HipError("launch_conv: the fused LayerNorm epilogue needs a column tile as wide as Cout, chosen " + c.name());
     switch (c.family) {
     case CC::HALO:
         launch_conv_halo(p, s, t.halo == ConvTune::HALO_FORCE_512 ? 1 : t.halo == ConvTune::HALO_FORCE_256 ? -1 : 0);

@@ -568,6 +568,7 @@ void ensure_film_cur(irsde_engine* e, int rows);
 void pack_conv_rows(const float* w_oihw, const float* bias, int O, int I, int KH, int KW, const std::vector<int>& perm, std::vector<float>& pw,
                     std::vector<float>& pb);                          // [O][I][KH][KW] -> [O][KH][KW][I], packed row n' = row perm[n'] (empty: identity)
 std::vector<int> naf_gate_perm(int c);                               // conv4's row order: SimpleGate pairs (j, j + c) adjacent
+std::vector<int> naf_shuffle_perm(int Cout);                         // ups.i.0's row order for the PixelShuffle(2) epilogue: row q * Cout / 4 + co <- co * 4 + q
 std::vector<float> pack_dwconv_taps(const float* w, int c2);         // conv2.weight [2c][1][3][3] -> [9][2c]
 // naf_chain_kernel's fp16 fragment streams (naf_chain_weight_halves) + fp32 vectors (naf_chain_vec_floats) of consecutive 512-channel blocks
 void pack_naf_chain_host(const std::vector<NafChainHostW>& blocks, std::vector<unsigned short>& w, std::vector<float>& vecs);

@@ -269,6 +269,13 @@ SplitGemmArgs split_pairs(Scratch& mem, const float* A, const float* Bm, float* 
     return g;
 }
 
+// The line irsde_debug_conv_choice and irsde_debug_conv_features report a ConvChoice with
+void write_choice_line(const ConvChoice& c, char* out, int out_len) {
+    snprintf(out, (size_t)out_len, "name=%s family=%d tile=%dx%d op=%d act=%d inscale=%d zbatch=%d zrows=%d grid=%ux%ux%u threads=%d lds=%d row=%d of %d",
+             c.name().c_str(), (int)c.family, c.BM, c.BN, (int)c.op, (int)c.act, (int)c.inscale, c.zbatch, c.zrows, c.gx, c.gy, c.gz, c.threads, c.lds, c.row,
+             conv_instance_count());
+}
+
 // What irsde_debug_scam and irsde_debug_scam_full share; the projections run on the B x Hs x Ws map of each view.  In order: the argument check, the hook's own
 // check_shape(), the two views' packed projection weights, the uploads and the [in2 | qv | F] scratch, the hook's prologue(dev, s), the two [LN(x) | x] -> [Q | V]
 // GEMMs, the hook's tail(dev, s) = its core + epilogue
@@ -796,9 +803,110 @@ int irsde_debug_conv_choice(int B, int Hin, int Win, int C0, int C1, int Cout, i
         const ConvChoice c = conv_choose(p, conv_tune_from_code(tune), k, cu_count);
         const bool tabled = c.family != ConvChoice::NARROW3 && c.family != ConvChoice::HALO;
         if (tabled && c.row < 0) throw HipError("launch_conv: no kernel instance " + c.name());
-        snprintf(out, (size_t)out_len, "name=%s family=%d tile=%dx%d op=%d act=%d inscale=%d zbatch=%d zrows=%d grid=%ux%ux%u threads=%d lds=%d row=%d of %d",
-                 c.name().c_str(), (int)c.family, c.BM, c.BN, (int)c.op, (int)c.act, (int)c.inscale, c.zbatch, c.zrows, c.gx, c.gy, c.gz, c.threads, c.lds, c.row,
-                 conv_instance_count());
+        write_choice_line(c, out, out_len);
+    });
+}
+
+int irsde_debug_conv_features(const float* in0, int C0, const float* in1, int C1, int B, int Hin, int Win, int in_shift, const float* w_oihw, int Cout, int K,
+                              int stride, int pad, int operand, int storage, int pair, const float* bias, const float* ch_scale, const float* ln_g,
+                              const float* film, int film_bstride, const float* res, const float* in_scale, const float* gate_film, int gate_film_bstride,
+                              int silu, int gate, int shuffle, int nz, int splits, int tune, const int* knobs, float* out, char* choice, int choice_len,
+                              void* stream) {
+    return guard([&] {
+        if (!in0 || !w_oihw || !out || !choice || choice_len < 1) throw HipError("null argument");
+        if (B < 1 || Hin < 1 || Win < 1 || C0 < 1 || C1 < 0 || (C1 > 0) != (in1 != nullptr) || Cout < 1 || K < 1 || stride < 1 || pad < 0 || in_shift < 0 || in_shift > 1 ||
+            operand < 0 || operand > 2 || storage < 0 || storage > 2 || (pair && operand == 0) || nz < 1 || splits < 1 || film_bstride < 0 || gate_film_bstride < 0)
+            throw HipError("debug_conv_features: bad argument");
+        if ((gate && shuffle) || (gate && (Cout % 4 || res)) || (shuffle && Cout % 4) || (gate_film && !gate) || ((gate || shuffle) && film))
+            throw HipError("debug_conv_features: gate needs Cout % 4 == 0 and takes no residual, shuffle needs Cout % 4 == 0, gate_film goes with gate, film with neither");
+        if (nz > 1 && (B != 1 || Hin != 1 || K != 1 || stride != 1 || pad || in_shift || C1 || storage))
+            throw HipError("debug_conv_features: nz > 1 is a stack of 1x1 GEMMs: B = 1, Hin = 1, K = 1, one fp32 source");
+        const int Ho = ((Hin << in_shift) + 2 * pad - K) / stride + 1, Wo = ((Win << in_shift) + 2 * pad - K) / stride + 1;
+        if (Ho < 1 || Wo < 1) throw HipError("debug_conv_features: empty output");
+        hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+        conv_global_init();
+        const int Cin = C0 + C1;
+        // the engine's own packing, component by component: conv4's gate pairs, ups.i.0's pixel-shuffle order, else the identity
+        const std::vector<int> perm = gate ? naf_gate_perm(Cout / 2) : shuffle ? naf_shuffle_perm(Cout) : std::vector<int>();
+        const size_t wz = (size_t)Cout * K * K * Cin;
+        std::vector<float> pk(wz * nz), pb, one, oneb;
+        for (int z = 0; z < nz; ++z) {
+            pack_conv_rows(w_oihw + z * wz, z == 0 ? bias : nullptr, Cout, Cin, K, K, perm, one, z == 0 ? pb : oneb);
+            std::copy(one.begin(), one.end(), pk.begin() + z * wz);
+        }
+        Scratch mem(s);
+        float* dw = mem.upload(pk);
+        ConvParams p;
+        p.in0 = in0; p.C0 = C0; p.pix0 = C0; p.in1 = in1; p.C1 = C1; p.pix1 = C1;
+        p.Hin = Hin; p.Win = Win; p.in_shift = in_shift;
+        p.w = dw; p.Cout = Cout; p.KH = K; p.KW = K; p.stride = stride; p.pad_y = pad; p.pad_x = pad;
+        p.B = B; p.Ho = Ho; p.Wo = Wo;
+        const int ostride = gate ? Cout / 2 : shuffle ? Cout / 4 : Cout;
+        const size_t npix_in = (size_t)B * Hin * Win * nz, M = (size_t)B * Ho * Wo, nout = M * nz * (gate ? Cout / 2 : Cout);
+        p.out = out; p.out_stride = ostride; p.res = res; p.res_stride = ostride;
+        if (bias) p.bias = mem.upload(pb);
+        if (ch_scale) {   // (a row vector of the packed rows, like the bias)
+            std::vector<float> cs(Cout);
+            for (int o = 0; o < Cout; ++o) cs[o] = ch_scale[perm.empty() ? o : perm[o]];
+            p.ch_scale = mem.upload(cs);
+        }
+        if (ln_g) p.ln_g = mem.upload(ln_g, Cout);
+        p.film = film; p.film_bstride = film_bstride; p.silu = silu; p.in_scale = in_scale;
+        p.gate = gate ? 1 : 0; p.gate_film = gate_film; p.gate_film_bstride = gate_film ? gate_film_bstride : 0; p.shuffle = shuffle ? 1 : 0;
+        p.nz = nz;
+        if (nz > 1) { p.z_in = (long long)Win * C0; p.z_w = (long long)Cout * C0; p.z_out = (long long)Win * Cout; }
+        float* dz = mem.alloc<float>(256);
+        IRSDE_HIP_CHECK(hipMemset(dz, 0, 1024));
+        p.zeros = dz;
+        if (splits > 1) {
+            p.splits = splits;
+            p.partial = mem.alloc<float>((size_t)splits * M * Cout);
+        }
+        const bool f16 = operand == 2;
+        unsigned short *w16 = nullptr, *a0 = nullptr, *a1 = nullptr, *ar = nullptr, *ao = nullptr;
+        float wsc = 1.f;
+        if (pair) {
+            wsc = f16 ? pow2_scale_into_512(pk.data(), pk.size()) : 1.f;
+            w16 = mem.alloc<unsigned short>(2 * pk.size());
+            p.w_pair = w16; p.pair_scale = 1.0f / wsc;
+        } else if (operand) {
+            w16 = mem.alloc<unsigned short>(pk.size());
+            p.w_bf = w16;
+        }
+        p.f16 = f16 ? 1 : 0;
+        if (storage) {   // the caller's fp32 tensors are rounded into 16-bit copies of the same extents; the 16-bit result is widened back
+            a0 = mem.alloc<unsigned short>(npix_in * C0);
+            p.in0 = reinterpret_cast<const float*>(a0);
+            if (in1) { a1 = mem.alloc<unsigned short>(npix_in * C1); p.in1 = reinterpret_cast<const float*>(a1); }
+            if (res) { ar = mem.alloc<unsigned short>(nout); p.res = reinterpret_cast<const float*>(ar); }
+            ao = mem.alloc<unsigned short>(nout);
+            p.out = reinterpret_cast<float*>(ao);
+            p.in_bf16 = p.out_bf16 = storage == 1;
+            p.in_f16 = p.out_f16 = storage == 2;
+        }
+        ConvKnobs k;
+        static_assert(sizeof(ConvKnobs) == 11 * sizeof(int), "the hook's knob array is ConvKnobs, field by field");
+        if (knobs) memcpy(&k, knobs, sizeof k);
+        conv_validate(p);   // every refusal before the first launch, the hook's own conversions included
+        auto narrow = [&](const float* src, unsigned short* dst, size_t n) {
+            if (storage == 2) launch_f32_to_f16(src, dst, n, s);
+            else launch_f32_to_bf16(src, dst, n, s);
+        };
+        if (pair) launch_split_pairs(dw, w16, (size_t)Cout * nz, K * K * Cin, s, f16, wsc);
+        else if (operand == 2) launch_f32_to_f16(dw, w16, pk.size(), s);
+        else if (operand == 1) launch_f32_to_bf16(dw, w16, pk.size(), s);
+        if (storage) {
+            narrow(in0, a0, npix_in * C0);
+            if (in1) narrow(in1, a1, npix_in * C1);
+            if (res) narrow(res, ar, nout);
+            IRSDE_HIP_CHECK(hipMemsetAsync(ao, 0xFF, nout * 2, s));   // NaN in both 16-bit formats: an element the kernel leaves out stays visible after the widening
+        }
+        ConvChoice c;
+        launch_conv(p, s, conv_tune_from_code(tune), knobs ? &k : nullptr, &c);
+        if (storage == 2) launch_f16_to_f32(ao, out, nout, s);
+        else if (storage == 1) launch_bf16_to_f32(ao, out, nout, s);
+        IRSDE_HIP_CHECK(hipStreamSynchronize(s));
+        write_choice_line(c, choice, choice_len);
     });
 }
 

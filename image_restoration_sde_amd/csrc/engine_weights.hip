@@ -359,6 +359,14 @@ std::vector<int> naf_gate_perm(int c) {
     }
     return perm;
 }
+// PixelShuffle(2) behind a 1x1 conv with Cout rows: row n' = q * Cq + co  <-  co * 4 + q  (q = 2 dy + dx, Cq = Cout / 4: the row order of a packed ups.i.0)
+std::vector<int> naf_shuffle_perm(int Cout) {
+    const int Cq = Cout / 4;
+    std::vector<int> perm(Cout);
+    for (int q = 0; q < 4; ++q)
+        for (int co = 0; co < Cq; ++co) perm[q * Cq + co] = co * 4 + q;
+    return perm;
+}
 // conv2.weight [2c][1][3][3] -> [9][2c]  (tap-major: dwconv_gate_kernel reads one float4 of channels per tap)
 std::vector<float> pack_dwconv_taps(const float* w, int c2) {
     std::vector<float> p((size_t)9 * c2);
@@ -539,12 +547,8 @@ void finalize_naf(irsde_engine* e) {
     for (int j = 0; j < e->naf_mid_num; ++j) e->naf_mid.push_back(pack_nafblock(e, "middle_blks." + std::to_string(j) + ".", chan));
     e->naf_dec.resize(e->naf_dec_nums.size());
     for (size_t i = 0; i < e->naf_dec_nums.size(); ++i) {
-        // ups.i.0: 1x1 chan -> 2 chan, then PixelShuffle(2): row n' = q * Cq + co  <-  co * 4 + q
-        const int Cq = chan / 2;
-        std::vector<int> perm(2 * chan);
-        for (int q = 0; q < 4; ++q)
-            for (int co = 0; co < Cq; ++co) perm[q * Cq + co] = co * 4 + q;
-        e->naf_ups.push_back(pack_conv_perm(e, "ups." + std::to_string(i) + ".0.weight", "", perm));
+        // ups.i.0: 1x1 chan -> 2 chan, then PixelShuffle(2)
+        e->naf_ups.push_back(pack_conv_perm(e, "ups." + std::to_string(i) + ".0.weight", "", naf_shuffle_perm(2 * chan)));
         chan /= 2;
         for (int j = 0; j < e->naf_dec_nums[i]; ++j)
             e->naf_dec[i].push_back(pack_nafblock(e, "decoders." + std::to_string(i) + "." + std::to_string(j) + ".", chan));

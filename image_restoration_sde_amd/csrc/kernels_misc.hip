@@ -2322,6 +2322,15 @@ void launch_bf16_to_f32(const unsigned short* in, float* out, size_t n, hipStrea
     IRSDE_HIP_CHECK(hipGetLastError());
 }
 
+__global__ void f16_to_f32_kernel(const _Float16* __restrict__ in, float* __restrict__ out, size_t n) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = (float)in[i];
+}
+void launch_f16_to_f32(const unsigned short* in, float* out, size_t n, hipStream_t s) {
+    hipLaunchKernelGGL(f16_to_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const _Float16*>(in), out, n);
+    IRSDE_HIP_CHECK(hipGetLastError());
+}
+
 // out = a + b (latent NAFNet: ending(x + intro); latent UNet: final_conv(x + h[0]))
 __global__ void add_kernel(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ out, size_t n4) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;

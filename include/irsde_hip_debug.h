@@ -43,7 +43,9 @@ extern "C" {
  *   100 + v: tuning variant v of the fp32 kernel: 0 production dispatch, 3 / 50 the 256x128 / 256x256 tile, 5 one block per CU, 6 generic pointer staging
  *           instead of buffer descriptors, 7 LDS-transposed instead of direct epilogue, 70 the tile-loop kernel off, 71 / 72 its batch-loop form with all / 2
  *           components per block, 73 the tile-loop kernel forced for 1x1 layers
- * Any other code is refused, 42 / 43 (the retired plane-major prototype GEMM) among them.  splits > 1 forces split-K.  Synchronises `stream`. */
+ * Any other code is refused, 42 / 43 (the retired plane-major prototype GEMM) among them.  splits > 1 forces split-K.  Synchronises `stream`.
+ * Everything of the ConvParams contract beyond bias / FiLM / SiLU / residual (in_scale, ch_scale, gate, shuffle, ln_g, fp16 storage, batched launches, knobs):
+ * irsde_debug_conv_features below. */
 int irsde_debug_conv(const float* in0, int C0, const float* in1, int C1, int B, int Hin, int Win, int in_shift,
                      const float* w_oihw, int Cout, int KH, int KW, int stride, int pad, const float* bias,
                      const float* film, int film_bstride, int silu, const float* res, float* out, int naive,
@@ -62,6 +64,25 @@ int irsde_debug_conv(const float* in0, int C0, const float* in1, int C1, int B, 
  * without a kernel instance, fails with launch_conv's message. */
 int irsde_debug_conv_choice(int B, int Hin, int Win, int C0, int C1, int Cout, int K, int stride, int pad, int in_shift, int operand, int storage, int pair,
                             unsigned features, int splits, int nz, int tune, int cu_count, const int* knobs, char* out, int out_len);
+
+/* Kernel-level test hook: ONE production launch_conv (csrc/conv_igemm.hip) with the whole ConvParams contract, in irsde_debug_conv_choice's language.
+ * Geometry as for irsde_debug_conv (NHWC device tensors, in0 / in1 concat, in_shift, K x K taps).  operand / storage / pair as for irsde_debug_conv_choice; with
+ * 16-bit storage the caller's fp32 in0 / in1 / res are rounded on the device into bf16 / fp16 copies of the same extents and the 16-bit result (pre-filled with
+ * NaN) is widened back into out.  HOST, reference layout: w_oihw [nz][Cout][C0 + C1][K][K], bias / ch_scale / ln_g [Cout] (NULL = absent) — packed by the
+ * engine's own functions: pack_conv_rows with naf_gate_perm (gate) or naf_shuffle_perm (shuffle), launch_split_pairs + pow2_scale_into_512 (pair).  DEVICE:
+ * film [rows][2 Cout] with film_bstride, res, in_scale [B][C0], gate_film [B][Cout / 2 scales | Cout / 2 shifts] with gate_film_bstride.  Epilogue: bias -> FiLM ->
+ * SiLU -> ch_scale -> one of: gate (out [B][Ho][Wo][Cout / 2] = v[j] v[j + Cout / 2], then gate_film: (.)(s + 1) + t), shuffle (out and res [B][2Ho][2Wo][Cout / 4]:
+ * PixelShuffle(2), then + res), ln_g (after the bias: channel LayerNorm, gain ln_g, eps 1e-5, then + res), else + res (out and res [B][Ho][Wo][Cout]).
+ * nz > 1: a batched launch of nz 1x1 GEMMs (B = 1, Hin = 1, K = 1, one fp32 source): in0 [nz][Win][C0], w [nz][Cout][C0], out [nz][Win][Cout].
+ * splits / tune / knobs as for irsde_debug_conv_choice; the knobs are handed to this one launch (no process-wide state).  choice receives
+ * irsde_debug_conv_choice's line for the choice the launch made (the launch's own ConvChoice; the device's CU count).  Refused before anything is launched:
+ * whatever conv_validate refuses, nz > 1 with another geometry, gate with shuffle / res / film, shuffle with film, gate_film without gate.  Tensors are
+ * used at their exact extents.  Synchronises `stream`.  tests/test_gpu_conv_rows.py compares it with tests/conv_rows_oracle.py. */
+int irsde_debug_conv_features(const float* in0, int C0, const float* in1, int C1, int B, int Hin, int Win, int in_shift, const float* w_oihw, int Cout, int K,
+                              int stride, int pad, int operand, int storage, int pair, const float* bias, const float* ch_scale, const float* ln_g,
+                              const float* film, int film_bstride, const float* res, const float* in_scale, const float* gate_film, int gate_film_bstride,
+                              int silu, int gate, int shuffle, int nz, int splits, int tune, const int* knobs, float* out, char* choice, int choice_len,
+                              void* stream);
 
 /* Kernel-level test hook of csrc/gemm_split.hip: C_z[M][N] = A_z[M][K] . B_z[N][K]^T for z < ncomp (device f32 tensors, z-major),
  * operands split into 16-bit pieces on the device (nplanes = 42 / 44: the engine's

@@ -372,6 +372,9 @@ def test_fused_attention_16bit_plan_vs_qkv_tensor_plan(dtype):
     ef, eu, d = relerr(yf, y32), relerr(yu, y32), relerr(yf, yu)
     print("%s: fused attention plan vs fp32 %.3g, qkv-tensor plan vs fp32 %.3g, fused vs tensor plan %.3g" % (dtype, ef, eu, d))
     assert np.isfinite(yf).all() and 0 < ef < _ATTN16_TOL[dtype] and ef < 1.5 * eu and d > 0
+    # and the tensor plan is itself a valid yardstick: a broken one would make "ef < 1.5 eu" easier to meet, not harder (its to_out conv + fused LayerNorm
+    # once ran on column tiles narrower than Cout: profiles/conv_rows.md)
+    assert np.isfinite(yu).all() and 0 < eu < _ATTN16_TOL[dtype]
 
 
 def _fresh_unet64(dtype):

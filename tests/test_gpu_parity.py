@@ -12,6 +12,7 @@ Tolerances (floating point path, fp32 arithmetic on both sides):
 """
 import ctypes
 import os
+import zlib
 
 import numpy as np
 import pytest
@@ -141,7 +142,7 @@ HALO2_CASES = ["3x3_concat_192_128", "3x3_deep_k_1536", "3x3_wino_res_bias", "3x
 @pytest.mark.parametrize("name", list(CONV_CASES))
 def test_conv_kernel(name):
     B, C0, C1, H, W, Cout, K, stride, pad, in_shift, has_bias, has_film, silu, has_res = CONV_CASES[name]
-    rs = np.random.RandomState(hash(name) % 2 ** 31)
+    rs = np.random.RandomState(zlib.crc32(name.encode()) % 2 ** 31)
     x0 = rs.standard_normal((B, C0, H, W)).astype(np.float32)
     x1 = rs.standard_normal((B, C1, H, W)).astype(np.float32) if C1 else None
     w = (rs.standard_normal((Cout, C0 + C1, K, K)) / np.sqrt((C0 + C1) * K * K)).astype(np.float32)
@@ -347,7 +348,7 @@ def test_conv_kernel_bf16(name):
     """IRSDE_FLAG_BF16 kernel (v_mfma_f32_32x32x16_bf16): same operands as the oracle once both round to bf16 (RNE),
     products are exact in fp32, so only the fp32 accumulation order differs."""
     B, C0, C1, H, W, Cout, K, stride, pad, in_shift, has_bias, has_film, silu, has_res = CONV_CASES[name]
-    rs = np.random.RandomState(hash(name) % 2 ** 31)
+    rs = np.random.RandomState(zlib.crc32(name.encode()) % 2 ** 31)
     x0 = rs.standard_normal((B, C0, H, W)).astype(np.float32)
     x1 = rs.standard_normal((B, C1, H, W)).astype(np.float32) if C1 else None
     w = (rs.standard_normal((Cout, C0 + C1, K, K)) / np.sqrt((C0 + C1) * K * K)).astype(np.float32)
@@ -375,7 +376,7 @@ def test_conv_kernel_fp16(name):
     both round to IEEE binary16 (RNE); products are exact in fp32, so only the fp32 accumulation order differs.  fp16
     keeps 11 significand bits: 8x closer to the fp32 result than the bf16 mode."""
     B, C0, C1, H, W, Cout, K, stride, pad, in_shift, has_bias, has_film, silu, has_res = CONV_CASES[name]
-    rs = np.random.RandomState(hash(name) % 2 ** 31)
+    rs = np.random.RandomState(zlib.crc32(name.encode()) % 2 ** 31)
     x0 = rs.standard_normal((B, C0, H, W)).astype(np.float32)
     x1 = rs.standard_normal((B, C1, H, W)).astype(np.float32) if C1 else None
     w = (rs.standard_normal((Cout, C0 + C1, K, K)) / np.sqrt((C0 + C1) * K * K)).astype(np.float32)
@@ -437,7 +438,7 @@ def test_conv_kernel_bf16_storage(name):
     the same roundings (operands, residual; fp32+ arithmetic; one final rounding of the stored result): one bf16 ulp
     (2^-8 relative to the value) is the most a different accumulation order can move a stored element."""
     B, C0, C1, H, W, Cout, K, stride, pad, in_shift, has_bias, has_film, silu, has_res = CONV_CASES[name]
-    rs = np.random.RandomState(hash(name) % 2 ** 31)
+    rs = np.random.RandomState(zlib.crc32(name.encode()) % 2 ** 31)
     x0 = rs.standard_normal((B, C0, H, W)).astype(np.float32)
     x1 = rs.standard_normal((B, C1, H, W)).astype(np.float32) if C1 else None
     w = (rs.standard_normal((Cout, C0 + C1, K, K)) / np.sqrt((C0 + C1) * K * K)).astype(np.float32)
@@ -464,7 +465,7 @@ def test_conv_halo2_kernel(name):
     (irsde_debug_conv 162 / 262 / 166) in its three instances — bf16 operands on fp32 tensors, bf16 tensors, fp16 operands — against the oracle with the
     same operand roundings, and against the 256-pixel kernel it replaces on the big feature maps (163 / 263 / 167)."""
     B, C0, C1, H, W, Cout, K, stride, pad, in_shift, has_bias, has_film, silu, has_res = CONV_CASES[name]
-    rs = np.random.RandomState(hash(name) % 2 ** 31)
+    rs = np.random.RandomState(zlib.crc32(name.encode()) % 2 ** 31)
     x0 = rs.standard_normal((B, C0, H, W)).astype(np.float32)
     x1 = rs.standard_normal((B, C1, H, W)).astype(np.float32) if C1 else None
     w = (rs.standard_normal((Cout, C0 + C1, K, K)) / np.sqrt((C0 + C1) * K * K)).astype(np.float32)
