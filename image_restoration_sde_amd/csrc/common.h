@@ -242,12 +242,14 @@ struct ConvTune {
     enum Tile { TILE_AUTO, TILE_128, TILE_256x128, TILE_256, TILE_128_ONE_PER_CU };
     enum Halo { HALO_AUTO, HALO_OFF, HALO_FORCE_512, HALO_FORCE_256 };
     enum ZLoop { ZLOOP_AUTO, ZLOOP_OFF, ZLOOP_ALL, ZLOOP_PAIRS, ZLOOP_FORCE_1X1 };
+    enum Order { ORDER_AUTO, ORDER_N_FAST, ORDER_N_SLOW };
     bool rules_off = false;        // off: the IRSDE_SMALL_BN(_F32) narrowing, the vector-pipe 3-channel kernel, the automatic 256 x 256 tile of the f32 kernels
     Tile tile = TILE_AUTO;         // f32, Cout >= 128: 256x128 / 256 / one 128 x 128 block per CU (120 KB of LDS); 16-bit operands and PAIR: 256 / 128
     bool no_buffer_desc = false;   // f32: generic pointer staging instead of buffer descriptors
     bool no_direct_epi = false;    // f32: LDS-transposed instead of direct epilogue
     Halo halo = HALO_AUTO;         // 16-bit operands, eligible 3x3 layers: generic tiles / the 512-pixel x 128-channel / the 256-pixel halo kernel
     ZLoop zloop = ZLOOP_AUTO;      // tile-loop kernel: both forms off / its batch-loop form with all / 2 components per block / forced (2 row tiles) for 1x1 layers
+    Order halo_order = ORDER_AUTO; // halo kernels, tile order inside an XCD's range: by rule / output-channel blocks fastest / slowest (where there are >= 2 of them)
 };
 // The tuning knobs the kernel choice reads (IRSDE_<FIELD NAME>, DESIGN.md "Tuning knobs"); the defaults are the production values.  conv_knobs_from_env
 // reads the environment once per process.
@@ -259,6 +261,18 @@ struct ConvKnobs {
     int zloop_maxnk = 32, zloop_minblk = 1024, zloop_deep = 1, zloop_ragged64 = 2048;
 };
 const ConvKnobs& conv_knobs_from_env();
+// What launch_conv_halo runs for one layer of the halo family (conv_halo.hip): conv_halo_choose is a pure function of its arguments.
+struct HaloChoice {
+    int pixels = 0;                    // pixels per block: 256 (conv3x3_halo_bf16_kernel, 16 x 16) or 512 (conv3x3_halo2_kernel, 16 x 32)
+    int BN = 0;                        // output channels per block: 64 / 128
+    int op = 0, act = 0;               // ConvChoice::Operand (2 bf16, 3 fp16) and ConvChoice::Storage (0 f32, 1 bf16) by number
+    int tiles_x = 0, tiles_y = 0, nblk_n = 0;
+    int n_slow = 0;                    // 1: the output-channel blocks run slowest inside an XCD's range
+    unsigned grid = 0;
+    int lds = 0;
+    int instance = -1;                 // 0 .. 8, in the order conv_halo_global_init lists the kernels
+};
+constexpr int kHaloInstances = 9;
 // What launch_conv runs for one layer: conv_choose is a pure function of its arguments (no device, no environment), conv_validate holds launch_conv's refusals.
 struct ConvChoice {
     enum Family { PAIR, NARROW3, ZLOOP_BATCH, ZLOOP_1X1, HALO, IGEMM };
@@ -271,6 +285,7 @@ struct ConvChoice {
     bool inscale = false;
     int zbatch = 0, zrows = 0;         // tile-loop forms: components resp. row tiles per block
     unsigned gx = 0, gy = 1, gz = 1;   // HALO: conv_halo.hip chooses its own kernel and grid (gx == 0 here)
+    HaloChoice halo;                   // HALO: what launch_conv_halo launched — filled by launch_conv, not by conv_choose (instance -1)
     int threads = 0, lds = 0;
     int row = -1;                      // index into the instance tables (implicit-GEMM / PAIR rows first, then the tile-loop rows); -1: the family has none, or no such instance
     std::string name() const;          // stable short name: igemm128x64, pair256x256, zloop64x128, zloop1x1_128x128, narrow3, halo
@@ -286,8 +301,13 @@ void conv_global_init();
 // bf16 mode: 3x3 s1 p1 layers with an LDS-resident halo tile (conv_halo.hip)
 void conv_halo_global_init();
 bool conv_halo_eligible(const ConvParams& p);
-bool conv_halo2_wanted(const ConvParams& p, int force);   // true: launch_conv_halo runs the layer on the 512-pixel x 128-channel kernel (irsde_plan_describe names it)
-void launch_conv_halo(const ConvParams& p, hipStream_t s, int force_halo2 = 0);   // force_halo2: 1 = the 512-pixel x 128-channel kernel, -1 = the 256-pixel one, 0 = by shape
+// Kernel (256 / 512 pixels), BN, tile order, grid and LDS bytes of one eligible layer: no HIP call, no static, no environment.  t.halo forces a kernel
+// (HALO_FORCE_512 where the layer has >= 128 output channels and fits its descriptors), t.halo_order a tile order; halo2 / nslow are the values of
+// IRSDE_HALO2 (1: the 512-pixel kernel where its rule wants it, 0: never by rule) and IRSDE_HALO_NSLOW (-1: by rule, 0 / 1: the order for every layer).
+// Throws for a layer the family does not take.
+HaloChoice conv_halo_choose(const ConvParams& p, const ConvTune& t, int halo2, int nslow);
+bool conv_halo2_wanted(const ConvParams& p);   // the production choice is the 512-pixel x 128-channel kernel (irsde_plan_describe names it)
+HaloChoice launch_conv_halo(const ConvParams& p, hipStream_t s, const ConvTune& t = {});   // returns what it launched
 void launch_fill_random(float* p, size_t n, unsigned seed, float scale, hipStream_t s);  // sets the dynamic-LDS attribute of every tile configuration (call before graph capture)
 // SiLU for the epilogues of the f32 MFMA kernels: v_exp_f32 + v_rcp_f32 (1 ulp each) — 5 vector instructions instead of the
 // ~25 of expf() + IEEE division.  On gfx950 the vector instructions of an f32-MFMA kernel are paid in matrix-pipe time

@@ -623,33 +623,32 @@ inline bool halo2_fits(const ConvParams& p) {
     return in0 < (1ll << 31) && in1 < (1ll << 31) && wb < (1ll << 31);
 }
 
+// (the descriptor extents are the tensors' own: not part of the choice)
 template <bool ABF, bool F16 = false>
-void launch_halo2(const ConvParams& p, hipStream_t s) {
-    const int tiles_x = (p.Wo + H2_TW - 1) / H2_TW, tiles_y = (p.Ho + H2_TH - 1) / H2_TH;
-    const int nblk_n = (p.Cout + H2_BN - 1) / H2_BN;
-    static const int env = tuning_env_int("IRSDE_HALO_NSLOW", -1);
-    const double wbytes = 2.0 * p.Cout * 9.0 * (p.C0 + p.C1);
-    const int n_slow = env >= 0 ? (env && nblk_n > 1) : (nblk_n >= 2 && wbytes > 4.0e6);
+void launch_halo2(const ConvParams& p, const HaloChoice& c, hipStream_t s) {
     const long long aesz = ABF ? 2 : 4;
     const long long npix = (long long)p.B * p.Hin * p.Win;
     const unsigned in0_bytes = (unsigned)(((npix - 1) * p.pix0 + p.C0) * aesz);
     const unsigned in1_bytes = p.C1 ? (unsigned)(((npix - 1) * p.pix1 + p.C1) * aesz) : 0u;
     const unsigned w_bytes = (unsigned)((long long)p.Cout * 9 * (p.C0 + p.C1) * 2);
-    hipLaunchKernelGGL((conv3x3_halo2_kernel<ABF, F16>), dim3((unsigned)(p.B * tiles_y * tiles_x * nblk_n)), dim3(NT), H2_LDS_BYTES, s, p, tiles_x, tiles_y,
-                       nblk_n, n_slow, in0_bytes, in1_bytes, w_bytes);
+    hipLaunchKernelGGL((conv3x3_halo2_kernel<ABF, F16>), dim3(c.grid), dim3(NT), c.lds, s, p, c.tiles_x, c.tiles_y, c.nblk_n, c.n_slow, in0_bytes, in1_bytes,
+                       w_bytes);
     IRSDE_HIP_CHECK(hipGetLastError());
 }
 
 template <int BN, bool ABF, bool F16 = false>
-void launch_halo(const ConvParams& p, hipStream_t s) {
-    const int tiles_x = (p.Wo + TS - 1) / TS, tiles_y = (p.Ho + TS - 1) / TS;
-    const int nblk_n = (p.Cout + BN - 1) / BN;
-    static const int env = tuning_env_int("IRSDE_HALO_NSLOW", -1);
-    const double wbytes = 2.0 * p.Cout * 9.0 * (p.C0 + p.C1);
-    const int n_slow = env >= 0 ? (env && nblk_n > 1) : (nblk_n >= 2 && wbytes > 4.0e6);  // one XCD L2 = 4 MiB
-    hipLaunchKernelGGL((conv3x3_halo_bf16_kernel<BN, ABF, F16>), dim3((unsigned)(p.B * tiles_y * tiles_x * nblk_n)), dim3(NT),
-                       HCfg<BN>::LDS_BYTES, s, p, tiles_x, tiles_y, nblk_n, n_slow);
+void launch_halo(const ConvParams& p, const HaloChoice& c, hipStream_t s) {
+    hipLaunchKernelGGL((conv3x3_halo_bf16_kernel<BN, ABF, F16>), dim3(c.grid), dim3(NT), c.lds, s, p, c.tiles_x, c.tiles_y, c.nblk_n, c.n_slow);
     IRSDE_HIP_CHECK(hipGetLastError());
+}
+
+// IRSDE_HALO2 / IRSDE_HALO_NSLOW, read once per process: the only environment the halo path sees (conv_halo_choose takes them as arguments)
+struct HaloEnv {
+    int halo2, nslow;
+};
+const HaloEnv& halo_env() {
+    static const HaloEnv e{tuning_env_int("IRSDE_HALO2", 1), tuning_env_int("IRSDE_HALO_NSLOW", -1)};
+    return e;
 }
 
 }  // namespace
@@ -678,13 +677,13 @@ bool conv_halo_eligible(const ConvParams& p) {
            p.Ho == (p.Hin << p.in_shift) && p.Wo == (p.Win << p.in_shift) && (!p.film || p.film_bstride >= 0) && p.zeros;
 }
 
-// r05: the 512-pixel x 128-channel kernel where it fills the chip (one block per CU: >= 256 blocks) without padding the feature map by more than a
-// quarter; force: 1 = always (if the layer fits its descriptors), -1 = never (ConvTune::halo: irsde_debug_conv 162 / 262 / 166 and 163 / 263 / 167, irsde_bench_conv 64 .. 67)
-bool conv_halo2_wanted(const ConvParams& p, int force) {
-    if (force < 0 || p.Cout < 128 || !halo2_fits(p)) return false;
-    if (force > 0) return true;
-    static const int env = tuning_env_int("IRSDE_HALO2", 1);
-    if (!env) return false;
+// The 512-pixel x 128-channel kernel (r05) where it fills the chip (one block per CU: >= 256 blocks) without padding the feature map by more than a quarter;
+// t.halo: HALO_FORCE_512 = always (if the layer has >= 128 output channels and fits its descriptors), HALO_FORCE_256 = never (irsde_debug_conv 162 / 262 / 166
+// and 163 / 263 / 167, irsde_bench_conv 64 .. 67); halo2 = IRSDE_HALO2: 0 switches the rule off
+static bool halo2_rule(const ConvParams& p, const ConvTune& t, int halo2) {
+    if (t.halo == ConvTune::HALO_FORCE_256 || p.Cout < 128 || !halo2_fits(p)) return false;
+    if (t.halo == ConvTune::HALO_FORCE_512) return true;
+    if (!halo2) return false;
     const long long tx = (p.Wo + H2_TW - 1) / H2_TW, ty = (p.Ho + H2_TH - 1) / H2_TH, nb = (p.Cout + H2_BN - 1) / H2_BN;
     const long long blocks = (long long)p.B * tx * ty * nb;
     // measured at the 16 x 256^2 layer shapes (profiles/r05_halo2_sweep.txt): one block per CU exposes the epilogue that the 256-pixel kernel's second
@@ -695,27 +694,47 @@ bool conv_halo2_wanted(const ConvParams& p, int force) {
     return deep && blocks >= 256 && tx * H2_TW * ty * H2_TH * 4 <= (long long)p.Ho * p.Wo * 5;
 }
 
-void launch_conv_halo(const ConvParams& p, hipStream_t s, int force_halo2) {
+HaloChoice conv_halo_choose(const ConvParams& p, const ConvTune& t, int halo2, int nslow) {
     if (!conv_halo_eligible(p)) throw HipError("launch_conv_halo: layer not eligible");
-    if (conv_halo2_wanted(p, force_halo2)) {
-        if (p.f16) {
-            if (p.in_bf16) throw HipError("launch_conv_halo: fp16 operands go with fp32 activation storage");
-            launch_halo2<false, true>(p, s);
-        } else if (p.in_bf16) {
-            launch_halo2<true>(p, s);
-        } else {
-            launch_halo2<false>(p, s);
-        }
-        return;
+    if (p.f16 && p.in_bf16) throw HipError("launch_conv_halo: fp16 operands go with fp32 activation storage");
+    HaloChoice c;
+    const bool big = halo2_rule(p, t, halo2);
+    c.pixels = big ? H2_TH * H2_TW : TS * TS;
+    c.BN = big || p.Cout >= 128 ? 128 : 64;
+    c.op = p.f16 ? 3 : 2;
+    c.act = p.in_bf16 ? 1 : 0;
+    c.tiles_x = (p.Wo + (big ? H2_TW : TS) - 1) / (big ? H2_TW : TS);
+    c.tiles_y = (p.Ho + (big ? H2_TH : TS) - 1) / (big ? H2_TH : TS);
+    c.nblk_n = (p.Cout + c.BN - 1) / c.BN;
+    // Tile order: output-channel blocks slowest where the weights exceed one XCD's L2 (4 MiB); IRSDE_HALO_NSLOW = 0 / 1 sets it for every layer
+    const double wbytes = 2.0 * p.Cout * 9.0 * (p.C0 + p.C1);
+    c.n_slow = t.halo_order == ConvTune::ORDER_N_SLOW ? c.nblk_n > 1
+             : t.halo_order == ConvTune::ORDER_N_FAST ? 0
+             : nslow >= 0 ? (nslow && c.nblk_n > 1) : (c.nblk_n >= 2 && wbytes > 4.0e6);
+    c.grid = (unsigned)(p.B * c.tiles_y * c.tiles_x * c.nblk_n);
+    c.lds = big ? H2_LDS_BYTES : c.BN == 128 ? HCfg<128>::LDS_BYTES : HCfg<64>::LDS_BYTES;
+    const int form = p.f16 ? 2 : p.in_bf16 ? 1 : 0;   // conv_halo_global_init's order: f32 tensors, bf16 tensors, fp16 operands; BN = 128 before 64; then the 512-pixel kernel
+    c.instance = big ? 6 + form : 2 * form + (c.BN == 128 ? 0 : 1);
+    return c;
+}
+
+bool conv_halo2_wanted(const ConvParams& p) { return conv_halo_choose(p, ConvTune{}, halo_env().halo2, halo_env().nslow).pixels == H2_TH * H2_TW; }
+
+HaloChoice launch_conv_halo(const ConvParams& p, hipStream_t s, const ConvTune& t) {
+    const HaloChoice c = conv_halo_choose(p, t, halo_env().halo2, halo_env().nslow);
+    switch (c.instance) {
+    case 0: launch_halo<128, false>(p, c, s); break;
+    case 1: launch_halo<64, false>(p, c, s); break;
+    case 2: launch_halo<128, true>(p, c, s); break;
+    case 3: launch_halo<64, true>(p, c, s); break;
+    case 4: launch_halo<128, false, true>(p, c, s); break;
+    case 5: launch_halo<64, false, true>(p, c, s); break;
+    case 6: launch_halo2<false>(p, c, s); break;
+    case 7: launch_halo2<true>(p, c, s); break;
+    case 8: launch_halo2<false, true>(p, c, s); break;
+    default: throw HipError("launch_conv_halo: no kernel instance");
     }
-    if (p.f16) {
-        if (p.in_bf16) throw HipError("launch_conv_halo: fp16 operands go with fp32 activation storage");
-        if (p.Cout >= 128) launch_halo<128, false, true>(p, s); else launch_halo<64, false, true>(p, s);
-    } else if (p.in_bf16) {
-        if (p.Cout >= 128) launch_halo<128, true>(p, s); else launch_halo<64, true>(p, s);
-    } else {
-        if (p.Cout >= 128) launch_halo<128, false>(p, s); else launch_halo<64, false>(p, s);
-    }
+    return c;
 }
 
 }  // namespace irsde

@@ -1546,9 +1546,11 @@ void launch_conv(const ConvParams& p, hipStream_t s, const ConvTune& t, const Co
     if (p.ln_g && (c.family != CC::IGEMM || c.BN != p.Cout))   // the epilogue's mean and variance run over BN columns
         throw HipError("launch_conv: the fused LayerNorm epilogue needs a column tile as wide as Cout, chosen " + c.name());
     switch (c.family) {
-    case CC::HALO:
-        launch_conv_halo(p, s, t.halo == ConvTune::HALO_FORCE_512 ? 1 : t.halo == ConvTune::HALO_FORCE_256 ? -1 : 0);
+    case CC::HALO: {
+        const HaloChoice h = launch_conv_halo(p, s, t);
+        if (chosen) chosen->halo = h;
         return;
+    }
     case CC::NARROW3:
         hipLaunchKernelGGL(conv3x3_narrow_kernel, grid, dim3(c.threads), 0, s, p, M);
         break;

@@ -87,6 +87,8 @@ ConvTune conv_tune_from_code(int code) {
         case 61: t.tile = ConvTune::TILE_128; t.halo = ConvTune::HALO_OFF; break;
         case 64: t.halo = ConvTune::HALO_FORCE_512; break;
         case 65: t.halo = ConvTune::HALO_FORCE_256; break;
+        case 68: t.halo = ConvTune::HALO_FORCE_512; t.halo_order = ConvTune::ORDER_N_SLOW; break;   // (66 / 67 are irsde_bench_conv's own variants)
+        case 69: t.halo = ConvTune::HALO_FORCE_256; t.halo_order = ConvTune::ORDER_N_SLOW; break;
         case 70: t.zloop = ConvTune::ZLOOP_OFF; break;
         case 71: t.zloop = ConvTune::ZLOOP_ALL; break;
         case 72: t.zloop = ConvTune::ZLOOP_PAIRS; break;
@@ -274,6 +276,38 @@ void write_choice_line(const ConvChoice& c, char* out, int out_len) {
     snprintf(out, (size_t)out_len, "name=%s family=%d tile=%dx%d op=%d act=%d inscale=%d zbatch=%d zrows=%d grid=%ux%ux%u threads=%d lds=%d row=%d of %d",
              c.name().c_str(), (int)c.family, c.BM, c.BN, (int)c.op, (int)c.act, (int)c.inscale, c.zbatch, c.zrows, c.gx, c.gy, c.gz, c.threads, c.lds, c.row,
              conv_instance_count());
+}
+
+// The line irsde_debug_conv_halo_choice reports a HaloChoice with (irsde_debug_conv_features appends it to the choice line of a halo launch)
+void write_halo_line(const HaloChoice& h, char* out, int out_len) {
+    snprintf(out, (size_t)out_len, "kernel=halo%d bn=%d op=%d act=%d tiles=%dx%d nblk_n=%d nslow=%d grid=%u lds=%d instance=%d of %d", h.pixels, h.BN, h.op, h.act,
+             h.tiles_x, h.tiles_y, h.nblk_n, h.n_slow, h.grid, h.lds, h.instance, kHaloInstances);
+}
+
+// The layer the two host-only choice hooks describe: pixel strides = channel counts, every tensor stands for "present"
+ConvParams choice_hook_params(int B, int Hin, int Win, int C0, int C1, int Cout, int K, int stride, int pad, int in_shift, int operand, int storage, int pair,
+                              unsigned features, int splits, int nz) {
+    static const float dummy[4] = {};   // stands for every tensor: the choice reads which pointers are set, never what they point at
+    float* const some = const_cast<float*>(dummy);
+    auto bit = [&](int i) { return (features >> i & 1u) ? some : nullptr; };
+    ConvParams p;
+    p.in0 = some; p.C0 = C0; p.pix0 = C0; p.in1 = C1 ? some : nullptr; p.C1 = C1; p.pix1 = C1;
+    p.Hin = Hin; p.Win = Win; p.in_shift = in_shift;
+    p.w = some; p.Cout = Cout; p.KH = K; p.KW = K; p.stride = stride; p.pad_y = pad; p.pad_x = pad;
+    p.B = B;
+    p.Ho = ((Hin << in_shift) + 2 * pad - K) / stride + 1;
+    p.Wo = ((Win << in_shift) + 2 * pad - K) / stride + 1;
+    p.out = some; p.out_stride = Cout; p.res_stride = Cout; p.zeros = some;
+    p.bias = bit(0); p.film = bit(1); p.silu = bit(2) != nullptr; p.res = bit(3); p.in_scale = bit(4); p.ch_scale = bit(5);
+    p.gate = bit(6) != nullptr; p.shuffle = bit(7) != nullptr; p.ln_g = bit(8);
+    if (pair) p.w_pair = reinterpret_cast<const unsigned short*>(some);
+    else if (operand) p.w_bf = reinterpret_cast<const unsigned short*>(some);
+    p.f16 = operand == 2;
+    p.in_bf16 = p.out_bf16 = storage == 1;
+    p.in_f16 = p.out_f16 = storage == 2;
+    p.nz = nz;
+    if (splits > 1) { p.splits = splits; p.partial = some; }
+    return p;
 }
 
 // What irsde_debug_scam and irsde_debug_scam_full share; the projections run on the B x Hs x Ws map of each view.  In order: the argument check, the hook's own
@@ -776,26 +810,7 @@ int irsde_debug_conv_choice(int B, int Hin, int Win, int C0, int C1, int Cout, i
     return guard([&] {
         if (!out || out_len < 1 || K < 1 || stride < 1 || cu_count < 1 || operand < 0 || operand > 2 || storage < 0 || storage > 2 || (pair && operand == 0))
             throw HipError("debug_conv_choice: bad argument");
-        static const float dummy[4] = {};   // stands for every tensor: the choice reads which pointers are set, never what they point at
-        float* const some = const_cast<float*>(dummy);
-        auto bit = [&](int i) { return (features >> i & 1u) ? some : nullptr; };
-        ConvParams p;
-        p.in0 = some; p.C0 = C0; p.pix0 = C0; p.in1 = C1 ? some : nullptr; p.C1 = C1; p.pix1 = C1;
-        p.Hin = Hin; p.Win = Win; p.in_shift = in_shift;
-        p.w = some; p.Cout = Cout; p.KH = K; p.KW = K; p.stride = stride; p.pad_y = pad; p.pad_x = pad;
-        p.B = B;
-        p.Ho = ((Hin << in_shift) + 2 * pad - K) / stride + 1;
-        p.Wo = ((Win << in_shift) + 2 * pad - K) / stride + 1;
-        p.out = some; p.out_stride = Cout; p.res_stride = Cout; p.zeros = some;
-        p.bias = bit(0); p.film = bit(1); p.silu = bit(2) != nullptr; p.res = bit(3); p.in_scale = bit(4); p.ch_scale = bit(5);
-        p.gate = bit(6) != nullptr; p.shuffle = bit(7) != nullptr; p.ln_g = bit(8);
-        if (pair) p.w_pair = reinterpret_cast<const unsigned short*>(some);
-        else if (operand) p.w_bf = reinterpret_cast<const unsigned short*>(some);
-        p.f16 = operand == 2;
-        p.in_bf16 = p.out_bf16 = storage == 1;
-        p.in_f16 = p.out_f16 = storage == 2;
-        p.nz = nz;
-        if (splits > 1) { p.splits = splits; p.partial = some; }
+        const ConvParams p = choice_hook_params(B, Hin, Win, C0, C1, Cout, K, stride, pad, in_shift, operand, storage, pair, features, splits, nz);
         ConvKnobs k;
         static_assert(sizeof(ConvKnobs) == 11 * sizeof(int), "the hook's knob array is ConvKnobs, field by field");
         if (knobs) memcpy(&k, knobs, sizeof k);
@@ -804,6 +819,22 @@ int irsde_debug_conv_choice(int B, int Hin, int Win, int C0, int C1, int Cout, i
         const bool tabled = c.family != ConvChoice::NARROW3 && c.family != ConvChoice::HALO;
         if (tabled && c.row < 0) throw HipError("launch_conv: no kernel instance " + c.name());
         write_choice_line(c, out, out_len);
+    });
+}
+
+int irsde_debug_conv_halo_choice(int B, int Hin, int Win, int C0, int C1, int Cout, int K, int stride, int pad, int in_shift, int operand, int storage, int pair,
+                                 unsigned features, int splits, int nz, int tune, int halo2, int nslow, char* out, int out_len) {
+    return guard([&] {
+        if (!out || out_len < 1 || K < 1 || stride < 1 || operand < 0 || operand > 2 || storage < 0 || storage > 2 || (pair && operand == 0))
+            throw HipError("debug_conv_halo_choice: bad argument");
+        const ConvParams p = choice_hook_params(B, Hin, Win, C0, C1, Cout, K, stride, pad, in_shift, operand, storage, pair, features, splits, nz);
+        conv_validate(p);
+        const ConvTune t = conv_tune_from_code(tune);
+        // (no branch that conv_choose tries before the halo family takes a layer the family would: they want w_pair, f32 operands or nz > 1; the CU
+        //  count and the knobs do not reach this choice)
+        const ConvChoice c = conv_choose(p, t, ConvKnobs{}, 256);
+        if (c.family != ConvChoice::HALO) throw HipError("debug_conv_halo_choice: conv_choose does not send this layer to the halo family, but to " + c.name());
+        write_halo_line(conv_halo_choose(p, t, halo2, nslow), out, out_len);
     });
 }
 
@@ -907,6 +938,13 @@ int irsde_debug_conv_features(const float* in0, int C0, const float* in1, int C1
         else if (storage == 1) launch_bf16_to_f32(ao, out, nout, s);
         IRSDE_HIP_CHECK(hipStreamSynchronize(s));
         write_choice_line(c, choice, choice_len);
+        if (c.family == ConvChoice::HALO) {   // + the halo path's own choice for this launch
+            const size_t n = strlen(choice);
+            if (n + 2 < (size_t)choice_len) {
+                choice[n] = ' ';
+                write_halo_line(c.halo, choice + n + 1, choice_len - (int)n - 1);
+            }
+        }
     });
 }
 

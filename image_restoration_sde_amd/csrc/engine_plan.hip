@@ -86,7 +86,7 @@ struct Builder {
             std::string kernel;
             if (!naive) {
                 const ConvChoice c = conv_choose(p, ConvTune{}, conv_knobs_from_env(), device_cu_count());
-                if (c.family == ConvChoice::HALO) kernel = conv_halo2_wanted(p, 0) ? " kernel=halo512" : " kernel=halo256";
+                if (c.family == ConvChoice::HALO) kernel = conv_halo2_wanted(p) ? " kernel=halo512" : " kernel=halo256";
                 else launched = c.blocks(), kernel = " kernel=" + c.name();
             }
             char buf[256];

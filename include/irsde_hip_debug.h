@@ -55,7 +55,7 @@ int irsde_debug_conv(const float* in0, int C0, const float* in1, int C1, int B, 
  * Geometry as for irsde_debug_conv (K x K taps; pixel strides = channel counts, out_stride = Cout).  operand: 0 f32, 1 bf16, 2 fp16 (pair != 0: the pieces'
  * type, 1 or 2).  storage: 0 f32, 1 bf16, 2 fp16 tensors on both sides.  features: bit 0 bias, 1 film, 2 silu, 3 res, 4 in_scale, 5 ch_scale, 6 gate,
  * 7 shuffle, 8 ln_g.  splits > 1: split-K with a partial buffer.  nz: components of a batched launch.  tune: a tuning code of irsde_bench_conv (0 production
- * dispatch, 3 5 6 7 50 60 61 64 65 70 - 73).  cu_count: compute units of the device to choose for.  knobs: NULL = the default tuning knobs, else 11 ints in
+ * dispatch, 3 5 6 7 50 60 61 64 65 68 69 70 - 73; 68 / 69 = 64 / 65, the halo tile order is not part of this line).  cu_count: compute units of the device to choose for.  knobs: NULL = the default tuning knobs, else 11 ints in
  * the order IRSDE_SMALL_BN, _SMALL_BN_F32, _PAIR_TILE256, _PAIR_INSCALE256, _NO_BUFA, _ZLOOP, _ZLOOP_1X1, _ZLOOP_MAXNK, _ZLOOP_MINBLK, _ZLOOP_DEEP,
  * _ZLOOP_RAGGED64 (the environment is never read).  Writes one line into out:
  *   name=<kernel> family=<n> tile=<BM>x<BN> op=<n> act=<n> inscale=<0|1> zbatch=<n> zrows=<n> grid=<x>x<y>x<z> threads=<n> lds=<bytes> row=<instance> of <rows>
@@ -64,6 +64,16 @@ int irsde_debug_conv(const float* in0, int C0, const float* in1, int C1, int B, 
  * without a kernel instance, fails with launch_conv's message. */
 int irsde_debug_conv_choice(int B, int Hin, int Win, int C0, int C1, int Cout, int K, int stride, int pad, int in_shift, int operand, int storage, int pair,
                             unsigned features, int splits, int nz, int tune, int cu_count, const int* knobs, char* out, int out_len);
+
+/* Host-only test hook: what the halo path (csrc/conv_halo.hip: conv_halo_choose) would launch for one layer that conv_choose sends to family 4.  Never touches
+ * a device.  The layer as for irsde_debug_conv_choice (the CU count and the knobs do not reach this choice).  tune: 0 the production rules, 64 / 65 the
+ * 512- / 256-pixel kernel forced, 68 / 69 the same two with the output-channel blocks running slowest wherever the layer has more than one.  halo2, nslow: the
+ * values of IRSDE_HALO2 and IRSDE_HALO_NSLOW to choose under (the defaults are 1 and -1; the environment is never read).  Writes one line into out:
+ *   kernel=halo256|halo512 bn=<64|128> op=<2|3> act=<0|1> tiles=<x>x<y> nblk_n=<n> nslow=<0|1> grid=<n> lds=<bytes> instance=<i> of 9
+ * (instance: conv3x3_halo_bf16_kernel<128> / <64> on f32 tensors, on bf16 tensors, with fp16 operands, then conv3x3_halo2_kernel in the same three forms).
+ * A layer launch_conv refuses fails with its message, a layer of another family with one that names the family's kernel. */
+int irsde_debug_conv_halo_choice(int B, int Hin, int Win, int C0, int C1, int Cout, int K, int stride, int pad, int in_shift, int operand, int storage, int pair,
+                                 unsigned features, int splits, int nz, int tune, int halo2, int nslow, char* out, int out_len);
 
 /* Kernel-level test hook: ONE production launch_conv (csrc/conv_igemm.hip) with the whole ConvParams contract, in irsde_debug_conv_choice's language.
  * Geometry as for irsde_debug_conv (NHWC device tensors, in0 / in1 concat, in_shift, K x K taps).  operand / storage / pair as for irsde_debug_conv_choice; with
@@ -75,7 +85,9 @@ int irsde_debug_conv_choice(int B, int Hin, int Win, int C0, int C1, int Cout, i
  * PixelShuffle(2), then + res), ln_g (after the bias: channel LayerNorm, gain ln_g, eps 1e-5, then + res), else + res (out and res [B][Ho][Wo][Cout]).
  * nz > 1: a batched launch of nz 1x1 GEMMs (B = 1, Hin = 1, K = 1, one fp32 source): in0 [nz][Win][C0], w [nz][Cout][C0], out [nz][Win][Cout].
  * splits / tune / knobs as for irsde_debug_conv_choice; the knobs are handed to this one launch (no process-wide state).  choice receives
- * irsde_debug_conv_choice's line for the choice the launch made (the launch's own ConvChoice; the device's CU count).  Refused before anything is launched:
+ * irsde_debug_conv_choice's line for the choice the launch made (the launch's own ConvChoice; the device's CU count); a launch of family 4 appends the fields of
+ * irsde_debug_conv_halo_choice's line for its own HaloChoice (tune 64 / 65: the 512- / 256-pixel halo kernel forced, 68 / 69: the same with the
+ * output-channel blocks slowest).  Refused before anything is launched:
  * whatever conv_validate refuses, nz > 1 with another geometry, gate with shuffle / res / film, shuffle with film, gate_film without gate.  Tensors are
  * used at their exact extents.  Synchronises `stream`.  tests/test_gpu_conv_rows.py compares it with tests/conv_rows_oracle.py. */
 int irsde_debug_conv_features(const float* in0, int C0, const float* in1, int C1, int B, int Hin, int Win, int in_shift, const float* w_oihw, int Cout, int K,

@@ -69,7 +69,45 @@ def launch(c, t, L=None):
     got = got if nz > 1 else got.transpose(0, 3, 1, 2)
     if rc != 0:
         return got, L.irsde_last_error().decode()
-    return got, dict(kv.split("=") for kv in line.value.decode().replace(" of ", "/").split())
+    text = line.value.decode()
+    head, _, halo = text.partition(" kernel=")   # a launch of the halo family appends its own choice (irsde_debug_conv_halo_choice's line)
+    d = dict(kv.split("=") for kv in head.replace(" of ", "/").split())
+    if halo:
+        d["halo"] = "kernel=" + halo
+    return got, d
+
+
+def figures(c, got, ref, ref_full=None):
+    """What the bounds are asserted on ({name: value}): ref is the oracle with the roundings of the case's mode, ref_full the unrounded one (16-bit operands on
+    f32 tensors only)"""
+    st = OPERANDS[c["mode"][1]]
+    fig = {}
+    if st:
+        err = np.abs(got - ref)
+        fig["worst_excess"] = float((err - (np.abs(ref) * STORE_ULPS[st] + 1e-6)).max())
+        fig["share_differing"] = float((err > 0).mean())
+    else:
+        fig["relerr"] = R.relerr(got, ref)
+        if ref_full is not None:
+            fig["relerr_vs_full"] = R.relerr(got, ref_full)
+    return fig
+
+
+def assert_bounds(c, got, ref, fig):
+    """Every output element written, and the bound of the case's mode (the module docstring lists them)"""
+    operand, storage, pair = c["mode"]
+    ops = None if pair else OPERANDS[operand]
+    st = OPERANDS[storage]
+    assert got.shape == ref.shape and bool(np.isfinite(got).all()), c["name"]
+    if st:
+        assert np.array_equal(got, STORE_ROUND[st](got)), c["name"]   # what comes back was stored in the 16-bit type
+        assert fig["worst_excess"] <= 0, (c["name"], fig)
+        assert fig["share_differing"] < 0.02, (c["name"], fig)
+    else:
+        assert fig["relerr"] < (2e-4 if pair and operand == 1 else 2e-5), (c["name"], fig)
+        if ops:
+            lo, hi = BAND[ops]
+            assert lo < fig["relerr_vs_full"] < hi, (c["name"], fig)
 
 
 def check_case(c, L=None):
@@ -83,29 +121,11 @@ def check_case(c, L=None):
     ops = None if pair else OPERANDS[operand]
     st = OPERANDS[storage]
     ref = R.reference(c, t, operands=ops, storage=st)
-    fig = {}
-    written = bool(np.isfinite(got).all())
-    if st:
-        err = np.abs(got - ref)
-        fig["worst_excess"] = float((err - (np.abs(ref) * STORE_ULPS[st] + 1e-6)).max())
-        fig["share_differing"] = float((err > 0).mean())
-    else:
-        fig["relerr"] = R.relerr(got, ref)
-        if ops:
-            fig["relerr_vs_full"] = R.relerr(got, R.reference(c, t))
-    print("conv_rows %s row=%s chose=%s written=%d %s" % (c["name"], c["row"], d if isinstance(d, str) else d["name"] + ":" + d["row"], written,
+    fig = figures(c, got, ref, R.reference(c, t) if ops and not st else None)
+    print("conv_rows %s row=%s chose=%s written=%d %s" % (c["name"], c["row"], d if isinstance(d, str) else d["name"] + ":" + d["row"], bool(np.isfinite(got).all()),
                                                          " ".join("%s=%.3g" % kv for kv in sorted(fig.items()))))
     check_choice(c, d)
-    assert got.shape == ref.shape and written, c["name"]
-    if st:
-        assert np.array_equal(got, STORE_ROUND[st](got)), c["name"]   # what comes back was stored in the 16-bit type
-        assert fig["worst_excess"] <= 0, (c["name"], fig)
-        assert fig["share_differing"] < 0.02, (c["name"], fig)
-    else:
-        assert fig["relerr"] < (2e-4 if pair and operand == 1 else 2e-5), (c["name"], fig)
-        if ops:
-            lo, hi = BAND[ops]
-            assert lo < fig["relerr_vs_full"] < hi, (c["name"], fig)
+    assert_bounds(c, got, ref, fig)
     return fig
 
 
