@@ -509,4 +509,9 @@ void launch_philox_normal(float* out, int B, int CHW, int t, uint64_t seed, uint
 void eval_metrics(const float* out, const float* gt, int B, int C, int H, int W, int crop, double* sums_host, hipStream_t s);
 void tensor2img_u8(const float* in, unsigned char* out, int B, int C, int H, int W, hipStream_t s);
 
+// Degradation front ends (degrade.hip): bicubic upscale by an integer factor 1..8 (NCHW fp32 -> [B][C][H scale][W scale]) and the inpainting
+// composite mask * x + (1 - mask) with uint8 masks [Bm][Hm][Wm][Cm] resized by nearest interpolation.  Stream-ordered, no synchronisation.
+void upscale_bicubic(const float* in, float* out, int B, int C, int H, int W, int scale, hipStream_t s);
+void mask_to(const float* x, const unsigned char* masks, int Bm, int Hm, int Wm, int Cm, float* out, int B, int C, int H, int W, hipStream_t s);
+
 }  // namespace irsde

@@ -806,4 +806,25 @@ int irsde_tensor2img(const float* in, unsigned char* out, int B, int C, int H, i
     });
 }
 
+int irsde_upscale_bicubic(const float* in, float* out, int B, int C, int H, int W, int scale, void* stream) {
+    return guard([&] {
+        if (!in || !out) throw HipError("upscale_bicubic: null argument");
+        if (B < 1 || C < 1 || H < 1 || W < 1) throw HipError("upscale_bicubic: B, C, H, W must be positive");
+        if (scale < 1 || scale > 8) throw HipError("upscale_bicubic: scale must be an integer in 1..8");
+        if ((int64_t)H * scale > INT32_MAX || (int64_t)W * scale > INT32_MAX) throw HipError("upscale_bicubic: output side beyond 2^31 - 1");
+        upscale_bicubic(in, out, B, C, H, W, scale, reinterpret_cast<hipStream_t>(stream));
+    });
+}
+
+int irsde_mask_to(const float* x, const unsigned char* masks, int Bm, int Hm, int Wm, int Cm, float* out, int B, int C, int H, int W,
+                  void* stream) {
+    return guard([&] {
+        if (!x || !masks || !out) throw HipError("mask_to: null argument");
+        if (B < 1 || C < 1 || H < 1 || W < 1 || Hm < 1 || Wm < 1) throw HipError("mask_to: B, C, H, W, Hm, Wm must be positive");
+        if (Bm != 1 && Bm != B) throw HipError("mask_to: Bm must be 1 or B");
+        if (Cm != 1 && Cm != C) throw HipError("mask_to: Cm must be 1 or C");
+        mask_to(x, masks, Bm, Hm, Wm, Cm, out, B, C, H, W, reinterpret_cast<hipStream_t>(stream));
+    });
+}
+
 }  // extern "C"

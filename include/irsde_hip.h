@@ -57,6 +57,8 @@
  *        GEMM launches at most one block per compute unit and a block walks several tiles; same results bit for bit; tuning knob IRSDE_SPLIT3_WALK).
  *        Debug header only, same version: irsde_debug_split_gemm nplanes 47, irsde_bench_conv 500 - 504 (the three-piece GEMM keeps nine LDS-DMA wave-loads per
  *        wave in flight across every barrier of its K loop; same results bit for bit; the twin that drains them is the tuning knob IRSDE_SPLIT3_DRAIN).
+ *        Additive, same version: irsde_upscale_bicubic, irsde_mask_to (the degradation steps of the sisr / stereo-sr / inpainting test loops,
+ *        codes/utils/deg_utils.py; csrc/degrade.hip).  No engine is involved.
  */
 #ifndef IRSDE_HIP_H
 #define IRSDE_HIP_H
@@ -395,6 +397,23 @@ int irsde_eval_metrics(const float* out, const float* gt, int B, int C, int H, i
 /* util.tensor2img (img_utils.py:136-163) for a batch: device NCHW fp32 -> device [B][H][W][C] uint8 with the channel
  * order reversed (RGB -> BGR, what cv2.imwrite expects): clamp to [0,1], x255, round half to even. */
 int irsde_tensor2img(const float* in, unsigned char* out, int B, int C, int H, int W, void* stream);
+
+/* Replaces util.upscale(tensor, scale) (codes/utils/deg_utils.py:38-40: F.interpolate(tensor, scale_factor=scale, mode='bicubic')), the
+ * step before sde.noise_state(LQ) of codes/config/sisr/test.py:102 and, per view, of codes/config/stereo-sr/test.py:105-109.
+ * in: device NCHW fp32 [B][C][H][W]; out: device [B][C][H scale][W scale]; scale an integer in 1..8 (other factors and modes are not built).
+ * align_corners=False: output o samples at (o + 0.5) / scale - 0.5; cubic convolution with A = -0.75, tap indices clamped to the image,
+ * separable, result not clamped (overshoot beyond [0, 1] is kept, as the reference keeps it).  scale == 1 copies the input bit for bit.
+ * Stream-ordered, no synchronisation.  IRSDE_ERR_INVALID: null pointer, non-positive size, scale outside 1..8. */
+int irsde_upscale_bicubic(const float* in, float* out, int B, int C, int H, int W, int scale, void* stream);
+
+/* Replaces the arithmetic of util.mask_to (codes/utils/deg_utils.py:30-34), the step before sde.noise_state(LQ) of
+ * codes/config/inpainting/test.py:103: mask = F.interpolate(torch.tensor(masks / 255.).permute(0, 3, 1, 2).float(), size=(H, W),
+ * mode='nearest'); out = mask * x + (1. - mask), one fp32 multiply, subtract and add in that order.
+ * x, out: device NCHW fp32 [B][C][H][W] (out may be x).  masks: device uint8 [Bm][Hm][Wm][Cm] as cv2.imread lays them out, Bm = 1 (one
+ * mask for the batch) or B, Cm = 1 or C; mask channel k goes with tensor channel k (no BGR / RGB reorder, as in the reference).
+ * Stream-ordered, no synchronisation.  IRSDE_ERR_INVALID: null pointer, non-positive size, Bm not in {1, B}, Cm not in {1, C}. */
+int irsde_mask_to(const float* x, const unsigned char* masks, int Bm, int Hm, int Wm, int Cm, float* out, int B, int C, int H, int W,
+                  void* stream);
 
 #ifdef __cplusplus
 }

@@ -29,6 +29,26 @@ image (no border crop, as there) and averaged:
 Its stated differences: equal-sized images are batched; the restored image is written as .png where test.py writes .tif without a suffix; the
 noise is the library's keyed Philox draw (`denoising_sde.add_noise`, key = (--seed, global image index)), so the result does not depend on
 batching or on the rank count; LPIPS is not computed — its AlexNet weights are not available here.
+
+`--task sisr | inpainting | stereo-sr` are the loops of codes/config/{sisr,inpainting,stereo-sr}/test.py, which put a degradation step of
+codes/utils/deg_utils.py in front of `sde.noise_state(LQ)`; here that step runs on the device (`degradations.upscale` / `mask_to`,
+csrc/degrade.hip), and the rest is the LQ / GT loop above:
+
+    python tools/eval_folder.py --task sisr --lq DIV2K/LR_x4 --gt DIV2K/HR --scale 4 --max-sigma 30 --weights sisr.pth --out results/sisr
+    python tools/eval_folder.py --task inpainting --gt celebaHQ/testHQ --mask-root gt_keep_masks/thin --max-sigma 30 --weights inp.pth
+    python tools/eval_folder.py --task stereo-sr --lq Flickr1024/LR_x4 --gt Flickr1024/HR --max-sigma 30 --weights stereo.pth \
+        --naf-width 64 --naf-enc 1,1,1,28 [--model unet --nf 64 --depth 4] [--wide-rows]
+
+    sisr       sisr/test.py:102        LQ = util.upscale(LQ, scale): bicubic by --scale; PSNR / SSIM on RGB and Y, cropped as above
+    inpainting inpainting/test.py:103  LQ = util.mask_to(GT, mask_root, mask_id=i), i the global image index -> '%06d.png' % i
+    stereo-sr  stereo-sr/test.py:105-126  --lq (and --gt) hold L / R files, paired in sorted order as StereoLQ_dataset.py:66-67 pairs them
+               (2i, 2i + 1); each view is upscaled x4 (the factor is hard-coded there), the pair [L | R] is sampled by the stereo network,
+               and the output is chunked into L / R for the images and for PSNR / SSIM per view (RGB only, no border crop, as there)
+The sampler defaults to `--mode sde`: these task directories' `denoising_model.test` hard-codes `reverse_sde` (stereo-sr: or `reverse_ode` with
+perform_ode = `--mode ode`).  Their stated differences, beyond those of the LQ / GT loop (batching, sharding, PIL, no LPIPS, the per-image
+seeded `noise_state` draw): the degraded LQ lives on the device, so the noise is drawn on the CPU as before and added there; inpainting does not
+write the intermediate states (`save_states=True` in inpainting/test.py:108); stereo-sr names the right view's files after the right view's own
+file instead of `img_name.replace('L', 'R')`, and also writes <name>_LQ.png / <name>_HQ.png per view.
 """
 import argparse
 import os
@@ -169,12 +189,127 @@ def run_denoising(a, P, torch, np, dev, world, rank, log):
     return summary
 
 
-def main(argv=None):
+DEGRADED_TASKS = ("sisr", "inpainting", "stereo-sr")
+
+
+def run_degraded(a, P, torch, np, dev, world, rank, log, crop_border, on_batch=None):
+    """The sisr / inpainting / stereo-sr loops: the degradation step of `P.degradations` on the device, then the LQ / GT loop's noise,
+    sampler, images and metrics.  `on_batch(global_indices, LQ, output)` receives every batch's device tensors."""
+    stereo = a.task == "stereo-sr"
+    if stereo:
+        if a.model == "nafnet":
+            net = {"which_model_G": "ConditionalNAFNet",
+                   "setting": dict(img_channel=3, width=a.naf_width, enc_blk_nums=_ints(a.naf_enc), middle_blk_num=a.naf_mid, dec_blk_nums=_ints(a.naf_dec))}
+        else:
+            net = {"which_model_G": "ConditionalUNet", "setting": dict(in_nc=3, out_nc=3, nf=a.nf, depth=a.depth)}
+        opt = {"model": "denoising", "network_G": net, "path": {"pretrain_model_G": a.weights, "strict_load": True}}
+        with torch.cuda.device(dev):
+            wrapper = P.create_model(opt, task="stereo-sr")
+        model = wrapper.model.eval()
+        if a.wide_rows:
+            model.set_wide_rows()
+    else:
+        model = build_model(a, P, torch).to(dev).eval()
+    if a.dtype != "fp32":
+        model.set_compute_dtype(a.dtype)
+    sde = P.IRSDE(max_sigma=a.max_sigma, T=a.T, schedule=a.schedule, eps=a.eps, device=dev)
+    sde.set_model(model)
+    sde.seed = a.seed
+
+    per = 2 if stereo else 1   # files per dataset item: stereo-sr pairs files 2i, 2i + 1 of the sorted list (StereoLQ_dataset.py:66-67)
+    src = list_images(a.gt if a.task == "inpainting" else a.lq)
+    gts = list_images(a.gt) if a.gt is not None else None
+    if gts is not None and len(gts) != len(src):
+        raise ValueError("GT and LQ datasets have different number of images - %d, %d" % (len(gts), len(src)))
+    if len(src) % per:
+        raise ValueError("stereo-sr needs an even number of images (L / R pairs in sorted order), not %d" % len(src))
+    n_items = len(src) // per
+    lo, hi = P.shard_bounds(n_items, world, rank)
+    mine = list(range(lo, hi))
+
+    def item(paths, i):   # [C, H, W]; stereo: cat([L, R], 0) (StereoLQ_dataset.py:87)
+        return np.concatenate([read_img(paths[per * i + v]) for v in range(per)], axis=0)
+
+    src_np = [item(src, i) for i in mine]
+    res = {"psnr": [], "ssim": []} if stereo else {"psnr": [], "ssim": [], "psnr_y": [], "ssim_y": []}
+    times = []
+    fn = {"sde": sde.reverse_sde, "ode": sde.reverse_ode, "posterior": sde.reverse_posterior}[a.mode]
+    for grp in batches_of_equal_size(mine, [x.shape for x in src_np], a.batch):
+        idx = [mine[j] for j in grp]
+        x = torch.from_numpy(np.stack([src_np[j] for j in grp])).to(dev)
+        GT = None
+        if a.task == "sisr":
+            LQ = P.degradations.upscale(x, a.scale)                        # util.upscale(LQ, scale), sisr/test.py:102
+        elif stereo:
+            LQ = torch.cat([P.degradations.upscale(v, 4) for v in x.chunk(2, dim=1)], dim=1)   # stereo-sr/test.py:105-108
+        else:
+            GT = x
+            LQ = torch.cat([P.degradations.mask_to(x[n:n + 1], a.mask_root, mask_id=i) for n, i in enumerate(idx)])  # mask_id = i, inpainting/test.py:103
+        if GT is None and gts is not None:
+            GT = torch.from_numpy(np.stack([item(gts, i) for i in idx])).to(dev)
+        noise = torch.stack([torch.randn(LQ.shape[1:], generator=torch.Generator().manual_seed(a.seed * 1000003 + i)) for i in idx])
+        noisy_state = LQ + (noise * sde.max_sigma).to(dev)                 # IRSDE.noise_state (sde_utils.py:360-361)
+        sde.image_offset = idx[0]
+        sde.set_mu(LQ)
+        torch.cuda.synchronize()
+        tic = time.time()
+        out = fn(noisy_state)
+        torch.cuda.synchronize()
+        times.append((time.time() - tic) / len(grp))
+        if on_batch is not None:
+            on_batch(idx, LQ, out)
+        # views of a batch as images: stereo-sr chunks the pair into L / R (stereo-sr/test.py:119-126)
+        views = (lambda t: torch.cat(t.chunk(2, dim=1), dim=0)) if stereo else (lambda t: t)
+        nb = len(grp)
+        names = [[os.path.splitext(os.path.basename((gts or src)[per * i + v]))[0] for i in idx] for v in range(per)]
+        if GT is not None:
+            m = P.metrics.evaluate_batch(views(out), views(GT), crop_border=0 if stereo else crop_border)   # stereo-sr/test.py:139-140: no crop
+            for n in range(nb):
+                for v in range(per):
+                    k = v * nb + n
+                    for key in res:
+                        res[key].append(float(m[key][k]))
+                    if stereo:
+                        log("img:%-15s - PSNR: %.6f dB; SSIM: %.6f." % (names[v][n], m["psnr"][k], m["ssim"][k]))
+                    else:
+                        log("img%3d:%-15s - PSNR: %.6f dB; SSIM: %.6f; PSNR_Y: %.6f dB; SSIM_Y: %.6f." %
+                            (idx[n], names[v][n], m["psnr"][k], m["ssim"][k], m["psnr_y"][k], m["ssim_y"][k]))
+        if a.out:
+            imgs = P.metrics.tensor2img_batch(views(out))
+            lqi = P.metrics.tensor2img_batch(views(LQ))
+            gti = P.metrics.tensor2img_batch(views(GT)) if GT is not None else None
+            for n in range(nb):
+                for v in range(per):
+                    k = v * nb + n
+                    save_img(imgs[k], os.path.join(a.out, names[v][n] + ".png"))
+                    save_img(lqi[k], os.path.join(a.out, names[v][n] + "_LQ.png"))
+                    if gti is not None:
+                        save_img(gti[k], os.path.join(a.out, names[v][n] + "_HQ.png"))
+    summary = None
+    if res["psnr"] or (world > 1 and (gts is not None or a.task == "inpainting")):
+        summary = P.metrics.reduce_metrics({k: np.asarray(v, dtype=np.float64) for k, v in res.items()})
+    if rank == 0 and summary is not None:
+        log("----Average PSNR/SSIM results for %s----\n\tPSNR: %.6f dB; SSIM: %.6f\n" %
+            (os.path.basename(os.path.normpath(a.gt if a.task == "inpainting" else a.lq)), summary["psnr"], summary["ssim"]))
+        if not stereo:
+            log("----Y channel, average PSNR/SSIM----\n\tPSNR_Y: %.6f dB; SSIM_Y: %.6f\n" % (summary["psnr_y"], summary["ssim_y"]))
+    if rank == 0 and times:
+        log("average test time per image: %.4f s (rank 0, %d images over %d rank(s))" % (float(np.mean(times)), n_items, world))
+    return summary
+
+
+def main(argv=None, on_batch=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--task", default=None, choices=["denoising"], help="denoising: the denoising-sde loop (clean --gt folder + --sigma, DenoisingSDE, "
-                    "reverse_ode from the optimal timestep; PSNR / SSIM, no LPIPS: its AlexNet weights are not available).  Absent: the LQ / GT loop")
-    ap.add_argument("--lq", default=None, help="degraded images (required unless --task denoising)")
+    ap.add_argument("--task", default=None, choices=["denoising", "sisr", "inpainting", "stereo-sr"],
+                    help="denoising: the denoising-sde loop (clean --gt folder + --sigma, DenoisingSDE, "
+                    "reverse_ode from the optimal timestep; PSNR / SSIM, no LPIPS: its AlexNet weights are not available).  sisr: --lq is the low-resolution "
+                    "folder, bicubic upscale by --scale on the device, then the LQ / GT loop with the reverse-SDE sampler.  inpainting: --gt + --mask-root, "
+                    "mask_to with the image index as mask id.  stereo-sr: --lq holds L / R files paired in sorted order, x4 upscale per view, the stereo "
+                    "ConditionalNAFNet (--naf-*) or, with --model unet, the stereo ConditionalUNet.  Absent: the LQ / GT loop")
+    ap.add_argument("--lq", default=None, help="degraded images (required unless --task denoising / inpainting)")
     ap.add_argument("--gt", default=None)
+    ap.add_argument("--mask-root", default=None, help="--task inpainting: folder of the '%%06d.png' keep-masks (opt['degradation']['mask_root'])")
+    ap.add_argument("--wide-rows", action="store_true", help="--task stereo-sr: set_wide_rows(), views wider than the SCAM strip kernels hold")
     ap.add_argument("--sigma", type=float, default=15, help="--task denoising: opt['degradation']['sigma'] (/ 255 when > 1)")
     ap.add_argument("--arch", default="nafnet", choices=["nafnet", "unet"], help="--task denoising: denoising_sde.ConditionalNAFNet (refusion.yml) "
                     "or denoising_sde.ConditionalUNet (ir-sde.yml; --nf / --depth)")
@@ -184,14 +319,15 @@ def main(argv=None):
     ap.add_argument("--naf-dec", default="1,1,1,1")
     ap.add_argument("--weights", required=True, help="reference checkpoint (state_dict .pth, optional 'module.' prefixes)")
     ap.add_argument("--out", default=None, help="results folder: <name>.png, <name>_LQ.png, <name>_HQ.png as test.py:118-128")
-    ap.add_argument("--model", default="unet", choices=["unet", "nafnet"])
+    ap.add_argument("--model", default=None, choices=["unet", "nafnet"], help="default unet; --task stereo-sr: default nafnet (the stereo ConditionalNAFNet, --naf-*)")
     ap.add_argument("--nf", type=int, default=64)
     ap.add_argument("--depth", type=int, default=4)
     ap.add_argument("--max-sigma", type=float, default=10)
     ap.add_argument("--T", type=int, default=100)
     ap.add_argument("--schedule", default="cosine")
     ap.add_argument("--eps", type=float, default=0.005)
-    ap.add_argument("--mode", default="posterior", choices=["sde", "ode", "posterior"])
+    ap.add_argument("--mode", default=None, choices=["sde", "ode", "posterior"], help="default posterior; --task sisr / inpainting / stereo-sr: default sde "
+                    "(their denoising_model.test runs reverse_sde)")
     ap.add_argument("--crop-border", type=int, default=None, help="opt['crop_border']; unset / 0 falls back to --scale exactly as test.py:134 does")
     ap.add_argument("--scale", type=int, default=4, help="opt['degradation']['scale'] (deraining options/test/ir-sde.yml:20 sets 4 and no crop_border, "
                     "so the published Rain100H PSNR / SSIM are computed on images cropped by 4 px)")
@@ -207,6 +343,16 @@ def main(argv=None):
         ap.error("the following arguments are required: --lq")
     if a.task == "denoising" and a.gt is None:
         ap.error("--task denoising needs the clean images: --gt")
+    if a.task in ("sisr", "stereo-sr") and a.lq is None:
+        ap.error("--task %s needs the low-resolution images: --lq" % a.task)
+    if a.task == "inpainting" and (a.gt is None or a.mask_root is None):
+        ap.error("--task inpainting needs the clean images and the masks: --gt, --mask-root")
+    if a.task == "stereo-sr" and a.mode == "posterior":
+        ap.error("--task stereo-sr samples with --mode sde or ode (stereo-sr/models/denoising_model.py: reverse_sde, or reverse_ode with perform_ode)")
+    if a.mode is None:
+        a.mode = "sde" if a.task in DEGRADED_TASKS else "posterior"
+    if a.model is None:
+        a.model = "nafnet" if a.task == "stereo-sr" else "unet"
     crop_border = a.crop_border if a.crop_border else a.scale   # test.py:134: `opt["crop_border"] if opt["crop_border"] else scale`
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -235,6 +381,11 @@ def main(argv=None):
 
     if a.task == "denoising":
         summary = run_denoising(a, P, torch, np, dev, world, rank, (lambda *s: print(*s, flush=True)))
+        if world > 1:
+            dist.destroy_process_group()
+        return summary
+    if a.task in DEGRADED_TASKS:
+        summary = run_degraded(a, P, torch, np, dev, world, rank, (lambda *s: print(*s, flush=True)), crop_border, on_batch)
         if world > 1:
             dist.destroy_process_group()
         return summary
