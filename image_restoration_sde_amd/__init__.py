@@ -17,7 +17,8 @@ csrc/ -> libirsde_hip.so) with the reference's own Python interface on top:
     stereo_sr.ConditionalUNet
                        codes/config/stereo-sr/models/modules/DenoisingUNet_arch.py (the IR-SDE UNet with a full-resolution SCAM on every level)
     metrics            codes/utils/img_utils.py:136-234 + codes/data/util.py:177-198 (tensor2img / PSNR / SSIM / Y channel)
-    degradations       codes/utils/deg_utils.py (upscale: bicubic by an integer factor; mask_to: the inpainting composite; add_noise)
+    degradations       codes/utils/deg_utils.py (upscale: bicubic by an integer factor; mask_to: the inpainting composite; add_noise) +
+                       codes/data/util.py:221-387 (imresize: the MATLAB-style antialiased cubic downscale that makes LQ from GT; modcrop)
 """
 from ._lib import IrsdeError, IrsdeLibraryError, build_library  # noqa: F401
 from .denoising_model import DenoisingModel, ReverseSDEDenoisingModel, create_model, define_G  # noqa: F401

@@ -513,5 +513,9 @@ void tensor2img_u8(const float* in, unsigned char* out, int B, int C, int H, int
 // composite mask * x + (1 - mask) with uint8 masks [Bm][Hm][Wm][Cm] resized by nearest interpolation.  Stream-ordered, no synchronisation.
 void upscale_bicubic(const float* in, float* out, int B, int C, int H, int W, int scale, hipStream_t s);
 void mask_to(const float* x, const unsigned char* masks, int Bm, int Hm, int Wm, int Cm, float* out, int B, int C, int H, int W, hipStream_t s);
+// imresize (codes/data/util.py:305-387): NCHW fp32 [B][C][H][W] -> [B][C][Ho][Wo] through per-axis device tables wH[Ho][KH] / sH[Ho] and
+// wW[Wo][KW] / sW[Wo] (weights and the image coordinate of each output's first tap; out-of-image taps read the symmetric extension); H pass first.
+void imresize(const float* in, float* out, int B, int C, int H, int W, int Ho, int Wo, const float* wH, const int* sH, int KH, const float* wW,
+              const int* sW, int KW, hipStream_t s);
 
 }  // namespace irsde

@@ -4,6 +4,8 @@
 // Both are streaming kernels on NCHW fp32: the upscale writes s^2 times what it reads, the composite reads and writes one float per element.
 // This file is compiled with -ffp-contract=off: the composite keeps the reference's multiply / subtract / add as three roundings.  The
 // upscale's filter sums are explicit fmaf chains (its contract is the 1e-5 parity with the float64 restatement, not an op order).
+//   imresize (codes/data/util.py:238-387)  the antialiased cubic downscale that makes LQ from GT (LQGT_dataset.py:106-130): one table-driven
+//   kernel, H pass into LDS, W pass out; explicit fmaf chains in tap order as well.
 #include "common.h"
 
 namespace irsde {
@@ -157,6 +159,118 @@ __global__ void __launch_bounds__(256) mask_to_kernel(const float* __restrict__ 
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// imresize (codes/data/util.py:305-387), the MATLAB-style separable cubic resize that makes LQ from GT.  Table-driven: the host builds, per
+// axis, weights w[n_out][K] and the 0-based image coordinate start[n_out] of each output's first tap (degradations.imresize_tables, the
+// reference's own float32 values), so one kernel serves every scale and both antialiasing settings.  A tap at p < 0 reads pixel -p - 1, a
+// tap at p >= n reads 2 n - 1 - p: the reference's symmetric border copies, taken in place.
+//
+// A work-group owns TY x IMR_TX outputs of one plane.  As in the reference the H axis is filtered first: for the tile's TY output rows
+// and the columns [sW[x0], sW[x1 - 1] + KW) its W filters reach (the start table is non-decreasing), lanes on consecutive columns sum KH
+// rows of the input into LDS — the reference's out_1, which never reaches memory; a reflected column of out_1 is the H filter of the
+// reflected input column, bit for bit.  The W pass then sums KW neighbours of an LDS row per output.  Every sum is w[0] v[0] followed by
+// fmaf in tap order; the values of four taps are fetched before their four fmaf, so that four loads are in flight, not one.
+// ---------------------------------------------------------------------------------------------
+constexpr int IMR_THREADS = 256, IMR_TX = 32, IMR_TY = 16, IMR_TAPS = 32, IMR_MID = 4608;   // LDS: 18 KB of H-pass rows + 6.3 KB of tables
+
+__device__ __forceinline__ int imr_reflect(int p, int n) {
+    p = p < 0 ? -p - 1 : p;
+    p = p >= n ? 2 * n - 1 - p : p;
+    return min(max(p, 0), n - 1);   // no table that imresize_tables accepts reaches this clamp; it keeps any other table inside the plane
+}
+
+// w[0] ld(0), then fmaf(w[k], ld(k), .) for k = 1 .. K - 1
+template <class Ld>
+__device__ __forceinline__ float imr_sum(const float* w, int K, Ld ld) {
+    float a;
+    int k;
+    if (K >= 4) {
+        const float v0 = ld(0), v1 = ld(1), v2 = ld(2), v3 = ld(3);
+        a = fmaf(w[3], v3, fmaf(w[2], v2, fmaf(w[1], v1, w[0] * v0)));
+        k = 4;
+    } else {
+        a = w[0] * ld(0);
+        k = 1;
+    }
+    for (; k + 4 <= K; k += 4) {
+        const float v0 = ld(k), v1 = ld(k + 1), v2 = ld(k + 2), v3 = ld(k + 3);
+        a = fmaf(w[k + 3], v3, fmaf(w[k + 2], v2, fmaf(w[k + 1], v1, fmaf(w[k], v0, a))));
+    }
+    for (; k < K; ++k) a = fmaf(w[k], ld(k), a);
+    return a;
+}
+
+__global__ void __launch_bounds__(IMR_THREADS) imresize_kernel(const float* __restrict__ in, float* __restrict__ out, int H, int W, int Ho, int Wo,
+                                                               const float* __restrict__ wH, const int* __restrict__ sH, int KH,
+                                                               const float* __restrict__ wW, const int* __restrict__ sW, int KW, int TY,
+                                                               int tiles_x, int tiles_y, int vec) {
+    __shared__ __attribute__((aligned(16))) float wHs[IMR_TY][IMR_TAPS];
+    __shared__ float wWs[IMR_TX][IMR_TAPS + 1];   // + 1: lanes of the W pass read one column of different rows
+    __shared__ int sHs[IMR_TY], sWs[IMR_TX];
+    __shared__ float mid[IMR_MID];
+    const int tid = threadIdx.x;
+    const int tx = blockIdx.x % tiles_x;
+    const int ty = (blockIdx.x / tiles_x) % tiles_y;
+    const size_t plane = blockIdx.x / ((size_t)tiles_x * tiles_y);
+    const int y0 = ty * TY, x0 = tx * IMR_TX;
+    const int ny = min(TY, Ho - y0), nx = min(IMR_TX, Wo - x0);
+    const float* src = in + plane * (size_t)H * W;
+    float* dst = out + plane * (size_t)Ho * Wo;
+
+    for (int e = tid; e < ny * KH; e += IMR_THREADS) {
+        const int r = e / KH, k = e - r * KH;
+        wHs[r][k] = wH[(size_t)(y0 + r) * KH + k];
+    }
+    for (int e = tid; e < nx * KW; e += IMR_THREADS) {
+        const int j = e / KW, l = e - j * KW;
+        wWs[j][l] = wW[(size_t)(x0 + j) * KW + l];
+    }
+    if (tid < ny) sHs[tid] = sH[y0 + tid];
+    if (tid < nx) sWs[tid] = sW[x0 + tid];
+    __syncthreads();
+    const int c0 = sWs[0];
+    const long long span64 = (long long)sWs[nx - 1] + KW - c0;
+    // the launcher sizes TY so that the tile's rows fit; a start table that decreases or jumps is not one of imresize_tables', and the whole
+    // group leaves before it could index past `mid`
+    if (span64 < KW || ny * span64 > IMR_MID) return;
+    const int span = (int)span64;
+    for (int e = tid; e < ny * span; e += IMR_THREADS) {
+        const int r = e / span, c = e - r * span;
+        const float* col = src + imr_reflect(c0 + c, W);
+        const int ys = sHs[r];
+        float a;
+        if (ys >= 0 && ys <= H - KH) {                          // every tap inside the image: rows ys .. ys + KH - 1
+            const float* p = col + (size_t)ys * W;
+            a = imr_sum(wHs[r], KH, [&](int k) { return p[(size_t)k * W]; });
+        } else {
+            a = imr_sum(wHs[r], KH, [&](int k) { return col[(size_t)imr_reflect(ys + k, H) * W]; });
+        }
+        mid[e] = a;                                             // mid[r][c], rows of `span` floats
+    }
+    __syncthreads();
+    if (vec) {
+        constexpr int GW = IMR_TX / 4;   // 16-byte pieces per tile row
+        for (int g = tid; g < ny * GW; g += IMR_THREADS) {
+            const int r = g / GW, j4 = (g - r * GW) * 4;
+            if (j4 >= nx) continue;                             // Wo % 4 == 0 here: a piece never straddles the edge
+            f32x4 o;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const float* m = mid + r * span + min(max(sWs[j4 + q] - c0, 0), span - KW);
+                o[q] = imr_sum(wWs[j4 + q], KW, [&](int l) { return m[l]; });
+            }
+            *reinterpret_cast<f32x4*>(dst + (size_t)(y0 + r) * Wo + x0 + j4) = o;
+        }
+    } else {
+        for (int e = tid; e < ny * IMR_TX; e += IMR_THREADS) {
+            const int r = e / IMR_TX, j = e - r * IMR_TX;
+            if (j >= nx) continue;
+            const float* m = mid + r * span + min(max(sWs[j] - c0, 0), span - KW);
+            dst[(size_t)(y0 + r) * Wo + x0 + j] = imr_sum(wWs[j], KW, [&](int l) { return m[l]; });
+        }
+    }
+}
+
 }  // namespace
 
 void upscale_bicubic(const float* in, float* out, int B, int C, int H, int W, int scale, hipStream_t s) {
@@ -183,6 +297,25 @@ void mask_to(const float* x, const unsigned char* masks, int Bm, int Hm, int Wm,
     if (blocks > 0x7fffffffull) throw HipError("mask_to: too many elements for one launch");
     const int vec = (W % 4 == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out)) & 15) == 0) ? 1 : 0;
     hipLaunchKernelGGL(mask_to_kernel, dim3((unsigned)blocks), dim3(256), 0, s, x, masks, Bm, Hm, Wm, Cm, out, B, C, H, W, vec);
+    IRSDE_HIP_CHECK(hipGetLastError());
+}
+
+void imresize(const float* in, float* out, int B, int C, int H, int W, int Ho, int Wo, const float* wH, const int* sH, int KH, const float* wW,
+              const int* sW, int KW, hipStream_t s) {
+    if (KH < 1 || KH > IMR_TAPS || KW < 1 || KW > IMR_TAPS) throw HipError("imresize: taps per output must be in 1..32");
+    // Columns the H pass of a tile covers: its nx outputs' centres lie (nx - 1) / scale apart and Wo = ceil(W scale) gives 1 / scale < W / (Wo - 1);
+    // the floor of the start adds at most one, the last output's own taps KW.  At K = 32 (scale 1/8) this is up to 290 columns: 15 rows of them.
+    const int nx = Wo < IMR_TX ? Wo : IMR_TX;
+    const long long span = (nx > 1 ? ((long long)(nx - 1) * W + Wo - 2) / (Wo - 1) : 0) + KW + 1;
+    if (span > IMR_MID) throw HipError("imresize: Wo is too small for W (one row of a tile's H pass does not fit the LDS rows)");
+    const int fit = (int)(IMR_MID / span);
+    const int TY = fit < IMR_TY ? fit : IMR_TY;
+    const int tiles_x = (Wo + IMR_TX - 1) / IMR_TX, tiles_y = (Ho + TY - 1) / TY;
+    const size_t blocks = (size_t)B * C * tiles_x * tiles_y;
+    if (blocks > 0x7fffffffull) throw HipError("imresize: too many tiles for one launch");
+    const int vec = (Wo % 4 == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0) ? 1 : 0;
+    hipLaunchKernelGGL(imresize_kernel, dim3((unsigned)blocks), dim3(IMR_THREADS), 0, s, in, out, H, W, Ho, Wo, wH, sH, KH, wW, sW, KW, TY, tiles_x,
+                       tiles_y, vec);
     IRSDE_HIP_CHECK(hipGetLastError());
 }
 

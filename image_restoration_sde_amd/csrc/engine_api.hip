@@ -827,4 +827,15 @@ int irsde_mask_to(const float* x, const unsigned char* masks, int Bm, int Hm, in
     });
 }
 
+int irsde_imresize(const float* in, float* out, int B, int C, int H, int W, int Ho, int Wo, const float* wH, const int* sH, int KH,
+                   const float* wW, const int* sW, int KW, void* stream) {
+    return guard([&] {
+        if (!in || !out || !wH || !sH || !wW || !sW) throw HipError("imresize: null argument");
+        if (B < 1 || C < 1 || H < 1 || W < 1 || Ho < 1 || Wo < 1) throw HipError("imresize: B, C, H, W, Ho, Wo must be positive");
+        if (KH < 1 || KH > 32 || KW < 1 || KW > 32) throw HipError("imresize: KH and KW, the taps per output, must be in 1..32");
+        if (H > (1 << 30) || W > (1 << 30)) throw HipError("imresize: input side beyond 2^30");
+        imresize(in, out, B, C, H, W, Ho, Wo, wH, sH, KH, wW, sW, KW, reinterpret_cast<hipStream_t>(stream));
+    });
+}
+
 }  // extern "C"

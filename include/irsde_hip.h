@@ -59,6 +59,8 @@
  *        wave in flight across every barrier of its K loop; same results bit for bit; the twin that drains them is the tuning knob IRSDE_SPLIT3_DRAIN).
  *        Additive, same version: irsde_upscale_bicubic, irsde_mask_to (the degradation steps of the sisr / stereo-sr / inpainting test loops,
  *        codes/utils/deg_utils.py; csrc/degrade.hip).  No engine is involved.
+ *        Additive, same version: irsde_imresize (util.imresize of codes/data/util.py:238-387, the antialiased cubic downscale with which
+ *        LQGT_dataset makes LQ from GT; csrc/degrade.hip).  No engine is involved.
  */
 #ifndef IRSDE_HIP_H
 #define IRSDE_HIP_H
@@ -414,6 +416,22 @@ int irsde_upscale_bicubic(const float* in, float* out, int B, int C, int H, int 
  * Stream-ordered, no synchronisation.  IRSDE_ERR_INVALID: null pointer, non-positive size, Bm not in {1, B}, Cm not in {1, C}. */
 int irsde_mask_to(const float* x, const unsigned char* masks, int Bm, int Hm, int Wm, int Cm, float* out, int B, int C, int H, int W,
                   void* stream);
+
+/* Replaces util.imresize(img, scale, antialiasing) (codes/data/util.py:305-387), the MATLAB-style separable cubic resize by which
+ * LQGT_dataset.py:106-130 makes the LQ image from GT.  The filter comes in per-axis tables, which the caller builds as
+ * calculate_weights_indices does (util.py:251-303; degradations.imresize_tables); all pointers are device pointers.
+ * in: NCHW fp32 [B][C][H][W]; out: [B][C][Ho][Wo].
+ * Table layout, per axis (H: wH, sH, KH over Ho outputs; W: wW, sW, KW over Wo outputs): w is fp32 [n_out][K], row i the K weights of output i in
+ * tap order; s is int32 [n_out], s[i] the 0-based image coordinate of output i's first tap, non-decreasing in i, possibly negative.  Tap k of
+ * output i reads coordinate p = s[i] + k.
+ * Reflection rule: p < 0 reads pixel -p - 1 and p >= n reads pixel 2 n - 1 - p (the symmetric extension that repeats the edge pixel,
+ * util.py:342-353); tables must keep every p within [-n, 2 n - 1], and the starts must spread over the axis as a resize spreads them
+ * (s[i + 31] - s[i] <= ceil(31 n / (n_out - 1)) + 1, which holds for n_out = ceil(n scale)): tiles of other tables are left unwritten.
+ * The H axis is filtered first, as in the reference; every filter sum is w[0] v[0] followed by fmaf in tap order; the result is not clamped.
+ * One launch, no intermediate tensor.  Stream-ordered, no synchronisation.
+ * IRSDE_ERR_INVALID: null pointer, non-positive size, KH or KW (taps per output) outside 1..32. */
+int irsde_imresize(const float* in, float* out, int B, int C, int H, int W, int Ho, int Wo, const float* wH, const int* sH, int KH,
+                   const float* wW, const int* sW, int KW, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,5 +1,5 @@
 """degrade_bench.py — time per call of the degradation kernels (csrc/degrade.hip) beside a device-to-device hipMemcpyAsync of the output's
-bytes, the yardstick of a kernel that mostly writes.  Device events around `--iters` back-to-back calls on one stream, after a warm-up; the
+bytes, the yardstick of a kernel that mostly writes (imresize, which mostly reads: of its input's bytes).  Device events around `--iters` back-to-back calls on one stream, after a warm-up; the
 figures of profiles/degradations.md come from here.
 
     python tools/degrade_bench.py [--iters 500] [--repeat 5]
@@ -84,6 +84,28 @@ def main(argv=None):
     k, c = timed(mk), timed(cp2)
     print("%-42s %10.2f %8.2f (%6.2f..%6.2f) %8.2f (%6.2f..%6.2f) %8.0f" %
           ("mask_to 16x3x256x256, masks 16x256x256x3", nbytes / 1e6, k[0], k[1], k[2], c[0], c[1], c[2], (2 * nbytes + m.numel()) / k[0] / 1e3))
+    # imresize x1/4 of a batch of 1024 x 1024 images (LQ from GT): it reads 16 times what it writes, so its yardstick is a copy of its INPUT
+    del x, m, out, out2
+    x = torch.rand((16, 3, 1024, 1024), device=dev)
+    x2 = torch.empty_like(x)
+    P.degradations.imresize(x[:1], 1 / 4)   # builds and uploads the tables
+    (wH, sH), (wW, sW) = (P.degradations._device_tables(n, 1 / 4, True, x.device) for n in (1024, 1024))
+    out = torch.empty((16, 3, 256, 256), device=dev)
+    in_bytes = x.numel() * 4
+
+    def rs():
+        _lib.check(L.irsde_imresize(ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(out.data_ptr()), 16, 3, 1024, 1024, 256, 256,
+                                    ctypes.c_void_p(wH.data_ptr()), ctypes.c_void_p(sH.data_ptr()), wH.shape[1],
+                                    ctypes.c_void_p(wW.data_ptr()), ctypes.c_void_p(sW.data_ptr()), wW.shape[1], s))
+
+    def cp3():
+        assert hip.hipMemcpyAsync(x2.data_ptr(), x.data_ptr(), in_bytes, D2D, s) == 0
+
+    k, c = timed(rs), timed(cp3)
+    assert torch.equal(out, P.degradations.imresize(x, 1 / 4))
+    print("%-42s %10.2f %8.2f (%6.2f..%6.2f) %8.2f (%6.2f..%6.2f) %8.0f   (copy of the %.1f MB input; GB/s = input + output bytes)" %
+          ("imresize 16x3x1024x1024 x1/4 -> 256x256", out.numel() * 4 / 1e6, k[0], k[1], k[2], c[0], c[1], c[2],
+           (in_bytes + out.numel() * 4) / k[0] / 1e3, in_bytes / 1e6))
 
 
 if __name__ == "__main__":

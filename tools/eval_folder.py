@@ -49,6 +49,16 @@ perform_ode = `--mode ode`).  Their stated differences, beyond those of the LQ /
 seeded `noise_state` draw): the degraded LQ lives on the device, so the noise is drawn on the CPU as before and added there; inpainting does not
 write the intermediate states (`save_states=True` in inpainting/test.py:108); stereo-sr names the right view's files after the right view's own
 file instead of `img_name.replace('L', 'R')`, and also writes <name>_LQ.png / <name>_HQ.png per view.
+
+`--task sisr --lq-from-gt` needs no LQ folder: like LQGT_dataset with no dataroot_LQ (codes/data/LQGT_dataset.py:94-96, 106-130) every GT image
+is cropped to a multiple of --scale (`degradations.modcrop`) and the low-resolution image is made from it on the device with the MATLAB-style
+antialiased cubic resize `degradations.imresize(GT, 1 / scale, True)` (codes/data/util.py:238-387, csrc/degrade.hip) — the filter the usual x2 /
+x3 / x4 LR test sets were made with; then the sisr loop as above, with PSNR / SSIM against the cropped GT:
+
+    python tools/eval_folder.py --task sisr --gt DIV2K/HR --lq-from-gt --scale 4 --max-sigma 30 --weights sisr.pth --out results/sisr
+
+Stated difference: the low-resolution image stays float32 (LQGT_dataset makes it from the float GT in the same way; a stored LR set has been
+rounded to 8 bits on the way to disk).
 """
 import argparse
 import os
@@ -217,7 +227,8 @@ def run_degraded(a, P, torch, np, dev, world, rank, log, crop_border, on_batch=N
     sde.seed = a.seed
 
     per = 2 if stereo else 1   # files per dataset item: stereo-sr pairs files 2i, 2i + 1 of the sorted list (StereoLQ_dataset.py:66-67)
-    src = list_images(a.gt if a.task == "inpainting" else a.lq)
+    from_gt = a.lq_from_gt   # sisr: LQ made from the modcropped GT (LQGT_dataset.py:94-96, 106-130)
+    src = list_images(a.gt if a.task == "inpainting" or from_gt else a.lq)
     gts = list_images(a.gt) if a.gt is not None else None
     if gts is not None and len(gts) != len(src):
         raise ValueError("GT and LQ datasets have different number of images - %d, %d" % (len(gts), len(src)))
@@ -231,6 +242,8 @@ def run_degraded(a, P, torch, np, dev, world, rank, log, crop_border, on_batch=N
         return np.concatenate([read_img(paths[per * i + v]) for v in range(per)], axis=0)
 
     src_np = [item(src, i) for i in mine]
+    if from_gt:
+        src_np = [P.degradations.modcrop(torch.from_numpy(x), a.scale).contiguous().numpy() for x in src_np]
     res = {"psnr": [], "ssim": []} if stereo else {"psnr": [], "ssim": [], "psnr_y": [], "ssim_y": []}
     times = []
     fn = {"sde": sde.reverse_sde, "ode": sde.reverse_ode, "posterior": sde.reverse_posterior}[a.mode]
@@ -238,7 +251,10 @@ def run_degraded(a, P, torch, np, dev, world, rank, log, crop_border, on_batch=N
         idx = [mine[j] for j in grp]
         x = torch.from_numpy(np.stack([src_np[j] for j in grp])).to(dev)
         GT = None
-        if a.task == "sisr":
+        if from_gt:
+            GT = x
+            LQ = P.degradations.upscale(P.degradations.imresize(x, 1 / a.scale, True), a.scale)   # util.imresize(img_GT, 1 / scale, True), then as below
+        elif a.task == "sisr":
             LQ = P.degradations.upscale(x, a.scale)                        # util.upscale(LQ, scale), sisr/test.py:102
         elif stereo:
             LQ = torch.cat([P.degradations.upscale(v, 4) for v in x.chunk(2, dim=1)], dim=1)   # stereo-sr/test.py:105-108
@@ -290,7 +306,7 @@ def run_degraded(a, P, torch, np, dev, world, rank, log, crop_border, on_batch=N
         summary = P.metrics.reduce_metrics({k: np.asarray(v, dtype=np.float64) for k, v in res.items()})
     if rank == 0 and summary is not None:
         log("----Average PSNR/SSIM results for %s----\n\tPSNR: %.6f dB; SSIM: %.6f\n" %
-            (os.path.basename(os.path.normpath(a.gt if a.task == "inpainting" else a.lq)), summary["psnr"], summary["ssim"]))
+            (os.path.basename(os.path.normpath(a.gt if a.task == "inpainting" or from_gt else a.lq)), summary["psnr"], summary["ssim"]))
         if not stereo:
             log("----Y channel, average PSNR/SSIM----\n\tPSNR_Y: %.6f dB; SSIM_Y: %.6f\n" % (summary["psnr_y"], summary["ssim_y"]))
     if rank == 0 and times:
@@ -303,11 +319,13 @@ def main(argv=None, on_batch=None):
     ap.add_argument("--task", default=None, choices=["denoising", "sisr", "inpainting", "stereo-sr"],
                     help="denoising: the denoising-sde loop (clean --gt folder + --sigma, DenoisingSDE, "
                     "reverse_ode from the optimal timestep; PSNR / SSIM, no LPIPS: its AlexNet weights are not available).  sisr: --lq is the low-resolution "
-                    "folder, bicubic upscale by --scale on the device, then the LQ / GT loop with the reverse-SDE sampler.  inpainting: --gt + --mask-root, "
+                    "folder (or --lq-from-gt), bicubic upscale by --scale on the device, then the LQ / GT loop with the reverse-SDE sampler.  inpainting: --gt + --mask-root, "
                     "mask_to with the image index as mask id.  stereo-sr: --lq holds L / R files paired in sorted order, x4 upscale per view, the stereo "
                     "ConditionalNAFNet (--naf-*) or, with --model unet, the stereo ConditionalUNet.  Absent: the LQ / GT loop")
     ap.add_argument("--lq", default=None, help="degraded images (required unless --task denoising / inpainting)")
     ap.add_argument("--gt", default=None)
+    ap.add_argument("--lq-from-gt", action="store_true", help="--task sisr without --lq: every --gt image is cropped to a multiple of --scale (modcrop) and "
+                    "its low-resolution image is made on the device by imresize(GT, 1 / scale), the MATLAB-style antialiased cubic resize of LQGT_dataset")
     ap.add_argument("--mask-root", default=None, help="--task inpainting: folder of the '%%06d.png' keep-masks (opt['degradation']['mask_root'])")
     ap.add_argument("--wide-rows", action="store_true", help="--task stereo-sr: set_wide_rows(), views wider than the SCAM strip kernels hold")
     ap.add_argument("--sigma", type=float, default=15, help="--task denoising: opt['degradation']['sigma'] (/ 255 when > 1)")
@@ -343,7 +361,13 @@ def main(argv=None, on_batch=None):
         ap.error("the following arguments are required: --lq")
     if a.task == "denoising" and a.gt is None:
         ap.error("--task denoising needs the clean images: --gt")
-    if a.task in ("sisr", "stereo-sr") and a.lq is None:
+    if a.lq_from_gt and a.task != "sisr":
+        ap.error("--lq-from-gt goes with --task sisr only")
+    if a.lq_from_gt and a.lq is not None:
+        ap.error("--lq-from-gt makes the low-resolution images from --gt: --lq must be absent")
+    if a.lq_from_gt and a.gt is None:
+        ap.error("--lq-from-gt needs the high-resolution images: --gt")
+    if a.task in ("sisr", "stereo-sr") and a.lq is None and not a.lq_from_gt:
         ap.error("--task %s needs the low-resolution images: --lq" % a.task)
     if a.task == "inpainting" and (a.gt is None or a.mask_root is None):
         ap.error("--task inpainting needs the clean images and the masks: --gt, --mask-root")
