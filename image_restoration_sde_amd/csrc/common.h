@@ -385,6 +385,15 @@ void launch_attention_kv_context(const float* xn, const float* wkv, int B, int N
                                  float w_inv_scale = 1.f, int op16 = 0, bool act_bf16 = false);
 // op16 (r05): 0 = f32 (or, with *_pair planes, the fp16 hi + lo pairs); 2 / 3 = ONE bf16 / fp16 operand plane in *_pair (IRSDE_FLAG_BF16 / _FP16:
 // [256][C] k | v rows, [128][C] q rows, [C][128] to_out rows, unscaled); act_bf16 (op16 == 2 only): xn / x / y are bf16 tensors (IRSDE_FLAG_BF16_ACT)
+// op16 = 4: fp32 tensors, the projections on THREE bf16 pieces per operand and six products (the exact-fp32 engine, IRSDE_SPLIT3_ATTN): *_pair = three unscaled
+// planes of the [256][C], [128][C], [C][128] matrices in MFMA-fragment order (launch_split_frag3); LayerNorm, softmax and the context products stay fp32
+inline bool attn_split3_has_instance(int C) { return C == 64 || C == 128 || C == 256; }
+// Fragment order of one plane of a [rows][K] matrix: [row / 32][k / 16][(k % 16) / 8][row % 32][k % 8] — lane (l31 = row % 32, h) of a wave finds its 8 values of
+// (32-row tile, 16-k step) at 16-byte slot ((row tile * K / 16 + step) * 64 + 32 h + l31): one contiguous KB per wave load
+__host__ __device__ inline size_t attn_frag3_index(size_t row, int k, int K) {
+    return ((((row >> 5) * (size_t)(K >> 4) + (size_t)(k >> 4)) * 2 + (size_t)((k >> 3) & 1)) * 32 + (row & 31)) * 8 + (size_t)(k & 7);
+}
+void launch_split_frag3(const float* in, unsigned short* out, size_t rows, int K, hipStream_t s);   // out: [3][rows * K]
 void launch_attention_q_out(const float* q, float* out, int B, int N, const AttnWorkspace& ws, hipStream_t s);
 // C = 64 / 128 / 256: q projection, softmax over d, context product, to_out (+ bias), LayerNorm (* g2) and the residual in one
 // kernel: y = LayerNorm(Wout . (ctx^T softmax(Wq . xn)) + bias) * g2 + x.  wq = rows 0..127 of to_qkv.weight ([128][C]),

@@ -69,6 +69,11 @@ inline long long split3_fused_min_tiles() { return tuning_env_int("IRSDE_SPLIT3_
 constexpr int kSplit3NotExactF32 = IRSDE_FLAG_NO_WINOGRAD | IRSDE_FLAG_NAIVE_CONV | IRSDE_FLAG_BF16 | IRSDE_FLAG_BF16_ACT | IRSDE_FLAG_FP16 | IRSDE_FLAG_F16_ACT |
                                    IRSDE_FLAG_SPLIT_BF16X2 | IRSDE_FLAG_SPLIT_F16X2 | IRSDE_FLAG_NO_SPLIT3;
 inline bool split3_wants_weights(int flags) { return !(flags & kSplit3NotExactF32) && split3_mode() > 0; }
+// The same engine's fused LinearAttention blocks (C = 64 / 128 / 256) with their k / v, q and to_out projections on three bf16 pieces (kernels_misc.hip, MODE 4): 0 never,
+// 1 by the rule of Builder::split3_attn_adopts, 2 wherever a kernel instance exists (irsde_debug_force_split3_attn overrides the knob for plans built afterwards).
+// Off with the GEMMs' master switch (IRSDE_SPLIT3 = 0, IRSDE_FLAG_NO_SPLIT3); the master's mode 2 does not force it.
+int split3_attn_mode();
+void set_force_split3_attn(int mode);   // irsde_debug_force_split3_attn
 
 inline int wino_min_c(int tile) {
     return tuning_env_int(tile == 4 ? "IRSDE_WINO4_MINC" : "IRSDE_WINO2_MINC", tile == 4 ? 64 : 256);
@@ -497,6 +502,21 @@ struct irsde_engine {
     std::map<const float*, PairCopy> pair_copies;
     PairCopy pair_copy(const float* w, size_t n) {
         return make_pair_copy(pair_copies, w, n, [&](unsigned short* d, bool f16, float sc) { launch_split_planes(w, d, n, n, 2, stream, f16, sc); });
+    }
+    // three unscaled bf16 planes [3][rows * K] of a packed fp32 [rows][K] weight matrix (hi, mid, lo: all 24 significand bits; bf16 has fp32's exponent range, so no
+    // scale) in MFMA-fragment order (attn_frag3_index), made once per tensor: the fused attention kernels' three-piece projections
+    std::map<const float*, unsigned short*> triple_copies;
+    const unsigned short* triple_copy(const float* w, size_t rows, int K) {
+        const size_t n = rows * (size_t)K;
+        auto it = triple_copies.find(w);
+        if (it != triple_copies.end()) return it->second;
+        unsigned short* d = nullptr;
+        IRSDE_HIP_CHECK(hipMalloc(&d, 3 * n * sizeof(unsigned short)));
+        dev_allocs.push_back(reinterpret_cast<float*>(d));
+        launch_split_frag3(w, d, rows, K, stream);
+        IRSDE_HIP_CHECK(hipStreamSynchronize(stream));
+        triple_copies[w] = d;
+        return d;
     }
     // The PAIR kernels of conv_igemm.hip read their weights pair-interleaved: [rows][K / 32][hi 32 | lo 32] (split_pairs_kernel), one
     // 128-byte line per 32-k block, fetched global -> LDS by global_load_lds.  K must be a multiple of 32.

@@ -979,6 +979,10 @@ int irsde_debug_force_split3(int mode) {
     return IRSDE_OK;
 }
 
+int irsde_debug_force_split3_attn(int mode) {
+    set_force_split3_attn(mode >= 0 && mode <= 2 ? mode : -1);
+    return IRSDE_OK;
+}
 int irsde_debug_force_split3_blocks(int n) {
     if (n >= 0 && n < 8) return guard([&] { throw HipError("debug_force_split3_blocks: n must be at least 8 (one block per XCD), or negative for the default"); });
     set_force_split3_blocks(n);

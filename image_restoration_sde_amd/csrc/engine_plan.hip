@@ -245,6 +245,19 @@ struct Builder {
         const long long T = (long long)p.B * (p.Ho / 4) * (p.Wo / 4);
         return T >= split3_fused_min_tiles() && split3_rule(T, p.C0 + p.C1, p.Cout, 36) && split3_adopts(w.wino_u4t, T, p.C0 + p.C1, p.Cout, 36);
     }
+    // Does a fused LinearAttention block (C channels, N pixels per image, batch B) run its projections on three bf16 pieces?  Exact-fp32 engine only, off with the
+    // GEMMs' master switch (mode 0, IRSDE_FLAG_NO_SPLIT3); IRSDE_SPLIT3_ATTN: 0 never, 2 wherever an instance exists, 1 = the measured rule.
+    // Rule (profiles/attn_split3.md, section 3): on 256 x 256 images both kernels of every fused block (C = 64 / 128 / 256; 4 K to 64 K pixels per image) are faster
+    // than their f32 twins at B = 16 and at B = 2, by 15 - 33 %, and 16 x 512 x 512 gains as much end to end: every instance is adopted, whatever N and B.
+    static bool split3_attn_rule(int C, int N, int B) {
+        (void)N; (void)B;
+        return attn_split3_has_instance(C);
+    }
+    bool split3_attn_adopts(int C, int N, int B) const {
+        if ((e->cfg.flags & kSplit3NotExactF32) || split3_mode() == 0 || !attn_split3_has_instance(C)) return false;
+        const int mode = split3_attn_mode();
+        return mode >= 2 || (mode == 1 && split3_attn_rule(C, N, B));
+    }
     float* alloc_triples(int ncomp, long long rows, int K) { return pl->alloc(((size_t)ncomp * split3_comp_elems((size_t)rows, (size_t)K) + 1) / 2, true); }
 
     bool push_wino_poly(const ConvParams& d, const float* U, const unsigned short* Ut = nullptr) {
@@ -829,6 +842,18 @@ struct Builder {
             float* yp = y.p;
             const int B = x.B, C = x.C;
             if (!bo) throw HipError("attention: to_out.0.bias missing");
+            if (split3_attn_adopts(C, N, B)) {   // exact fp32: the three projections on three bf16 pieces each, six products (kernels_misc.hip MODE 4)
+                const unsigned short* wkv3 = e->triple_copy(wkv, 256, C);
+                const unsigned short* wq3 = e->triple_copy(wq, 128, C);
+                const unsigned short* wo3 = e->triple_copy(wo, (size_t)C, 128);
+                push_other(OP_ATTN, [=](hipStream_t s) { launch_attention_kv_context(xp, wkv, B, N, C, ws, s, g1, 1e-5f, wkv3, 1.f, 4); });
+                pl->net_ops.back().desc = "linear_attention LayerNorm + k,v projection (bf16x3) + context (fused) C=" + std::to_string(C);
+                push_other(OP_ATTN, [=](hipStream_t s) {
+                    launch_attention_q_out_fused(xp, xp, wq, wo, bo, g2, yp, B, N, C, 1e-5f, ws, s, g1, wq3, wo3, 1.f, 1.f, 4);
+                });
+                pl->net_ops.back().desc = "linear_attention LayerNorm + q projection (bf16x3) + softmax + context + to_out + LayerNorm + residual (fused) C=" + std::to_string(C);
+                return y;
+            }
             const unsigned short* wkv_pair = nullptr;
             float kv_inv = 1.f;
             if (e->cfg.flags & IRSDE_FLAG_SPLIT_F16X2) {   // the k / v projection on fp16 hi + lo operand pairs
@@ -1064,6 +1089,12 @@ void set_force_split3(int mode) { g_force_split3.store(mode, std::memory_order_r
 int split3_mode() {
     const int f = g_force_split3.load(std::memory_order_relaxed);
     return f >= 0 ? f : tuning_env_int("IRSDE_SPLIT3", 1);
+}
+static std::atomic<int> g_force_split3_attn{-1};   // irsde_debug_force_split3_attn: -1 = the IRSDE_SPLIT3_ATTN knob
+void set_force_split3_attn(int mode) { g_force_split3_attn.store(mode, std::memory_order_relaxed); }
+int split3_attn_mode() {
+    const int f = g_force_split3_attn.load(std::memory_order_relaxed);
+    return f >= 0 ? f : tuning_env_int("IRSDE_SPLIT3_ATTN", 1);
 }
 static std::atomic<int> g_force_wino_poly{-1};   // irsde_debug_force_wino_poly: -1 = the IRSDE_WINO_POLY knob
 void set_force_wino_poly(int mode) { g_force_wino_poly.store(mode, std::memory_order_relaxed); }

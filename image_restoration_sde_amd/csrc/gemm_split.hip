@@ -539,7 +539,31 @@ __global__ __launch_bounds__(256) void split_planes_kernel(const float* __restri
     }
 }
 
+// f32 [rows][K] -> three bf16 planes in MFMA-fragment order (the fused attention kernels' three-piece weights, attn_frag3_index in common.h): the 64 x 16 bytes
+// one wave loads as the operand of v_mfma_f32_32x32x16_bf16 for (32-row tile, 16-k step) are one contiguous KB, so every line fetched from L2 is used whole
+__global__ __launch_bounds__(256) void split_frag3_kernel(const float* __restrict__ in, unsigned short* __restrict__ out, const size_t n, const int K) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const size_t row = i / K;
+    const int k = (int)(i - row * K);
+    float r = in[i];
+    const size_t o = attn_frag3_index(row, k, K);
+#pragma unroll
+    for (int p = 0; p < 3; ++p) {
+        const __bf16 hb = (__bf16)r;
+        out[p * n + o] = __builtin_bit_cast(unsigned short, hb);
+        r -= (float)hb;
+    }
+}
+
 }  // namespace
+
+void launch_split_frag3(const float* in, unsigned short* out, size_t rows, int K, hipStream_t s) {
+    if (rows % 32 || K % 16) throw HipError("split_frag3: rows must be a multiple of 32, K of 16");
+    const size_t n = rows * (size_t)K;
+    hipLaunchKernelGGL(split_frag3_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, in, out, n, K);
+    IRSDE_HIP_CHECK(hipGetLastError());
+}
 
 void gemm_split_global_init() {
     IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split2i_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));

@@ -378,6 +378,17 @@ constexpr int kKvTile = 128;
 // MODE (r05): 0 = f32, 1 = PAIR, 2 / 3 = the 16-bit operand modes (IRSDE_FLAG_BF16 / IRSDE_FLAG_FP16; the reference is fp32 only): ONE bf16 / fp16 plane
 // of the staged tile and of the weights (wkv_pair: [256][C], unscaled), one product per f32 product — with the projection at 1/16 of its f32
 // cycles the kernel is bound by the tile it streams.  ABF (IRSDE_FLAG_BF16_ACT, MODE 2): xn is a bf16 tensor, pieces of 8 channels.
+// MODE 4 (exact-fp32 engine, IRSDE_SPLIT3_ATTN): the k / v projection on v_mfma_f32_32x32x16_bf16 with every operand as THREE bf16 pieces (all 24 significand
+// bits) and the six products of gemm_split3i_kernel (dropped terms <= 3 * 2^-27 |ab|): 6 MFMAs of 32 cycles instead of 8 of 64 per 16 channels.  The tile is split
+// while it is staged (three planes, rows of 2 C + 16 bytes), the weights come as three unscaled planes in MFMA-fragment order (wkv_pair: 3 x [256][C], attn_frag3_index; bf16 has fp32's exponent
+// range).  Softmax and the context product stay on the f32 pipe.  Sized to LDS: a 64-pixel tile (kKvTileTri) = 3 * 64 * (2 C + 16) bytes = 27.6 / 52.2 / 101.4 KB
+// at C = 64 / 128 / 256, against the f32 kernel's 34.8 / 67.6 / 133 KB: LDS leaves room for 5 / 3 / 1 blocks per CU (f32: 4 / 2 / 1; launch_bounds caps both at
+// two), so the serial phases of two blocks still overlap at C <= 128.  Cost of the smaller tile: a wave pulls its 64 weight rows x 3 planes = 384 C bytes from L2
+// per 64 pixels (f32: 256 C per 128); with ~10 k cycles per tile and two waves per SIMD that is 4 * 384 C * 2 / 20 k = 9.8 / 19.7 / 39 B/clk per CU at
+// C = 64 / 128 / 256 (C = 256, one block per CU: half of that) against the 27 - 35 B/clk the return path sustains (profiles/r06_notes.md, section 1).  That is
+// the rate of USEFUL bytes: row-major planes return 128-byte lines of which a fragment load uses 32 bytes, four times the traffic — measured slower than the f32
+// kernel (profiles/attn_split3.md, section 2) — hence the fragment order, in which a wave's load is one contiguous KB.
+constexpr int kKvTileTri = 64;
 template <int C, int MODE = 0, bool ABF = false>
 __global__ __launch_bounds__(256, 2) void attn_kv_ctx_kernel(const float* __restrict__ xn, const float* __restrict__ wkv,
                                                              float* __restrict__ pmax, float* __restrict__ pctx,
@@ -385,9 +396,10 @@ __global__ __launch_bounds__(256, 2) void attn_kv_ctx_kernel(const float* __rest
                                                              const int nch, const float* __restrict__ ln_g, const float ln_eps,
                                                              const unsigned short* __restrict__ wkv_pair = nullptr, const float w_inv_scale = 1.f) {
     extern __shared__ __attribute__((aligned(16))) float kv_smem[];
-    constexpr bool PAIR = MODE == 1, P16 = MODE != 0;
+    constexpr bool PAIR = MODE == 1, TRI = MODE == 4, P16 = MODE != 0;
     using M16 = Mf16<MODE == 1 || MODE == 3>;
     static_assert(!ABF || MODE == 2, "bf16 activation storage goes with the bf16 operand mode");
+    constexpr int TP = TRI ? kKvTileTri : kKvTile, NRT = TP / 32;   // pixels per tile, 32-pixel row tiles per tile
     constexpr int RB = 2 * C + 16;   // 16-bit modes: bytes per LDS row (an odd number of 16-byte slots)
     const int ch = blockIdx.x, b = blockIdx.y;
     const int tid = threadIdx.x, lane = tid & 63, head = tid >> 6;
@@ -402,7 +414,7 @@ __global__ __launch_bounds__(256, 2) void attn_kv_ctx_kernel(const float* __rest
 #pragma unroll
     for (int r = 0; r < 16; ++r) ctx[r] = 0.f;
     float ssum = 0.f, mrun = -INFINITY;
-    for (int t0 = n0; t0 < n1; t0 += kKvTile) {
+    for (int t0 = n0; t0 < n1; t0 += TP) {
         // stage the tile (rows past the chunk repeat its last pixel; they are masked below)
         auto stage_tile = [&](auto full_tag) {
             // r05: a full tile is one contiguous run of 128 * C floats (NHWC): element 4 i of it is piece i — no per-piece row / column / clamp arithmetic
@@ -410,7 +422,7 @@ __global__ __launch_bounds__(256, 2) void attn_kv_ctx_kernel(const float* __rest
             const float* tile = xn + ((size_t)b * N + t0) * C;
             // r05: 8 loads in flight before the first LDS write of a pass, passes unrolled (r02: a rolled loop of 4 — four exposed HBM round trips per
             // tile; the 144 accumulator registers it was fitted next to are not live while the tile is staged: they are zeroed behind the barrier)
-            constexpr int NP = kKvTile * c4n / 256;
+            constexpr int NP = TP * c4n / 256;
             constexpr int NB = NP % 8 == 0 ? 8 : 4;
 #pragma unroll
             for (int j0 = 0; j0 < NP; j0 += NB) {
@@ -437,7 +449,16 @@ __global__ __launch_bounds__(256, 2) void attn_kv_ctx_kernel(const float* __rest
                         const f16x4 lo = __builtin_convertvector(st[j] - __builtin_convertvector(hi, floatx4), f16x4);
                         char* dst = reinterpret_cast<char*>(kv_smem) + row * RB + 8 * c4;
                         *reinterpret_cast<f16x4*>(dst) = hi;
-                        *reinterpret_cast<f16x4*>(dst + kKvTile * RB) = lo;
+                        *reinterpret_cast<f16x4*>(dst + TP * RB) = lo;
+                    } else if constexpr (TRI) {   // three bf16 planes (the arithmetic of split_triples_kernel: every residual is exact in f32)
+                        const bf16x4 p0 = __builtin_convertvector(st[j], bf16x4);
+                        const floatx4 r1 = st[j] - __builtin_convertvector(p0, floatx4);
+                        const bf16x4 p1 = __builtin_convertvector(r1, bf16x4);
+                        const bf16x4 p2 = __builtin_convertvector(r1 - __builtin_convertvector(p1, floatx4), bf16x4);
+                        char* dst = reinterpret_cast<char*>(kv_smem) + row * RB + 8 * c4;
+                        *reinterpret_cast<bf16x4*>(dst) = p0;
+                        *reinterpret_cast<bf16x4*>(dst + TP * RB) = p1;
+                        *reinterpret_cast<bf16x4*>(dst + 2 * TP * RB) = p2;
                     } else if constexpr (P16) {   // one plane, RNE
                         *reinterpret_cast<typename M16::x4*>(reinterpret_cast<char*>(kv_smem) + row * RB + 8 * c4) = __builtin_convertvector(st[j], typename M16::x4);
                     } else {
@@ -452,7 +473,7 @@ __global__ __launch_bounds__(256, 2) void attn_kv_ctx_kernel(const float* __rest
             constexpr int c8n = C >> 3;
             const char* xb = reinterpret_cast<const char*>(xn);
             const char* tile = xb + ((size_t)b * N + t0) * C * 2;
-            constexpr int NP = kKvTile * c8n / 256;
+            constexpr int NP = TP * c8n / 256;
             constexpr int NB = NP % 8 == 0 ? 8 : 4;
             static_assert(256 % c8n == 0 && NP % NB == 0, "piece / thread mapping");
 #pragma unroll
@@ -472,15 +493,29 @@ __global__ __launch_bounds__(256, 2) void attn_kv_ctx_kernel(const float* __rest
                 }
             }
         };
+        // TRI: the weight fragments (three planes of the lane's k and v row) one K step ahead in two register slots; the first step's go out in front of the
+        // staging, which hides their L2 round trip (they do not depend on the tile)
+        [[maybe_unused]] bf16x8 wk3[2][3], wv3[2][3];   // [slot][piece]
+        [[maybe_unused]] const char* wkp3 = TRI ? reinterpret_cast<const char*>(wkv_pair) + ((size_t)head * (C / 16) * 64 + 32 * h + l31) * 16 : nullptr;          // row tile = head
+        [[maybe_unused]] const char* wvp3 = TRI ? reinterpret_cast<const char*>(wkv_pair) + ((size_t)(kHeads + head) * (C / 16) * 64 + 32 * h + l31) * 16 : nullptr;   // row tile = 4 + head
+        constexpr size_t WPL3 = (size_t)2 * kHid * C * 2;   // bytes between two weight planes (wkv_pair: three planes of [256][C] in fragment order, attn_frag3_index: a K step = 1 KB)
+        if constexpr (TRI) {
+#pragma unroll
+            for (int p = 0; p < 3; ++p) {
+                wk3[0][p] = *reinterpret_cast<const bf16x8*>(wkp3 + p * WPL3);
+                wv3[0][p] = *reinterpret_cast<const bf16x8*>(wvp3 + p * WPL3);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
         if constexpr (ABF) {
-            if (t0 + kKvTile <= n1) stage_tile_bf(std::true_type{}); else stage_tile_bf(std::false_type{});
+            if (t0 + TP <= n1) stage_tile_bf(std::true_type{}); else stage_tile_bf(std::false_type{});
         } else {
-            if (t0 + kKvTile <= n1) stage_tile(std::true_type{}); else stage_tile(std::false_type{});
+            if (t0 + TP <= n1) stage_tile(std::true_type{}); else stage_tile(std::false_type{});
         }
         __syncthreads();
-        floatx16 ak[4], av[4];
+        floatx16 ak[NRT], av[NRT];
 #pragma unroll
-        for (int rt = 0; rt < 4; ++rt)
+        for (int rt = 0; rt < NRT; ++rt)
 #pragma unroll
             for (int r = 0; r < 16; ++r) { ak[rt][r] = 0.f; av[rt][r] = 0.f; }
         if constexpr (PAIR) {
@@ -503,9 +538,9 @@ __global__ __launch_bounds__(256, 2) void attn_kv_ctx_kernel(const float* __rest
                 wv2[nxt][0] = *reinterpret_cast<const f16x8*>(wvp + kp);
                 wv2[nxt][1] = *reinterpret_cast<const f16x8*>(wvp + WPL + kp);
 #pragma unroll
-                for (int rt = 0; rt < 4; ++rt) {
+                for (int rt = 0; rt < NRT; ++rt) {
                     const f16x8 ah = *reinterpret_cast<const f16x8*>(arow + rt * 32 * RB + 32 * ks);
-                    const f16x8 al = *reinterpret_cast<const f16x8*>(arow + kKvTile * RB + rt * 32 * RB + 32 * ks);
+                    const f16x8 al = *reinterpret_cast<const f16x8*>(arow + TP * RB + rt * 32 * RB + 32 * ks);
                     ak[rt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, wk2[cur][1], ak[rt], 0, 0, 0);
                     av[rt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, wv2[cur][1], av[rt], 0, 0, 0);
                     ak[rt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, wk2[cur][0], ak[rt], 0, 0, 0);
@@ -524,9 +559,48 @@ __global__ __launch_bounds__(256, 2) void attn_kv_ctx_kernel(const float* __rest
                 for (int ks = 0; ks < NK16; ++ks) kstep(ks);
             }
 #pragma unroll
-            for (int rt = 0; rt < 4; ++rt)
+            for (int rt = 0; rt < NRT; ++rt)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) { ak[rt][r] *= w_inv_scale; av[rt][r] *= w_inv_scale; }
+        } else if constexpr (TRI) {
+            // three bf16 pieces per operand, the six products of gemm_split3i_kernel in its order (a0 b2, a1 b1, a2 b0, a0 b1, a1 b0, a0 b0: smallest first),
+            // K steps of 16: lane (row l31, half h) holds k = 16 ks + 8 h .. + 7 of its pixel rows (three LDS planes) and of its weight rows
+            const char* arow = reinterpret_cast<const char*>(kv_smem) + l31 * RB + 16 * h;
+            constexpr int NK16 = C / 16;
+            auto kstep = [&](const int ks) {
+                const int cur = ks & 1, nxt = cur ^ 1;
+                const int kp = (ks + 1 < NK16 ? ks + 1 : ks) * 1024;
+#pragma unroll
+                for (int p = 0; p < 3; ++p) {
+                    wk3[nxt][p] = *reinterpret_cast<const bf16x8*>(wkp3 + p * WPL3 + kp);
+                    wv3[nxt][p] = *reinterpret_cast<const bf16x8*>(wvp3 + p * WPL3 + kp);
+                }
+#pragma unroll
+                for (int rt = 0; rt < NRT; ++rt) {
+                    const bf16x8 a0 = *reinterpret_cast<const bf16x8*>(arow + rt * 32 * RB + 32 * ks);
+                    const bf16x8 a1 = *reinterpret_cast<const bf16x8*>(arow + TP * RB + rt * 32 * RB + 32 * ks);
+                    const bf16x8 a2 = *reinterpret_cast<const bf16x8*>(arow + 2 * TP * RB + rt * 32 * RB + 32 * ks);
+                    ak[rt] = M16::mfma(a0, wk3[cur][2], ak[rt]);
+                    av[rt] = M16::mfma(a0, wv3[cur][2], av[rt]);
+                    ak[rt] = M16::mfma(a1, wk3[cur][1], ak[rt]);
+                    av[rt] = M16::mfma(a1, wv3[cur][1], av[rt]);
+                    ak[rt] = M16::mfma(a2, wk3[cur][0], ak[rt]);
+                    av[rt] = M16::mfma(a2, wv3[cur][0], av[rt]);
+                    ak[rt] = M16::mfma(a0, wk3[cur][1], ak[rt]);
+                    av[rt] = M16::mfma(a0, wv3[cur][1], av[rt]);
+                    ak[rt] = M16::mfma(a1, wk3[cur][0], ak[rt]);
+                    av[rt] = M16::mfma(a1, wv3[cur][0], av[rt]);
+                    ak[rt] = M16::mfma(a0, wk3[cur][0], ak[rt]);
+                    av[rt] = M16::mfma(a0, wv3[cur][0], av[rt]);
+                }
+            };
+            if constexpr (C > 64) {   // (as PAIR: the register ping-pong needs an even factor)
+#pragma unroll 2
+                for (int ks = 0; ks < NK16; ++ks) kstep(ks);
+            } else {
+#pragma unroll
+                for (int ks = 0; ks < NK16; ++ks) kstep(ks);
+            }
         } else if constexpr (P16) {
             // one 16-bit plane: K steps of 16, lane (row l31, half h) holds k = 16 ks + 8 h .. + 7 of its pixel rows and of its weight rows
             using x8 = typename M16::x8;
@@ -544,7 +618,7 @@ __global__ __launch_bounds__(256, 2) void attn_kv_ctx_kernel(const float* __rest
                 wk1[nxt] = *reinterpret_cast<const x8*>(wkp + kp);
                 wv1[nxt] = *reinterpret_cast<const x8*>(wvp + kp);
 #pragma unroll
-                for (int rt = 0; rt < 4; ++rt) {
+                for (int rt = 0; rt < NRT; ++rt) {
                     const x8 a = *reinterpret_cast<const x8*>(arow + rt * 32 * RB + 32 * ks);
                     ak[rt] = M16::mfma(a, wk1[cur], ak[rt]);
                     av[rt] = M16::mfma(a, wv1[cur], av[rt]);
@@ -573,7 +647,7 @@ __global__ __launch_bounds__(256, 2) void attn_kv_ctx_kernel(const float* __rest
                 __builtin_amdgcn_sched_barrier(0);  // keep the prefetch in front of this step's MFMAs
                 const floatx4 bk = wkr[u], bv = wvr[u];
 #pragma unroll
-                for (int rt = 0; rt < 4; ++rt) {
+                for (int rt = 0; rt < NRT; ++rt) {
                     const floatx4 a = *reinterpret_cast<const floatx4*>(arow + rt * 32 * LDA + k8);
                     ak[rt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, bk.x, ak[rt], 0, 0, 0);
                     av[rt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, bv.x, av[rt], 0, 0, 0);
@@ -588,9 +662,9 @@ __global__ __launch_bounds__(256, 2) void attn_kv_ctx_kernel(const float* __rest
         }
         // accumulator register r of row tile rt: pixel t0 + 32 rt + (r&3) + 8 (r>>2) + 4h, column d (k) / e (v) = l31
         float mit = -INFINITY;
-        if (t0 + kKvTile > n1) {   // (uniform) only the last tile of a chunk has pixels to mask: 128 compares + 256 selects per lane otherwise
+        if (t0 + TP > n1) {   // (uniform) only the last tile of a chunk has pixels to mask: 128 compares + 256 selects per lane otherwise
 #pragma unroll
-            for (int rt = 0; rt < 4; ++rt)
+            for (int rt = 0; rt < NRT; ++rt)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int n = t0 + 32 * rt + (r & 3) + 8 * (r >> 2) + 4 * h;
@@ -598,7 +672,7 @@ __global__ __launch_bounds__(256, 2) void attn_kv_ctx_kernel(const float* __rest
                 }
         }
 #pragma unroll
-        for (int rt = 0; rt < 4; ++rt)
+        for (int rt = 0; rt < NRT; ++rt)
 #pragma unroll
             for (int r = 0; r < 16; ++r) mit = fmaxf(mit, ak[rt][r]);
         mit = half_max(mit);
@@ -619,7 +693,7 @@ __global__ __launch_bounds__(256, 2) void attn_kv_ctx_kernel(const float* __rest
         {
             const float ml = mrun * 1.44269504088896341f;
 #pragma unroll
-            for (int rt = 0; rt < 4; ++rt)
+            for (int rt = 0; rt < NRT; ++rt)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     ak[rt][r] = __builtin_amdgcn_exp2f(__builtin_fmaf(ak[rt][r], 1.44269504088896341f, -ml));
@@ -627,13 +701,13 @@ __global__ __launch_bounds__(256, 2) void attn_kv_ctx_kernel(const float* __rest
                 }
         }
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (MODE >= 2) {
+        if constexpr (MODE == 2 || MODE == 3) {
             // 16-bit operand modes: the context product on the 16-bit MFMA too — exp(k - m) in [0, 1] and v rounded once (RNE), fp32 accumulation.  A K step
             // of 16 pixels takes the lane's registers 8 s .. 8 s + 7 of a row tile for A (its column d) and B (its column e) alike: the same pixel
             // order in both operands, 8 MFMAs of 8 passes instead of 64 of 16.  (ssum stays the fp32 sum of the unrounded exponentials.)
             using x8 = typename M16::x8;
 #pragma unroll
-            for (int rt = 0; rt < 4; ++rt)
+            for (int rt = 0; rt < NRT; ++rt)
 #pragma unroll
                 for (int sh = 0; sh < 2; ++sh) {
                     const floatx8 ka = {ak[rt][8 * sh], ak[rt][8 * sh + 1], ak[rt][8 * sh + 2], ak[rt][8 * sh + 3],
@@ -644,7 +718,7 @@ __global__ __launch_bounds__(256, 2) void attn_kv_ctx_kernel(const float* __rest
                 }
         } else {
 #pragma unroll
-            for (int rt = 0; rt < 4; ++rt)
+            for (int rt = 0; rt < NRT; ++rt)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) ctx = __builtin_amdgcn_mfma_f32_32x32x2f32(ak[rt][r], av[rt][r], ctx, 0, 0, 0);
         }
@@ -781,6 +855,18 @@ __global__ __launch_bounds__(256) void attn_out_kernel(const T* __restrict__ qkv
 // of two that wq_inv / wout_inv undo on the accumulators).  Softmax, the context product, LayerNorm and the residual stay f32.
 // MODE 2 / 3 (r05; IRSDE_FLAG_BF16 / IRSDE_FLAG_FP16): one bf16 / fp16 plane per operand (wq_pair [128][C], wout_pair [C][128], unscaled), one product.
 // ABF (IRSDE_FLAG_BF16_ACT, MODE 2): xn / xres / y are bf16 tensors (pieces of 8 channels); the arithmetic between them is the same fp32.
+// MODE 4 (exact-fp32 engine, IRSDE_SPLIT3_ATTN): the two projections on three bf16 pieces per operand and six products (see attn_kv_ctx_kernel), the xn tile and the
+// attention-output tile split while they are written to LDS, weights as three unscaled planes in MFMA-fragment order (wq_pair 3 x [128][C], wout_pair 3 x [C][128]).  Sized to LDS: a
+// 64-pixel tile (kQoTileTri).  Region = max(xn planes 3 * 64 * (2 C + 16), output planes 3 * 64 * 272 = 52.2 KB, normalised rows 64 * (max(C, 128) + 4) * 4) + 1 KB of
+// LayerNorm partial sums = 53.2 / 53.2 / 102.4 KB at C = 64 / 128 / 256 (f32: 67.6 / 67.6 / 133 KB): two blocks per CU at C <= 128 (launch_bounds; LDS would
+// hold three), one at C = 256, as the f32 kernel.  Waves: phases B - E wave = head over two 32-pixel tiles; phase F wave = (pixel tile, half of the output channels).  Weight
+// fragments from L2 per block and tile: 3 * 2 * (128 C + C 128) = 1536 C bytes (f32, per 128 pixels: 1024 C) — at ~12 k cycles per tile and two waves per SIMD
+// 2 * 1536 C / 24 k = 8 / 16 / 33 B/clk per CU at C = 64 / 128 / 256 (C = 256 with one block per CU: half).
+constexpr int kQoTileTri = 64;
+constexpr size_t qo_tri_main_bytes(const int C) {
+    const size_t px = (size_t)3 * kQoTileTri * (2 * C + 16), po = (size_t)3 * kQoTileTri * (2 * kHid + 16), ys = (size_t)kQoTileTri * ((C > kHid ? C : kHid) + 4) * 4;
+    return px > po ? (px > ys ? px : ys) : (po > ys ? po : ys);
+}
 template <int C, int MODE = 0, bool ABF = false>
 __global__ __launch_bounds__(256, 2) void attn_q_out_fused_kernel(const float* __restrict__ xn, const float* __restrict__ xres,
                                                                const float* __restrict__ wq, const float* __restrict__ ctx,
@@ -790,8 +876,9 @@ __global__ __launch_bounds__(256, 2) void attn_q_out_fused_kernel(const float* _
                                                                const unsigned short* __restrict__ wq_pair = nullptr,
                                                                const unsigned short* __restrict__ wout_pair = nullptr, const float wq_inv = 1.f,
                                                                const float wout_inv = 1.f) {
-    constexpr int TP = 128, LDA = C + 4, LDO = kHid + 4, RT = C / 32;
-    constexpr bool PAIR = MODE == 1, P16 = MODE != 0;
+    constexpr bool PAIR = MODE == 1, TRI = MODE == 4, P16 = MODE != 0;
+    constexpr int TP = TRI ? kQoTileTri : 128, LDA = C + 4, LDO = kHid + 4, RT = C / 32;
+    constexpr int NCT = TP / 32, SL = TP / 4;   // 32-pixel tiles per block; rows of the slab a wave stages (phase A) and stores (phase G)
     using M16 = Mf16<MODE == 1 || MODE == 3>;
     static_assert(!ABF || MODE == 2, "bf16 activation storage goes with the bf16 operand mode");
     constexpr int RBX = 2 * C + 16, RBO = 2 * kHid + 16;   // 16-bit modes: bytes per row of the xn / attention-output planes
@@ -812,7 +899,7 @@ __global__ __launch_bounds__(256, 2) void attn_q_out_fused_kernel(const float* _
     // r05: wave w stages ITS OWN 32-row slab of the tile (pieces i = lane + 64 j of the slab: the same pieces it adds back and stores in phase G), so when
     // the residual IS the staged tensor (xres == xn: the PreNorm-fused plan) the raw pieces stay in registers across the block (C <= 128: 32 / 64
     // registers of the 256 a wave has) and phase G neither re-reads the tile nor waits for it
-    constexpr int NQ = 32 * C4 / 64;
+    constexpr int NQ = SL * C4 / 64;
     constexpr bool KEEP = !PAIR && !ABF && C <= 128;
     floatx4 xkeep[KEEP ? NQ : 1];
     // ABF: the wave's slab is 32 * C bf16; pieces of 8 channels, a row = C8 consecutive lanes; the raw pieces stay in registers (C / 4 of them) for C <= 128
@@ -822,21 +909,22 @@ __global__ __launch_bounds__(256, 2) void attn_q_out_fused_kernel(const float* _
     bf16x8 xkeep8[KEEP8 ? NQ8 : 1];
     auto stage_tile = [&](auto full_tag) {
         constexpr bool FULL = decltype(full_tag)::value;
-        const float* slab_in = xn + (img + t0 + wave * 32) * C;
+        const float* slab_in = xn + (img + t0 + wave * SL) * C;
         // 8 loads in flight before the first LDS write of a pass (a rolled loop waits for every load in turn)
+        constexpr int NB = NQ < 8 ? NQ : 8;
 #pragma unroll
-        for (int j0 = 0; j0 < NQ; j0 += 8) {
-            floatx4 st[8];
+        for (int j0 = 0; j0 < NQ; j0 += NB) {
+            floatx4 st[NB];
 #pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int i = lane + 64 * (j0 + j), row = wave * 32 + lane / C4 + (64 / C4) * (j0 + j), c4 = lane % C4;   // (C4 divides 64)
+            for (int j = 0; j < NB; ++j) {
+                const int i = lane + 64 * (j0 + j), row = wave * SL + lane / C4 + (64 / C4) * (j0 + j), c4 = lane % C4;   // (C4 divides 64)
                 if constexpr (FULL) st[j] = *reinterpret_cast<const floatx4*>(slab_in + 4 * i);
                 else st[j] = *reinterpret_cast<const floatx4*>(xn + (img + min(t0 + row, N - 1)) * C + 4 * c4);
                 if constexpr (FULL && KEEP) xkeep[j0 + j] = st[j];
             }
 #pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int row = wave * 32 + lane / C4 + (64 / C4) * (j0 + j), c4 = lane % C4;
+            for (int j = 0; j < NB; ++j) {
+                const int row = wave * SL + lane / C4 + (64 / C4) * (j0 + j), c4 = lane % C4;
                 // ln_g != nullptr: xn == the block's x and PreNorm's LayerNorm runs here on the staged pieces
                 if (ln_g) st[j] = ln_piece<C4>(st[j], *reinterpret_cast<const floatx4*>(ln_g + 4 * c4), eps);
                 if constexpr (PAIR) {
@@ -845,6 +933,15 @@ __global__ __launch_bounds__(256, 2) void attn_q_out_fused_kernel(const float* _
                     char* dst = reinterpret_cast<char*>(qo_smem) + row * RBX + 8 * c4;
                     *reinterpret_cast<f16x4*>(dst) = hi;
                     *reinterpret_cast<f16x4*>(dst + TP * RBX) = lo;
+                } else if constexpr (TRI) {   // three bf16 planes (the arithmetic of split_triples_kernel)
+                    const bf16x4 p0 = __builtin_convertvector(st[j], bf16x4);
+                    const floatx4 r1 = st[j] - __builtin_convertvector(p0, floatx4);
+                    const bf16x4 p1 = __builtin_convertvector(r1, bf16x4);
+                    const bf16x4 p2 = __builtin_convertvector(r1 - __builtin_convertvector(p1, floatx4), bf16x4);
+                    char* dst = reinterpret_cast<char*>(qo_smem) + row * RBX + 8 * c4;
+                    *reinterpret_cast<bf16x4*>(dst) = p0;
+                    *reinterpret_cast<bf16x4*>(dst + TP * RBX) = p1;
+                    *reinterpret_cast<bf16x4*>(dst + 2 * TP * RBX) = p2;
                 } else if constexpr (P16) {   // one plane, RNE
                     *reinterpret_cast<typename M16::x4*>(reinterpret_cast<char*>(qo_smem) + row * RBX + 8 * c4) = __builtin_convertvector(st[j], typename M16::x4);
                 } else {
@@ -876,6 +973,19 @@ __global__ __launch_bounds__(256, 2) void attn_q_out_fused_kernel(const float* _
             }
         }
     };
+    // TRI: a K step of phase B is 12 MFMAs of 32 cycles — less than one L2 round trip — so the Wq fragments (three planes) run DB K steps ahead in a ring of
+    // DB + 1 slots, and the ring's opening loads go out in front of the staging, which hides them (they do not depend on the tile)
+    constexpr int NKB = C / 16, DB = TRI ? (NKB - 1 < 3 ? NKB - 1 : 3) : 0;
+    [[maybe_unused]] bf16x8 wq3[DB + 1][3];
+    [[maybe_unused]] const char* wq3row = TRI ? reinterpret_cast<const char*>(wq_pair) + ((size_t)wave * (C / 16) * 64 + 32 * h + l31) * 16 : nullptr;   // wq_pair: three planes of [128][C] in fragment order (attn_frag3_index), row tile = head
+    constexpr size_t WQPL = (size_t)kHid * C * 2;   // bytes between two planes of Wq
+    if constexpr (TRI) {
+#pragma unroll
+        for (int pf = 0; pf < DB; ++pf)
+#pragma unroll
+            for (int p = 0; p < 3; ++p) wq3[pf][p] = *reinterpret_cast<const bf16x8*>(wq3row + p * WQPL + 1024 * pf);
+        __builtin_amdgcn_sched_barrier(0);
+    }
     if constexpr (ABF) {
         if (full_tile) stage_tile_bf(std::true_type{}); else stage_tile_bf(std::false_type{});
     } else {
@@ -899,9 +1009,9 @@ __global__ __launch_bounds__(256, 2) void attn_q_out_fused_kernel(const float* _
     __syncthreads();
 
     // ---- B: Q^T of head = wave
-    floatx16 q[4];
+    floatx16 q[NCT];
 #pragma unroll
-    for (int ct = 0; ct < 4; ++ct)
+    for (int ct = 0; ct < NCT; ++ct)
 #pragma unroll
         for (int r = 0; r < 16; ++r) q[ct][r] = 0.f;
     if constexpr (PAIR) {
@@ -919,7 +1029,7 @@ __global__ __launch_bounds__(256, 2) void attn_q_out_fused_kernel(const float* _
             wa2[nxt][0] = *reinterpret_cast<const f16x8*>(wrow + kp);
             wa2[nxt][1] = *reinterpret_cast<const f16x8*>(wrow + WPL + kp);
 #pragma unroll
-            for (int ct = 0; ct < 4; ++ct) {
+            for (int ct = 0; ct < NCT; ++ct) {
                 const f16x8 bh = *reinterpret_cast<const f16x8*>(brow + ct * 32 * RBX + 32 * ks);
                 const f16x8 bl = *reinterpret_cast<const f16x8*>(brow + TP * RBX + ct * 32 * RBX + 32 * ks);
                 q[ct] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wa2[cur][0], bl, q[ct], 0, 0, 0);
@@ -928,9 +1038,33 @@ __global__ __launch_bounds__(256, 2) void attn_q_out_fused_kernel(const float* _
             }
         }
 #pragma unroll
-        for (int ct = 0; ct < 4; ++ct)
+        for (int ct = 0; ct < NCT; ++ct)
 #pragma unroll
             for (int r = 0; r < 16; ++r) q[ct][r] *= wq_inv;
+    } else if constexpr (TRI) {
+        // three pieces, six products (x0 w2, x1 w1, x2 w0, x0 w1, x1 w0, x0 w0: smallest first)
+        const char* brow = reinterpret_cast<const char*>(qo_smem) + l31 * RBX + 16 * h;
+#pragma unroll
+        for (int ks = 0; ks < NKB; ++ks) {
+            if (ks + DB < NKB) {
+#pragma unroll
+                for (int p = 0; p < 3; ++p) wq3[(ks + DB) % (DB + 1)][p] = *reinterpret_cast<const bf16x8*>(wq3row + p * WQPL + 1024 * (ks + DB));
+            }
+            __builtin_amdgcn_sched_barrier(0);  // keep the prefetch in front of this step's MFMAs
+            const bf16x8* wa3c = wq3[ks % (DB + 1)];
+#pragma unroll
+            for (int ct = 0; ct < NCT; ++ct) {
+                const bf16x8 b0 = *reinterpret_cast<const bf16x8*>(brow + ct * 32 * RBX + 32 * ks);
+                const bf16x8 b1 = *reinterpret_cast<const bf16x8*>(brow + TP * RBX + ct * 32 * RBX + 32 * ks);
+                const bf16x8 b2 = *reinterpret_cast<const bf16x8*>(brow + 2 * TP * RBX + ct * 32 * RBX + 32 * ks);
+                q[ct] = M16::mfma(wa3c[2], b0, q[ct]);
+                q[ct] = M16::mfma(wa3c[1], b1, q[ct]);
+                q[ct] = M16::mfma(wa3c[0], b2, q[ct]);
+                q[ct] = M16::mfma(wa3c[1], b0, q[ct]);
+                q[ct] = M16::mfma(wa3c[0], b1, q[ct]);
+                q[ct] = M16::mfma(wa3c[0], b0, q[ct]);
+            }
+        }
     } else if constexpr (P16) {
         using x8 = typename M16::x8;
         const char* wrow = reinterpret_cast<const char*>(wq_pair) + ((size_t)(wave * kDh + l31) * C + 8 * h) * 2;
@@ -943,7 +1077,7 @@ __global__ __launch_bounds__(256, 2) void attn_q_out_fused_kernel(const float* _
             const int cur = ks & 1, nxt = cur ^ 1;
             wa1[nxt] = *reinterpret_cast<const x8*>(wrow + (ks + 1 < NK16 ? ks + 1 : ks) * 32);
 #pragma unroll
-            for (int ct = 0; ct < 4; ++ct)
+            for (int ct = 0; ct < NCT; ++ct)
                 q[ct] = M16::mfma(wa1[cur], *reinterpret_cast<const x8*>(brow + ct * 32 * RBX + 32 * ks), q[ct]);
         }
     } else
@@ -961,7 +1095,7 @@ __global__ __launch_bounds__(256, 2) void attn_q_out_fused_kernel(const float* _
             __builtin_amdgcn_sched_barrier(0);  // keep the prefetch in front of this step's MFMAs (the scheduler sinks it to its use)
             const floatx4 a = wa[ks % 3];
 #pragma unroll
-            for (int ct = 0; ct < 4; ++ct) {
+            for (int ct = 0; ct < NCT; ++ct) {
                 const floatx4 bb = *reinterpret_cast<const floatx4*>(brow + ct * 32 * LDA + 8 * ks);
                 q[ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, bb.x, q[ct], 0, 0, 0);
                 q[ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, bb.y, q[ct], 0, 0, 0);
@@ -970,10 +1104,28 @@ __global__ __launch_bounds__(256, 2) void attn_q_out_fused_kernel(const float* _
             }
         }
     }
+    // TRI: the to_out fragments of phase F (a K step there is 6 RTW MFMAs) run DF K steps ahead — the whole K range at C = 64; the ring's opening loads go out
+    // here, in front of phases C - E, which hide them
+    constexpr int RTW = TRI ? RT / 2 : RT;
+    constexpr int NKF = kHid / 16, DF = !TRI ? 0 : RTW == 1 ? NKF - 1 : RTW == 2 ? 3 : 1;
+    const int rt0 = TRI ? (wave >> 1) * RTW : 0;          // first 32-channel row tile of this wave (phases F, G)
+    const int prow = TRI ? (wave & 1) * 32 : wave * 32;   // first pixel row (of the tile) of this wave (phases F, G)
+    [[maybe_unused]] bf16x8 wo3[DF + 1][3][TRI ? RTW : 1];
+    [[maybe_unused]] const char* wo3row = TRI ? reinterpret_cast<const char*>(wout_pair) + ((size_t)rt0 * (kHid / 16) * 64 + 32 * h + l31) * 16 : nullptr;   // wout_pair: three planes of [C][128] in fragment order
+    constexpr size_t WOPL = (size_t)C * kHid * 2;   // bytes between two planes of Wout
+    if constexpr (TRI) {
+#pragma unroll
+        for (int pf = 0; pf < DF; ++pf)
+#pragma unroll
+            for (int p = 0; p < 3; ++p)
+#pragma unroll
+                for (int rt = 0; rt < RTW; ++rt) wo3[pf][p][rt] = *reinterpret_cast<const bf16x8*>(wo3row + p * WOPL + (size_t)rt * 32 * kHid * 2 + 1024 * pf);
+        __builtin_amdgcn_sched_barrier(0);
+    }
     __syncthreads();  // every wave is done reading Xs: the region becomes Os
     // ---- C + D + E per pixel tile: q[ct][r] = Q[d = (r&3) + 8(r>>2) + 4h][pixel 32 ct + l31]
 #pragma unroll
-    for (int ct = 0; ct < 4; ++ct) {
+    for (int ct = 0; ct < NCT; ++ct) {
         float m = q[ct][0];
 #pragma unroll
         for (int r = 1; r < 16; ++r) m = fmaxf(m, q[ct][r]);
@@ -990,7 +1142,7 @@ __global__ __launch_bounds__(256, 2) void attn_q_out_fused_kernel(const float* _
         floatx16 o;
 #pragma unroll
         for (int r = 0; r < 16; ++r) o[r] = 0.f;
-        if constexpr (MODE >= 2) {
+        if constexpr (MODE == 2 || MODE == 3) {
             // 16-bit operand modes: the context operand (rounded once per block) and the softmax probabilities (in [0, 1]) on the 16-bit MFMA, fp32
             // accumulation.  K step sh = the d values of the lane's registers 8 sh .. 8 sh + 7, the same order in cb[] and q[]: 2 MFMAs instead of 16.
             using x8 = typename M16::x8;
@@ -1017,6 +1169,19 @@ __global__ __launch_bounds__(256, 2) void attn_q_out_fused_kernel(const float* _
                 *reinterpret_cast<f16x4*>(orow + 16 * gq) = hi;
                 *reinterpret_cast<f16x4*>(orow + TP * RBO + 16 * gq) = lo;
             }
+        } else if constexpr (TRI) {
+            char* orow = reinterpret_cast<char*>(qo_smem) + (ct * 32 + l31) * RBO + (wave * kDh + 4 * h) * 2;
+#pragma unroll
+            for (int gq = 0; gq < 4; ++gq) {
+                const floatx4 v = floatx4{o[4 * gq], o[4 * gq + 1], o[4 * gq + 2], o[4 * gq + 3]};
+                const bf16x4 p0 = __builtin_convertvector(v, bf16x4);
+                const floatx4 r1 = v - __builtin_convertvector(p0, floatx4);
+                const bf16x4 p1 = __builtin_convertvector(r1, bf16x4);
+                const bf16x4 p2 = __builtin_convertvector(r1 - __builtin_convertvector(p1, floatx4), bf16x4);
+                *reinterpret_cast<bf16x4*>(orow + 16 * gq) = p0;
+                *reinterpret_cast<bf16x4*>(orow + TP * RBO + 16 * gq) = p1;
+                *reinterpret_cast<bf16x4*>(orow + 2 * TP * RBO + 16 * gq) = p2;
+            }
         } else if constexpr (P16) {
             char* orow = reinterpret_cast<char*>(qo_smem) + (ct * 32 + l31) * RBO + (wave * kDh + 4 * h) * 2;
 #pragma unroll
@@ -1033,12 +1198,44 @@ __global__ __launch_bounds__(256, 2) void attn_q_out_fused_kernel(const float* _
     __syncthreads();  // Os complete
 
     // ---- F: y^T[c][px] of the 32-pixel tile = wave
-    floatx16 yv[RT];
+    // TRI (64-pixel tile = two 32-pixel tiles): wave = (pixel tile wave & 1) x (half of the output channels wave >> 1) — RTW = RT / 2 row tiles of 32 channels per wave;
+    // the LayerNorm sums of phase G then span two waves and are exchanged through LDS
+    floatx16 yv[RTW];
 #pragma unroll
-    for (int rt = 0; rt < RT; ++rt)
+    for (int rt = 0; rt < RTW; ++rt)
 #pragma unroll
         for (int r = 0; r < 16; ++r) yv[rt][r] = 0.f;
-    if constexpr (PAIR) {
+    if constexpr (TRI) {
+        // six products per K step of 16 (o0 w2, o1 w1, o2 w0, o0 w1, o1 w0, o0 w0: smallest first)
+        const char* brow = reinterpret_cast<const char*>(qo_smem) + (prow + l31) * RBO + 16 * h;
+#pragma unroll
+        for (int ks = 0; ks < NKF; ++ks) {
+            if (ks + DF < NKF) {
+#pragma unroll
+                for (int p = 0; p < 3; ++p)
+#pragma unroll
+                    for (int rt = 0; rt < RTW; ++rt)
+                        wo3[(ks + DF) % (DF + 1)][p][rt] = *reinterpret_cast<const bf16x8*>(wo3row + p * WOPL + (size_t)rt * 32 * kHid * 2 + 1024 * (ks + DF));
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            const auto& wa3c = wo3[ks % (DF + 1)];
+            const bf16x8 b0 = *reinterpret_cast<const bf16x8*>(brow + 32 * ks);
+            const bf16x8 b1 = *reinterpret_cast<const bf16x8*>(brow + TP * RBO + 32 * ks);
+            const bf16x8 b2 = *reinterpret_cast<const bf16x8*>(brow + 2 * TP * RBO + 32 * ks);
+#pragma unroll
+            for (int rt = 0; rt < RTW; ++rt) yv[rt] = M16::mfma(wa3c[2][rt], b0, yv[rt]);
+#pragma unroll
+            for (int rt = 0; rt < RTW; ++rt) yv[rt] = M16::mfma(wa3c[1][rt], b1, yv[rt]);
+#pragma unroll
+            for (int rt = 0; rt < RTW; ++rt) yv[rt] = M16::mfma(wa3c[0][rt], b2, yv[rt]);
+#pragma unroll
+            for (int rt = 0; rt < RTW; ++rt) yv[rt] = M16::mfma(wa3c[1][rt], b0, yv[rt]);
+#pragma unroll
+            for (int rt = 0; rt < RTW; ++rt) yv[rt] = M16::mfma(wa3c[0][rt], b1, yv[rt]);
+#pragma unroll
+            for (int rt = 0; rt < RTW; ++rt) yv[rt] = M16::mfma(wa3c[0][rt], b0, yv[rt]);
+        }
+    } else if constexpr (PAIR) {
         const char* wrow = reinterpret_cast<const char*>(wout_pair) + ((size_t)l31 * kHid + 8 * h) * 2;
         constexpr size_t WPL = (size_t)C * kHid * 2;   // bytes between the hi and the lo plane of Wout
         const char* brow = reinterpret_cast<const char*>(qo_smem) + (wave * 32 + l31) * RBO + 16 * h;
@@ -1137,43 +1334,57 @@ __global__ __launch_bounds__(256, 2) void attn_q_out_fused_kernel(const float* _
     // ---- G: bias, LayerNorm over the C channels of pixel 32 wave + l31 (this lane holds c = 32 rt + (r&3) + 8(r>>2) + 4h)
     float sum = 0.f;
 #pragma unroll
-    for (int rt = 0; rt < RT; ++rt)
+    for (int rt = 0; rt < RTW; ++rt)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            yv[rt][r] += bias[32 * rt + (r & 3) + 8 * (r >> 2) + 4 * h];
+            yv[rt][r] += bias[32 * (rt0 + rt) + (r & 3) + 8 * (r >> 2) + 4 * h];
             sum += yv[rt][r];
         }
     sum = half_sum(sum);
+    // TRI: the other half of the pixel's channels sits in wave ^ 2 — partial sums through LDS (behind the planes; added in a fixed order: deterministic)
+    [[maybe_unused]] float* red = reinterpret_cast<float*>(reinterpret_cast<char*>(qo_smem) + qo_tri_main_bytes(C));   // [sum | sq][channel half][64 pixels]
+    if constexpr (TRI) {
+        if (h == 0) red[(wave >> 1) * TP + prow + l31] = sum;
+        __syncthreads();   // (every wave has left phase F: the region is free for the normalised rows below)
+        sum = red[prow + l31] + red[TP + prow + l31];
+    }
     const float mean = sum * (1.0f / (float)C);
     float sq = 0.f;
 #pragma unroll
-    for (int rt = 0; rt < RT; ++rt)
+    for (int rt = 0; rt < RTW; ++rt)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             yv[rt][r] -= mean;
             sq += yv[rt][r] * yv[rt][r];
         }
     sq = half_sum(sq);
+    if constexpr (TRI) {
+        if (h == 0) red[2 * TP + (wave >> 1) * TP + prow + l31] = sq;
+        __syncthreads();
+        sq = red[2 * TP + prow + l31] + red[3 * TP + prow + l31];
+    }
     const float rstd = __builtin_amdgcn_rsqf(sq * (1.0f / (float)C) + eps);
     // Ys = this wave's own 32 rows of the region.  C <= 128: row stride LDO, exactly the Os rows only this wave read in phase F.
     // C = 256: the rows are wider than an Os row, so they overlap other waves' Os rows -> wait until every wave has left phase F.
     // PAIR: the fp16 planes put other waves' Os rows inside this wave's Ys rows for every C -> always wait.
-    if constexpr (C > kHid || P16) __syncthreads();
-    float* yrow = Os + (wave * 32 + l31) * LDY + 4 * h;
+    if constexpr (!TRI && (C > kHid || P16)) __syncthreads();
+    float* yrow = Os + (prow + l31) * LDY + 32 * rt0 + 4 * h;
 #pragma unroll
-    for (int rt = 0; rt < RT; ++rt)
+    for (int rt = 0; rt < RTW; ++rt)
 #pragma unroll
         for (int gq = 0; gq < 4; ++gq) {
-            const floatx4 g4 = *reinterpret_cast<const floatx4*>(g2 + 32 * rt + 8 * gq + 4 * h);
+            const floatx4 g4 = *reinterpret_cast<const floatx4*>(g2 + 32 * (rt0 + rt) + 8 * gq + 4 * h);
             *reinterpret_cast<floatx4*>(yrow + 32 * rt + 8 * gq) =
                 floatx4{yv[rt][4 * gq] * rstd * g4.x, yv[rt][4 * gq + 1] * rstd * g4.y, yv[rt][4 * gq + 2] * rstd * g4.z,
                         yv[rt][4 * gq + 3] * rstd * g4.w};
         }
     // the wave re-reads only its own rows: LDS operations of one wave complete in order, no block barrier needed
-    __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0)
+    // (TRI: a wave stores the 16-row slab it staged, which four waves normalised -> block barrier)
+    if constexpr (TRI) __syncthreads();
+    else __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0)
     auto residual_store = [&](auto full_tag) {
         constexpr bool FULL = decltype(full_tag)::value;
-        const size_t slab = (img + t0 + wave * 32) * C;   // the wave's 32 rows are contiguous: element 4 i of the slab is piece i
+        const size_t slab = (img + t0 + wave * SL) * C;   // the wave's 32 rows are contiguous: element 4 i of the slab is piece i
         floatx4 xr[NQ];
         if (FULL && KEEP && keep_res) {
 #pragma unroll
@@ -1183,14 +1394,14 @@ __global__ __launch_bounds__(256, 2) void attn_q_out_fused_kernel(const float* _
             for (int j = 0; j < NQ; ++j) {  // residual loads first, all in flight
                 const int i = lane + 64 * j, row = lane / C4 + (64 / C4) * j, c4 = lane % C4;   // (C4 divides 64)
                 if constexpr (FULL) xr[j] = *reinterpret_cast<const floatx4*>(xres + slab + 4 * i);
-                else xr[j] = *reinterpret_cast<const floatx4*>(xres + (img + min(t0 + wave * 32 + row, N - 1)) * C + 4 * c4);
+                else xr[j] = *reinterpret_cast<const floatx4*>(xres + (img + min(t0 + wave * SL + row, N - 1)) * C + 4 * c4);
             }
         }
 #pragma unroll
         for (int j = 0; j < NQ; ++j) {
             const int i = lane + 64 * j, row = lane / C4 + (64 / C4) * j, c4 = lane % C4;   // (C4 divides 64)
-            const int n = t0 + wave * 32 + row;
-            const floatx4 v = *reinterpret_cast<const floatx4*>(Os + (wave * 32 + row) * LDY + 4 * c4);
+            const int n = t0 + wave * SL + row;
+            const floatx4 v = *reinterpret_cast<const floatx4*>(Os + (wave * SL + row) * LDY + 4 * c4);
             if constexpr (FULL) *reinterpret_cast<floatx4*>(y + slab + 4 * i) = v + xr[j];
             else if (n < N) *reinterpret_cast<floatx4*>(y + (img + n) * C + 4 * c4) = v + xr[j];
         }
@@ -2099,6 +2310,7 @@ void attention_global_init() {
     IRSDE_A16_ATTR(64, 2, false); IRSDE_A16_ATTR(128, 2, false); IRSDE_A16_ATTR(256, 2, false);
     IRSDE_A16_ATTR(64, 2, true); IRSDE_A16_ATTR(128, 2, true); IRSDE_A16_ATTR(256, 2, true);
     IRSDE_A16_ATTR(64, 3, false); IRSDE_A16_ATTR(128, 3, false); IRSDE_A16_ATTR(256, 3, false);
+    IRSDE_A16_ATTR(64, 4, false); IRSDE_A16_ATTR(128, 4, false); IRSDE_A16_ATTR(256, 4, false);
 #undef IRSDE_A16_ATTR
     IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_q_out_fused_kernel<64>),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -2115,6 +2327,17 @@ void launch_attention_kv_context(const float* xn, const float* wkv, int B, int N
     const int len = attn_chunk_len(N, B);
     const int nch = attn_num_chunks(N, B);
     if (nch != ws.nch) throw HipError("attention workspace chunk mismatch");
+    if (op16 == 4) {   // fp32 on three bf16 pieces (the exact-fp32 engine, IRSDE_SPLIT3_ATTN): wkv_pair = three planes of [256][C] in fragment order
+        if (!wkv_pair || act_bf16 || !attn_split3_has_instance(C)) throw HipError("attention_kv_context: the three-piece mode needs its weight planes, fp32 tensors, C = 64 / 128 / 256");
+        const size_t lds3 = (size_t)3 * kKvTileTri * (2 * C + 16);
+#define IRSDE_KV3_LAUNCH(CC) hipLaunchKernelGGL((attn_kv_ctx_kernel<CC, 4>), dim3(nch, B), dim3(256), lds3, s, xn, wkv, ws.pmax, ws.pctx, ws.psum, N, len, nch, ln_g, ln_eps, wkv_pair, 1.f)
+        if (C == 64) IRSDE_KV3_LAUNCH(64); else if (C == 128) IRSDE_KV3_LAUNCH(128); else IRSDE_KV3_LAUNCH(256);
+#undef IRSDE_KV3_LAUNCH
+        hipLaunchKernelGGL(attn_ctx_finalize_kernel, dim3(B * kHeads, 4), dim3(1024), 0, s, ws.pctx, ws.psum, ws.pmax, ws.ctx, nch,
+                           1.0f / (float)N, 1.0f / sqrtf((float)kDh));
+        IRSDE_HIP_CHECK(hipGetLastError());
+        return;
+    }
     if (op16) {   // one bf16 / fp16 operand plane (IRSDE_FLAG_BF16 / IRSDE_FLAG_FP16): C = 64 / 128 / 256
         if (!wkv_pair || (op16 != 2 && op16 != 3) || (act_bf16 && op16 != 2) || (C != 64 && C != 128 && C != 256))
             throw HipError("attention_kv_context: the 16-bit operand modes need their weight plane, C = 64 / 128 / 256; bf16 storage goes with bf16 operands");
@@ -2175,6 +2398,16 @@ void launch_attention_q_out_fused(const float* xn, const float* x, const float* 
                                   const float* ln_g, const unsigned short* wq_pair, const unsigned short* wout_pair, float wq_inv,
                                   float wout_inv, int op16, bool act_bf16) {
     if (C != 64 && C != 128 && C != 256) throw HipError("attention_q_out_fused: C must be 64, 128 or 256");
+    if (op16 == 4) {   // fp32 on three bf16 pieces: wq_pair / wout_pair = three planes each; 64-pixel tiles
+        if (!wq_pair || !wout_pair || act_bf16) throw HipError("attention_q_out_fused: the three-piece mode needs its weight planes and fp32 tensors");
+        const size_t lds3 = qo_tri_main_bytes(C) + (size_t)4 * kQoTileTri * sizeof(float);   // + the LayerNorm partial sums
+        const dim3 grid3((N + kQoTileTri - 1) / kQoTileTri, B);
+#define IRSDE_QO3_LAUNCH(CC) hipLaunchKernelGGL((attn_q_out_fused_kernel<CC, 4>), grid3, dim3(256), lds3, s, xn, x, wq, ws.ctx, wout, bias, g2, y, N, eps, ln_g, wq_pair, wout_pair, 1.f, 1.f)
+        if (C == 64) IRSDE_QO3_LAUNCH(64); else if (C == 128) IRSDE_QO3_LAUNCH(128); else IRSDE_QO3_LAUNCH(256);
+#undef IRSDE_QO3_LAUNCH
+        IRSDE_HIP_CHECK(hipGetLastError());
+        return;
+    }
     if (op16) {   // one bf16 / fp16 operand plane per projection
         if (!wq_pair || !wout_pair || (op16 != 2 && op16 != 3) || (act_bf16 && op16 != 2))
             throw HipError("attention_q_out_fused: the 16-bit operand modes need their weight planes; bf16 storage goes with bf16 operands");

@@ -148,6 +148,10 @@ int irsde_debug_force_wino_poly(int mode);
  * are made at irsde_finalize_weights) — 0 never, 1 by the plan's rule, 2 wherever eligible (exact fp32, K a multiple of 32, 32-bit component offsets);
  * any other value returns to the default (the rule; the IRSDE_SPLIT3 tuning knob).  IRSDE_FLAG_NO_SPLIT3 wins over every mode. */
 int irsde_debug_force_split3(int mode);
+/* Test / measurement hook (process-wide): the three-piece bf16 projections of the exact-fp32 engine's fused LinearAttention blocks (C = 64 / 128 / 256) in plans
+ * BUILT from now on — 0 never, 1 by the plan's rule, 2 wherever a kernel instance exists; any other value returns to the default (the rule; the IRSDE_SPLIT3_ATTN
+ * tuning knob).  IRSDE_FLAG_NO_SPLIT3 and irsde_debug_force_split3(0) win over every mode; irsde_debug_force_split3(2) does not force it. */
+int irsde_debug_force_split3_attn(int mode);
 /* Test / measurement hook (process-wide, read at every launch): caps the grid of the three-piece GEMM's persistent launch at n blocks, n >= 8 (one per XCD),
  * so that a small problem makes every block walk several items; a negative n returns to the default (one block per compute unit).  0 .. 7: IRSDE_ERR_INVALID,
  * nothing changes.  Results do not depend on it (tests/test_gpu_split3_walk.py). */
