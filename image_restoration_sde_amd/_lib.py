@@ -47,7 +47,7 @@ SYMBOLS = [
     "irsde_last_error", "irsde_version", "irsde_create", "irsde_create_nafnet", "irsde_destroy", "irsde_num_weights",
     "irsde_weight_name", "irsde_weight_shape", "irsde_load_weight", "irsde_finalize_weights",
     "irsde_set_schedule", "irsde_unet_forward", "irsde_sample", "irsde_sde_step", "irsde_philox_normal",
-    "irsde_get_profile", "irsde_debug_tap", "irsde_work_model", "irsde_debug_conv", "irsde_debug_conv_choice", "irsde_debug_conv_halo_choice", "irsde_debug_conv_features", "irsde_plan_describe", "irsde_bench_conv", "irsde_op_profile", "irsde_debug_split_gemm", "irsde_bench_naf_chain", "irsde_debug_force_subbatches", "irsde_debug_force_chain_groups", "irsde_debug_force_wino_poly", "irsde_debug_force_split3", "irsde_debug_force_split3_attn", "irsde_debug_force_split3_blocks", "irsde_debug_scam", "irsde_debug_scam_full",
+    "irsde_get_profile", "irsde_debug_tap", "irsde_work_model", "irsde_debug_conv", "irsde_debug_conv_choice", "irsde_debug_conv_halo_choice", "irsde_debug_conv_features", "irsde_plan_describe", "irsde_bench_conv", "irsde_op_profile", "irsde_debug_split_gemm", "irsde_bench_naf_chain", "irsde_debug_force_subbatches", "irsde_debug_force_chain_groups", "irsde_debug_force_wino_poly", "irsde_debug_force_split3", "irsde_debug_force_split3_attn", "irsde_debug_force_split3_blocks", "irsde_debug_force_split3_1x1", "irsde_debug_split3_1x1", "irsde_debug_split3_1x1_choice", "irsde_debug_scam", "irsde_debug_scam_full",
     "irsde_debug_scam_stream", "irsde_debug_scam_full_stream", "irsde_debug_force_scam_stream",
     "irsde_debug_naf_gate_sca", "irsde_debug_tlsc", "irsde_debug_ln_film", "irsde_debug_naf_lnconv", "irsde_debug_naf_chain", "irsde_debug_naf_chain_split_order",
     "irsde_debug_full_attention16",
@@ -144,6 +144,9 @@ def _declare(lib):
     lib.irsde_debug_force_wino_poly.argtypes = [c.c_int]
     lib.irsde_debug_force_split3.argtypes = [c.c_int]
     lib.irsde_debug_force_split3_attn.argtypes = [c.c_int]
+    lib.irsde_debug_force_split3_1x1.argtypes = [c.c_int]
+    lib.irsde_debug_split3_1x1.argtypes = [P, c.c_int, c.c_int, P, c.c_int, c.c_int, P, P, P, c.c_int, c.c_int, c.c_int, c.c_int, P]
+    lib.irsde_debug_split3_1x1_choice.argtypes = [c.c_int] * 13 + [c.c_uint] + [c.c_int] * 6 + [c.c_char_p, c.c_int]
     lib.irsde_debug_force_split3_blocks.argtypes = [c.c_int]
     lib.irsde_debug_scam.argtypes = [P, c.c_int, c.c_int, c.c_int, c.c_int] + [P] * 12 + [P, P]
     lib.irsde_debug_scam_full.argtypes = [P, c.c_int, c.c_int, c.c_int, c.c_int] + [P] * 12 + [P, P]

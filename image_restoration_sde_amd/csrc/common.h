@@ -188,6 +188,35 @@ void launch_gemm_split_triples(const SplitGemmArgs& a, int ncomp, hipStream_t s,
 void set_force_split3_blocks(int n);   // irsde_debug_force_split3_blocks: caps the persistent launch's grid (>= 8); -1 = one block per CU
 bool gemm_split_triples_fits(long long M, long long N, long long K, long long ldc);   // K % 32 == 0 and every component slice inside the 32-bit offset range
 void launch_split_triples(const float* in, unsigned short* out, int ncomp, size_t rows, int K, hipStream_t s);   // f32 [ncomp][rows][K] -> that layout
+// The plain 1x1 convolution on three bf16 pieces with the A operand split INSIDE the kernel (gemm_split3a_kernel; "a" = activations in f32):
+//   out[m][n] = sum_k A[m][k] W[n][k] (+ bias[n]),   A = up to two f32 NHWC sources side by side (in0: C0 channels, pixel stride pix0; in1: C1, pix1),
+// W as the triples launch_split_triples writes for [N][K = C0 + C1].  Bit-identical to split_triples_kernel on A followed by gemm_split3i_kernel.
+struct Split3aArgs {
+    const float* in0 = nullptr;
+    const float* in1 = nullptr;   // second source or null (C1 = 0)
+    int C0 = 0, C1 = 0;           // multiples of 32: a 32-k step lies in one source
+    int pix0 = 0, pix1 = 0;       // floats between consecutive rows (pixels) of each source
+    const unsigned short* w3 = nullptr;
+    const float* bias = nullptr;  // [N] or null
+    float* out = nullptr;         // element (m, n) at out + m * out_stride + n
+    int M = 0, N = 0, out_stride = 0;
+    int nblk_n = 0;               // set by the launcher
+};
+// every source and the weight triples inside the 32-bit offset range, C0 / C1 multiples of 32; why_not (optional) names the first reason
+bool gemm_split3a_fits(const Split3aArgs& a, const char** why_not = nullptr);
+int gemm_split3a_blocks(long long M, int N, int cus, bool walk = true);   // the launch's grid: pure (the cap of irsde_debug_force_split3_blocks comes on top)
+constexpr size_t kSplit3aLds = (size_t)2 * (256 * 128 + 128 * 192);
+void launch_gemm_split3a(const Split3aArgs& a, hipStream_t s, const Split3Launch& o = {});   // (o.walk / o.drain RULE = the production walk with the ring)
+// Does a direct-path layer run on gemm_split3a_kernel?  A pure function of its arguments (it reads neither the environment nor a device).
+//   p: the layer as Builder::conv() has it in front of push_conv (p.splits: what push_conv would choose);  exact_f32: the engine's arithmetic is the exact-fp32
+//   one and the plan is not the naive one;  master: split3_mode();  knob: split3_1x1_mode() (0 never, 1 the measured rule, 2 wherever eligible);  cus: CU count
+struct Split3x1Choice {
+    bool adopt = false;
+    const char* why_not = "";   // the first reason of a refusal
+    int grid = 0, lds = 0;
+};
+Split3x1Choice split3_1x1_choose(const ConvParams& p, bool exact_f32, int master, int knob, int cus);
+Split3aArgs split3_1x1_args(const ConvParams& p, const unsigned short* w3);   // the kernel's arguments of an adopted layer
 void launch_split_planes(const float* in, unsigned short* out, size_t n, size_t plane, int nplanes, hipStream_t s, bool f16 = false,
                          float scale = 1.0f);  // f32 -> bf16 pieces (f16: two IEEE fp16 pieces of in * scale), plane-major
 void launch_wino_output(const WinoParams& p, hipStream_t s);

@@ -16,6 +16,7 @@
 #include <memory>
 #include <mutex>
 #include <string>
+#include <tuple>
 #include <vector>
 
 #include "../../include/irsde_hip.h"
@@ -74,6 +75,11 @@ inline bool split3_wants_weights(int flags) { return !(flags & kSplit3NotExactF3
 // Off with the GEMMs' master switch (IRSDE_SPLIT3 = 0, IRSDE_FLAG_NO_SPLIT3); the master's mode 2 does not force it.
 int split3_attn_mode();
 void set_force_split3_attn(int mode);   // irsde_debug_force_split3_attn
+// The same engine's plain 1x1 convolutions (bias-only epilogue: the res_conv of the up path, to_qkv of the unfused attention blocks) on three bf16 pieces with the
+// activations split inside the GEMM (gemm_split3a_kernel): IRSDE_SPLIT3_1X1 = 0 never, 1 by the rule of split3_1x1_choose, 2 wherever eligible
+// (irsde_debug_force_split3_1x1 overrides the knob for plans built afterwards).  Off with the master switch, which does not force it, as for the attention mode.
+int split3_1x1_mode();
+void set_force_split3_1x1(int mode);   // irsde_debug_force_split3_1x1
 
 inline int wino_min_c(int tile) {
     return tuning_env_int(tile == 4 ? "IRSDE_WINO4_MINC" : "IRSDE_WINO2_MINC", tile == 4 ? 64 : 256);
@@ -504,18 +510,22 @@ struct irsde_engine {
         return make_pair_copy(pair_copies, w, n, [&](unsigned short* d, bool f16, float sc) { launch_split_planes(w, d, n, n, 2, stream, f16, sc); });
     }
     // three unscaled bf16 planes [3][rows * K] of a packed fp32 [rows][K] weight matrix (hi, mid, lo: all 24 significand bits; bf16 has fp32's exponent range, so no
-    // scale) in MFMA-fragment order (attn_frag3_index), made once per tensor: the fused attention kernels' three-piece projections
-    std::map<const float*, unsigned short*> triple_copies;
-    const unsigned short* triple_copy(const float* w, size_t rows, int K) {
-        const size_t n = rows * (size_t)K;
-        auto it = triple_copies.find(w);
+    // scale), made once per tensor and layout.  TRIPLES_FRAG3: MFMA-fragment order (attn_frag3_index), the fused attention kernels' three-piece projections;
+    // TRIPLES_ROWPAIR: the row-pair-interleaved blocks of split3_layout.h, the B operand of gemm_split3a_kernel (the plain 1x1 convolutions)
+    enum TripleLayout { TRIPLES_FRAG3 = 0, TRIPLES_ROWPAIR = 1 };
+    std::map<std::tuple<const float*, int, size_t>, unsigned short*> triple_copies;   // (a q projection is the first 128 rows of its to_qkv tensor: the rows are part of the key)
+    const unsigned short* triple_copy(const float* w, size_t rows, int K, TripleLayout layout = TRIPLES_FRAG3) {
+        const auto key = std::make_tuple(w, (int)layout, rows);
+        auto it = triple_copies.find(key);
         if (it != triple_copies.end()) return it->second;
+        const size_t elems = layout == TRIPLES_ROWPAIR ? split3_comp_elems(rows, (size_t)K) : 3 * rows * (size_t)K;
         unsigned short* d = nullptr;
-        IRSDE_HIP_CHECK(hipMalloc(&d, 3 * n * sizeof(unsigned short)));
+        IRSDE_HIP_CHECK(hipMalloc(&d, elems * sizeof(unsigned short)));
         dev_allocs.push_back(reinterpret_cast<float*>(d));
-        launch_split_frag3(w, d, rows, K, stream);
+        if (layout == TRIPLES_ROWPAIR) launch_split_triples(w, d, 1, rows, K, stream);
+        else launch_split_frag3(w, d, rows, K, stream);
         IRSDE_HIP_CHECK(hipStreamSynchronize(stream));
-        triple_copies[w] = d;
+        triple_copies[key] = d;
         return d;
     }
     // The PAIR kernels of conv_igemm.hip read their weights pair-interleaved: [rows][K / 32][hi 32 | lo 32] (split_pairs_kernel), one

@@ -124,6 +124,7 @@ enum class ConvPath {
     Fused64,       // 64 couts per block: launch variant
     Fused64Pair,   // its fp16-pair twin: launch variant
     Fused64T,      // wino_fused_t.hip, two tile groups: launch variant
+    Split3a,       // a plain 1x1 layer on gemm_split3a_kernel (three bf16 pieces, the activations split inside the GEMM)
 };
 struct DebugConvRow {
     int code;
@@ -147,7 +148,7 @@ constexpr DebugConvRow kDebugConv[] = {
     wino(3, ConvPath::WinoF4, 0), wino(13, ConvPath::WinoF4, 71), wino(23, ConvPath::WinoF4, 72),
     poly(24, ConvPath::Poly, false), poly(25, ConvPath::Poly, true),
     poly(26, ConvPath::PolyTriples, false), poly(27, ConvPath::PolyTriples, true), poly(28, ConvPath::PolyTriples, true, true),
-    on_path(48, ConvPath::F4Triples),
+    on_path(48, ConvPath::F4Triples), on_path(49, ConvPath::Split3a),
     on_path(44, ConvPath::F4Pairs, Operand::F16), on_path(45, ConvPath::F4Pairs, Operand::BF16),
     on_path(46, ConvPath::DirectPair, Operand::F16), on_path(47, ConvPath::DirectPair, Operand::BF16),
     on_path(33, ConvPath::Fused32),
@@ -178,6 +179,7 @@ enum class BenchKind {
     Fused64TStamps,   // once, with its per-wave cycle stamps printed: stamp variant
     PairGemm,         // the pair GEMM alone: ablation twin
     TripleGemm,       // the three-piece GEMM alone: 5 launch twin + ablation twin
+    Split3aGemm,      // a 1x1 layer on gemm_split3a_kernel alone: 5 launch twin + ablation twin
 };
 struct BenchRow {
     int lo, hi;   // the codes lo .. hi
@@ -214,6 +216,7 @@ constexpr BenchRow kBenchConv[] = {
     bench(4650, 4653, BenchKind::Fused64TStamps, 12),                  // no patch traffic / output stores dropped / residual loads dropped / the coalesced-epilogue twin
     bench(472, 476, BenchKind::PairGemm, 0),                           // full, no loads, (none), no MFMAs, no output stores: launch_gemm_split_pairs refuses the one it lacks
     bench(490, 504, BenchKind::TripleGemm, 0),                         // split3_launch_twin(arg / 5, arg % 5)
+    bench(510, 524, BenchKind::Split3aGemm, 0),                        // the same numbering on gemm_split3a_kernel (K = 1, stride 1, no epilogue but none)
 };
 
 template <class Row, size_t N, class Lo, class Hi>
@@ -699,6 +702,15 @@ int irsde_debug_conv(const float* in0, int C0, const float* in1, int C1, int B, 
             launch_wino_output(sp.out, s);
             break;
         }
+        case ConvPath::Split3a: {
+            if (splits > 1) p.splits = splits;
+            const Split3x1Choice c = split3_1x1_choose(p, true, 2, 2, device_cu_count());
+            if (!c.adopt) throw HipError(std::string("debug_conv: selector 49 runs a plain 1x1 layer (bias only): ") + c.why_not);
+            unsigned short* dwt = mem.alloc<unsigned short>(split3_comp_elems((size_t)Cout, (size_t)Cin));
+            launch_split_triples(dw, dwt, 1, (size_t)Cout, Cin, s);
+            launch_gemm_split3a(split3_1x1_args(p, dwt), s);
+            break;
+        }
         case ConvPath::F4Pairs: {
             const bool f16 = r.op == Operand::F16;
             if (!wino_shape_ok(p, 4) || Cin % 32) throw HipError("debug_conv: shape not eligible for the pair GEMM");
@@ -983,6 +995,42 @@ int irsde_debug_force_split3_attn(int mode) {
     set_force_split3_attn(mode >= 0 && mode <= 2 ? mode : -1);
     return IRSDE_OK;
 }
+int irsde_debug_force_split3_1x1(int mode) {
+    set_force_split3_1x1(mode >= 0 && mode <= 2 ? mode : -1);
+    return IRSDE_OK;
+}
+
+int irsde_debug_split3_1x1(const float* in0, int C0, int pix0, const float* in1, int C1, int pix1, const float* w, const float* bias, float* out, int M, int N,
+                           int out_stride, int mode, void* stream) {
+    return guard([&] {
+        if (!in0 || !w || !out || (C1 && !in1) || mode < 0 || mode > 2) throw HipError("debug_split3_1x1: bad argument");
+        hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+        conv_global_init();
+        Split3aArgs a;
+        a.in0 = in0; a.C0 = C0; a.pix0 = pix0; a.in1 = C1 ? in1 : nullptr; a.C1 = C1; a.pix1 = C1 ? pix1 : 0;
+        a.bias = bias; a.out = out; a.M = M; a.N = N; a.out_stride = out_stride;
+        const char* why = nullptr;
+        if (!gemm_split3a_fits(a, &why)) throw HipError(std::string("debug_split3_1x1: ") + why);
+        Scratch mem(s);
+        unsigned short* wt = mem.alloc<unsigned short>(split3_comp_elems((size_t)N, (size_t)(C0 + C1)));
+        launch_split_triples(w, wt, 1, (size_t)N, C0 + C1, s);
+        a.w3 = wt;
+        launch_gemm_split3a(a, s, split3_launch_twin(mode));
+        IRSDE_HIP_CHECK(hipStreamSynchronize(s));
+    });
+}
+
+int irsde_debug_split3_1x1_choice(int B, int Hin, int Win, int C0, int C1, int Cout, int K, int stride, int pad, int in_shift, int operand, int storage, int pair,
+                                  unsigned features, int splits, int nz, int engine_flags, int master, int knob, int cu_count, char* out, int out_len) {
+    return guard([&] {
+        if (!out || out_len < 1 || K < 1 || stride < 1 || cu_count < 1 || operand < 0 || operand > 2 || storage < 0 || storage > 2 || (pair && operand == 0))
+            throw HipError("debug_split3_1x1_choice: bad argument");
+        const ConvParams p = choice_hook_params(B, Hin, Win, C0, C1, Cout, K, stride, pad, in_shift, operand, storage, pair, features, splits, nz);
+        const Split3x1Choice c = split3_1x1_choose(p, !(engine_flags & kSplit3NotExactF32), master, knob, cu_count);
+        snprintf(out, (size_t)out_len, "adopt=%d grid=%d lds=%d why_not=%s", c.adopt ? 1 : 0, c.grid, c.lds, c.why_not);
+    });
+}
+
 int irsde_debug_force_split3_blocks(int n) {
     if (n >= 0 && n < 8) return guard([&] { throw HipError("debug_force_split3_blocks: n must be at least 8 (one block per XCD), or negative for the default"); });
     set_force_split3_blocks(n);
@@ -1150,6 +1198,17 @@ int irsde_bench_conv(int variant, int B, int H, int W, int Cin, int Cout, int K,
             unsigned short* dwp = mem.alloc<unsigned short>(2 * nw);
             launch_split_pairs(dw, dwp, (size_t)Cout, K * K * Cin, s, f16, 64.0f);
             p.w_pair = dwp; p.pair_scale = 1.0f / 64.0f; p.f16 = f16 ? 1 : 0;
+        }
+        if (kind == BenchKind::Split3aGemm) {   // the layer on gemm_split3a_kernel alone (weights split ahead of the timed launches)
+            const Split3x1Choice c = split3_1x1_choose(p, true, 2, 2, device_cu_count());
+            if (!c.adopt || up || epi) throw HipError(std::string("bench_conv: variants 510 - 524 run a plain 1x1 layer: ") + (c.adopt ? "no epilogue" : c.why_not));
+            unsigned short* dwt = mem.alloc<unsigned short>(split3_comp_elems((size_t)Cout, (size_t)Cin));
+            launch_split_triples(dw, dwt, 1, (size_t)Cout, Cin, s);
+            const Split3aArgs a = split3_1x1_args(p, dwt);
+            const Split3Launch twin = split3_launch_twin(arg / 5, arg % 5);
+            for (int i = 0; i < 2; ++i) launch_gemm_split3a(a, s, twin);
+            *ms_out = time_launches(s, iters, [&] { launch_gemm_split3a(a, s, twin); });
+            return;
         }
         if (kind == BenchKind::TripleGemm || kind == BenchKind::PairGemm) {   // the 36 component GEMMs of the layer alone, on random operands
             if (K != 3 || stride != 1 || !wino_shape_ok(p, 4)) throw HipError("bench_conv: Winograd variants need an eligible 3x3 stride-1 layer");

@@ -44,9 +44,9 @@ struct Builder {
         pl->net_ops.push_back(std::move(op));
     }
 
-    void push_conv(ConvParams p) {
+    // split-K for under-filled grids (small batch / deep levels): the slice count push_conv gives a layer
+    int conv_splits(const ConvParams& p) const {
         const int M = p.B * p.Ho * p.Wo;
-        // split-K for under-filled grids (small batch / deep levels)
         const int bn = conv_base_bn(p.Cout);
         const int blocks = ((M + 127) / 128) * ((p.Cout + bn - 1) / bn);
         const int nk = p.KH * p.KW * ((p.C0 + p.C1) / 32);
@@ -55,6 +55,37 @@ struct Builder {
             splits = std::min(std::min(nk / 8, (512 + blocks - 1) / blocks), 16);
             if (splits < 2) splits = 1;
         }
+        return splits;
+    }
+
+    // A plain 1x1 layer of the exact-fp32 engine on gemm_split3a_kernel (split3_1x1_choose decides; profiles/split3_1x1.md).  The op is what push_conv would
+    // push (OP_CONV, the same flops / exec_flops / bytes and text), its kernel named split3a bf16x3.
+    bool push_split3_1x1(const ConvParams& p0) {
+        if (p0.KH != 1 || p0.KW != 1 || naive) return false;
+        ConvParams p = p0;
+        p.splits = conv_splits(p);
+        const Split3x1Choice c = split3_1x1_choose(p, !(e->cfg.flags & kSplit3NotExactF32), split3_mode(), split3_1x1_mode(), device_cu_count());
+        if (!c.adopt) return false;
+        const int M = p.B * p.Ho * p.Wo, K = p.C0 + p.C1;
+        const Split3aArgs a = split3_1x1_args(p, e->triple_copy(p.w, (size_t)p.Cout, K, irsde_engine::TRIPLES_ROWPAIR));
+        Op op;
+        op.kind = OP_CONV;
+        op.flops = conv_flops(p);
+        op.exec_flops = op.flops;
+        op.bytes = 4.0 * (double)p.B * p.Hin * p.Win * (double)K + 4.0 * (double)M * p.Cout + 4.0 * (double)p.Cout * K;
+        char buf[256];
+        snprintf(buf, sizeof buf, "conv M=%d Cout=%d Cin=%d k=%dx%d s=%d up=%d splits=%d blocks=%d flops=%.4g kernel=split3a bf16x3", M, p.Cout, K, p.KH, p.KW,
+                 p.stride, p.in_shift, 1, c.grid, op.flops);
+        op.desc = buf;
+        op.fn = [a](hipStream_t s) { launch_gemm_split3a(a, s); };
+        push_op(std::move(op));
+        return true;
+    }
+
+    void push_conv(ConvParams p) {
+        const int M = p.B * p.Ho * p.Wo;
+        const int blocks = ((M + 127) / 128) * ((p.Cout + conv_base_bn(p.Cout) - 1) / conv_base_bn(p.Cout));
+        const int splits = conv_splits(p);
         if (splits > 1) {
             p.splits = splits;
             p.partial = pl->alloc((size_t)splits * M * p.Cout, true);
@@ -138,6 +169,7 @@ struct Builder {
             if (w.wino_uf && push_wino_fused(p, w.wino_uf, false)) return out;
             if (w.wino_u4 && wino_shape_ok(p, 4) && push_wino(p, w.wino_u4, 4, nullptr, 1.f, w.wino_u4t)) return out;
             if (w.wino_u2 && wino_shape_ok(p, 2) && push_wino(p, w.wino_u2, 2)) return out;
+            if (push_split3_1x1(p)) return out;
         }
         push_conv(p);
         return out;
@@ -1095,6 +1127,12 @@ void set_force_split3_attn(int mode) { g_force_split3_attn.store(mode, std::memo
 int split3_attn_mode() {
     const int f = g_force_split3_attn.load(std::memory_order_relaxed);
     return f >= 0 ? f : tuning_env_int("IRSDE_SPLIT3_ATTN", 1);
+}
+static std::atomic<int> g_force_split3_1x1{-1};   // irsde_debug_force_split3_1x1: -1 = the IRSDE_SPLIT3_1X1 knob
+void set_force_split3_1x1(int mode) { g_force_split3_1x1.store(mode, std::memory_order_relaxed); }
+int split3_1x1_mode() {
+    const int f = g_force_split3_1x1.load(std::memory_order_relaxed);
+    return f >= 0 ? f : tuning_env_int("IRSDE_SPLIT3_1X1", 1);
 }
 static std::atomic<int> g_force_wino_poly{-1};   // irsde_debug_force_wino_poly: -1 = the IRSDE_WINO_POLY knob
 void set_force_wino_poly(int mode) { g_force_wino_poly.store(mode, std::memory_order_relaxed); }

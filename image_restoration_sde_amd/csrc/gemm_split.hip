@@ -27,6 +27,7 @@ typedef float floatx16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned uintx4 __attribute__((ext_vector_type(4)));
+typedef float floatx4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -468,6 +469,265 @@ __global__ __launch_bounds__(512, 1) void gemm_split3i_kernel(const SplitGemmArg
                 for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
     }
 }
+// ---------------------------------------------------------------------------------------------------------------
+// The plain 1x1 convolutions on three pieces ("a" = the A operand is an ordinary f32 activation tensor, split INSIDE the kernel; profiles/split3_1x1.md):
+//     out[m][n] = sum_k A[m][k] W[n][k] (+ bias[n]),   A = up to two f32 NHWC sources side by side (the never-materialised concat [x | skip]),
+// W = the triples of split_triples_kernel (split3_layout.h), exactly gemm_split3i_kernel's B operand.  A separate triple writer for A would add an HBM pass of
+// 6 bytes per element, more than the GEMM saves: the raw f32 rows go to LDS by LDS-DMA instead, and a wave splits its own fragment in registers
+// (hi = RNE bf16(x), mid = RNE bf16(x - hi), lo = RNE bf16(x - hi - mid): split_triples_kernel's chain) and feeds the three planes straight to the MFMAs.
+// Per output element: the six products of a 16-k sub-step in gemm_split3i_kernel's order, over the same K order, with the same k -> lane assignment (lane
+// (row l31, h) holds k = 16 sb + 8 h .. + 7), so the result is BIT-IDENTICAL to split_triples_kernel on A followed by gemm_split3i_kernel.
+// Block tile 256 x 128, 8 waves of 32 rows x all 128 columns (1 x 4 MFMA tiles): every A element is split once per column tile, and there is no LDS write of
+// pieces.  A wave reads per K-step 4 KB of A and the 24 KB of B: 28 KB, against gemm_split3i's 24.
+// LDS: two stages of A 256 rows x 128 B (raw f32; 16-byte pieces XOR-swizzled by (row >> 1) & 7 on the SOURCE address, gemm_split2i's image) + B 128 rows x
+// 192 B (gemm_split3i's image and rotation) = 56 KB.
+// The ring is gemm_split3i's with the operands' roles swapped: the two PHASES of a K-step are the two column halves (64 columns = 2 MFMA tiles, 24 MFMAs per
+// wave), the A fragments of a K-step stay in registers through both.  Units: A(t) 32 KB = 4 wave-loads per wave, B0(t) / B1(t) = the 64 rows of a column half,
+// 12 KB = 96 lane slots per wave: 2 wave-loads, the second over slots 32 .. 95 (it fetches slots 32 .. 63 again: every wave issues whole wave-loads and the
+// counts are the same constants for all waves).
+//     phase 0 of step t   multiplies columns 0 - 63: sub-step 0 from set 0 (read in the phase before), reads sub-step 1 of A(t), B0(t) behind its first MFMA
+//                         group and splits A three groups later; issues B1(t+1) (2 loads); ends with vmcnt(2): B1(t), A(t+1), B0(t+1) have landed
+//                         (vmcnt(0) in the last step)
+//     phase 1 of step t   multiplies columns 64 - 127 against the same A pieces: reads sub-step 0 of B1(t) (uncovered: B1(t) is retired only at the end of
+//                         phase 0, so once per K-step the matrix pipe waits for an LDS read), sub-step 1 behind the first group, and behind the
+//                         first group of sub-step 1 sub-step 0 of A(t+1), B0(t+1) (split three groups later); issues A(t+2), B0(t+2) (6 loads); no vmcnt wait
+// A unit is restaged one phase after the phase that last read it and first read one phase after the wait + barrier that retired it, as there.
+// WALK / DRAIN: the same twins (irsde_debug_split3_1x1 modes 1 / 2).  The bias is loaded at an item's opening, in front of its LDS-DMA loads, and is retired
+// by the opening's vmcnt(0): no ordinary load is pending while the ring runs.
+template <int ABL = 0, bool WALK = true, bool DRAIN = false>
+__global__ __launch_bounds__(512, 1) void gemm_split3a_kernel(const Split3aArgs g) {
+    constexpr int TN = 4, BM = 256, BN = 128;
+    constexpr int AROW = 128, BROW = 192;                                           // bytes per LDS row: 32 f32 of A, 12 pieces of B
+    constexpr int A_STAGE = BM * AROW, B_HALF = 64 * BROW, STAGE = A_STAGE + 2 * B_HALF;   // bytes
+    constexpr int PA[6] = {0, 1, 2, 0, 1, 0};
+    constexpr int PB[6] = {2, 1, 0, 1, 0, 0};
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int l31 = lane & 31, h = lane >> 5;
+    // XCD-contiguous row tiles with their column tiles side by side; the walk deals an XCD's items round-robin to its blocks (gemm_split3i_kernel)
+    const int units = (g.M + BM - 1) / BM;
+    const int xcd = blockIdx.x & 7, jx = blockIdx.x >> 3;
+    const int ulo = (int)((long long)xcd * units / 8), uhi = (int)((long long)(xcd + 1) * units / 8);
+    const int nitems = (uhi - ulo) * g.nblk_n;
+    const int it_step = WALK ? ((int)gridDim.x - xcd + 7) >> 3 : nitems;
+    int it = jx;
+    if (it >= nitems) return;
+    const int nk0 = g.C0 / SG_BK, nk = (g.C0 + g.C1) / SG_BK;
+    const unsigned pairb = (unsigned)nk * 384u;   // bytes per row pair of W
+
+    // staging.  A: wave-load ps = the 8 rows of chunk ps * 8 + wave, lane = (row lane / 8, slot lane % 8) fetches the row's piece slot ^ ((row >> 1) & 7).
+    // B half hb: the wave's rows 8 wave .. + 7 of the half, lane slot s = (row s / 12, position s % 12), wave-load 0 = slots 0 .. 63, 1 = slots 32 .. 95.
+    // Rows past M / N are clamped: they feed accumulator rows / columns that are never stored.
+    int m0, n0;
+    unsigned a_voff0[4], a_voff1[4], b_voff[2][2];
+    float bias_r[TN];
+    auto set_item = [&](int i) {
+        const int unit = ulo + i / g.nblk_n, nblk = i % g.nblk_n;
+        m0 = unit * BM;
+        n0 = nblk * BN;
+#pragma unroll
+        for (int ps = 0; ps < 4; ++ps) {
+            const int row = (ps * 8 + wave) * 8 + (lane >> 3);
+            const unsigned pc = (unsigned)((lane & 7) ^ ((row >> 1) & 7)) * 16u;
+            int m = m0 + row;
+            m = m < g.M ? m : g.M - 1;
+            a_voff0[ps] = (unsigned)m * (unsigned)g.pix0 * 4u + pc;
+            a_voff1[ps] = (unsigned)m * (unsigned)g.pix1 * 4u + pc;
+        }
+#pragma unroll
+        for (int hb = 0; hb < 2; ++hb)
+#pragma unroll
+            for (int wl = 0; wl < 2; ++wl) {
+                const int sl = wl * 32 + lane;
+                const int r = sl / 12, pos = sl - r * 12;
+                const int rowt = wave * 8 + r;
+                int j = pos - ((rowt >> 2) & 3);
+                j = j < 0 ? j + 12 : j;
+                int n = n0 + hb * 64 + rowt;
+                n = n < g.N ? n : g.N - 1;
+                b_voff[hb][wl] = (unsigned)(n >> 1) * pairb + (unsigned)(n & 1) * 192u + (unsigned)j * 16u;
+            }
+        if (g.bias) {
+#pragma unroll
+            for (int j = 0; j < TN; ++j) {
+                int n = n0 + j * 32 + l31;
+                n = n < g.N ? n : g.N - 1;
+                bias_r[j] = g.bias[n];
+            }
+        }
+    };
+    auto issue_a = [&](int kb, int ps) {   // one of the wave's 4 loads of A(kb)
+        const bool second = kb >= nk0;
+        const char* gsrc = second ? reinterpret_cast<const char*>(g.in1) + (size_t)(kb - nk0) * 128 : reinterpret_cast<const char*>(g.in0) + (size_t)kb * 128;
+        IRSDE_GLDS16(gsrc + (second ? a_voff1[ps] : a_voff0[ps]), lds + (kb & 1) * STAGE + (ps * 8 + wave) * 1024);
+    };
+    auto issue_b = [&](int kb, int hb, int wl) {   // one of the wave's 2 loads of column half hb of B(kb)
+        const char* gsrc = reinterpret_cast<const char*>(g.w3) + (size_t)kb * 384;
+        IRSDE_GLDS16(gsrc + b_voff[hb][wl], lds + (kb & 1) * STAGE + A_STAGE + hb * B_HALF + wave * 8 * BROW + wl * 512);
+    };
+    auto issue_first = [&]() {   // an item's opening loads, in the ring's order: B0, A, B1 of step 0, then A, B0 of step 1
+        issue_b(0, 0, 0); issue_b(0, 0, 1);
+#pragma unroll
+        for (int ps = 0; ps < 4; ++ps) issue_a(0, ps);
+        issue_b(0, 1, 0); issue_b(0, 1, 1);
+        if (nk > 1) {
+#pragma unroll
+            for (int ps = 0; ps < 4; ++ps) issue_a(1, ps);
+            issue_b(1, 0, 0); issue_b(1, 0, 1);
+        }
+    };
+
+    floatx16 acc[TN];
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
+
+    set_item(it);
+    issue_first();
+
+    // fragment offsets.  A: row l31 of the wave's 32, the two 16-byte pieces 2 q, 2 q + 1 of k block q = 2 sb + h, swizzled.  B: as gemm_split3i_kernel.
+    const int swz = (l31 >> 1) & 7;
+    int fa_off[2][2], fr_off[3][2];
+#pragma unroll
+    for (int sb = 0; sb < 2; ++sb)
+#pragma unroll
+        for (int e = 0; e < 2; ++e) fa_off[sb][e] = l31 * AROW + (((2 * (2 * sb + h) + e) ^ swz) * 16);
+#pragma unroll
+    for (int p = 0; p < 3; ++p)
+#pragma unroll
+        for (int sb = 0; sb < 2; ++sb) fr_off[p][sb] = l31 * BROW + ((p * 4 + sb * 2 + h + ((l31 >> 2) & 3)) % 12) * 16;
+    // fragment sets: [sb] = the 16-k sub-step; fa holds the A pieces of a K-step through both phases, ra the raw f32 of the sub-step read last
+    bf16x8 fa[2][3], fb[2][3][2];
+    floatx4 ra[2];
+    auto read_a = [&](int sb, const char* a) {
+#pragma unroll
+        for (int e = 0; e < 2; ++e) ra[e] = *reinterpret_cast<const floatx4*>(a + fa_off[sb][e]);
+    };
+    auto split_a = [&](int sb) {   // split_triples_kernel's chain: every residual is exact in f32
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            float r = ra[e >> 2][e & 3];
+#pragma unroll
+            for (int p = 0; p < 3; ++p) {
+                const __bf16 hb = (__bf16)r;
+                fa[sb][p][e] = hb;
+                r -= (float)hb;
+            }
+        }
+    };
+    auto read_b = [&](int sb, const char* b) {
+#pragma unroll
+        for (int p = 0; p < 3; ++p)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) fb[sb][p][j] = *reinterpret_cast<const bf16x8*>(b + j * 32 * BROW + fr_off[p][sb]);
+    };
+    const bool late = wave >= 4;
+    const int a_base = wave * 32 * AROW;
+    for (;;) {
+        IRSDE_WAIT_VM(0);   // the item's opening loads and its bias have landed (and, behind an earlier item, that item's stores have left)
+        IRSDE_PHASE_BARRIER();
+        read_a(0, lds + a_base);   // sub-step 0 of step 0: no MFMA covers these reads (nor, in every K-step, phase 1's read of sub-step 0 of B1 below)
+        read_b(0, lds + A_STAGE);
+        split_a(0);
+        __builtin_amdgcn_sched_barrier(0);
+        for (int st = 0; st < nk; ++st) {
+            const bool more1 = st + 1 < nk, more2 = st + 2 < nk;
+            const char* a = lds + (st & 1) * STAGE + a_base;
+            const char* b = lds + (st & 1) * STAGE + A_STAGE;
+            const char* an = lds + ((st + 1) & 1) * STAGE + a_base;
+            const char* bn = lds + ((st + 1) & 1) * STAGE + A_STAGE;
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {   // phase i: column half i
+                if (i == 1) {   // B1(st) was retired by the wait + barrier that ended phase 0: its sub-step 0 cannot be read earlier, and no MFMA covers the read
+                    read_b(0, b + B_HALF);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+#pragma unroll
+                for (int sb = 0; sb < 2; ++sb)
+#pragma unroll
+                    for (int pr = 0; pr < 6; ++pr) {
+#pragma unroll
+                        for (int j = 0; j < 2; ++j) {
+                            if (ABL != 3) acc[2 * i + j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[sb][PA[pr]], fb[sb][PB[pr]][j], acc[2 * i + j], 0, 0, 0);
+                            else acc[2 * i + j][0] += (float)fa[sb][PA[pr]][0] * (float)fb[sb][PB[pr]][j][0];
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
+                        // fragment reads a whole sub-step ahead of their first use, behind the first MFMA group of the sub-step that covers them; the raw A
+                        // values are split three groups later, when they have arrived
+                        if (sb == 0 && pr == 0) {
+                            if (i == 0) {
+                                read_a(1, a);
+                                read_b(1, b);
+                            } else {
+                                read_b(1, b + B_HALF);
+                            }
+                        }
+                        if (i == 0 && sb == 0 && pr == 3) split_a(1);
+                        if (i == 1 && sb == 1 && more1) {   // sub-step 0 of the next step: A, B0(st + 1) were retired at the end of phase 0
+                            if (pr == 0) {
+                                read_a(0, an);
+                                read_b(0, bn);
+                            }
+                            if (pr == 3) split_a(0);
+                        }
+                        // the phase's loads one per MFMA group; the two waves of a SIMD (w and w + 4) issue theirs in different sub-steps
+                        if (ABL != 1 && (sb == 1) == late) {
+                            if (i == 0 && pr >= 1 && pr <= 2 && more1) issue_b(st + 1, 1, pr - 1);
+                            if (i == 1 && more2) {
+                                if (pr < 4) issue_a(st + 2, pr);
+                                else issue_b(st + 2, 0, pr - 4);
+                            }
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                // phase 0 retires B1(st) and A, B0(st + 1) and leaves B1(st + 1) in flight; phase 1 retires nothing and leaves that and A, B0(st + 2) in flight
+                if (DRAIN || (i == 0 && !more1)) IRSDE_WAIT_VM(0);
+                else if (i == 0) IRSDE_WAIT_VM(2);
+                IRSDE_PHASE_BARRIER();
+            }
+        }
+
+        // + bias, then registers -> buffer stores: rows past M dropped by the descriptor, columns past N masked
+        if (g.bias) {
+#pragma unroll
+            for (int j = 0; j < TN; ++j)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[j][r] += bias_r[j];
+        }
+        const int rowb_ = m0 + wave * 32, colb = n0;
+        float* ob = g.out + (long long)rowb_ * g.out_stride;
+        const int rows = g.M - rowb_;
+        const unsigned nrec = rows <= 0 ? 0u : (unsigned)(rows < 32 ? rows : 32) * (unsigned)g.out_stride * 4u;
+        const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(ob, 0, nrec, 0x00020000);
+        it += it_step;
+        const bool next = WALK && it < nitems;
+        if (next) {   // both stages are free behind the last step's barrier: the next item's opening loads go out ahead of this item's stores
+            __builtin_amdgcn_sched_barrier(0);
+            set_item(it);
+            issue_first();
+            __builtin_amdgcn_sched_barrier(0);
+        }
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+            const int colu = colb + j * 32;
+            if (colu + l31 < g.N && (ABL != 4 || acc[j][0] == 1.2345e30f)) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const float v = acc[j][r];   // (a copy: __builtin_bit_cast on the vector element itself reads element 0)
+                    const unsigned voff = (unsigned)(((r & 3) + 8 * (r >> 2) + 4 * h) * g.out_stride + colu + l31) * 4u;
+                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), ro, (int)voff, 0, 0);
+                }
+            }
+        }
+        if (!next) break;
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
+    }
+}
 #undef IRSDE_PHASE_BARRIER
 #undef IRSDE_WAIT_VM
 #undef IRSDE_GLDS16
@@ -575,7 +835,16 @@ void gemm_split_global_init() {
     IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split3i_kernel<0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split3i_kernel<0, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split3i_kernel<0, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split3a_kernel<0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split3a_kernel<0, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split3a_kernel<0, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
 #ifdef IRSDE_PROBES
+    for (const void* f : {reinterpret_cast<const void*>(gemm_split3a_kernel<1, true>), reinterpret_cast<const void*>(gemm_split3a_kernel<3, true>),
+                          reinterpret_cast<const void*>(gemm_split3a_kernel<4, true>), reinterpret_cast<const void*>(gemm_split3a_kernel<1, false>),
+                          reinterpret_cast<const void*>(gemm_split3a_kernel<3, false>), reinterpret_cast<const void*>(gemm_split3a_kernel<4, false>),
+                          reinterpret_cast<const void*>(gemm_split3a_kernel<1, true, true>), reinterpret_cast<const void*>(gemm_split3a_kernel<3, true, true>),
+                          reinterpret_cast<const void*>(gemm_split3a_kernel<4, true, true>)})
+        IRSDE_HIP_CHECK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split3i_kernel<1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split3i_kernel<3, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     IRSDE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_split3i_kernel<4, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -668,6 +937,122 @@ void launch_gemm_split_triples(const SplitGemmArgs& a, int ncomp, hipStream_t s,
         case Split3Launch::NO_STORES: launch_split3_abl<4>(walk, drain, grid, lds, s, g); break;
 #endif
         default: throw HipError("gemm_split_triples: the ablation twins are part of the PROBES build");
+    }
+    IRSDE_HIP_CHECK(hipGetLastError());
+}
+
+bool gemm_split3a_fits(const Split3aArgs& a, const char** why_not) {
+    const char* why = nullptr;
+    const unsigned long long lim = 0xffffffffull;
+    const long long K = (long long)a.C0 + a.C1;
+    if (a.M < 1 || a.N < 1) why = "empty";
+    else if (a.C0 < 32 || a.C0 % SG_BK) why = "C0 not a multiple of 32";
+    else if (a.C1 < 0 || a.C1 % SG_BK) why = "C1 not a multiple of 32";
+    else if (a.pix0 < a.C0 || a.pix0 % 4 || (a.C1 && (a.pix1 < a.C1 || a.pix1 % 4)) || a.out_stride < a.N) why = "bad stride";
+    // (the sources and the weights are addressed by 32-bit offsets from their bases; the output through a 64-bit base per wave and an offset inside its 32 rows)
+    else if ((unsigned long long)a.M * a.pix0 * 4ull >= lim || (unsigned long long)a.M * a.pix1 * 4ull >= lim ||
+             (unsigned long long)split3_comp_elems((size_t)a.N, (size_t)K) * 2ull >= lim || 32ull * a.out_stride * 4ull >= lim)
+        why = "beyond the 32-bit offset range";
+    if (why_not) *why_not = why;
+    return !why;
+}
+
+int gemm_split3a_blocks(long long M, int N, int cus, bool walk) {
+    const long long units = (M + 255) / 256;
+    long long per_xcd = 0;
+    for (int x = 0; x < 8; ++x) per_xcd = std::max(per_xcd, (x + 1) * units / 8 - x * units / 8);
+    long long blocks = 8 * per_xcd * ((N + 127) / 128);   // one per item of the fullest XCD, times eight
+    if (walk) blocks = std::min<long long>(blocks, std::max(8, cus));
+    return blocks >= 0x7fffffffll ? -1 : (int)blocks;
+}
+
+Split3aArgs split3_1x1_args(const ConvParams& p, const unsigned short* w3) {
+    Split3aArgs a;
+    a.in0 = p.in0; a.C0 = p.C0; a.pix0 = p.pix0;
+    a.in1 = p.C1 ? p.in1 : nullptr; a.C1 = p.C1; a.pix1 = p.C1 ? p.pix1 : 0;
+    a.w3 = w3; a.bias = p.bias; a.out = p.out;
+    a.M = p.B * p.Ho * p.Wo; a.N = p.Cout; a.out_stride = p.out_stride;
+    return a;
+}
+
+// The rule (knob 1; measured per layer against the f32 kernels at B = 16 and B = 2 on 256 x 256 and at 16 x 512 x 512, and end to end; profiles/split3_1x1.md,
+// sections 3 and 5):
+//   * at least 128 output channels: the column tile is 128 wide, and the one narrower layer of the UNet (128 -> 64 at level 0, HBM-bound) is 5 - 19 % SLOWER;
+//   * at least 1e10 executed FLOP.  Kernel for kernel every layer with Cout >= 128 is faster at all three batch shapes, but END TO END the B = 2 plan with its
+//     layers adopted (6.4e9 FLOP each and less) ran 4 % slower than the parent (3.287 -> 3.151 img/s): the launches behind the adopted layers took longer than
+//     the layers gained.  The floor sits above those layers; at B = 16 it keeps the eight res_conv (5.2e10) and the to_qkv from 1.3e10 on;
+//   * 2048 rows and K = 128: the smallest values measured to win kernel for kernel.
+static constexpr long long kSplit3x1MinRows = 2048;
+static constexpr int kSplit3x1MinK = 128, kSplit3x1MinCout = 128;
+static constexpr double kSplit3x1MinFlop = 1e10;
+Split3x1Choice split3_1x1_choose(const ConvParams& p, bool exact_f32, int master, int knob, int cus) {
+    Split3x1Choice c;
+    const long long M = (long long)p.B * p.Ho * p.Wo;
+    const char* why = nullptr;
+    if (!exact_f32) why = "not the exact-fp32 engine";
+    else if (master <= 0) why = "IRSDE_SPLIT3 = 0";
+    else if (knob <= 0) why = "IRSDE_SPLIT3_1X1 = 0";
+    else if (p.KH != 1 || p.KW != 1) why = "not a 1x1 convolution";
+    else if (p.stride != 1) why = "stride";
+    else if (p.in_shift) why = "in_shift";
+    else if (p.pad_y || p.pad_x) why = "padding";
+    else if (p.film) why = "film";
+    else if (p.silu) why = "silu";
+    else if (p.res) why = "res";
+    else if (p.in_scale) why = "in_scale";
+    else if (p.ch_scale) why = "ch_scale";
+    else if (p.gate || p.gate_film) why = "gate";
+    else if (p.shuffle) why = "shuffle";
+    else if (p.ln_g) why = "ln_g";
+    else if (p.in_bf16 || p.out_bf16 || p.in_f16 || p.out_f16) why = "16-bit storage";
+    else if (p.w_bf || p.w_pair) why = "16-bit operands";
+    else if (p.splits > 1) why = "split-K";
+    else if (p.nz != 1) why = "batched";
+    else if (M < 1 || M >= 0x7fffffffll) why = "empty";
+    else gemm_split3a_fits(split3_1x1_args(p, nullptr), &why);
+    if (!why && knob == 1) {
+        const int K = p.C0 + p.C1;
+        if (M < kSplit3x1MinRows) why = "rule: rows";
+        else if (K < kSplit3x1MinK) why = "rule: K";
+        else if (p.Cout < kSplit3x1MinCout) why = "rule: Cout";
+        else if (2.0 * (double)M * K * p.Cout < kSplit3x1MinFlop) why = "rule: FLOP";
+    }
+    if (why) {
+        c.why_not = why;
+        return c;
+    }
+    c.adopt = true;
+    c.grid = gemm_split3a_blocks(M, p.Cout, cus, true);
+    c.lds = (int)kSplit3aLds;
+    return c;
+}
+
+template <int ABL>
+static void launch_split3a_abl(bool walk, bool drain, dim3 grid, hipStream_t s, const Split3aArgs& g) {
+    if (drain) hipLaunchKernelGGL((gemm_split3a_kernel<ABL, true, true>), grid, dim3(512), kSplit3aLds, s, g);
+    else if (walk) hipLaunchKernelGGL((gemm_split3a_kernel<ABL, true>), grid, dim3(512), kSplit3aLds, s, g);
+    else hipLaunchKernelGGL((gemm_split3a_kernel<ABL, false>), grid, dim3(512), kSplit3aLds, s, g);
+}
+void launch_gemm_split3a(const Split3aArgs& a, hipStream_t s, const Split3Launch& o) {
+    const char* why = nullptr;
+    if (!gemm_split3a_fits(a, &why)) throw HipError(std::string("gemm_split3a: ") + why);
+    if (!a.in0 || (a.C1 && !a.in1) || !a.w3 || !a.out) throw HipError("gemm_split3a: null operand");
+    const bool walk = o.walk != Split3Launch::OFF, drain = o.drain == Split3Launch::ON;
+    if (drain && !walk) throw HipError("gemm_split3a: the drain twin exists on the walk only");
+    Split3aArgs g = a;
+    g.nblk_n = (a.N + 127) / 128;
+    const int forced = g_force_split3_blocks.load(std::memory_order_relaxed);
+    const int blocks = gemm_split3a_blocks(a.M, a.N, forced > 0 ? forced : device_cu_count(), walk);
+    if (blocks < 1) throw HipError("gemm_split3a: grid too large");
+    const dim3 grid((unsigned)blocks);
+    switch (o.abl) {
+        case Split3Launch::FULL: launch_split3a_abl<0>(walk, drain, grid, s, g); break;
+#ifdef IRSDE_PROBES
+        case Split3Launch::NO_LOADS: launch_split3a_abl<1>(walk, drain, grid, s, g); break;
+        case Split3Launch::NO_MFMA: launch_split3a_abl<3>(walk, drain, grid, s, g); break;
+        case Split3Launch::NO_STORES: launch_split3a_abl<4>(walk, drain, grid, s, g); break;
+#endif
+        default: throw HipError("gemm_split3a: the ablation twins are part of the PROBES build");
     }
     IRSDE_HIP_CHECK(hipGetLastError());
 }

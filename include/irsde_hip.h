@@ -61,6 +61,9 @@
  *        codes/utils/deg_utils.py; csrc/degrade.hip).  No engine is involved.
  *        Additive, same version: irsde_imresize (util.imresize of codes/data/util.py:238-387, the antialiased cubic downscale with which
  *        LQGT_dataset makes LQ from GT; csrc/degrade.hip).  No engine is involved.
+ *        Debug header only, same version: irsde_debug_split3_1x1, irsde_debug_split3_1x1_choice, irsde_debug_force_split3_1x1, irsde_debug_conv selector 49,
+ *        irsde_bench_conv 510 - 524 (the exact-fp32 engine runs its plain 1x1 convolutions on three bf16 pieces where the plan's rule adopts them, the
+ *        activations split inside the GEMM; fp32-equivalent; IRSDE_FLAG_NO_SPLIT3 restores the f32 kernels; tuning knob IRSDE_SPLIT3_1X1).
  */
 #ifndef IRSDE_HIP_H
 #define IRSDE_HIP_H

@@ -26,6 +26,8 @@ extern "C" {
  *   48 three-launch Winograd F(4x4,3x3) on the exact-fp32 engine's three-piece GEMM (gemm_split3i_kernel: row-pair-interleaved bf16 triples, six products);
  *      26 / 27 selectors 24 / 25 on that GEMM (V written as triples by the polyphase input transform); 28: selector 27 with the transform's per-thread V
  *      writer instead of its whole-line writer (the bit-identity twin)
+ *   49 a plain 1x1 layer (stride 1, no padding, C0 and C1 multiples of 32, bias only) on gemm_split3a_kernel: the weights as three bf16 pieces, the activations
+ *      split inside the GEMM (csrc/gemm_split.hip); anything else is refused with the reason irsde_debug_split3_1x1_choice names
  *   46 / 47 the direct implicit GEMM on the PAIR kernels (conv_igemm.hip: fp32 storage, activations split into 16-bit hi + lo pieces while
  *           staged, three cross products on the 16-bit MFMA): fp16 / bf16 pieces
  *   44 / 45 three-launch Winograd F(4x4,3x3) with the engine's pair GEMM (pair-interleaved operands, LDS-DMA): fp16 / bf16 hi + lo pieces
@@ -123,6 +125,8 @@ int irsde_debug_split_gemm(const float* A, const float* B, float* C, int M, int 
  *   490 the three-piece GEMM (gemm_split3i_kernel) alone on the layer's 36 F(4x4,3x3) component shapes, 491 / 493 / 494 without its global loads / MFMAs /
  *     output stores (PROBES build; 492: no such twin, the launch refuses it); 495 - 499: the same five on the one-item-per-block launch (the walk's twin)
  *     500 - 504: the same five on the drain twin (vmcnt(0) in front of every barrier of the K loop: what the load ring's span across barriers buys)
+ *   510 a plain 1x1 layer (K = 1, stride 1, epi 0) on gemm_split3a_kernel alone, 511 / 513 / 514 without its global loads / MFMAs / output stores (PROBES
+ *     build; 512: no such twin); 515 - 519: the same five on the one-item-per-block launch; 520 - 524: on the drain twin
  *   480 / 481 / 482 a direct layer on the PAIR kernels (fp16 / bf16 pieces / fp16 without the 256 x 256 tile)
  * epi: 0 none, 1 FiLM+SiLU, 2 SiLU+residual. */
 int irsde_bench_conv(int variant, int B, int H, int W, int Cin, int Cout, int K, int stride, int up, int epi, int iters,
@@ -156,6 +160,23 @@ int irsde_debug_force_split3_attn(int mode);
  * so that a small problem makes every block walk several items; a negative n returns to the default (one block per compute unit).  0 .. 7: IRSDE_ERR_INVALID,
  * nothing changes.  Results do not depend on it (tests/test_gpu_split3_walk.py). */
 int irsde_debug_force_split3_blocks(int n);
+/* Test / measurement hook (process-wide): the plain 1x1 convolutions of the exact-fp32 engine on three bf16 pieces (gemm_split3a_kernel) in plans BUILT from
+ * now on — 0 never, 1 by the plan's rule, 2 wherever eligible; any other value returns to the default (the rule; the IRSDE_SPLIT3_1X1 tuning knob).
+ * IRSDE_FLAG_NO_SPLIT3 and irsde_debug_force_split3(0) win over every mode; irsde_debug_force_split3(2) does not force it. */
+int irsde_debug_force_split3_1x1(int mode);
+/* Kernel-level test hook of gemm_split3a_kernel (csrc/gemm_split.hip): out[m][n] = sum_k A[m][k] w[n][k] (+ bias[n]) with A = up to two f32 sources side by
+ * side (in0: C0 channels at pixel stride pix0; in1: C1, pix1, or NULL with C1 = 0; C0, C1 multiples of 32), w [N][C0 + C1] f32, bias [N] or NULL, out at row
+ * stride out_stride >= N — all DEVICE pointers.  w is split into three bf16 pieces on the device, the activations inside the kernel: bit-identical to
+ * irsde_debug_split_gemm(nplanes 43) on the concatenated A.  mode: 0 the production walk, 1 one item per block, 2 the walk with vmcnt(0) in front of every
+ * barrier of the K loop (the bit-identity twins).  irsde_debug_force_split3_blocks caps this walk's grid too.  Synchronises `stream`. */
+int irsde_debug_split3_1x1(const float* in0, int C0, int pix0, const float* in1, int C1, int pix1, const float* w, const float* bias, float* out, int M, int N,
+                           int out_stride, int mode, void* stream);
+/* Host-only test hook: does a layer run on gemm_split3a_kernel (split3_1x1_choose)?  Never touches a device, never reads the environment.  The layer as for
+ * irsde_debug_conv_choice; engine_flags: the engine's IRSDE_FLAG_* word; master: the mode of IRSDE_SPLIT3 / irsde_debug_force_split3; knob: the mode of
+ * IRSDE_SPLIT3_1X1; cu_count: compute units.  Writes one line into out:
+ *   adopt=<0|1> grid=<blocks> lds=<bytes> why_not=<the first reason of a refusal, empty when adopted> */
+int irsde_debug_split3_1x1_choice(int B, int Hin, int Win, int C0, int C1, int Cout, int K, int stride, int pad, int in_shift, int operand, int storage, int pair,
+                                  unsigned features, int splits, int nz, int engine_flags, int master, int knob, int cu_count, char* out, int out_len);
 
 /* Kernel-level test hook: ONE SCAM of the stereo-sr NAFBlock (csrc/scam.hip + the projection GEMM on the implicit-GEMM kernel, the engine's
  * fp32 path).  x / out: device NHWC [2 B_pairs][H][W][C] (views stacked [L_0..L_{B-1}, R_0..R_{B-1}] as inside the reference network);
