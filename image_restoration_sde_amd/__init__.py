@@ -17,6 +17,8 @@ csrc/ -> libirsde_hip.so) with the reference's own Python interface on top:
     stereo_sr.ConditionalUNet
                        codes/config/stereo-sr/models/modules/DenoisingUNet_arch.py (the IR-SDE UNet with a full-resolution SCAM on every level)
     metrics            codes/utils/img_utils.py:136-234 + codes/data/util.py:177-198 (tensor2img / PSNR / SSIM / Y channel)
+    LPIPS (metrics.LPIPS)
+                       lpips.LPIPS(net='alex') of codes/config/deraining/test.py:74, 149-154 (an AlexNet feature tower + the distance, fp32)
     degradations       codes/utils/deg_utils.py (upscale: bicubic by an integer factor; mask_to: the inpainting composite; add_noise) +
                        codes/data/util.py:221-387 (imresize: the MATLAB-style antialiased cubic downscale that makes LQ from GT; modcrop)
 """
@@ -29,11 +31,12 @@ from .nafnet import ConditionalNAFNet  # noqa: F401
 from . import denoising_sde  # noqa: F401
 from .denoising_sde import DenoisingSDE  # noqa: F401
 from . import metrics  # noqa: F401
+from .metrics import LPIPS  # noqa: F401
 from . import degradations  # noqa: F401
 from . import latent  # noqa: F401
 from . import latent_bokeh  # noqa: F401
 from . import stereo_sr  # noqa: F401
 from .latent import CNAFNetLocal, LatentDenoisingModel  # noqa: F401
 
-__all__ = ["IRSDE", "DenoisingSDE", "denoising_sde", "metrics", "degradations", "latent", "latent_bokeh", "stereo_sr", "LatentDenoisingModel", "CNAFNetLocal", "ConditionalUNet", "ConditionalNAFNet", "DenoisingModel", "ReverseSDEDenoisingModel", "create_model", "define_G", "build_library",
+__all__ = ["IRSDE", "DenoisingSDE", "denoising_sde", "metrics", "LPIPS", "degradations", "latent", "latent_bokeh", "stereo_sr", "LatentDenoisingModel", "CNAFNetLocal", "ConditionalUNet", "ConditionalNAFNet", "DenoisingModel", "ReverseSDEDenoisingModel", "create_model", "define_G", "build_library",
            "IrsdeError", "IrsdeLibraryError", "shard_bounds", "gather_batch", "sample_shard", "sample_sharded"]

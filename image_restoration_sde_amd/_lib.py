@@ -52,6 +52,7 @@ SYMBOLS = [
     "irsde_debug_naf_gate_sca", "irsde_debug_tlsc", "irsde_debug_ln_film", "irsde_debug_naf_lnconv", "irsde_debug_naf_chain", "irsde_debug_naf_chain_split_order",
     "irsde_debug_full_attention16",
     "irsde_eval_metrics", "irsde_tensor2img", "irsde_upscale_bicubic", "irsde_mask_to", "irsde_imresize",
+    "irsde_create_lpips", "irsde_lpips", "irsde_debug_lpips_tap",
     "irsde_set_lens_info", "irsde_nafnet_set_local_pool", "irsde_create_latent_unet", "irsde_latent_shapes", "irsde_latent_encode", "irsde_latent_decode", "irsde_latent_hidden",
 ]
 
@@ -166,6 +167,9 @@ def _declare(lib):
     lib.irsde_upscale_bicubic.argtypes = [P, P, c.c_int, c.c_int, c.c_int, c.c_int, c.c_int, P]
     lib.irsde_mask_to.argtypes = [P, P, c.c_int, c.c_int, c.c_int, c.c_int, P, c.c_int, c.c_int, c.c_int, c.c_int, P]
     lib.irsde_imresize.argtypes = [P, P] + [c.c_int] * 6 + [P, P, c.c_int, P, P, c.c_int, P]
+    lib.irsde_create_lpips.argtypes = [c.POINTER(P)]
+    lib.irsde_lpips.argtypes = [P, P, P, c.c_int, c.c_int, c.c_int, c.c_int, c.POINTER(c.c_double), c.POINTER(c.c_double), P]
+    lib.irsde_debug_lpips_tap.argtypes = [P, P, c.c_int, c.c_int, c.c_int, c.c_int, c.c_int, P, c.POINTER(c.c_int64), P]
     lib.irsde_set_lens_info.argtypes =[P, c.POINTER(c.c_float), c.c_int]
     lib.irsde_nafnet_set_local_pool.argtypes = [P, c.c_int, c.c_int, c.c_int, c.c_int]
     lib.irsde_create_latent_unet.argtypes = [c.POINTER(LatentConfig), c.POINTER(P)]

@@ -4,6 +4,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <functional>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -546,6 +547,27 @@ void launch_philox_normal(float* out, int B, int CHW, int t, uint64_t seed, uint
 // {squared-error sum RGB, SSIM-map sum RGB, squared-error sum Y, SSIM-map sum Y}.  Synchronises the stream.
 void eval_metrics(const float* out, const float* gt, int B, int C, int H, int W, int crop, double* sums_host, hipStream_t s);
 void tensor2img_u8(const float* in, unsigned char* out, int B, int C, int H, int W, hipStream_t s);
+
+// LPIPS v0.1 / AlexNet in fp32 (lpips.hip): the feature tower (prologue, five convolutions on the f32 MFMA with bias + ReLU, two max-pools) and the distance.
+struct LpipsLayer { int k, stride, pad, cin, cout; };   // AlexNet `features`; a 3x3 stride-2 max-pool (floor mode) sits in front of layers 2 and 3
+constexpr LpipsLayer kLpipsLayers[5] = {{11, 4, 2, 3, 64}, {5, 1, 2, 64, 192}, {3, 1, 1, 192, 384}, {3, 1, 1, 384, 256}, {3, 1, 1, 256, 256}};
+inline int lpips_cin_padded(int l) { return (kLpipsLayers[l].cin + 3) & ~3; }   // conv1 runs on 4 input channels (the 4th is zero)
+struct LpipsWeights {
+    const float* w[5];     // conv l + 1, K-major [KH * KW * Cin][Cout], k = (ky * KW + kx) * Cin + ci (conv1: Cin padded from 3 to 4 with zero rows)
+    const float* bias[5];  // [Cout]
+    const float* lin[5];   // the 1x1 lin layer of tap l + 1: [C]
+};
+struct LpipsGeom {
+    int h[5], w[5];    // the five taps' maps
+    int ph[2], pw[2];  // the pooled maps in front of conv2 / conv3
+};
+LpipsGeom lpips_geometry(int H, int W);   // throws below 31 x 31
+int lpips_dist_blocks(int hw);            // partial sums per image of a tap with hw pixels
+size_t lpips_workspace_floats(int N, int H, int W);
+void lpips_features(const LpipsWeights& wt, const float* in0, const float* in1, int B, int H, int W, int normalize, float* ws, float* taps[5], hipStream_t s,
+                    const std::function<void(const char*)>& mark);
+void lpips_distances(const LpipsWeights& wt, float* const taps[5], int B, int H, int W, double* partial, hipStream_t s,
+                     const std::function<void(const char*)>& mark);
 
 // Degradation front ends (degrade.hip): bicubic upscale by an integer factor 1..8 (NCHW fp32 -> [B][C][H scale][W scale]) and the inpainting
 // composite mask * x + (1 - mask) with uint8 masks [Bm][Hm][Wm][Cm] resized by nearest interpolation.  Stream-ordered, no synchronisation.

@@ -454,6 +454,13 @@ struct irsde_engine {
     std::vector<ConvW> lat_down, lat_up;
     std::vector<std::unique_ptr<LatentPlan>> lat_plans;
 
+    // LPIPS v0.1 / AlexNet (arch == 3, irsde_create_lpips): no score network, no schedule, no plans; csrc/lpips.hip
+    LpipsWeights lpips{};
+    float* lpips_ws = nullptr;        // the tower's workspace, kept between calls and grown on demand
+    size_t lpips_ws_floats = 0;
+    double* lpips_partial = nullptr;  // the distance kernel's per-block partial sums
+    size_t lpips_partial_n = 0;
+
     // schedule / FiLM tables
     int T = 0;
     float* coef_table = nullptr;  // [(T+1)][12]
@@ -572,6 +579,7 @@ inline bool stereo_engine(const irsde_engine* e) { return naf_stereo(e) || unet_
 inline bool uncond_engine(const irsde_engine* e) {
     return (e->arch == 0 && (e->cfg.flags & IRSDE_FLAG_UNCOND_FULLATTN) != 0) || (e->arch == 1 && (e->cfg.flags & IRSDE_FLAG_NAF_UNCOND) != 0);
 }
+inline bool lpips_engine(const irsde_engine* e) { return e->arch == 3; }
 inline int rup32(int c) { return (c + 31) & ~31; }
 // CNAFNetLocal: the pool window (K0, K1) of the NAFBlocks at `level` (encoder i and decoder n_enc - 1 - i: level i; middle: n_enc) — what the reference's
 // conversion forward on rand(train_size) freezes as kernel_size (local_arch.py:26-32): map size there x base_size / train_size.  false: no local pooling
@@ -591,6 +599,7 @@ inline float* film_of(const irsde_engine* e, const Plan* pl) { return pl->own_fi
 void build_inventory(irsde_engine* e);
 void build_inventory_naf(irsde_engine* e);
 void build_inventory_latent(irsde_engine* e);
+void build_inventory_lpips(irsde_engine* e);
 void finalize(irsde_engine* e);
 void compute_film_rows(irsde_engine* e, const float* tvals, int rows, float* dst, hipStream_t s);
 void ensure_film_cur(irsde_engine* e, int rows);
@@ -615,5 +624,6 @@ LatentPlan* get_latent_plan(irsde_engine* e, int B, int H, int W, bool decode);
 
 // engine_api.hip: runs the body of a C-ABI entry point; an exception becomes the IRSDE_ERR_* code and the thread's irsde_last_error() string
 int guard(const std::function<void()>& f);
+float* lpips_workspace(irsde_engine* e, int N, int H, int W);   // arch == 3: the tower's workspace for N images (grow-only)
 
 }  // namespace irsde

@@ -107,6 +107,25 @@ int guard(const std::function<void()>& f) {
     }
 }
 
+// The LPIPS tower's workspace for N images of H x W: kept in the engine, grown (after a device synchronisation) when a call needs more
+float* lpips_workspace(irsde_engine* e, int N, int H, int W) {
+    const size_t need = lpips_workspace_floats(N, H, W);
+    if (e->lpips_ws_floats < need) {
+        IRSDE_HIP_CHECK(hipDeviceSynchronize());
+        if (e->lpips_ws) (void)hipFree(e->lpips_ws);
+        e->lpips_ws = nullptr;
+        e->lpips_ws_floats = 0;
+        const hipError_t err = hipMalloc(&e->lpips_ws, need * sizeof(float));
+        if (err == hipErrorOutOfMemory) {
+            (void)hipGetLastError();
+            throw HipError("lpips: hipMalloc of " + std::to_string(need * sizeof(float)) + " bytes of workspace failed (out of memory): use a smaller batch");
+        }
+        IRSDE_HIP_CHECK(err);
+        e->lpips_ws_floats = need;
+    }
+    return e->lpips_ws;
+}
+
 }  // namespace irsde
 
 // =============================================================================================
@@ -230,6 +249,8 @@ void irsde_destroy(irsde_engine* e) {
     for (auto& kv : e->bf16_copies) (void)hipFree(kv.second);
     if (e->coef_table) (void)hipFree(e->coef_table);
     if (e->film_table) (void)hipFree(e->film_table);
+    if (e->lpips_ws) (void)hipFree(e->lpips_ws);
+    if (e->lpips_partial) (void)hipFree(e->lpips_partial);
     if (prev_dev >= 0) (void)hipSetDevice(prev_dev);  // destroy runs from a Python finaliser: leave the current device alone
     delete e;
 }
@@ -277,6 +298,7 @@ int irsde_finalize_weights(irsde_engine* e) {
 int irsde_set_schedule(irsde_engine* e, int T, const float* coef) {
     return guard([&] {
         if (!e || !coef || T < 1) throw HipError("bad schedule arguments");
+        if (lpips_engine(e)) throw HipError("set_schedule: an LPIPS engine (irsde_create_lpips) has no schedule");
         if (!e->finalized) throw HipError("set_schedule: weights not finalized");
         DeviceScope dev_scope(e->cfg.device);
         IRSDE_HIP_CHECK(hipDeviceSynchronize());
@@ -795,6 +817,81 @@ int irsde_eval_metrics(const float* out, const float* gt, int B, int C, int H, i
             metrics[b * 4 + 1] = sums[b * 4 + 1] / v_rgb;
             metrics[b * 4 + 2] = C == 3 ? psnr(sums[b * 4 + 2], n_y) : NAN;
             metrics[b * 4 + 3] = C == 3 ? sums[b * 4 + 3] / v_y : NAN;
+        }
+    });
+}
+
+int irsde_create_lpips(irsde_engine** out) {
+    return guard([&] {
+        if (!out) throw HipError("null argument");
+        auto* e = new irsde_engine();
+        e->arch = 3;
+        build_inventory_lpips(e);
+        *out = e;
+    });
+}
+
+int irsde_lpips(irsde_engine* e, const float* in0, const float* in1, int B, int H, int W, int normalize, double* dist, double* terms, void* stream) {
+    return guard([&] {
+        if (!e || !in0 || !in1 || !dist) throw HipError("lpips: null argument");
+        if (!lpips_engine(e)) throw HipError("lpips: not an LPIPS engine (irsde_create_lpips)");
+        if (!e->finalized) throw HipError("lpips: weights not finalized");
+        if (B < 1) throw HipError("lpips: B must be positive");
+        const LpipsGeom g = lpips_geometry(H, W);   // throws below 31 x 31
+        std::lock_guard<std::mutex> lk(e->mu);
+        DeviceScope dev_scope(e->cfg.device);
+        hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+        float* ws = lpips_workspace(e, 2 * B, H, W);
+        size_t np = 0;
+        for (int l = 0; l < 5; ++l) np += (size_t)B * lpips_dist_blocks(g.h[l] * g.w[l]);
+        if (e->lpips_partial_n < np) {
+            IRSDE_HIP_CHECK(hipDeviceSynchronize());
+            if (e->lpips_partial) (void)hipFree(e->lpips_partial);
+            e->lpips_partial = nullptr;
+            e->lpips_partial_n = 0;
+            IRSDE_HIP_CHECK(hipMalloc(&e->lpips_partial, np * sizeof(double)));
+            e->lpips_partial_n = np;
+        }
+        // an event in front of every launch group and one behind the last: the per-kernel times of this call (irsde_op_profile)
+        std::vector<std::string> desc;
+        auto mark = [&](const char* d) {
+            IRSDE_HIP_CHECK(hipEventRecord(get_event(e, desc.size()), s));
+            desc.push_back(d);
+        };
+        float* taps[5];
+        lpips_features(e->lpips, in0, in1, B, H, W, normalize, ws, taps, s, mark);
+        lpips_distances(e->lpips, taps, B, H, W, e->lpips_partial, s, mark);
+        IRSDE_HIP_CHECK(hipEventRecord(get_event(e, desc.size()), s));
+        std::vector<double> hp(np);
+        IRSDE_HIP_CHECK(hipMemcpyAsync(hp.data(), e->lpips_partial, np * sizeof(double), hipMemcpyDeviceToHost, s));
+        IRSDE_HIP_CHECK(hipStreamSynchronize(s));
+        e->op_ms.assign(desc.size(), 0.0);
+        e->op_desc = desc;
+        e->op_steps = 1;
+        for (size_t i = 0; i < desc.size(); ++i) {
+            float ms = 0.f;
+            IRSDE_HIP_CHECK(hipEventElapsedTime(&ms, e->ev_pool[i], e->ev_pool[i + 1]));
+            e->op_ms[i] = ms;
+        }
+        size_t off = 0;
+        for (int b = 0; b < B; ++b) dist[b] = 0.0;
+        std::vector<double> tl((size_t)B * 5);
+        for (int l = 0; l < 5; ++l) {
+            const int hw = g.h[l] * g.w[l], nb = lpips_dist_blocks(hw);
+            for (int b = 0; b < B; ++b) {
+                double acc = 0.0;
+                for (int k = 0; k < nb; ++k) acc += hp[off + (size_t)b * nb + k];
+                tl[(size_t)b * 5 + l] = acc / hw;
+            }
+            off += (size_t)B * nb;
+        }
+        for (int b = 0; b < B; ++b) {
+            double acc = 0.0;
+            for (int l = 0; l < 5; ++l) {
+                acc += tl[(size_t)b * 5 + l];
+                if (terms) terms[(size_t)b * 5 + l] = tl[(size_t)b * 5 + l];
+            }
+            dist[b] = acc;
         }
     });
 }

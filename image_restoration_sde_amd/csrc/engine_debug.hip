@@ -1371,4 +1371,24 @@ int irsde_bench_conv(int variant, int B, int H, int W, int Cin, int Cout, int K,
     });
 }
 
+int irsde_debug_lpips_tap(irsde_engine* e, const float* in, int B, int H, int W, int normalize, int tap, float* dst, int64_t dims[4], void* stream) {
+    return guard([&] {
+        if (!e || !in || !dims) throw HipError("debug_lpips_tap: null argument");
+        if (!lpips_engine(e)) throw HipError("debug_lpips_tap: not an LPIPS engine (irsde_create_lpips)");
+        if (!e->finalized) throw HipError("debug_lpips_tap: weights not finalized");
+        if (B < 1 || tap < 1 || tap > 5) throw HipError("debug_lpips_tap: B must be positive and tap in 1..5");
+        const LpipsGeom g = lpips_geometry(H, W);
+        dims[0] = B; dims[1] = g.h[tap - 1]; dims[2] = g.w[tap - 1]; dims[3] = kLpipsLayers[tap - 1].cout;
+        if (!dst) return;
+        std::lock_guard<std::mutex> lk(e->mu);
+        DeviceScope dev_scope(e->cfg.device);
+        hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+        float* ws = lpips_workspace(e, B, H, W);
+        float* taps[5];
+        lpips_features(e->lpips, in, nullptr, B, H, W, normalize, ws, taps, s, nullptr);
+        IRSDE_HIP_CHECK(hipMemcpyAsync(dst, taps[tap - 1], (size_t)dims[0] * dims[1] * dims[2] * dims[3] * sizeof(float), hipMemcpyDeviceToDevice, s));
+        IRSDE_HIP_CHECK(hipStreamSynchronize(s));
+    });
+}
+
 }  // extern "C"

@@ -1201,6 +1201,7 @@ static void init_plan_geometry(irsde_engine* e, Plan* pl, int B, int H, int W, i
 // (16 x 512^2: several GiB), so a build that runs out of memory drops the least recently used plans and tries again instead of failing the sampler call
 // (ADVICE r05).
 Plan* get_plan(irsde_engine* e, int B, int H, int W, bool per_sample_film, int slot, int b0) {
+    if (lpips_engine(e)) throw HipError("an LPIPS engine (irsde_create_lpips) holds no score network: only irsde_lpips runs on it");
     for (auto& p : e->plans)
         if (p->B == B && p->H == H && p->W == W && p->per_sample_film == per_sample_film && p->slot == slot && p->b0 == b0) {
             p->last_use = ++e->use_counter;

@@ -705,10 +705,44 @@ void finalize_latent(irsde_engine* e) {
     e->lat_final = pack_conv_pad(e, "final_conv.weight", "final_conv.bias", {ch}, false);
 }
 
+// ---------------------------------------------------------------------------------------------
+// LPIPS v0.1 / AlexNet (arch == 3): 15 tensors under our own names (the Python side maps the published checkpoints' keys onto them).
+// conv weights OIHW as torchvision stores them, lin weights (1, C, 1, 1) as lpips stores them.
+// ---------------------------------------------------------------------------------------------
+void build_inventory_lpips(irsde_engine* e) {
+    for (int l = 0; l < 5; ++l) add_w(e, "conv" + std::to_string(l + 1) + ".weight", {kLpipsLayers[l].cout, kLpipsLayers[l].cin, kLpipsLayers[l].k, kLpipsLayers[l].k});
+    for (int l = 0; l < 5; ++l) add_w(e, "conv" + std::to_string(l + 1) + ".bias", {kLpipsLayers[l].cout});
+    for (int l = 0; l < 5; ++l) add_w(e, "lin" + std::to_string(l + 1) + ".weight", {1, kLpipsLayers[l].cout, 1, 1});
+}
+void finalize_lpips(irsde_engine* e) {
+    for (int l = 0; l < 5; ++l) {
+        const LpipsLayer& L = kLpipsLayers[l];
+        const std::string p = "conv" + std::to_string(l + 1);
+        const HostTensor& t = need(e, p + ".weight");
+        const int cin_p = lpips_cin_padded(l);   // conv1: 3 -> 4, zero rows
+        // OIHW -> K-major [(ky * KW + kx) * cin_p + ci][Cout]
+        std::vector<float> kw((size_t)L.k * L.k * cin_p * L.cout, 0.f);
+        for (int o = 0; o < L.cout; ++o)
+            for (int i = 0; i < L.cin; ++i)
+                for (int ky = 0; ky < L.k; ++ky)
+                    for (int kx = 0; kx < L.k; ++kx)
+                        kw[((size_t)(ky * L.k + kx) * cin_p + i) * L.cout + o] = t.data[(((size_t)o * L.cin + i) * L.k + ky) * L.k + kx];
+        e->lpips.w[l] = e->upload(kw);
+        e->lpips.bias[l] = e->upload(need(e, p + ".bias").data);
+        e->lpips.lin[l] = e->upload(need(e, "lin" + std::to_string(l + 1) + ".weight").data);
+    }
+}
+
 void finalize(irsde_engine* e) {
+    if (lpips_engine(e)) IRSDE_HIP_CHECK(hipGetDevice(&e->cfg.device));   // irsde_create_lpips takes no configuration: the device current at this call
     DeviceScope dev_scope(e->cfg.device);
     for (auto& n : e->names)
         if (!e->host[n].loaded) throw HipError("missing weight: " + n);
+    if (lpips_engine(e)) {
+        finalize_lpips(e);
+        finalize_common(e);
+        return;
+    }
     if (e->arch == 2) {
         finalize_latent(e);
         finalize_common(e);

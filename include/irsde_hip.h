@@ -64,6 +64,8 @@
  *        Debug header only, same version: irsde_debug_split3_1x1, irsde_debug_split3_1x1_choice, irsde_debug_force_split3_1x1, irsde_debug_conv selector 49,
  *        irsde_bench_conv 510 - 524 (the exact-fp32 engine runs its plain 1x1 convolutions on three bf16 pieces where the plan's rule adopts them, the
  *        activations split inside the GEMM; fp32-equivalent; IRSDE_FLAG_NO_SPLIT3 restores the f32 kernels; tuning knob IRSDE_SPLIT3_1X1).
+ *        Additive, same version: irsde_create_lpips, irsde_lpips (LPIPS v0.1 / AlexNet, the third metric of the reference's test loops; csrc/lpips.hip);
+ *        debug header: irsde_debug_lpips_tap.
  */
 #ifndef IRSDE_HIP_H
 #define IRSDE_HIP_H
@@ -435,6 +437,23 @@ int irsde_mask_to(const float* x, const unsigned char* masks, int Bm, int Hm, in
  * IRSDE_ERR_INVALID: null pointer, non-positive size, KH or KW (taps per output) outside 1..32. */
 int irsde_imresize(const float* in, float* out, int B, int C, int H, int W, int Ho, int Wo, const float* wH, const int* sH, int KH,
                    const float* wW, const int* sW, int KW, void* stream);
+
+/* LPIPS v0.1, net = 'alex' — replaces lpips.LPIPS(net='alex') of the pip package `lpips`, the third metric of codes/config/deraining/test.py:74, 149-154
+ * (lpips_fn(GT * 2 - 1, SR * 2 - 1)), in fp32 on the device (csrc/lpips.hip): x = (x - shift) / scale per channel with shift (-.030, -.088, -.188) and
+ * scale (.458, .448, .450); AlexNet `features` tapped after each of its five ReLUs (convolutions on the f32 MFMA: exact fp32 accumulation); per tap
+ * n = f / (sqrt(sum_c f^2) + 1e-10), d = (n0 - n1)^2, term = mean over the pixels of sum_c w[c] d[c]; the distance is the sum of the five terms.
+ * The engine made here is host-only like the others and holds no score network: the weight inventory calls (irsde_num_weights ... irsde_finalize_weights,
+ * irsde_destroy) serve it, every sampler / forward / schedule / latent call refuses it, and the calls below refuse every other engine.  It runs on the HIP device that
+ * is current at irsde_finalize_weights.  Inventory: 15 tensors, conv{1..5}.weight (OIHW: 64x3x11x11, 192x64x5x5, 384x192x3x3, 256x384x3x3, 256x256x3x3),
+ * conv{1..5}.bias, lin{1..5}.weight (1, C, 1, 1) with C = 64, 192, 384, 256, 256. */
+int irsde_create_lpips(irsde_engine** out);
+/* in0, in1: device NCHW fp32 [B][3][H][W] in [-1, 1], or in [0, 1] with normalize != 0 (2 x - 1 is then applied first); H, W >= 31, the smallest size at
+ * which both max-pools still have a 3x3 window (smaller: IRSDE_ERR_INVALID).  dist: HOST [B]; terms: HOST [B][5], the five per-tap terms, or NULL;
+ * dist[b] is the float64 sum of terms[b][0..4].  Both images of every pair go through the tower as one batch of 2B; an image's result does not depend on its
+ * position in the batch or on B, and every sum has a fixed order (no atomics): the call is deterministic, lpips(a, a) == 0 and lpips(a, b) == lpips(b, a)
+ * exactly.  Synchronises `stream`.  irsde_op_profile afterwards gives the call's per-kernel times.
+ * Errors: IRSDE_ERR_INVALID for a NULL pointer, B < 1, a size below 31, an engine that is not irsde_create_lpips' or whose weights are not finalized. */
+int irsde_lpips(irsde_engine* e, const float* in0, const float* in1, int B, int H, int W, int normalize, double* dist, double* terms, void* stream);
 
 #ifdef __cplusplus
 }

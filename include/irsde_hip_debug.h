@@ -267,6 +267,12 @@ int irsde_debug_scam_full_stream(const float* x, int B_pairs, int H, int W, int 
  * choice: use a fresh engine per setting. */
 int irsde_debug_force_scam_stream(int block_w);
 
+/* Kernel-level test hook: the ReLU'd feature map of ONE tap (1..5) of the LPIPS tower (csrc/lpips.hip: prologue, convolutions, max-pools) on an engine of
+ * irsde_create_lpips with finalized weights.  in: device NCHW fp32 [B][3][H][W], scaled as irsde_lpips scales it (normalize as there); dst: device NHWC
+ * [B][h][w][C] of the tap, or NULL to query dims only; dims receives {B, h, w, C}.  H, W >= 31.  Synchronises `stream`.  tests/test_gpu_lpips.py compares
+ * it with tests/lpips_oracle.py. */
+int irsde_debug_lpips_tap(irsde_engine* e, const float* in, int B, int H, int W, int normalize, int tap, float* dst, int64_t dims[4], void* stream);
+
 #ifdef __cplusplus
 }
 #endif

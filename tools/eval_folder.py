@@ -14,8 +14,8 @@ reference's 31.65 dB, /root/reference/README.md:42-46) once `rain100h_sde.pth` a
 Differences from the reference loop, all stated: images of equal size are sampled as one batch (`--batch`); with
 `--gpus N` the image list is sharded over N ranks (one process per GPU, no collective except the final metric
 all_reduce); image I/O is PIL instead of cv2 (PNG decoding is lossless, so the tensors are identical; JPEG decoders
-may differ in the last bit); LPIPS is not computed (the `lpips` package and its AlexNet weights are external
-downloads); the noise of `noise_state` is drawn per image from a generator seeded by (--seed, image index) so a run is
+may differ in the last bit); LPIPS is computed when --lpips-weights is given (the AlexNet and lin weights are external
+downloads: `metrics.LPIPS`, csrc/lpips.hip); the noise of `noise_state` is drawn per image from a generator seeded by (--seed, image index) so a run is
 reproducible and independent of batching / sharding.
 
 `--task denoising` is the loop of codes/config/denoising-sde/test.py:91-142 instead (Gaussian denoising, options/test/refusion.yml and
@@ -28,7 +28,7 @@ image (no border crop, as there) and averaged:
 
 Its stated differences: equal-sized images are batched; the restored image is written as .png where test.py writes .tif without a suffix; the
 noise is the library's keyed Philox draw (`denoising_sde.add_noise`, key = (--seed, global image index)), so the result does not depend on
-batching or on the rank count; LPIPS is not computed — its AlexNet weights are not available here.
+batching or on the rank count; LPIPS is computed when --lpips-weights is given.
 
 `--task sisr | inpainting | stereo-sr` are the loops of codes/config/{sisr,inpainting,stereo-sr}/test.py, which put a degradation step of
 codes/utils/deg_utils.py in front of `sde.noise_state(LQ)`; here that step runs on the device (`degradations.upscale` / `mask_to`,
@@ -45,7 +45,7 @@ csrc/degrade.hip), and the rest is the LQ / GT loop above:
                (2i, 2i + 1); each view is upscaled x4 (the factor is hard-coded there), the pair [L | R] is sampled by the stereo network,
                and the output is chunked into L / R for the images and for PSNR / SSIM per view (RGB only, no border crop, as there)
 The sampler defaults to `--mode sde`: these task directories' `denoising_model.test` hard-codes `reverse_sde` (stereo-sr: or `reverse_ode` with
-perform_ode = `--mode ode`).  Their stated differences, beyond those of the LQ / GT loop (batching, sharding, PIL, no LPIPS, the per-image
+perform_ode = `--mode ode`).  Their stated differences, beyond those of the LQ / GT loop (batching, sharding, PIL, LPIPS only with --lpips-weights, the per-image
 seeded `noise_state` draw): the degraded LQ lives on the device, so the noise is drawn on the CPU as before and added there; inpainting does not
 write the intermediate states (`save_states=True` in inpainting/test.py:108); stereo-sr names the right view's files after the right view's own
 file instead of `img_name.replace('L', 'R')`, and also writes <name>_LQ.png / <name>_HQ.png per view.
@@ -140,6 +140,19 @@ def build_model(a, P, torch):
     return m
 
 
+def load_lpips(a, P):
+    """lpips.LPIPS(net='alex') of test.py:74 from the user's weight files, or None without --lpips-weights."""
+    return P.metrics.LPIPS.from_files(*a.lpips_weights) if a.lpips_weights else None
+
+
+def _with_lpips(line, lp_value):
+    """A per-image log line with `LPIPS: x` behind its SSIM entry, where test.py:181 has it."""
+    head, sep, tail = line.partition("; PSNR_Y")
+    if sep:
+        return "%s; LPIPS: %.6f%s%s" % (head, lp_value, sep, tail)
+    return "%s; LPIPS: %.6f." % (line[:-1], lp_value)
+
+
 def _ints(s):
     return [int(v) for v in s.split(",") if v != ""]
 
@@ -164,6 +177,9 @@ def run_denoising(a, P, torch, np, dev, world, rank, log):
     mine = list(range(lo, hi))
     gt_np = [read_img(paths[i]) for i in mine]
     res = {"psnr": [], "ssim": []}
+    lp = load_lpips(a, P)
+    if lp is not None:
+        res["lpips"] = []
     times = []
     for grp in batches_of_equal_size(mine, [x.shape for x in gt_np], a.batch):
         GT = torch.from_numpy(np.stack([gt_np[j] for j in grp])).to(dev)
@@ -175,12 +191,16 @@ def run_denoising(a, P, torch, np, dev, world, rank, log):
         model.test(sde, sigma=a.sigma, save_states=False)
         torch.cuda.synchronize()
         times.append((time.time() - tic) / len(grp))
-        m = P.metrics.evaluate_batch(model.output, GT, crop_border=0)   # calculate_psnr / calculate_ssim(output, GT): no crop (test.py:128-129)
+        m = P.metrics.evaluate_batch(model.output, GT, crop_border=0, lpips=lp)   # calculate_psnr / calculate_ssim(output, GT): no crop (test.py:128-129)
         names = [os.path.splitext(os.path.basename(paths[mine[j]]))[0] for j in grp]
         for n, name in enumerate(names):
             res["psnr"].append(float(m["psnr"][n]))
             res["ssim"].append(float(m["ssim"][n]))
-            log("img%3d:%-15s - PSNR: %.6f dB; SSIM: %.6f." % (mine[grp[n]], name, m["psnr"][n], m["ssim"][n]))
+            line = "img%3d:%-15s - PSNR: %.6f dB; SSIM: %.6f." % (mine[grp[n]], name, m["psnr"][n], m["ssim"][n])
+            if lp is not None:
+                res["lpips"].append(float(m["lpips"][n]))
+                line = _with_lpips(line, m["lpips"][n])
+            log(line)
         if a.out:
             imgs, lqi, gti = (P.metrics.tensor2img_batch(t) for t in (model.output, LQ, GT))
             for n, name in enumerate(names):
@@ -194,6 +214,8 @@ def run_denoising(a, P, torch, np, dev, world, rank, log):
     if rank == 0 and summary is not None:
         log("----Average PSNR/SSIM results for %s_sigma%g----\n\tPSNR: %.6f dB; SSIM: %.6f\n" %
             (os.path.basename(os.path.normpath(a.gt)), a.sigma, summary["psnr"], summary["ssim"]))
+        if "lpips" in summary:
+            log("----average LPIPS\t: %.6f\n" % summary["lpips"])
     if rank == 0 and times:
         log("average test time per image: %.4f s (rank 0, %d images over %d rank(s))" % (float(np.mean(times)), len(paths), world))
     return summary
@@ -245,6 +267,9 @@ def run_degraded(a, P, torch, np, dev, world, rank, log, crop_border, on_batch=N
     if from_gt:
         src_np = [P.degradations.modcrop(torch.from_numpy(x), a.scale).contiguous().numpy() for x in src_np]
     res = {"psnr": [], "ssim": []} if stereo else {"psnr": [], "ssim": [], "psnr_y": [], "ssim_y": []}
+    lp = load_lpips(a, P)
+    if lp is not None:
+        res["lpips"] = []
     times = []
     fn = {"sde": sde.reverse_sde, "ode": sde.reverse_ode, "posterior": sde.reverse_posterior}[a.mode]
     for grp in batches_of_equal_size(mine, [x.shape for x in src_np], a.batch):
@@ -279,17 +304,18 @@ def run_degraded(a, P, torch, np, dev, world, rank, log, crop_border, on_batch=N
         nb = len(grp)
         names = [[os.path.splitext(os.path.basename((gts or src)[per * i + v]))[0] for i in idx] for v in range(per)]
         if GT is not None:
-            m = P.metrics.evaluate_batch(views(out), views(GT), crop_border=0 if stereo else crop_border)   # stereo-sr/test.py:139-140: no crop
+            m = P.metrics.evaluate_batch(views(out), views(GT), crop_border=0 if stereo else crop_border, lpips=lp)   # stereo-sr/test.py:139-140: no crop
             for n in range(nb):
                 for v in range(per):
                     k = v * nb + n
                     for key in res:
                         res[key].append(float(m[key][k]))
                     if stereo:
-                        log("img:%-15s - PSNR: %.6f dB; SSIM: %.6f." % (names[v][n], m["psnr"][k], m["ssim"][k]))
+                        line = "img:%-15s - PSNR: %.6f dB; SSIM: %.6f." % (names[v][n], m["psnr"][k], m["ssim"][k])
                     else:
-                        log("img%3d:%-15s - PSNR: %.6f dB; SSIM: %.6f; PSNR_Y: %.6f dB; SSIM_Y: %.6f." %
-                            (idx[n], names[v][n], m["psnr"][k], m["ssim"][k], m["psnr_y"][k], m["ssim_y"][k]))
+                        line = ("img%3d:%-15s - PSNR: %.6f dB; SSIM: %.6f; PSNR_Y: %.6f dB; SSIM_Y: %.6f." %
+                                (idx[n], names[v][n], m["psnr"][k], m["ssim"][k], m["psnr_y"][k], m["ssim_y"][k]))
+                    log(line if lp is None else _with_lpips(line, m["lpips"][k]))
         if a.out:
             imgs = P.metrics.tensor2img_batch(views(out))
             lqi = P.metrics.tensor2img_batch(views(LQ))
@@ -309,6 +335,8 @@ def run_degraded(a, P, torch, np, dev, world, rank, log, crop_border, on_batch=N
             (os.path.basename(os.path.normpath(a.gt if a.task == "inpainting" or from_gt else a.lq)), summary["psnr"], summary["ssim"]))
         if not stereo:
             log("----Y channel, average PSNR/SSIM----\n\tPSNR_Y: %.6f dB; SSIM_Y: %.6f\n" % (summary["psnr_y"], summary["ssim_y"]))
+        if "lpips" in summary:
+            log("----average LPIPS\t: %.6f\n" % summary["lpips"])
     if rank == 0 and times:
         log("average test time per image: %.4f s (rank 0, %d images over %d rank(s))" % (float(np.mean(times)), n_items, world))
     return summary
@@ -318,7 +346,7 @@ def main(argv=None, on_batch=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--task", default=None, choices=["denoising", "sisr", "inpainting", "stereo-sr"],
                     help="denoising: the denoising-sde loop (clean --gt folder + --sigma, DenoisingSDE, "
-                    "reverse_ode from the optimal timestep; PSNR / SSIM, no LPIPS: its AlexNet weights are not available).  sisr: --lq is the low-resolution "
+                    "reverse_ode from the optimal timestep; PSNR / SSIM; LPIPS computed when --lpips-weights is given).  sisr: --lq is the low-resolution "
                     "folder (or --lq-from-gt), bicubic upscale by --scale on the device, then the LQ / GT loop with the reverse-SDE sampler.  inpainting: --gt + --mask-root, "
                     "mask_to with the image index as mask id.  stereo-sr: --lq holds L / R files paired in sorted order, x4 upscale per view, the stereo "
                     "ConditionalNAFNet (--naf-*) or, with --model unet, the stereo ConditionalUNet.  Absent: the LQ / GT loop")
@@ -336,6 +364,9 @@ def main(argv=None, on_batch=None):
     ap.add_argument("--naf-mid", type=int, default=1)
     ap.add_argument("--naf-dec", default="1,1,1,1")
     ap.add_argument("--weights", required=True, help="reference checkpoint (state_dict .pth, optional 'module.' prefixes)")
+    ap.add_argument("--lpips-weights", nargs="+", default=None, metavar="FILE",
+                    help="LPIPS (lpips.LPIPS(net='alex'), test.py:74) for every task that has a GT: one saved state_dict of it, or the two published files "
+                    "(torchvision's AlexNet checkpoint and lpips' alex.pth).  Adds `LPIPS: x` to the per-image lines and the `average LPIPS` line; absent: not computed")
     ap.add_argument("--out", default=None, help="results folder: <name>.png, <name>_LQ.png, <name>_HQ.png as test.py:118-128")
     ap.add_argument("--model", default=None, choices=["unet", "nafnet"], help="default unet; --task stereo-sr: default nafnet (the stereo ConditionalNAFNet, --naf-*)")
     ap.add_argument("--nf", type=int, default=64)
@@ -426,6 +457,9 @@ def main(argv=None, on_batch=None):
     lq_np = [read_img(pairs[i][0]) for i in mine]
     sizes = [x.shape for x in lq_np]
     res = {"psnr": [], "ssim": [], "psnr_y": [], "ssim_y": []}
+    lp = load_lpips(a, P) if a.gt is not None else None
+    if lp is not None:
+        res["lpips"] = []
     times = []
     log = (lambda *s: print(*s, flush=True))
     for grp in batches_of_equal_size(mine, sizes, a.batch):
@@ -445,12 +479,13 @@ def main(argv=None, on_batch=None):
         GT = None
         if a.gt is not None:
             GT = torch.from_numpy(np.stack([read_img(pairs[mine[j]][1]) for j in grp])).to(dev)
-            m = P.metrics.evaluate_batch(out, GT, crop_border=crop_border)
+            m = P.metrics.evaluate_batch(out, GT, crop_border=crop_border, lpips=lp)
             for k in res:
                 res[k].extend(m[k].tolist())
             for n, name in enumerate(names):
-                log("img%3d:%-15s - PSNR: %.6f dB; SSIM: %.6f; PSNR_Y: %.6f dB; SSIM_Y: %.6f." %
-                    (mine[grp[n]], name, m["psnr"][n], m["ssim"][n], m["psnr_y"][n], m["ssim_y"][n]))
+                line = ("img%3d:%-15s - PSNR: %.6f dB; SSIM: %.6f; PSNR_Y: %.6f dB; SSIM_Y: %.6f." %
+                        (mine[grp[n]], name, m["psnr"][n], m["ssim"][n], m["psnr_y"][n], m["ssim_y"][n]))
+                log(line if lp is None else _with_lpips(line, m["lpips"][n]))
         if a.out:
             imgs = P.metrics.tensor2img_batch(out)
             lqi = P.metrics.tensor2img_batch(LQ.to(dev))
@@ -468,6 +503,8 @@ def main(argv=None, on_batch=None):
     if rank == 0 and summary is not None:
         log("----Average PSNR/SSIM results for %s----\n\tPSNR: %.6f dB; SSIM: %.6f\n" % (os.path.basename(os.path.normpath(a.lq)), summary["psnr"], summary["ssim"]))
         log("----Y channel, average PSNR/SSIM----\n\tPSNR_Y: %.6f dB; SSIM_Y: %.6f\n" % (summary["psnr_y"], summary["ssim_y"]))
+        if "lpips" in summary:
+            log("----average LPIPS\t: %.6f\n" % summary["lpips"])
     if rank == 0 and times:
         log("average test time per image: %.4f s (rank 0, %d images over %d rank(s))" % (float(np.mean(times)), len(pairs), world))
     if world > 1:
