@@ -405,19 +405,25 @@ int attn_num_chunks(int N, int B);
 void launch_linear_attention(const float* qkv, float* out, int B, int N, const AttnWorkspace& ws, hipStream_t s,
                              bool bf16 = false);
 
-// fp32 fused form of the same block: k, v and their softmax / context from the LayerNorm output and the k | v rows of
-// to_qkv.weight ([256][C]) without a k / v tensor in HBM; q is a separate [B][N][128] tensor (its own 1x1 convolution).
+// Fused forms of the same block (linear_attn.hip).  What the three projections run on; LayerNorm, softmax and the context products are fp32 in every mode.
+enum class AttnMode : int {
+    F32 = 0,       // the fp32 weights alone
+    PairF16 = 1,   // fp16 hi + lo planes [2][rows][K] of w * 2^k, *_inv = 2^-k (IRSDE_FLAG_SPLIT_F16X2)
+    Bf16 = 2,      // one unscaled bf16 plane (IRSDE_FLAG_BF16); act_bf16: xn / x / y are bf16 tensors (IRSDE_FLAG_BF16_ACT)
+    Fp16 = 3,      // one unscaled IEEE fp16 plane (IRSDE_FLAG_FP16)
+    Bf16x3 = 4,    // three unscaled bf16 planes in MFMA-fragment order (launch_split_frag3), six products: the exact-fp32 engine (IRSDE_SPLIT3_ATTN)
+};
+struct AttnProj {
+    AttnMode mode = AttnMode::F32;
+    bool act_bf16 = false;
+    const unsigned short *kv = nullptr, *q = nullptr, *out = nullptr;   // planes of the [256][C] k | v rows, the [128][C] q rows, to_out.0.weight [C][128]
+    float kv_inv = 1.f, q_inv = 1.f, out_inv = 1.f;
+};
+bool attn_fused_has_instance(int C, AttnMode mode, bool act_bf16);   // do both fused kernels exist for this shape and mode?
+// k, v, their softmax and the context from xn and wkv (the k | v rows of to_qkv.weight) without a k / v tensor in HBM.
 // ln_g != nullptr: `xn` is the un-normalised block input and PreNorm's LayerNorm (* ln_g, eps) runs inside the kernel.
-// wkv_pair != nullptr (IRSDE_FLAG_SPLIT_F16X2; C = 64 / 128 / 256): the projection on fp16 hi + lo operand pairs — wkv_pair = the two
-// planes [2][256][C] of wkv * 2^k, w_inv_scale = 2^-k
 void launch_attention_kv_context(const float* xn, const float* wkv, int B, int N, int C, const AttnWorkspace& ws, hipStream_t s,
-                                 const float* ln_g = nullptr, float ln_eps = 1e-5f, const unsigned short* wkv_pair = nullptr,
-                                 float w_inv_scale = 1.f, int op16 = 0, bool act_bf16 = false);
-// op16 (r05): 0 = f32 (or, with *_pair planes, the fp16 hi + lo pairs); 2 / 3 = ONE bf16 / fp16 operand plane in *_pair (IRSDE_FLAG_BF16 / _FP16:
-// [256][C] k | v rows, [128][C] q rows, [C][128] to_out rows, unscaled); act_bf16 (op16 == 2 only): xn / x / y are bf16 tensors (IRSDE_FLAG_BF16_ACT)
-// op16 = 4: fp32 tensors, the projections on THREE bf16 pieces per operand and six products (the exact-fp32 engine, IRSDE_SPLIT3_ATTN): *_pair = three unscaled
-// planes of the [256][C], [128][C], [C][128] matrices in MFMA-fragment order (launch_split_frag3); LayerNorm, softmax and the context products stay fp32
-inline bool attn_split3_has_instance(int C) { return C == 64 || C == 128 || C == 256; }
+                                 const float* ln_g = nullptr, float ln_eps = 1e-5f, const AttnProj& proj = {});
 // Fragment order of one plane of a [rows][K] matrix: [row / 32][k / 16][(k % 16) / 8][row % 32][k % 8] — lane (l31 = row % 32, h) of a wave finds its 8 values of
 // (32-row tile, 16-k step) at 16-byte slot ((row tile * K / 16 + step) * 64 + 32 h + l31): one contiguous KB per wave load
 __host__ __device__ inline size_t attn_frag3_index(size_t row, int k, int K) {
@@ -430,8 +436,7 @@ void launch_attention_q_out(const float* q, float* out, int B, int N, const Attn
 // wout = to_out.0.weight ([C][128]); needs ws.ctx from launch_attention_kv_context.
 void launch_attention_q_out_fused(const float* xn, const float* x, const float* wq, const float* wout, const float* bias,
                                   const float* g2, float* y, int B, int N, int C, float eps, const AttnWorkspace& ws, hipStream_t s,
-                                  const float* ln_g = nullptr, const unsigned short* wq_pair = nullptr, const unsigned short* wout_pair = nullptr,
-                                  float wq_inv = 1.f, float wout_inv = 1.f, int op16 = 0, bool act_bf16 = false);   // *_pair: fp16 hi / lo planes (IRSDE_FLAG_SPLIT_F16X2), see kernels_misc.hip
+                                  const float* ln_g = nullptr, const AttnProj& proj = {});
 
 // Stereo-sr SCAM (scam.hip): x [2B][H][W][c] NHWC, views stacked [L_0..L_{B-1}, R_0..R_{B-1}]; H' = H / 4, W' = W / 4 (floor).
 //   prologue  xs2 [2B][H'][W'][LN(xs) (norm_l / norm_r gain) | xs], xs = bicubic quarter-downsample of x

@@ -70,7 +70,7 @@ inline long long split3_fused_min_tiles() { return tuning_env_int("IRSDE_SPLIT3_
 constexpr int kSplit3NotExactF32 = IRSDE_FLAG_NO_WINOGRAD | IRSDE_FLAG_NAIVE_CONV | IRSDE_FLAG_BF16 | IRSDE_FLAG_BF16_ACT | IRSDE_FLAG_FP16 | IRSDE_FLAG_F16_ACT |
                                    IRSDE_FLAG_SPLIT_BF16X2 | IRSDE_FLAG_SPLIT_F16X2 | IRSDE_FLAG_NO_SPLIT3;
 inline bool split3_wants_weights(int flags) { return !(flags & kSplit3NotExactF32) && split3_mode() > 0; }
-// The same engine's fused LinearAttention blocks (C = 64 / 128 / 256) with their k / v, q and to_out projections on three bf16 pieces (kernels_misc.hip, MODE 4): 0 never,
+// The same engine's fused LinearAttention blocks (C = 64 / 128 / 256) with their k / v, q and to_out projections on three bf16 pieces (linear_attn.hip, AttnMode::Bf16x3): 0 never,
 // 1 by the rule of Builder::split3_attn_adopts, 2 wherever a kernel instance exists (irsde_debug_force_split3_attn overrides the knob for plans built afterwards).
 // Off with the GEMMs' master switch (IRSDE_SPLIT3 = 0, IRSDE_FLAG_NO_SPLIT3); the master's mode 2 does not force it.
 int split3_attn_mode();

@@ -283,10 +283,10 @@ struct Builder {
     // than their f32 twins at B = 16 and at B = 2, by 15 - 33 %, and 16 x 512 x 512 gains as much end to end: every instance is adopted, whatever N and B.
     static bool split3_attn_rule(int C, int N, int B) {
         (void)N; (void)B;
-        return attn_split3_has_instance(C);
+        return attn_fused_has_instance(C, AttnMode::Bf16x3, false);
     }
     bool split3_attn_adopts(int C, int N, int B) const {
-        if ((e->cfg.flags & kSplit3NotExactF32) || split3_mode() == 0 || !attn_split3_has_instance(C)) return false;
+        if ((e->cfg.flags & kSplit3NotExactF32) || split3_mode() == 0 || !attn_fused_has_instance(C, AttnMode::Bf16x3, false)) return false;
         const int mode = split3_attn_mode();
         return mode >= 2 || (mode == 1 && split3_attn_rule(C, N, B));
     }
@@ -818,7 +818,7 @@ struct Builder {
         return out;
     }
 
-    // The scratch of the linear-attention kernels (kernels_misc.hip sizes it the same way): per-chunk maxima, contexts and sums of the pixel chunks, and the merged context
+    // The scratch of the linear-attention kernels (linear_attn.hip sizes it the same way): per-chunk maxima, contexts and sums of the pixel chunks, and the merged context
     AttnWorkspace attn_workspace(int B, int N) {
         AttnWorkspace ws;
         ws.nch = attn_num_chunks(N, B);
@@ -829,81 +829,60 @@ struct Builder {
         return ws;
     }
 
+    // The weight copies a mode of the fused attention kernels reads (made once per tensor, engine.h): wqkv = to_qkv.weight ([384][C]: q | k | v rows), wo = to_out.0.weight
+    AttnProj attn_proj(AttnMode mode, bool act_bf16, const float* wqkv, const float* wo, int C) {
+        AttnProj p;
+        p.mode = mode;
+        p.act_bf16 = act_bf16;
+        const float *wq = wqkv, *wkv = wqkv + (size_t)128 * C;
+        if (mode == AttnMode::Bf16 || mode == AttnMode::Fp16) {   // (IRSDE_FLAG_FP16: the copy holds IEEE fp16)
+            p.q = e->bf16_copy(wqkv, (size_t)384 * C);
+            p.out = e->bf16_copy(wo, (size_t)C * 128);
+            p.kv = p.q + (size_t)128 * C;
+        } else if (mode == AttnMode::Bf16x3) {
+            p.kv = e->triple_copy(wkv, 256, C);
+            p.q = e->triple_copy(wq, 128, C);
+            p.out = e->triple_copy(wo, (size_t)C, 128);
+        } else if (mode == AttnMode::PairF16) {
+            const auto kv = e->pair_copy(wkv, (size_t)256 * C), q = e->pair_copy(wq, (size_t)128 * C), o = e->pair_copy(wo, (size_t)C * 128);
+            p.kv = kv.p; p.kv_inv = kv.inv_scale;
+            p.q = q.p; p.q_inv = q.inv_scale;
+            p.out = o.p; p.out_inv = o.inv_scale;
+        }
+        return p;
+    }
+
     // Residual(PreNorm(dim, LinearAttention(dim))) — module_util.py:20-26,82-90,150-178
     Tensor attn(const AttnW& w, const Tensor& x) {
         const int64_t M = (int64_t)x.B * x.H * x.W;
         const int N = x.H * x.W;
         const bool fused_kv = w.g2 && !naive && !x.bf16 && !(e->cfg.flags & (IRSDE_FLAG_BF16 | IRSDE_FLAG_NO_FUSED_ATTN)) &&
                               x.C % 32 == 0 && x.C <= 256;
-        const bool fused_all = fused_kv && (x.C == 64 || x.C == 128 || x.C == 256) && !(e->cfg.flags & IRSDE_FLAG_NO_FUSED_LN);
-        // r05: the 16-bit operand modes (IRSDE_FLAG_BF16 [+ _ACT] / IRSDE_FLAG_FP16) take the same two fused kernels with ONE bf16 / fp16 plane per
-        // projection operand (fp32 LayerNorm, softmax, context, accumulation); with IRSDE_FLAG_BF16_ACT they read and write the bf16 tensors directly
-        const bool fused_16 = w.g2 && !naive && (e->cfg.flags & IRSDE_FLAG_BF16) && !(e->cfg.flags & (IRSDE_FLAG_NO_FUSED_ATTN | IRSDE_FLAG_NO_FUSED_LN)) &&
-                              (x.C == 64 || x.C == 128 || x.C == 256) && x.bf16 == act_bf16();
-        if (fused_16) {
+        // Whole Residual(PreNorm(LinearAttention)) block in two kernels + the context merge: PreNorm's LayerNorm runs on the tiles both kernels stage, so no
+        // normalised copy of x, no q / k / v, no attention output reach HBM.  The mode of the three projections: one bf16 / fp16 plane per operand under
+        // IRSDE_FLAG_BF16 [+ _ACT] / IRSDE_FLAG_FP16 (r05; with _ACT the kernels read and write the bf16 tensors directly), else fp32 on three bf16 pieces
+        // (split3_attn_adopts), on fp16 hi + lo pairs (IRSDE_FLAG_SPLIT_F16X2) or on the f32 MFMA
+        const bool ops16 = (e->cfg.flags & IRSDE_FLAG_BF16) != 0;
+        const AttnMode mode = ops16 ? ((e->cfg.flags & IRSDE_FLAG_FP16) ? AttnMode::Fp16 : AttnMode::Bf16)
+                              : split3_attn_adopts(x.C, N, x.B) ? AttnMode::Bf16x3
+                              : (e->cfg.flags & IRSDE_FLAG_SPLIT_F16X2) ? AttnMode::PairF16 : AttnMode::F32;
+        const bool fused_all = w.g2 && !naive && !(e->cfg.flags & (IRSDE_FLAG_NO_FUSED_ATTN | IRSDE_FLAG_NO_FUSED_LN)) && x.bf16 == (ops16 && act_bf16()) &&
+                               attn_fused_has_instance(x.C, mode, x.bf16);
+        if (fused_all) {
             const AttnWorkspace ws = attn_workspace(x.B, N);
             Tensor y = talloc(x.B, x.H, x.W, x.C);
             if (y.bf16 != x.bf16) throw HipError("attention: mixed activation storage types");
-            const float *xp = x.p, *wqkv = w.qkv.w, *wo = w.out.w, *bo = w.out.bias, *g1 = w.g1, *g2 = w.g2;
-            float* yp = y.p;
-            const int B = x.B, C = x.C;
-            if (!bo) throw HipError("attention: to_out.0.bias missing");
-            const unsigned short* wqkv16 = e->bf16_copy(wqkv, (size_t)384 * C);   // bf16, or IEEE fp16 under IRSDE_FLAG_FP16 (rows: q | k | v)
-            const unsigned short* wo16 = e->bf16_copy(wo, (size_t)C * 128);
-            const unsigned short* wkv16 = wqkv16 + (size_t)128 * C;
-            const int op16 = (e->cfg.flags & IRSDE_FLAG_FP16) ? 3 : 2;
-            const bool abf = x.bf16;
-            const char* tag = op16 == 3 ? " (fp16 operands)" : abf ? " (bf16 operands + storage)" : " (bf16 operands)";
-            push_other(OP_ATTN, [=](hipStream_t s) {
-                launch_attention_kv_context(xp, wqkv + (size_t)128 * C, B, N, C, ws, s, g1, 1e-5f, wkv16, 1.f, op16, abf);
-            });
-            pl->net_ops.back().desc = std::string("linear_attention LayerNorm + k,v projection") + tag + " + context (fused) C=" + std::to_string(C);
-            push_other(OP_ATTN, [=](hipStream_t s) {
-                launch_attention_q_out_fused(xp, xp, wqkv, wo, bo, g2, yp, B, N, C, 1e-5f, ws, s, g1, wqkv16, wo16, 1.f, 1.f, op16, abf);
-            });
-            pl->net_ops.back().desc = std::string("linear_attention LayerNorm + q projection") + tag +
-                                      " + softmax + context + to_out + LayerNorm + residual (fused) C=" + std::to_string(C);
-            return y;
-        }
-        if (fused_all) {
-            // whole Residual(PreNorm(LinearAttention)) block in two kernels + the context merge: PreNorm's LayerNorm runs on
-            // the tiles both kernels stage, so no normalised copy of x, no q / k / v, no attention output reach HBM
-            const AttnWorkspace ws = attn_workspace(x.B, N);
-            Tensor y = talloc(x.B, x.H, x.W, x.C);
             const float *xp = x.p, *wq = w.qkv.w, *wkv = w.qkv.w + (size_t)128 * x.C, *wo = w.out.w, *bo = w.out.bias, *g1 = w.g1, *g2 = w.g2;
             float* yp = y.p;
             const int B = x.B, C = x.C;
             if (!bo) throw HipError("attention: to_out.0.bias missing");
-            if (split3_attn_adopts(C, N, B)) {   // exact fp32: the three projections on three bf16 pieces each, six products (kernels_misc.hip MODE 4)
-                const unsigned short* wkv3 = e->triple_copy(wkv, 256, C);
-                const unsigned short* wq3 = e->triple_copy(wq, 128, C);
-                const unsigned short* wo3 = e->triple_copy(wo, (size_t)C, 128);
-                push_other(OP_ATTN, [=](hipStream_t s) { launch_attention_kv_context(xp, wkv, B, N, C, ws, s, g1, 1e-5f, wkv3, 1.f, 4); });
-                pl->net_ops.back().desc = "linear_attention LayerNorm + k,v projection (bf16x3) + context (fused) C=" + std::to_string(C);
-                push_other(OP_ATTN, [=](hipStream_t s) {
-                    launch_attention_q_out_fused(xp, xp, wq, wo, bo, g2, yp, B, N, C, 1e-5f, ws, s, g1, wq3, wo3, 1.f, 1.f, 4);
-                });
-                pl->net_ops.back().desc = "linear_attention LayerNorm + q projection (bf16x3) + softmax + context + to_out + LayerNorm + residual (fused) C=" + std::to_string(C);
-                return y;
-            }
-            const unsigned short* wkv_pair = nullptr;
-            float kv_inv = 1.f;
-            if (e->cfg.flags & IRSDE_FLAG_SPLIT_F16X2) {   // the k / v projection on fp16 hi + lo operand pairs
-                const auto pc = e->pair_copy(wkv, (size_t)256 * C);
-                wkv_pair = pc.p; kv_inv = pc.inv_scale;
-            }
-            push_other(OP_ATTN, [=](hipStream_t s) { launch_attention_kv_context(xp, wkv, B, N, C, ws, s, g1, 1e-5f, wkv_pair, kv_inv); });
-            pl->net_ops.back().desc = std::string("linear_attention LayerNorm + k,v projection") + (wkv_pair ? " (split f16x2)" : "") + " + context (fused) C=" + std::to_string(C);
-            const unsigned short *wq_pair = nullptr, *wo_pair = nullptr;
-            float wq_inv = 1.f, wo_inv = 1.f;
-            if (e->cfg.flags & IRSDE_FLAG_SPLIT_F16X2) {   // the q and to_out projections on fp16 hi + lo operand pairs
-                const auto pq = e->pair_copy(wq, (size_t)128 * C), po = e->pair_copy(wo, (size_t)C * 128);
-                wq_pair = pq.p; wq_inv = pq.inv_scale; wo_pair = po.p; wo_inv = po.inv_scale;
-            }
-            push_other(OP_ATTN, [=](hipStream_t s) {
-                launch_attention_q_out_fused(xp, xp, wq, wo, bo, g2, yp, B, N, C, 1e-5f, ws, s, g1, wq_pair, wo_pair, wq_inv, wo_inv);
-            });
-            pl->net_ops.back().desc = std::string("linear_attention LayerNorm + q projection") + (wq_pair ? " (split f16x2)" : "") +
+            const AttnProj proj = attn_proj(mode, x.bf16, w.qkv.w, wo, C);
+            static const char* const kTag[] = {"", " (split f16x2)", " (bf16 operands)", " (fp16 operands)", " (bf16x3)"};   // by AttnMode
+            const char* tag = proj.act_bf16 ? " (bf16 operands + storage)" : kTag[(int)mode];
+            push_other(OP_ATTN, [=](hipStream_t s) { launch_attention_kv_context(xp, wkv, B, N, C, ws, s, g1, 1e-5f, proj); });
+            pl->net_ops.back().desc = std::string("linear_attention LayerNorm + k,v projection") + tag + " + context (fused) C=" + std::to_string(C);
+            push_other(OP_ATTN, [=](hipStream_t s) { launch_attention_q_out_fused(xp, xp, wq, wo, bo, g2, yp, B, N, C, 1e-5f, ws, s, g1, proj); });
+            pl->net_ops.back().desc = std::string("linear_attention LayerNorm + q projection") + tag +
                                       " + softmax + context + to_out + LayerNorm + residual (fused) C=" + std::to_string(C);
             return y;
         }

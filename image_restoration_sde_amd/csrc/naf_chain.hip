@@ -126,7 +126,7 @@ __device__ __forceinline__ void nc_group_exit(unsigned* cnt, const unsigned G, c
     }
 }
 
-// Cross-lane sums on the vector pipe (r05; kernels_misc.hip has the same helpers and the story of why the swaps are inline assembly): the LayerNorm
+// Cross-lane sums on the vector pipe (r05; linear_attn.hip has the same helpers and the story of why the swaps are inline assembly): the LayerNorm
 // partials are summed over the four lane quarters q = lane >> 4 (xor 16, xor 32), the SCA pool over the 16 pixel lanes n = lane & 15 of a quarter
 // (DPP quad permutes + row mirrors) — instead of __shfl_xor's ds_bpermute round trips through the LDS the GEMM passes need.
 struct NcSwap { float a, b; };

@@ -44,7 +44,7 @@ constexpr unsigned WT_ROW_OOB = 0x80000000u;    // row / column part of a gather
 constexpr unsigned WT_COL_OOB = 0x40000000u;    // past the end of any tensor this kernel accepts (<= 1 GiB, wino_fused64t_eligible)
 
 // rows 1 (lanes 32 - 63) of a change places with rows 0 (lanes 0 - 31) of b, six register pairs per statement.  Inline assembly: hipcc (ROCm 7.2)
-// miscompiles __builtin_amdgcn_permlane32_swap's result pair (kernels_misc.hip, group_sum); s_nop 1 = the wait states behind a VALU write of the operands.
+// miscompiles __builtin_amdgcn_permlane32_swap's result pair (linear_attn.hip, group_sum); s_nop 1 = the wait states behind a VALU write of the operands.
 __device__ __forceinline__ void swap32x6(float& a0, float& b0, float& a1, float& b1, float& a2, float& b2, float& a3, float& b3, float& a4, float& b4,
                                          float& a5, float& b5) {
     asm volatile(

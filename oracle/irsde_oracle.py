@@ -290,7 +290,7 @@ class fused_attn_16:
 
 def attn_block_fused16(p, prefix, x, f16=False, store_bf16=False, heads=4, dim_head=32):
     """Residual(PreNorm(LinearAttention)) — module_util.py:20-26,82-90,150-178 — with the roundings of the engine's fused attention kernels in the 16-bit operand modes
-    (image_restoration_sde_amd/csrc/kernels_misc.hip: attn_kv_ctx_kernel / attn_q_out_fused_kernel, MODE 2 = bf16, MODE 3 = fp16; r05).  Rounded once, to nearest even:
+    (image_restoration_sde_amd/csrc/linear_attn.hip: attn_kv_ctx_kernel / attn_q_out_fused_kernel, AttnMode::Bf16 / AttnMode::Fp16; r05).  Rounded once, to nearest even:
     the LayerNorm output (operand of the three projections), the to_qkv / to_out weights, exp(k - max) and v (operands of the context sum), the merged context and the
     softmax(q) probabilities (operands of the output product), the attention output (operand of to_out).  Everything else — LayerNorms, both softmaxes, the softmax
     denominator of k (the UNROUNDED exponentials), every accumulation, bias, residual — in the working precision.  fp16: context and attention output pass the

@@ -1,4 +1,4 @@
-"""GPU tests of the fused LinearAttention kernels' three-piece mode (csrc/kernels_misc.hip, MODE 4 of attn_kv_ctx_kernel / attn_q_out_fused_kernel: the k / v, q and
+"""GPU tests of the fused LinearAttention kernels' three-piece mode (csrc/linear_attn.hip, AttnMode::Bf16x3 of attn_kv_ctx_kernel / attn_q_out_fused_kernel: the k / v, q and
 to_out projections on three bf16 pieces per operand and six products; plan rule Builder::split3_attn_adopts, knob IRSDE_SPLIT3_ATTN, hook
 irsde_debug_force_split3_attn).
 

@@ -1,4 +1,4 @@
-// GPU check of the vector-pipe group sums of csrc/kernels_misc.hip (group_sum<W>, half_sum, half_max: DPP quad permutes / row mirrors +
+// GPU check of the vector-pipe group sums of csrc/linear_attn.hip (group_sum<W>, half_sum, half_max: DPP quad permutes / row mirrors +
 // v_permlane16_swap / v_permlane32_swap) against the __shfl_xor butterflies they replace.   build: hipcc --offload-arch=gfx950 -O3 group_sum_probe.hip -o group_sum_probe
 #include <hip/hip_runtime.h>
 #include <cmath>
