@@ -50,7 +50,7 @@ SYMBOLS = [
     "irsde_get_profile", "irsde_debug_tap", "irsde_work_model", "irsde_debug_conv", "irsde_debug_conv_choice", "irsde_debug_conv_halo_choice", "irsde_debug_conv_features", "irsde_plan_describe", "irsde_bench_conv", "irsde_op_profile", "irsde_debug_split_gemm", "irsde_bench_naf_chain", "irsde_debug_force_subbatches", "irsde_debug_force_chain_groups", "irsde_debug_force_wino_poly", "irsde_debug_force_split3", "irsde_debug_force_split3_attn", "irsde_debug_force_split3_blocks", "irsde_debug_force_split3_1x1", "irsde_debug_split3_1x1", "irsde_debug_split3_1x1_choice", "irsde_debug_scam", "irsde_debug_scam_full",
     "irsde_debug_scam_stream", "irsde_debug_scam_full_stream", "irsde_debug_force_scam_stream",
     "irsde_debug_naf_gate_sca", "irsde_debug_tlsc", "irsde_debug_ln_film", "irsde_debug_naf_lnconv", "irsde_debug_naf_chain", "irsde_debug_naf_chain_split_order",
-    "irsde_debug_full_attention16",
+    "irsde_debug_full_attention16", "irsde_debug_attn_block", "irsde_debug_attn_core", "irsde_debug_attn_choice",
     "irsde_eval_metrics", "irsde_tensor2img", "irsde_upscale_bicubic", "irsde_mask_to", "irsde_imresize",
     "irsde_create_lpips", "irsde_lpips", "irsde_debug_lpips_tap",
     "irsde_set_lens_info", "irsde_nafnet_set_local_pool", "irsde_create_latent_unet", "irsde_latent_shapes", "irsde_latent_encode", "irsde_latent_decode", "irsde_latent_hidden",
@@ -161,6 +161,9 @@ def _declare(lib):
     lib.irsde_debug_naf_chain.argtypes = [P, P, c.c_int, c.c_int] + [P] * 16 + [P, c.c_int, c.c_int, P, c.c_int, c.c_int, c.c_int, P]
     lib.irsde_debug_naf_chain_split_order.argtypes = [c.c_int, c.c_int, c.POINTER(c.c_int), c.c_int64]
     lib.irsde_debug_full_attention16.argtypes = [P, c.c_int, c.c_int, P, P]
+    lib.irsde_debug_attn_block.argtypes = [P, c.c_int, c.c_int, c.c_int] + [P] * 5 + [c.c_int, c.c_int, P, P]
+    lib.irsde_debug_attn_core.argtypes = [c.c_int, P, c.c_int, c.c_int, c.c_int, P, P, c.c_int, P, P]
+    lib.irsde_debug_attn_choice.argtypes = [c.c_int] * 5 + [c.c_char_p, c.c_int]
     lib.irsde_debug_split_gemm.argtypes = [P, P, P, c.c_int, c.c_int, c.c_int, c.c_int, c.c_int, P]
     lib.irsde_eval_metrics.argtypes = [P, P, c.c_int, c.c_int, c.c_int, c.c_int, c.c_int, c.POINTER(c.c_double), P]
     lib.irsde_tensor2img.argtypes = [P, P, c.c_int, c.c_int, c.c_int, c.c_int, P]

@@ -400,6 +400,7 @@ struct AttnWorkspace {
     float* ctx = nullptr;    // [B][4][32][32]
     int nch = 0;             // N-chunks per image
 };
+int attn_chunk_len(int N, int B);    // pixels per context chunk (a multiple of 8, at least one 128-pixel tile)
 int attn_num_chunks(int N, int B);
 // qkv: [B][N][384] (q | k | v, 4 heads x 32 each).  out: [B][N][128].
 void launch_linear_attention(const float* qkv, float* out, int B, int N, const AttnWorkspace& ws, hipStream_t s,
@@ -420,6 +421,16 @@ struct AttnProj {
     float kv_inv = 1.f, q_inv = 1.f, out_inv = 1.f;
 };
 bool attn_fused_has_instance(int C, AttnMode mode, bool act_bf16);   // do both fused kernels exist for this shape and mode?
+// The kernel-level hooks' view of the two instance tables (engine_debug.hip; host only, nothing is launched).  attn_require_instance: throws what the k / v
+// (q_out: the q + out) launcher would throw for this shape and mode.  attn_choice: the rows a launch would take (-1: none), their dynamic LDS, the pixels per
+// tile and the chunk geometry of attn_chunk_len / attn_num_chunks.
+void attn_require_instance(bool q_out, int C, AttnMode mode, bool act_bf16);
+struct AttnChoice {
+    int kv_row = -1, kv_rows = 0, qo_row = -1, qo_rows = 0;
+    size_t kv_lds = 0, qo_lds = 0;
+    int kv_tile = 0, qo_tile = 0, chunk_len = 0, nch = 0;
+};
+AttnChoice attn_choice(int C, AttnMode mode, bool act_bf16, int N, int B);
 // k, v, their softmax and the context from xn and wkv (the k | v rows of to_qkv.weight) without a k / v tensor in HBM.
 // ln_g != nullptr: `xn` is the un-normalised block input and PreNorm's LayerNorm (* ln_g, eps) runs inside the kernel.
 void launch_attention_kv_context(const float* xn, const float* wkv, int B, int N, int C, const AttnWorkspace& ws, hipStream_t s,

@@ -366,6 +366,23 @@ void scam_hook(const ScamHookArgs& a, int B, int Hs, int Ws, int C, void* stream
     IRSDE_HIP_CHECK(hipStreamSynchronize(s));
 }
 
+// the hooks' common shape check: what a network level can produce (N a multiple of 4) inside the grids of the kernels (4 B blocks in y)
+void attn_hook_shape(const char* who, int B, int N) {
+    if (B < 1 || B > 16383 || N < 4 || N % 4) throw HipError(std::string(who) + ": B in [1, 16383], N a positive multiple of 4");
+}
+// Builder::attn_workspace on hook scratch, every float NaN: a partial a kernel does not write shows in the result
+AttnWorkspace attn_hook_workspace(Scratch& mem, int B, int N, hipStream_t s) {
+    AttnWorkspace ws;
+    ws.nch = attn_num_chunks(N, B);
+    const size_t n[4] = {(size_t)B * ws.nch * 128, (size_t)B * 4 * ws.nch * 1024, (size_t)B * 4 * ws.nch * 32, (size_t)B * 4 * 1024};
+    float** const dst[4] = {&ws.pmax, &ws.pctx, &ws.psum, &ws.ctx};
+    for (int i = 0; i < 4; ++i) {
+        *dst[i] = mem.alloc<float>(n[i]);
+        IRSDE_HIP_CHECK(hipMemsetAsync(*dst[i], 0xFF, n[i] * sizeof(float), s));
+    }
+    return ws;
+}
+
 }  // namespace
 }  // namespace irsde
 
@@ -507,6 +524,105 @@ int irsde_debug_full_attention16(const void* qkv_bf16, int B, int N, void* out_b
         if (!qkv_bf16 || !out_bf16) throw HipError("null argument");
         hipStream_t s = reinterpret_cast<hipStream_t>(stream);
         launch_full_attention16(static_cast<const unsigned short*>(qkv_bf16), static_cast<unsigned short*>(out_bf16), B, N, s);
+        IRSDE_HIP_CHECK(hipStreamSynchronize(s));
+    });
+}
+
+int irsde_debug_attn_choice(int C, int mode, int act_bf16, int N, int B, char* out, int out_len) {
+    return guard([&] {
+        if (!out || out_len < 1 || mode < 0 || mode > 4 || N < 1 || B < 1) throw HipError("debug_attn_choice: bad argument");
+        const AttnChoice c = attn_choice(C, static_cast<AttnMode>(mode), act_bf16 != 0, N, B);
+        snprintf(out, (size_t)out_len, "kv_row=%d of %d qo_row=%d of %d kv_lds=%zu qo_lds=%zu kv_tile=%d qo_tile=%d chunk_len=%d nch=%d", c.kv_row, c.kv_rows,
+                 c.qo_row, c.qo_rows, c.kv_lds, c.qo_lds, c.kv_tile, c.qo_tile, c.chunk_len, c.nch);
+    });
+}
+
+int irsde_debug_attn_block(const float* x, int B, int N, int C, const float* norm_g, const float* to_qkv_w, const float* to_out_w, const float* to_out_b,
+                           const float* to_out_g, int mode, int act_bf16, float* y, void* stream) {
+    return guard([&] {
+        if (!x || !norm_g || !to_qkv_w || !to_out_w || !to_out_b || !to_out_g || !y) throw HipError("null argument");
+        if (mode < 0 || mode > 4) throw HipError("debug_attn_block: mode must be 0 .. 4 (AttnMode)");
+        attn_hook_shape("debug_attn_block", B, N);
+        AttnProj p;
+        p.mode = static_cast<AttnMode>(mode);
+        p.act_bf16 = act_bf16 != 0;
+        attn_require_instance(false, C, p.mode, p.act_bf16);   // every refusal of the two launchers before the first launch
+        attn_require_instance(true, C, p.mode, p.act_bf16);
+        hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+        conv_global_init();
+        Scratch mem(s);
+        const size_t nq = (size_t)128 * C, nkv = (size_t)256 * C, no = (size_t)C * 128, nx = (size_t)B * N * C;
+        float *dqkv = mem.upload(to_qkv_w, nq + nkv), *dwo = mem.upload(to_out_w, no), *dbo = mem.upload(to_out_b, C);
+        float *g1 = mem.upload(norm_g, C), *g2 = mem.upload(to_out_g, C);
+        const float *wq = dqkv, *wkv = dqkv + nq;
+        // the planes of the mode, by the functions behind the engine's bf16_copy / pair_copy / triple_copy (Builder::attn_proj)
+        if (p.mode == AttnMode::Bf16 || p.mode == AttnMode::Fp16) {
+            unsigned short *q16 = mem.alloc<unsigned short>(nq + nkv), *o16 = mem.alloc<unsigned short>(no);
+            if (p.mode == AttnMode::Fp16) { launch_f32_to_f16(dqkv, q16, nq + nkv, s); launch_f32_to_f16(dwo, o16, no, s); }
+            else { launch_f32_to_bf16(dqkv, q16, nq + nkv, s); launch_f32_to_bf16(dwo, o16, no, s); }
+            p.q = q16; p.kv = q16 + nq; p.out = o16;
+        } else if (p.mode == AttnMode::Bf16x3) {
+            unsigned short *kv3 = mem.alloc<unsigned short>(3 * nkv), *q3 = mem.alloc<unsigned short>(3 * nq), *o3 = mem.alloc<unsigned short>(3 * no);
+            launch_split_frag3(wkv, kv3, 256, C, s);
+            launch_split_frag3(wq, q3, 128, C, s);
+            launch_split_frag3(dwo, o3, (size_t)C, 128, s);
+            p.kv = kv3; p.q = q3; p.out = o3;
+        } else if (p.mode == AttnMode::PairF16) {
+            auto pair = [&](const float* host, const float* dev, size_t n, float& inv) {
+                const float sc = pow2_scale_into_512(host, n);
+                unsigned short* d = mem.alloc<unsigned short>(2 * n);
+                launch_split_planes(dev, d, n, n, 2, s, true, sc);
+                inv = 1.0f / sc;
+                return d;
+            };
+            p.kv = pair(to_qkv_w + nq, wkv, nkv, p.kv_inv);
+            p.q = pair(to_qkv_w, wq, nq, p.q_inv);
+            p.out = pair(to_out_w, dwo, no, p.out_inv);
+        }
+        const AttnWorkspace ws = attn_hook_workspace(mem, B, N, s);
+        const float* xin = x;
+        float* yout = y;
+        unsigned short* y16 = nullptr;
+        if (p.act_bf16) {   // the caller's fp32 x rounded into a bf16 copy; the bf16 result starts as NaN and is widened back
+            unsigned short* x16 = mem.alloc<unsigned short>(nx);
+            y16 = mem.alloc<unsigned short>(nx);
+            launch_f32_to_bf16(x, x16, nx, s);
+            IRSDE_HIP_CHECK(hipMemsetAsync(y16, 0xFF, nx * 2, s));
+            xin = reinterpret_cast<const float*>(x16);
+            yout = reinterpret_cast<float*>(y16);
+        }
+        launch_attention_kv_context(xin, wkv, B, N, C, ws, s, g1, 1e-5f, p);
+        launch_attention_q_out_fused(xin, xin, wq, dwo, dbo, g2, yout, B, N, C, 1e-5f, ws, s, g1, p);
+        if (y16) launch_bf16_to_f32(y16, y, nx, s);
+        IRSDE_HIP_CHECK(hipStreamSynchronize(s));
+    });
+}
+
+int irsde_debug_attn_core(int route, const float* in, int B, int N, int C, const float* wkv, const float* q, int bf16, float* out, void* stream) {
+    return guard([&] {
+        if (route != 1 && route != 2) throw HipError("debug_attn_core: route must be 1 (k / v context from xn + q tensor) or 2 (q | k | v tensor)");
+        if (!in || !out || (route == 1 && (!wkv || !q))) throw HipError("null argument");
+        attn_hook_shape("debug_attn_core", B, N);
+        if (route == 1 && bf16) throw HipError("debug_attn_core: route 1 runs on fp32 tensors only");
+        if (route == 1) attn_require_instance(false, C, AttnMode::F32, false);
+        hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+        conv_global_init();
+        Scratch mem(s);
+        const AttnWorkspace ws = attn_hook_workspace(mem, B, N, s);
+        if (route == 1) {
+            const float* dwkv = mem.upload(wkv, (size_t)256 * C);
+            launch_attention_kv_context(in, dwkv, B, N, C, ws, s);
+            launch_attention_q_out(q, out, B, N, ws, s);
+        } else if (bf16) {
+            const size_t ni = (size_t)B * N * 384, no = (size_t)B * N * 128;
+            unsigned short *i16 = mem.alloc<unsigned short>(ni), *o16 = mem.alloc<unsigned short>(no);
+            launch_f32_to_bf16(in, i16, ni, s);
+            IRSDE_HIP_CHECK(hipMemsetAsync(o16, 0xFF, no * 2, s));
+            launch_linear_attention(reinterpret_cast<const float*>(i16), reinterpret_cast<float*>(o16), B, N, ws, s, true);
+            launch_bf16_to_f32(o16, out, no, s);
+        } else {
+            launch_linear_attention(in, out, B, N, ws, s, false);
+        }
         IRSDE_HIP_CHECK(hipStreamSynchronize(s));
     });
 }

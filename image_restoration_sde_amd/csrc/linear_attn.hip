@@ -831,9 +831,11 @@ __global__ __launch_bounds__(256, 2) void attn_q_out_fused_kernel(const float* _
         for (int s2 = 0; s2 < 16; ++s2) cb[s2] = cp[((s2 & 3) + 8 * (s2 >> 2) + 4 * h) * 32];
     }
     // fp16 operands (MODE 3): the context carries v / N (module_util.py:168) — O(1e-6) on a 256 x 256 map, in fp16's subnormal range — so it and with it the
-    // attention output go through the 16-bit MFMAs scaled by ctx_up = 2^ceil(log2 N) (exact), undone on the to_out accumulators in front of the bias
+    // attention output go through the 16-bit MFMAs scaled by ctx_up = 2^ceil(log2 N) (exact), undone on the to_out accumulators in front of the bias.
+    // fp16 pairs (MODE 1) the same: unscaled, the lo piece of an attention output of O(1 / N) falls into fp16's subnormal range (absolute spacing 2^-24) and the
+    // pair loses its 22 bits — a relative error of the block that grows with N (2e-4 of the branch at 520 pixels; tests/test_gpu_linear_attn.py found it)
     float ctx_up = 1.f;
-    if constexpr (MODE == AttnMode::Fp16) {
+    if constexpr (MODE == AttnMode::Fp16 || PAIR) {
         ctx_up = exp2f(ceilf(log2f((float)N)));
 #pragma unroll
         for (int s2 = 0; s2 < 16; ++s2) cb[s2] *= ctx_up;
@@ -980,7 +982,7 @@ __global__ __launch_bounds__(256, 2) void attn_q_out_fused_kernel(const float* _
             using x8 = typename M16::x8;
 #pragma unroll
             for (int sh = 0; sh < 2; ++sh) {
-                // (MODE 3: cb carries the power of two `ctx_up`, see below)
+                // (MODE 3: cb carries the power of two `ctx_up`, see above)
                 const floatx8 ca = {cb[8 * sh], cb[8 * sh + 1], cb[8 * sh + 2], cb[8 * sh + 3], cb[8 * sh + 4], cb[8 * sh + 5], cb[8 * sh + 6], cb[8 * sh + 7]};
                 const floatx8 qa = {q[ct][8 * sh], q[ct][8 * sh + 1], q[ct][8 * sh + 2], q[ct][8 * sh + 3],
                                     q[ct][8 * sh + 4], q[ct][8 * sh + 5], q[ct][8 * sh + 6], q[ct][8 * sh + 7]};
@@ -1102,10 +1104,11 @@ __global__ __launch_bounds__(256, 2) void attn_q_out_fused_kernel(const float* _
                 for (int rt = 0; rt < RH; ++rt) yv[r0 + rt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wa2[cur][0][rt], bh, yv[r0 + rt], 0, 0, 0);
             }
         }
+        const float dn = wout_inv * (1.0f / ctx_up);   // two powers of two: the weights' scale and the context's
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) yv[rt][r] *= wout_inv;
+            for (int r = 0; r < 16; ++r) yv[rt][r] *= dn;
     } else if constexpr (P16) {
         using x8 = typename M16::x8;
         const char* wrow = reinterpret_cast<const char*>(wout_pair) + ((size_t)l31 * kHid + 8 * h) * 2;
@@ -1279,7 +1282,7 @@ __global__ __launch_bounds__(256, 2) void attn_q_out_fused_kernel(const float* _
 
 // pixels per context chunk: 32 chunks per image, more for small batches so that the chunk grid (chunks x B blocks) still fills
 // the 256 CUs (r03: at B = 2 the 64-block k/v kernels ran 4-5x slower per image than at B = 16); never below one 128-pixel tile
-static int attn_chunk_len(int N, int B) {
+int attn_chunk_len(int N, int B) {
     const int want = std::max(32, (512 + B - 1) / std::max(B, 1));
     int len = (N + want - 1) / want;
     if (len < 128) len = 128;
@@ -1373,6 +1376,29 @@ void launch_ctx_finalize(int B, int N, int nch, const AttnWorkspace& ws, hipStre
 
 bool attn_fused_has_instance(int C, AttnMode mode, bool act_bf16) {
     return find_inst(kKvInst, C, mode, act_bf16) && find_inst(kQoInst, C, mode, act_bf16);
+}
+
+// pick_inst's verdict on one launcher's table without a launch (the kernel-level hooks refuse with the launcher's own message)
+void attn_require_instance(bool q_out, int C, AttnMode mode, bool act_bf16) {
+    AttnProj p;
+    p.mode = mode;
+    p.act_bf16 = act_bf16;
+    if (q_out) pick_inst("attention_q_out_fused", kQoInst, C, p, true);
+    else pick_inst("attention_kv_context", kKvInst, C, p, true);
+}
+
+// what the two launchers read for one shape: table rows, LDS bytes, tiles and the chunk geometry (host only)
+AttnChoice attn_choice(int C, AttnMode mode, bool act_bf16, int N, int B) {
+    AttnChoice c;
+    c.kv_rows = (int)(sizeof(kKvInst) / sizeof(kKvInst[0]));
+    c.qo_rows = (int)(sizeof(kQoInst) / sizeof(kQoInst[0]));
+    if (const KvInst* r = find_inst(kKvInst, C, mode, act_bf16)) { c.kv_row = (int)(r - kKvInst); c.kv_lds = r->lds; }
+    if (const QoInst* r = find_inst(kQoInst, C, mode, act_bf16)) { c.qo_row = (int)(r - kQoInst); c.qo_lds = r->lds; }
+    c.kv_tile = mode == M::Bf16x3 ? kKvTileTri : kKvTile;
+    c.qo_tile = qo_tile(mode);
+    c.chunk_len = attn_chunk_len(N, B);
+    c.nch = attn_num_chunks(N, B);
+    return c;
 }
 
 // > 64 KB of dynamic LDS needs the attribute on the CURRENT device: called from conv_global_init() (engine finalize, per

@@ -242,6 +242,33 @@ int irsde_debug_naf_chain_split_order(int nblocks, int groups, int* order_out, l
  * tests/test_gpu_dsde_unet16.py compares it with tests/dsde_unet16_oracle.py. */
 int irsde_debug_full_attention16(const void* qkv_bf16, int B, int N, void* out_bf16, void* stream);
 
+/* Kernel-level test hooks of csrc/linear_attn.hip (tests/test_gpu_linear_attn.py compares them with tests/linear_attn_oracle.py; outside the drop-in boundary,
+ * irsde_version() unchanged).  Activations are DEVICE tensors in NHWC order with the pixels flattened ([B][N][channels]), weights HOST pointers in reference
+ * layout.  B in [1, 16383]; N a positive multiple of 4 (the least a network level produces), anything else is refused.  The chunk workspace is sized as
+ * Builder::attn_workspace sizes it and starts as NaN.  Rows behind row N of an output are not written.  Both synchronise `stream`.
+ *
+ * irsde_debug_attn_block: ONE Residual(PreNorm(LinearAttention)) on the fused route of Builder::attn — launch_attention_kv_context (PreNorm's LayerNorm, k / v
+ * projection, context) and launch_attention_q_out_fused (LayerNorm, q projection, softmax, context product, to_out, LayerNorm, residual), nothing else.
+ * x / y [B][N][C] fp32; norm_g = norm.g [C], to_qkv_w = to_qkv.weight [384][C], to_out_w = to_out.0.weight [C][128], to_out_b = to_out.0.bias [C],
+ * to_out_g = to_out.1.g [C].  mode: AttnMode by number (0 f32, 1 fp16 hi + lo pairs, 2 bf16, 3 fp16, 4 three bf16 pieces); the mode's weight planes are made by
+ * the functions behind the engine's own copies (launch_f32_to_bf16 / launch_f32_to_f16, launch_split_planes with pow2_scale_into_512, launch_split_frag3).
+ * act_bf16 (mode 2 only): x is rounded into a bf16 copy on the device, the kernels read and write bf16 tensors, the bf16 result (pre-filled with NaN) is widened
+ * back into y.  A (C, mode, act_bf16) without a row in either instance table is refused with the launcher's message before anything is launched. */
+int irsde_debug_attn_block(const float* x, int B, int N, int C, const float* norm_g, const float* to_qkv_w, const float* to_out_w, const float* to_out_b,
+                           const float* to_out_g, int mode, int act_bf16, float* y, void* stream);
+/* irsde_debug_attn_core: the attention core alone on the two routes that have a tensor in front of it; out [B][N][128] (heads x 32 channels).
+ *   route 1  Builder::attn's fused_kv route: in = xn [B][N][C], ALREADY normalised; wkv = the k | v rows of to_qkv.weight ([256][C], HOST); q = DEVICE [B][N][128]
+ *            (the q convolution's output).  launch_attention_kv_context without ln_g (fp32, C a multiple of 32 up to 256), then launch_attention_q_out.  bf16 = 0.
+ *   route 2  in = q | k | v [B][N][384] (wkv, q: NULL; C is ignored): launch_linear_attention.  bf16 != 0: the tensor is rounded into a bf16 copy, the kernels run
+ *            on bf16 storage, the result (pre-filled with NaN) is widened back.
+ * The q convolution, to_out and its LayerNorm are convolutions / glue that other hooks cover. */
+int irsde_debug_attn_core(int route, const float* in, int B, int N, int C, const float* wkv, const float* q, int bf16, float* out, void* stream);
+/* Host only (never touches a device, never reads the environment): what the two fused launchers read for (C, mode, act_bf16) on B images of N pixels — their
+ * instance tables and attn_chunk_len / attn_num_chunks.  Writes one line into out:
+ *   kv_row=<i|-1> of 23 qo_row=<i|-1> of 18 kv_lds=<bytes> qo_lds=<bytes> kv_tile=<px> qo_tile=<px> chunk_len=<px> nch=<n>
+ * (row -1, lds 0: the table has no such instance; `of` = the tables' lengths).  The three-pass kernels of route 2 use chunk_len and nch alone. */
+int irsde_debug_attn_choice(int C, int mode, int act_bf16, int N, int B, char* out, int out_len);
+
 /* Kernel-level test hook: ONE full-resolution SCAM of the stereo-sr ConditionalUNet (csrc/scam.hip *_full kernels + the projection GEMM on the
  * implicit-GEMM kernel, fp32) — the counterpart of irsde_debug_scam, same argument order.  x / out: device NHWC [2 B_pairs][H][W][C], views stacked
  * [L_0..L_{B-1}, R_0..R_{B-1}]; every weight is a HOST pointer in reference layout.  C a multiple of 32 in [32, 2048], H, W >= 1, W <= 1024

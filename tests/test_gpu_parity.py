@@ -9,6 +9,9 @@ Tolerances (floating point path, fp32 arithmetic on both sides):
   one reverse step (elementwise) vs golden ......... 2e-6 abs / 1e-5 rel
   full sampler vs reference golden ................. 2e-3 relative to max|ref|  (reverse drift expands
       perturbations ~200x; the reference's own fp32-vs-fp64 gap is of the same size)
+
+LinearAttention: the blocks of a whole network are compared here (test_fused_attention_block_vs_oracle); every kernel instance, route and chunk tail on its own,
+against the same float64 block: tests/test_gpu_linear_attn.py.
 """
 import ctypes
 import os
